@@ -4,13 +4,25 @@
     python bench.py --gpus 1 --steps K --warmup W                                  (the driver's N = 1 line)
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N --steps K --warmup W
     python bench.py --config 2 --loopback 8          (a partitioned configuration rehearsed on ONE GPU, see below)
+    python bench.py --full                           (the headline figure and everything else this file measures)
+    python bench.py --dump-outputs DIR               (also write what the last timed step computed, DIR/<name>.npy)
+
+A plain run sets up, warms up, times the K steps and prints one JSON line (metric, value, unit, ms_per_step, dtype, the
+workload's config).  --full adds what needs runs of its own: per-kernel HIP-event times and the roofline, the loop with the
+solver's history dropped, the palette-off / graded and 100^3 K*p measurements, the CPU baselines, the end-to-end call
+site and the other BASELINE configurations (the --no-* / --*-cells switches below then leave single parts out).
+--dump-outputs: after the timed steps, the last step is run once more with its result downloaded (same system, same start
+from zero: the same numbers the timed step computed) and written as float64 .npy files, 64 MB at most - the solution u and
+the BSR(6x6) K of the step applied to a fixed seeded probe; configs[3]: the last design iteration's compliance, gradient,
+solution and the radii it ends with.  Inputs are synthetic and deterministic, so two builds compare output for output.
 
 Workloads (BASELINE.json `configs`; cell size 1, VeroClear, joint penalisation on, cantilever: all
 6 dofs clamped on Xmin, total force -0.1 in Z on Xmax):
   --config 1 (default)  configs[1]: 50x50x50 Octet, r = 0.03, fp64.  N > 1 GPUs: 50 x (50 N) x 50 cut into N y-slabs
                         (weak scaling: 3.03 M struts per GPU; growing along y keeps the cantilever's aspect ratio).
   --config 2            configs[2]: 100x100x100 BCC, r = 0.05, fp64, N x-slabs of the SAME lattice (strong scaling).
-  --config 3            configs[3]: graded-radius 24^3 BCC, 50 objective + adjoint-gradient evaluations, one GPU.
+  --config 3            configs[3]: graded-radius 24^3 BCC, --steps objective + adjoint-gradient evaluations (50 in
+                        the --full line's record), one GPU.
   --config 4            configs[4]: 200x200x50 BCC + Octet, r = [0.04, 0.03], fp32 inner PCG with fp64 refinement
                         (opts.precision = 1), N x-slabs (strong scaling).
 Ranks: one process per GPU under torchrun (RCCL inside libpylattice_hip), or --loopback R: R slab handles of THIS process
@@ -366,7 +378,7 @@ def other_configs(args, local_rank):
         gc.collect()
     t0 = time.perf_counter()
     sub = argparse.Namespace(**vars(args))
-    sub.cells, sub.warmup = None, 2
+    sub.cells, sub.warmup, sub.steps, sub.dump_outputs = None, 2, 50, None
     d3 = design_loop(sub, local_rank)
     out["configs[3]"] = {"workload": d3["config"]["workload"], "value": d3["value"], "unit": "beams/s",
                          "ms_per_step": d3["ms_per_step"], "steps": d3["steps"], "warmup": d3["warmup"], "dtype": d3["dtype"],
@@ -493,11 +505,11 @@ def drop_in_optimisation():
 
 def design_loop(args, local_rank):
     """configs[3]: graded-radius 24^3 BCC ("gyroid-like" radius field of SURVEY 8d item 4), unit_cell parameterisation,
-    50 evaluations of compliance + its adjoint gradient (self-adjoint: one solve + the per-strut sensitivity pass) with a
+    args.steps evaluations of compliance + its adjoint gradient (self-adjoint: one solve + the per-strut sensitivity pass) with a
     projected-gradient update of the radii in between - pl_update_radii, pl_assemble, pl_solve, pl_sens per iteration."""
     from pylatticedso_amd import _capi, lattice_arrays as LA
     n = args.cells[0] if args.cells else 24
-    iters = 50
+    iters = args.steps
     i3 = np.stack(np.meshgrid(np.arange(n), np.arange(n), np.arange(n), indexing="ij"), axis=-1).reshape(-1, 3) + 0.5
     x, y, z = (2 * np.pi * i3[:, k] / 8 for k in range(3))
     rc = np.clip(0.05 + 0.03 * (np.sin(x) * np.cos(y) + np.sin(y) * np.cos(z) + np.sin(z) * np.cos(x)) / 1.5, 0.01, 0.1)
@@ -513,6 +525,7 @@ def design_loop(args, local_rank):
         dev.set_bc(fixed, None, f)
         r = rc.copy()
         its = []
+        last = {}
 
         def evaluate(r):
             dev.update_radii(r[cell_of])
@@ -521,6 +534,7 @@ def design_loop(args, local_rank):
             C = float((f * u).sum())
             g = -np.bincount(cell_of, weights=dev.sens(None), minlength=len(r))  # dC/dr_cell = -u^T dK/dr u (u: on the device)
             its.append(st["iterations"])
+            last["u"] = u
             return C, g
         for k in range(args.warmup):      # (warm-up on slightly different radii: the first timed solve must not start from
             evaluate(np.clip(r * (1.0 + 0.02 * (k + 1)), 0.01, 0.1))     # the answer of its own system)
@@ -534,21 +548,25 @@ def design_loop(args, local_rank):
             r = np.clip(r - 0.002 * g / max(np.abs(g).max(), 1e-300), 0.01, 0.1)
         torch.cuda.synchronize()
         dt = time.perf_counter() - t0
+        if getattr(args, "dump_outputs", None):
+            # what the last design iteration handed its caller (compliance, gradient, solution) and the radii it ends with
+            dump_outputs(args.dump_outputs, {"compliance": np.array([C]), "gradient": g, "u": last["u"], "radii": r})
         st = dev.last_stats
-        ms_op, ms_it = dev.time_kernel(10, 50), dev.time_kernel(11, 50)
-        ab = dev.algorithmic_bytes()
-        kp_form, passes = int(st["kp_form"]), (2 if int(st["condensed_nodes"]) else 1)
-        roof = roofline_of("K*p: " + KP_FORMS.get(kp_form, "?") + (" (both passes of the node-eliminated operator)"
-                                                                   if passes == 2 else ""),
-                           kp_form in (1, 4), ab["spmv"], ms_op, None, "no counters for this workload", passes=passes)
-        roof["note"] = ("110 592 struts: a launch lasts 3-6 us whatever it moves - the path is bound by the latency of the "
-                        "dependent launches of an iteration (pcg_iteration_us), not by HBM")
-        extra = {"solve_ms_last": st["ms_solve"], "assembly_ms_last": st["ms_assembly"], "pcg_iteration_us": ms_it * 1e3,
-                 "operator_us": ms_op * 1e3, "condensed_nodes": int(st["condensed_nodes"]),
-                 "short_iteration_used": int(st.get("short_iteration_used", 0)),
+        extra = {"solve_ms_last": st["ms_solve"], "assembly_ms_last": st["ms_assembly"],
+                 "condensed_nodes": int(st["condensed_nodes"]), "short_iteration_used": int(st.get("short_iteration_used", 0)),
                  "pcg_iterations_mean": float(np.mean(its[args.warmup:]))}
-    return {"roofline": roof, "breakdown": extra,
-            "metric": "beams/s assembly+PCG-solve", "value": lat.n_beams * iters / dt, "unit": "beams/s", "n_gpus": 1,
+        roof = None
+        if args.full:
+            ms_op, ms_it = dev.time_kernel(10, 50), dev.time_kernel(11, 50)
+            ab = dev.algorithmic_bytes()
+            kp_form, passes = int(st["kp_form"]), (2 if int(st["condensed_nodes"]) else 1)
+            roof = roofline_of("K*p: " + KP_FORMS.get(kp_form, "?") + (" (both passes of the node-eliminated operator)"
+                                                                       if passes == 2 else ""),
+                               kp_form in (1, 4), ab["spmv"], ms_op, None, "no counters for this workload", passes=passes)
+            roof["note"] = ("110 592 struts: a launch lasts 3-6 us whatever it moves - the path is bound by the latency of the "
+                            "dependent launches of an iteration (pcg_iteration_us), not by HBM")
+            extra.update(pcg_iteration_us=ms_it * 1e3, operator_us=ms_op * 1e3)
+    out = {"metric": "beams/s assembly+PCG-solve", "value": lat.n_beams * iters / dt, "unit": "beams/s", "n_gpus": 1,
             "steps": iters, "warmup": args.warmup, "ms_per_step": dt / iters * 1e3, "higher_is_better": True,
             "scaling": None, "vs_baseline": None, "dtype": "f64", "data": "synthetic",
             "config": {"workload": f"{n}^3 BCC, graded radius per cell ({len(rc)} design variables, unit_cell "
@@ -568,6 +586,27 @@ def design_loop(args, local_rank):
                                          "inside the timed step)"}.get(args.warm_start, str(args.warm_start)) +
                                      ": the system changes by one projected-gradient step; the stopping test is the same "
                                      "||r|| <= rtol ||b|| of the current right-hand side"}}
+    out["breakdown"] = extra
+    if roof is not None:
+        out["roofline"] = roof
+    return out
+
+
+def dump_outputs(path, arrays, budget=60_000_000):
+    """DIR/<name>.npy in float64 for every array; if they would exceed `budget` bytes together (below the 64 MB promised,
+    headers included), the same fixed, seeded choice of rows is kept of each (leading axis)."""
+    arrays = {k: np.asarray(v, dtype=np.float64) for k, v in arrays.items()}
+    total = sum(a.nbytes for a in arrays.values())
+    if total > budget:
+        rng = np.random.default_rng(0)
+        for k, a in arrays.items():
+            if a.ndim and len(a) > 1:
+                keep = max(1, int(len(a) * budget / total) - 1)
+                arrays[k] = a[np.sort(rng.choice(len(a), keep, replace=False))]
+    os.makedirs(path, exist_ok=True)
+    for k, a in arrays.items():
+        np.save(os.path.join(path, k + ".npy"), a)
+    log(f"[dump-outputs] {', '.join(f'{k} {a.shape}' for k, a in arrays.items())} -> {path}")
 
 
 def main():
@@ -638,7 +677,14 @@ def main():
                          "neighbour exchange")
     ap.add_argument("--force-dist", action="store_true",
                     help="take the multi-GPU code path (slab build, RCCL communicator) even with one rank (rehearsal)")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline figure, everything else this file measures (see the module docstring); "
+                         "without it a run does only what its headline figure needs")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last step computed as DIR/<name>.npy (float64, 64 MB at most)")
     args = ap.parse_args()
+    if args.steps < 1:
+        raise SystemExit("--steps must be at least 1")
 
     # Libraries (RCCL prints a version banner) write to the C-level stdout: keep fd 1 for the ONE JSON line only.
     sys.stdout.flush()
@@ -683,6 +729,8 @@ def main():
     if loop and world > 1:
         raise SystemExit("--loopback is a single-process mode")
     multi = world > 1 or args.force_dist
+    if multi and args.dump_outputs:
+        raise SystemExit("--dump-outputs is for single-process runs (one handle, or --loopback R handles)")
     if args.precond == 0:
         # 4 (rank-local dense level) was measured on the single-GPU rehearsal of the multi-rank path: +11 us per
         # iteration and +2 ms per assembly for 12-14 % fewer iterations when the global level is coarse - a wash, so 3
@@ -764,16 +812,17 @@ def main():
         fixed, f, _ = cantilever_bc(xyz, x_max, n_tgt)
         dev.set_bc(fixed, None, f)
 
-    def step():
+    def step(download=False):
         if loop:
             group.assemble()
             if not args.no_bsr:
                 group.each(lambda r: group.devs[r].assemble_bsr(False))
-            return group.solve(rtol=args.rtol, max_iter=args.max_iter, download=False)[0]
+            res = group.solve(rtol=args.rtol, max_iter=args.max_iter, download=download)
+            return res if download else res[0]
         dev.assemble()
         if not args.no_bsr:
             dev.assemble_bsr(False)
-        return dev.solve(rtol=args.rtol, max_iter=args.max_iter, download=False)
+        return dev.solve(rtol=args.rtol, max_iter=args.max_iter, download=download)
 
     def sync():
         torch.cuda.synchronize()     # device-wide: covers the library's own streams
@@ -796,6 +845,75 @@ def main():
         t = torch.tensor([dt], dtype=torch.float64)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         dt = float(t.item())
+
+    part = "single GPU"
+    if loop:
+        part = (f"{loop} {'xyz'[axis]}-slabs as {loop} handles on ONE GPU (loopback transport: the multi-rank device path without "
+                f"RCCL; value is a one-GPU number)")
+    elif world > 1 or multi:
+        part = (f"{world} {'xyz'[axis]}-slabs, RCCL " + ("interface all-reduce" if args.interface_allreduce else
+                                                         "neighbour exchange of interface rows (ncclSend/ncclRecv)") +
+                " + fused scalar all-reduces")
+    out = {
+        "metric": "beams/s assembly+PCG-solve", "value": n_beams_total * args.steps / dt, "unit": "beams/s",
+        "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": dt / args.steps * 1e3,
+        "higher_is_better": True, "scaling": (cfg["scaling"] if (world > 1 or loop) else None), "vs_baseline": None,
+        "dtype": {0: "f64", 1: "f32 storage + f64 refinement (f64 arithmetic)", 2: "f32 p/Kp storage, f64 x/r"}[args.precision],
+        "data": "synthetic",
+        "config": {"workload": f"{ncell[0]}x{ncell[1]}x{ncell[2]} {'+'.join(cfg['geom'])} r={cfg['radii']} cantilever "
+                               f"({cfg['name']}{' per GPU' if cfg['scaling'] == 'weak' else ''})",
+                   "struts": n_beams_total, "struts_per_gpu": per_rank[0], "nodes_per_gpu": per_rank[1],
+                   "partition": part, "ranks": nranks,
+                   # what the COMMUNICATOR says (ncclCommCount / ncclCommUserRank read inside pl_dist_init, or the loopback
+                   # group's size), not the launcher's environment
+                   "communicator": ({"ranks": int(st.get("comm_world", 0)), "this_rank": int(st.get("comm_rank", 0)),
+                                     "source": "pl_stats_t.comm_world / comm_rank"} if (multi or loop) else None),
+                   "rtol": args.rtol, "pcg_iterations": st["iterations"], "converged": st["converged"],
+                   "rel_residual": st["rel_residual"], "precision": args.precision,
+                   "inner_solves": st.get("restarts", 0.0), "condensed_nodes": int(st.get("condensed_nodes", 0)),
+                   "cg_form": int(st.get("cg_form_used", 0)),
+                   "preconditioner": {1: "Jacobi", 2: "two-level (Jacobi + rigid-body coarse space)",
+                                      3: "multi-level (Jacobi + tile blocks + dense rigid-body coarse space)",
+                                      4: "multi-level (Jacobi + tile blocks + rank-local dense level + all-reduced "
+                                         "dense rigid-body coarse space)"}[args.precond],
+                   "step": "records + Jacobi diag" + (" + coarse operator/factorisation" if args.precond >= 2 else "")
+                           + ("" if args.no_bsr else " + BSR(6x6) K") + " + matrix-free PCG",
+                   "spmv_kernel": args.kernel, "reorder": args.reorder, "record_palette": args.palette,
+                   "convergence_checks": "the host reads the residual history every 32 iterations, then as the observed "
+                                         "decay predicts; from the second solve of a handle on, the FIRST look is taken 3 "
+                                         "iterations before the previous solve's count (pl_solver.h) - in this loop of "
+                                         "identical solves that removes the intermediate stream drains (~5 x 40 us per "
+                                         "solve); the iteration count is the first one whose residual meets rtol either way",
+                   "model": "reference_compat = False (the default of LatticeSim): every strut once, boundary data on design "
+                            "nodes.  The reference's own model of this geometry - a strut lying in a cell face is kept once "
+                            "per owner cell, penalisation points in the loaded faces carry boundary data - is "
+                            "LatticeSim(reference_compat=True): same kernels with a per-strut multiplicity, timed once "
+                            "through the drop-in call site in end_to_end_reference_compat_s"
+                            if "Octet" in cfg["geom"] else None},
+    }
+
+    if args.dump_outputs:
+        # the last step once more with its solution downloaded (same system, solves start from zero: the numbers the last
+        # timed step computed), and the BSR K it filled applied to a fixed seeded probe
+        res = step(download=True)
+        arrays, rng = {}, np.random.default_rng(0)
+        for r, (u, _) in enumerate(res if loop else [res]):
+            d, sfx = (group.devs[r], f"_slab{r}") if loop else (dev, "")
+            arrays["u" + sfx] = u
+            if not args.no_bsr:
+                arrays["K_bsr_probe" + sfx] = d.spmv_bsr(rng.standard_normal((d.n_nodes, 6)))
+        dump_outputs(args.dump_outputs, arrays)
+    if not args.full:
+        if loop:
+            group.close()
+        else:
+            dev.close()
+        if rank == 0:
+            os.write(json_fd, (json.dumps(out) + "\n").encode())
+        if multi:
+            dist.barrier()
+            dist.destroy_process_group()
+        return
 
     # The same loop with the handle's memory of its previous solve dropped before every solve (pl_forget_history): the host then
     # looks at the residual history every 32 iterations on the way, as in a first solve - the value a loop of DIFFERENT
@@ -947,57 +1065,14 @@ def main():
                 large["algorithmic_bytes"] = lab["spmv"]
         del llat, lpen
 
-    part = "single GPU"
-    if loop:
-        part = (f"{loop} {'xyz'[axis]}-slabs as {loop} handles on ONE GPU (loopback transport: the multi-rank device path without "
-                f"RCCL; value is a one-GPU number)")
-    elif world > 1 or multi:
-        part = (f"{world} {'xyz'[axis]}-slabs, RCCL " + ("interface all-reduce" if args.interface_allreduce else
-                                                         "neighbour exchange of interface rows (ncclSend/ncclRecv)") +
-                " + fused scalar all-reduces")
-    out = {
-        "metric": "beams/s assembly+PCG-solve", "value": n_beams_total * args.steps / dt, "unit": "beams/s",
-        "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": dt / args.steps * 1e3,
-        "higher_is_better": True, "scaling": (cfg["scaling"] if (world > 1 or loop) else None), "vs_baseline": None,
-        "dtype": {0: "f64", 1: "f32 storage + f64 refinement (f64 arithmetic)", 2: "f32 p/Kp storage, f64 x/r"}[args.precision],
-        "data": "synthetic",
-        "config": {"workload": f"{ncell[0]}x{ncell[1]}x{ncell[2]} {'+'.join(cfg['geom'])} r={cfg['radii']} cantilever "
-                               f"({cfg['name']}{' per GPU' if cfg['scaling'] == 'weak' else ''})",
-                   "struts": n_beams_total, "struts_per_gpu": per_rank[0], "nodes_per_gpu": per_rank[1],
-                   "partition": part, "ranks": nranks,
-                   # what the COMMUNICATOR says (ncclCommCount / ncclCommUserRank read inside pl_dist_init, or the loopback
-                   # group's size), not the launcher's environment
-                   "communicator": ({"ranks": int(st.get("comm_world", 0)), "this_rank": int(st.get("comm_rank", 0)),
-                                     "source": "pl_stats_t.comm_world / comm_rank"} if (multi or loop) else None),
-                   "rtol": args.rtol, "pcg_iterations": st["iterations"], "converged": st["converged"],
-                   "rel_residual": st["rel_residual"], "precision": args.precision,
-                   "inner_solves": st.get("restarts", 0.0), "condensed_nodes": int(st.get("condensed_nodes", 0)),
-                   "cg_form": int(st.get("cg_form_used", 0)),
-                   "preconditioner": {1: "Jacobi", 2: "two-level (Jacobi + rigid-body coarse space)",
-                                      3: "multi-level (Jacobi + tile blocks + dense rigid-body coarse space)",
-                                      4: "multi-level (Jacobi + tile blocks + rank-local dense level + all-reduced "
-                                         "dense rigid-body coarse space)"}[args.precond],
-                   "step": "records + Jacobi diag" + (" + coarse operator/factorisation" if args.precond >= 2 else "")
-                           + ("" if args.no_bsr else " + BSR(6x6) K") + " + matrix-free PCG",
-                   "spmv_kernel": args.kernel, "reorder": args.reorder, "record_palette": args.palette,
-                   "convergence_checks": "the host reads the residual history every 32 iterations, then as the observed "
-                                         "decay predicts; from the second solve of a handle on, the FIRST look is taken 3 "
-                                         "iterations before the previous solve's count (pl_solver.h) - in this loop of "
-                                         "identical solves that removes the intermediate stream drains (~5 x 40 us per "
-                                         "solve); the iteration count is the first one whose residual meets rtol either way",
-                   "model": "reference_compat = False (the default of LatticeSim): every strut once, boundary data on design "
-                            "nodes.  The reference's own model of this geometry - a strut lying in a cell face is kept once "
-                            "per owner cell, penalisation points in the loaded faces carry boundary data - is "
-                            "LatticeSim(reference_compat=True): same kernels with a per-strut multiplicity, timed once "
-                            "through the drop-in call site in end_to_end_reference_compat_s"
-                            if "Octet" in cfg["geom"] else None},
+    out.update({
         "roofline": roofline_of("K*p: " + KP_FORMS.get(kp_form, dev_kernel_name(args.kernel, args.reorder, args.palette)),
                                 kp_form in (1, 4), ab["spmv"], ms_spmv, issue, issue_why, traffic, traffic_src,
                                 passes=2 if int(st.get("condensed_nodes", 0)) else 1),
         "kernels_ms": {"spmv": ms_spmv, "pcg_iteration": ms_iter, "record_build": ms_rec, "bsr_fill": ms_bsr,
                        "pcg_iter_GBps": ab["pcg_iter"] / (ms_iter * 1e-3) / 1e9,
                        "solve_ms_last": st["ms_solve"], "assembly_ms_last": st["ms_assembly"], "fp32_modes": ms_f32},
-    }
+    })
     if cold is not None:
         out["value_cold_first_look"] = cold
     if streaming is not None:

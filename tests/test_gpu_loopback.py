@@ -273,7 +273,7 @@ def test_bench_force_dist_rehearsal(config, cells, extra):
     env = dict(os.environ, MASTER_ADDR="127.0.0.1", MASTER_PORT=str(29600 + config), RANK="0", LOCAL_RANK="0",
                WORLD_SIZE="1")
     cmd = [sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--config", str(config), "--force-dist",
-           "--steps", "2", "--warmup", "1", "--cells", *cells, "--cpu-cells", "0", "--no-e2e", "--no-streaming",
+           "--steps", "2", "--warmup", "1", "--cells", *cells, "--full", "--cpu-cells", "0", "--no-e2e", "--no-streaming",
            "--large-cells", "0", *extra]
     p = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=600)
     assert p.returncode == 0, p.stderr[-2000:]

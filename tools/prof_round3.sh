@@ -6,9 +6,9 @@
 set -e
 cd /tmp && export TMPDIR=/tmp
 set -uo pipefail; R=${GRAFT_REPO_ROOT:-$(cd "$(dirname "$0")/.." && pwd)}; TAG=${1:-r03_c}; O=$R/gpurun_out/$TAG; mkdir -p $O; cd $R
-python bench.py > $O/bench.json 2> $O/bench.log
+python bench.py --full > $O/bench.json 2> $O/bench.log
 python tools/bench_line.py $TAG < $O/bench.json
-rocprofv3 --kernel-trace --stats -d $O/stats -o b --output-format csv -- python3 bench.py --cpu-cells 0 --no-e2e --no-streaming --large-cells 0 > $O/bench_profiled.json 2> $O/bench_profiled.log
+rocprofv3 --kernel-trace --stats -d $O/stats -o b --output-format csv -- python3 bench.py --full --cpu-cells 0 --no-e2e --no-streaming --large-cells 0 > $O/bench_profiled.json 2> $O/bench_profiled.log
 cp $(find $O/stats -name "*kernel_stats.csv" | head -1) $O/bench_kernel_stats.csv
 head -12 $O/bench_kernel_stats.csv | cut -c1-200
 rm -rf $O/stats
