@@ -341,6 +341,22 @@ int pl_energy(pl_handle h, const double *u, double *energy);
  * (schur_complement.py:75-147).  S is [6*nb x 6*nb] row-major. */
 int pl_schur(pl_handle h, const int32_t *boundary_nodes, int32_t nb, double rtol, int32_t max_iter, double *S);
 
+/* The same condensation, exact and batched, without a handle: n_inst small lattices of ONE topology (a unit cell at
+ * several radius sets - the exact DDM mode, Schur datasets), each condensed by a dense Cholesky of K_II in one workgroup
+ * of a single launch.  Material, pen_coef and device come from o (stamped by pl_default_opts; the solver fields are
+ * ignored).  beam_conn and boundary_nodes are shared by every instance; boundary_nodes gives the row order of S (6 dofs
+ * per node, as pl_schur), every other node is interior.  Per instance: node_xyz[3 n_nodes], beam_radius[n_beams],
+ * seg_len / seg_nsub[3 n_beams] (pl_mesh_t), S[6nb][6nb] row-major, exactly symmetric, and info: 0 = ok, k > 0 = pivot k
+ * of the Cholesky factor of K_II not positive (a mechanism, a floating interior node), -1 = a non-positive radius or
+ * segment count; S of a failed instance is NaN, the others are unaffected.  Supported: nb <= 32 boundary nodes,
+ * n_nodes - nb <= 16 interior nodes, n_beams <= 512 (PL_ERR_ARG beyond). */
+int pl_schur_cells(const pl_opts_t *o, int32_t n_inst, int32_t n_nodes, int32_t n_beams,
+                   const int32_t *beam_conn /*[2*n_beams], shared*/, int32_t nb,
+                   const int32_t *boundary_nodes /*[nb], shared: the row order of S*/,
+                   const double *node_xyz /*[n_inst][3*n_nodes]*/, const double *beam_radius /*[n_inst][n_beams]*/,
+                   const double *seg_len /*[n_inst][3*n_beams]*/, const int32_t *seg_nsub /*[n_inst][3*n_beams]*/,
+                   double *S /*[n_inst][6nb][6nb]*/, int32_t *info /*[n_inst]*/);
+
 /* Debug / test access to the condensed per-strut records: rec[8*B] = (a, c, e1, e2, e3, dx, dy, dz). */
 int pl_get_records(pl_handle h, double *rec);
 

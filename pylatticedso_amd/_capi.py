@@ -22,7 +22,7 @@ EXPORTS = ["pl_default_opts", "pl_opts_size", "pl_stats_size", "pl_abi_version",
            "pl_ddm_set_preconditioner", "pl_ddm_set_geometry", "pl_ddm_update_matrices", "pl_destroy", "pl_set_bc", "pl_set_periodic",
            "pl_update_radii", "pl_set_multiplicity", "pl_update_segments", "pl_assemble", "pl_assemble_bsr", "pl_get_bsr", "pl_spmv",
            "pl_spmv_free", "pl_spmv_bsr", "pl_solve", "pl_reactions", "pl_sens", "pl_energy", "pl_node_mod", "pl_schur",
-           "pl_get_records", "pl_time_kernel", "pl_algorithmic_bytes", "pl_forget_history", "pl_debug_spd_solve", "pl_dist_unique_id_bytes",
+           "pl_schur_cells", "pl_get_records", "pl_time_kernel", "pl_algorithmic_bytes", "pl_forget_history", "pl_debug_spd_solve", "pl_dist_unique_id_bytes",
            "pl_dist_unique_id", "pl_dist_loopback_id", "pl_dist_abort", "pl_dist_init", "pl_dist_set_peers", "pl_generate_lattice", "pl_lattice_fetch",
            "pl_lattice_free", "pl_penalize", "pl_boundary_index", "pl_boundary_index_rows"]
 
@@ -90,7 +90,8 @@ def load_library(path: str | None = None):
            "pl_assemble_bsr": [V, I32, V, V], "pl_get_bsr": [V, V, V, V], "pl_spmv": [V, V, V],
            "pl_spmv_free": [V, V, V], "pl_spmv_bsr": [V, V, V], "pl_solve": [V, D, I32, V, V],
            "pl_reactions": [V, V, V], "pl_sens": [V, V, V, V], "pl_energy": [V, V, V], "pl_node_mod": [V, V, V],
-           "pl_schur": [V, V, I32, D, I32, V], "pl_get_records": [V, V], "pl_time_kernel": [V, I32, I32, V],
+           "pl_schur": [V, V, I32, D, I32, V], "pl_schur_cells": [V, I32, I32, I32, V, I32, V, V, V, V, V, V, V],
+           "pl_get_records": [V, V], "pl_time_kernel": [V, I32, I32, V],
            "pl_algorithmic_bytes": [V, V], "pl_forget_history": [V], "pl_debug_spd_solve": [I32, I32, V, V, V, V, I32], "pl_dist_unique_id_bytes": [], "pl_dist_unique_id": [V], "pl_dist_loopback_id": [V], "pl_dist_abort": [V],
            "pl_dist_init": [V, I32, I32, V, V, V, I32, I32], "pl_dist_set_peers": [V, V],
            "pl_generate_lattice": [I64, V, V, V, I32, I32, V, V, V, V], "pl_lattice_fetch": [V] * 12,
@@ -154,6 +155,69 @@ def debug_spd_solve(A, b, device=0, fp32_factor=False):
     q = C.c_double()
     _check(lib, lib.pl_debug_spd_solve(device, len(b), _ptr(A), _ptr(b), _ptr(x), C.byref(q), int(bool(fp32_factor))))
     return x, q.value
+
+
+# what one workgroup of pl_schur_cells holds (include/pylattice_hip.h): larger cells go through pl_schur
+SCHUR_CELLS_MAX_BOUNDARY, SCHUR_CELLS_MAX_INTERIOR, SCHUR_CELLS_MAX_BEAMS = 32, 16, 512
+
+
+def schur_cells_fits(n_nodes, n_beams, n_boundary):
+    """Whether pl_schur_cells condenses a cell of this size."""
+    return (0 < n_boundary <= SCHUR_CELLS_MAX_BOUNDARY and n_nodes - n_boundary <= SCHUR_CELLS_MAX_INTERIOR
+            and 0 < n_beams <= SCHUR_CELLS_MAX_BEAMS)
+
+
+def _per_instance(name, a, tail, n_inst):
+    """a of shape tail (shared by every instance) or (n_inst,) + tail, as a contiguous (n_inst,) + tail array."""
+    if a.shape == tail:
+        a = np.broadcast_to(a, (n_inst,) + tail)
+    elif a.shape != (n_inst,) + tail:
+        raise ValueError(f"{name} must have shape {tail} or {(n_inst,) + tail}, got {a.shape}")
+    return np.ascontiguousarray(a)
+
+
+def schur_cells(node_xyz, beam_conn, boundary_nodes, beam_radius, seg_len, seg_nsub, young, poisson, kappa=0.9,
+                pen_coef=1.5, device=0, n_inst=None):
+    """Exact Schur complements of n_inst instances of one cell topology in one launch (pl_schur_cells).
+
+    beam_conn (B, 2) and boundary_nodes (n_b,) are shared; node_xyz (N, 3), beam_radius (B,), seg_len (B, 3) and
+    seg_nsub (B, 3) are either shared or given per instance with a leading n_inst axis.  Returns (S (n_inst, 6 n_b, 6 n_b),
+    info (n_inst,) int32): info 0 = ok, k > 0 = Cholesky pivot k of K_II not positive, -1 = bad radius / segment data
+    (S of such an instance is NaN)."""
+    conn = np.asarray(beam_conn)
+    bn = np.asarray(boundary_nodes)
+    if conn.ndim != 2 or conn.shape[1] != 2 or not np.issubdtype(conn.dtype, np.integer):
+        raise ValueError("beam_conn must be an integer (B, 2) array")
+    if bn.ndim != 1 or not np.issubdtype(bn.dtype, np.integer):
+        raise ValueError("boundary_nodes must be a 1-D integer array")
+    xyz, rad = np.asarray(node_xyz, dtype=np.float64), np.asarray(beam_radius, dtype=np.float64)
+    slen, nsub = np.asarray(seg_len, dtype=np.float64), np.asarray(seg_nsub)
+    if not np.issubdtype(nsub.dtype, np.integer):
+        raise ValueError("seg_nsub must be an integer array")
+    if xyz.ndim not in (2, 3) or xyz.shape[-1] != 3:
+        raise ValueError("node_xyz must be (N, 3) or (n_inst, N, 3)")
+    B, N = len(conn), xyz.shape[-2]
+    lead = [a.shape[0] for a, nd in ((xyz, 3), (rad, 2), (slen, 3), (nsub, 3)) if a.ndim == nd]
+    if n_inst is None:
+        n_inst = max(lead) if lead else 1
+    n_inst = int(n_inst)
+    if n_inst < 1:
+        raise ValueError("n_inst must be >= 1")
+    xyz = _per_instance("node_xyz", xyz, (N, 3), n_inst)
+    rad = _per_instance("beam_radius", rad, (B,), n_inst)
+    slen = _per_instance("seg_len", slen, (B, 3), n_inst)
+    nsub = _per_instance("seg_nsub", nsub.astype(np.int32, copy=False), (B, 3), n_inst)
+    conn = np.ascontiguousarray(conn, dtype=np.int32)
+    bn = np.ascontiguousarray(bn, dtype=np.int32)
+    lib = load_library()
+    opts = default_opts(lib)
+    opts.young, opts.poisson, opts.kappa, opts.pen_coef, opts.device = young, poisson, kappa, pen_coef, device
+    m = 6 * len(bn)
+    S = np.empty((n_inst, m, m), np.float64)
+    info = np.empty(n_inst, np.int32)
+    _check(lib, lib.pl_schur_cells(C.byref(opts), n_inst, N, B, _ptr(conn), len(bn), _ptr(bn), _ptr(xyz), _ptr(rad),
+                                   _ptr(slen), _ptr(nsub), _ptr(S), _ptr(info)))
+    return S, info
 
 
 class PlLatticeInfo(C.Structure):

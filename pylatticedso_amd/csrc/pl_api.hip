@@ -1,6 +1,7 @@
 // libpylattice_hip.so - the C ABI declared in include/pylattice_hip.h (gfx950 / MI355X).  One translation unit:
 // pl_context.h (handle state) <- pl_ops.h (operator launches) <- pl_assembly.h <- pl_solver.h <- this file.
 #include "pl_solver.h"
+#include "pl_condense.h"
 
 
 // ==========================================================================================================
@@ -1574,6 +1575,107 @@ int pl_schur(pl_handle h, const int32_t *boundary_nodes, int32_t nb, double rtol
     for (int i = 0; i < m; ++i) S[(size_t)i * m + j] = R[6 * (size_t)boundary_nodes[i / 6] + (i % 6)];
     ubar[dofj] = 0.0;
   }
+  return PL_OK;
+}
+
+int pl_schur_cells(const pl_opts_t *o, int32_t n_inst, int32_t n_nodes, int32_t n_beams, const int32_t *beam_conn,
+                   int32_t nb, const int32_t *boundary_nodes, const double *node_xyz, const double *beam_radius,
+                   const double *seg_len, const int32_t *seg_nsub, double *S, int32_t *info) {
+  if (!o || !beam_conn || !boundary_nodes || !node_xyz || !beam_radius || !seg_len || !seg_nsub || !S || !info)
+    return fail(PL_ERR_ARG, "pl_schur_cells: null argument");
+  if (int rc_abi = check_opts_abi(o, "pl_schur_cells")) return rc_abi;
+  if (n_inst <= 0 || n_nodes <= 0 || n_beams <= 0 || nb <= 0 || nb > n_nodes)
+    return fail(PL_ERR_ARG, "pl_schur_cells: bad sizes");
+  const int32_t ni = n_nodes - nb;
+  if (nb > pl::kCondMaxBoundary || ni > pl::kCondMaxInterior || n_beams > pl::kCondMaxBeams)
+    return fail(PL_ERR_ARG, "pl_schur_cells: cell too large for the batched condensation (" + std::to_string(nb) +
+                                " boundary nodes, " + std::to_string(ni) + " interior nodes, " + std::to_string(n_beams) +
+                                " struts; at most " + std::to_string(pl::kCondMaxBoundary) + " / " +
+                                std::to_string(pl::kCondMaxInterior) + " / " + std::to_string(pl::kCondMaxBeams) + ")");
+  if (!(o->young > 0.0) || !(o->poisson > -1.0) || !(o->kappa > 0.0) || !(o->pen_coef > 0.0))
+    return fail(PL_ERR_ARG, "pl_schur_cells: bad material");
+  StageTimer stage("pl_schur_cells");
+  // slot of every node: its position in boundary_nodes (the row order of S), or -1 - its rank among the other nodes
+  std::vector<int32_t> slot((size_t)n_nodes, INT32_MIN);
+  for (int i = 0; i < nb; ++i) {
+    const int32_t v = boundary_nodes[i];
+    if (v < 0 || v >= n_nodes) return fail(PL_ERR_ARG, "pl_schur_cells: boundary node out of range");
+    if (slot[v] != INT32_MIN) return fail(PL_ERR_ARG, "pl_schur_cells: boundary node listed twice");
+    slot[v] = i;
+  }
+  for (int32_t v = 0, k = 0; v < n_nodes; ++v)
+    if (slot[v] == INT32_MIN) slot[v] = -1 - k++;
+  std::vector<int32_t> end_slot(2 * (size_t)n_beams);
+  for (int64_t h = 0; h < 2 * (int64_t)n_beams; ++h) {
+    const int32_t v = beam_conn[h];
+    if (v < 0 || v >= n_nodes) return fail(PL_ERR_ARG, "pl_schur_cells: strut end out of range");
+    if ((h & 1) && v == beam_conn[h - 1]) return fail(PL_ERR_ARG, "pl_schur_cells: strut with both ends on one node");
+    end_slot[h] = slot[v];
+  }
+  int ndev = 0;
+  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0)
+    return fail(PL_ERR_NODEVICE, "pl_schur_cells: no HIP device visible (libpylattice_hip has no CPU fallback)");
+  if (o->device < 0 || o->device >= ndev) return fail(PL_ERR_ARG, "pl_schur_cells: bad device ordinal");
+  // one panel when K_II and the whole of V fit 64 KiB (two workgroups per CU); otherwise the widest pair of panels that
+  // fits 64 KiB, then 150 KiB (the largest supported cell: 96 x 96 factor, 32 KiB of records, panels of 5 nodes)
+  int pw = nb, panels = 1;
+  size_t lds = pl::condense_lds_doubles(n_beams, ni, nb, 1) * sizeof(double);
+  if (lds > 64 * 1024) {
+    pw = 0;
+    for (size_t budget : {(size_t)64 * 1024, (size_t)150 * 1024}) {
+      for (int w = nb - 1; w >= 1 && pw == 0; --w)
+        if (pl::condense_lds_doubles(n_beams, ni, w, 2) * sizeof(double) <= budget) pw = w;
+      if (pw) break;
+    }
+    if (pw == 0) return fail(PL_ERR_ARG, "pl_schur_cells: the cell does not fit the LDS");
+    panels = (nb + pw - 1) / pw;
+    lds = pl::condense_lds_doubles(n_beams, ni, pw, panels) * sizeof(double);
+  }
+  stage.mark("validate");
+  PL_HIP(hipSetDevice(o->device));
+  const size_t m = 6 * (size_t)nb, ninst = (size_t)n_inst;
+  DevBuf<int32_t> dconn, dslot, dnsub, dinfo;
+  DevBuf<double> dxyz, drad, dlen, dS;
+  PL_HIP(dconn.alloc(2 * (size_t)n_beams));
+  PL_HIP(dslot.alloc(2 * (size_t)n_beams));
+  PL_HIP(dxyz.alloc(ninst * 3 * n_nodes));
+  PL_HIP(drad.alloc(ninst * n_beams));
+  PL_HIP(dlen.alloc(ninst * 3 * n_beams));
+  PL_HIP(dnsub.alloc(ninst * 3 * n_beams));
+  PL_HIP(dS.alloc(ninst * m * m));
+  PL_HIP(dinfo.alloc(ninst));
+  PL_HIP(hipMemcpy(dconn.p, beam_conn, dconn.n * sizeof(int32_t), hipMemcpyHostToDevice));
+  PL_HIP(hipMemcpy(dslot.p, end_slot.data(), dslot.n * sizeof(int32_t), hipMemcpyHostToDevice));
+  PL_HIP(hipMemcpy(dxyz.p, node_xyz, dxyz.n * sizeof(double), hipMemcpyHostToDevice));
+  PL_HIP(hipMemcpy(drad.p, beam_radius, drad.n * sizeof(double), hipMemcpyHostToDevice));
+  PL_HIP(hipMemcpy(dlen.p, seg_len, dlen.n * sizeof(double), hipMemcpyHostToDevice));
+  PL_HIP(hipMemcpy(dnsub.p, seg_nsub, dnsub.n * sizeof(int32_t), hipMemcpyHostToDevice));
+  stage.mark("upload");
+  pl::CondenseArgs a;
+  a.n_nodes = n_nodes;
+  a.n_beams = n_beams;
+  a.nb = nb;
+  a.ni = ni;
+  a.pw = pw;
+  a.conn = dconn.p;
+  a.end_slot = dslot.p;
+  a.xyz = dxyz.p;
+  a.radius = drad.p;
+  a.seg_len = dlen.p;
+  a.seg_nsub = dnsub.p;
+  a.m = {o->young, o->young / (2.0 * (1.0 + o->poisson)), o->kappa, o->pen_coef};
+  a.S = dS.p;
+  a.info = dinfo.p;
+  if (lds > 64 * 1024)
+    PL_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&pl::k_schur_cells),
+                               hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+  hipLaunchKernelGGL(pl::k_schur_cells, dim3((unsigned)n_inst), dim3(pl::kCondBlock), lds, nullptr, a);
+  PL_HIP(hipGetLastError());
+  PL_HIP(hipDeviceSynchronize());
+  stage.mark("kernel");
+  PL_HIP(hipMemcpy(S, dS.p, dS.n * sizeof(double), hipMemcpyDeviceToHost));
+  PL_HIP(hipMemcpy(info, dinfo.p, ninst * sizeof(int32_t), hipMemcpyDeviceToHost));
+  stage.mark("download");
   return PL_OK;
 }
 

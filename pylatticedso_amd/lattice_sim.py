@@ -647,50 +647,103 @@ class LatticeSim(LatticeViews):
     @timing.timeit
     def calculate_schur_complement_cells(self):
         """Exact Schur complement of one representative cell per (geometry, radii) group (lattice_sim.py:846-919),
-        condensed on the device (pl_schur) from that cell's own struts with their penalised segments."""
-        from ._capi import HipLattice
+        condensed from that cell's own struts with their penalised segments.  The representatives - and, with gradients
+        on, their central-difference variants - of one cell topology (connectivity + boundary order) go to the device
+        in ONE batched condensation (pl_schur_cells); a topology beyond that kernel's size takes pl_schur per cell."""
+        from . import _capi
         if self.type_schur_complement_computation != "exact":
             return self._surrogate_schur_complement_cells()
         lat, pen = self.lattice, self.penalized
         cb = self.cell_boundary_nodes()
         par = self._cell_parameter_radii()       # the reference groups by Cell.radii, which ignores the preset gradient
         keys = [tuple(np.round(par[c], 8)) for c in range(lat.n_cells)]
-        groups, mats, grads, idx = {}, [], [], np.zeros(lat.n_cells, np.int32)
+        groups, reps, idx = {}, [], np.zeros(lat.n_cells, np.int32)
         for c, k in enumerate(keys):
             if k not in groups:
-                beams = lat.cell_beam_idx[lat.cell_beam_ptr[c]:lat.cell_beam_ptr[c + 1]]
-                nodes = np.unique(lat.beam_conn[beams])
-                remap = np.full(lat.n_nodes, -1, np.int64)
-                remap[nodes] = np.arange(len(nodes))
-                with HipLattice(lat.node_xyz[nodes], remap[lat.beam_conn[beams]], lat.beam_radius[beams],
-                                pen.seg_len[beams], pen.seg_nsub[beams], self.young_modulus, self.poisson_ratio,
-                                pen_coef=self.penalization_coefficient, reorder=0,
-                                **({"precond": 5} if 6 * len(nodes) <= DDM_DENSE_MAX else {})) as dev:   # (see cell_device)
-                    dev.assemble()
-                    mats.append(dev.schur(remap[cb[c]], rtol=1e-13, max_iter=200000))
-                    if self.enable_gradient_computing:
-                        # _compute_schur_gradients (lattice_sim.py:1020-1054): central differences in every radius
-                        # parameter of the cell, h = max(1e-8, 1e-6 max(1, |r|)), radii changed at FIXED penalised
-                        # segment lengths (Cell.change_beam_radius, cell.py:896-917)
-                        gl = []
-                        for j, rj in enumerate(par[c]):
-                            h = max(1e-8, 1e-6 * max(1.0, abs(rj)))
-                            rp, rm = rj + h, max(1e-12, rj - h)
-                            S_pm = []
-                            for rv in (rp, rm):
-                                rad = lat.beam_radius[beams].copy()
-                                sel = lat.beam_type[beams] == j
-                                rad[sel] = rv * self._cell_gfac[c]
-                                dev.update_radii(rad)
-                                dev.assemble()
-                                S_pm.append(dev.schur(remap[cb[c]], rtol=1e-13, max_iter=200000))
-                            gl.append((S_pm[0] - S_pm[1]) / (rp - rm))
-                        grads.append(gl)
-                groups[k] = len(mats) - 1
+                groups[k] = len(reps)
+                reps.append(c)
             idx[c] = groups[k]
+        mats, grads = [None] * len(reps), [None] * len(reps)
+        by_topology = {}
+        for q, c in enumerate(reps):
+            beams = lat.cell_beam_idx[lat.cell_beam_ptr[c]:lat.cell_beam_ptr[c + 1]]
+            nodes = np.unique(lat.beam_conn[beams])
+            remap = np.full(lat.n_nodes, -1, np.int64)
+            remap[nodes] = np.arange(len(nodes))
+            conn, order = remap[lat.beam_conn[beams]], remap[cb[c]]
+            key = (len(nodes), conn.tobytes(), order.tobytes())
+            by_topology.setdefault(key, []).append((q, c, beams, nodes, conn, order))
+        for (n_nodes, _, _), members in by_topology.items():
+            _, _, beams0, _, conn, order = members[0]
+            if not _capi.schur_cells_fits(n_nodes, len(beams0), len(order)):
+                for q, c, beams, nodes, conn, order in members:
+                    mats[q], grads[q] = self._schur_cell_by_columns(c, beams, nodes, conn, order, par[c])
+                continue
+            # instances: every representative, then (gradients on) its +h / -h variants per radius parameter - the
+            # reference's _compute_schur_gradients (lattice_sim.py:1020-1054): h = max(1e-8, 1e-6 max(1, |r|)), radii
+            # changed at FIXED penalised segment lengths (Cell.change_beam_radius, cell.py:896-917)
+            xyz, rad, slen, nsub, steps = [], [], [], [], []
+            for q, c, beams, nodes, _, _ in members:
+                base = lat.beam_radius[beams]
+                variants = [base]
+                if self.enable_gradient_computing:
+                    for j, rj in enumerate(par[c]):
+                        h = max(1e-8, 1e-6 * max(1.0, abs(rj)))
+                        rp, rm = rj + h, max(1e-12, rj - h)
+                        steps.append(rp - rm)
+                        sel = lat.beam_type[beams] == j
+                        for rv in (rp, rm):
+                            r = base.copy()
+                            r[sel] = rv * self._cell_gfac[c]
+                            variants.append(r)
+                for r in variants:
+                    xyz.append(lat.node_xyz[nodes])
+                    rad.append(r)
+                    slen.append(pen.seg_len[beams])
+                    nsub.append(pen.seg_nsub[beams])
+            S, info = _capi.schur_cells(np.stack(xyz), conn, order, np.stack(rad), np.stack(slen), np.stack(nsub),
+                                        self.young_modulus, self.poisson_ratio, pen_coef=self.penalization_coefficient)
+            bad = np.flatnonzero(info != 0)
+            if len(bad):
+                raise RuntimeError(f"exact Schur complement: cell {members[bad[0] // len(variants)][1]} cannot be condensed "
+                                   f"(pl_schur_cells info {int(info[bad[0]])}: a mechanism or bad strut data)")
+            per = len(variants)                   # instances per representative (the same for every member)
+            for i, (q, c, *_rest) in enumerate(members):
+                mats[q] = S[i * per]
+                if self.enable_gradient_computing:
+                    st = steps[i * len(par[c]):(i + 1) * len(par[c])]
+                    grads[q] = [(S[i * per + 1 + 2 * j] - S[i * per + 2 + 2 * j]) / st[j] for j in range(len(par[c]))]
         self.schur_gradients = grads if self.enable_gradient_computing else None
         self._schur_gradients_array = None
         self.set_schur_complements(np.stack(mats), idx)
+
+    def _schur_cell_by_columns(self, c, beams, nodes, conn, order, radii):
+        """Exact Schur complement (and, with gradients on, its central differences) of cell c by pl_schur: one PCG solve
+        per boundary dof on a handle of the cell's struts - for cells beyond the batched kernel's size."""
+        from ._capi import HipLattice
+        lat, pen = self.lattice, self.penalized
+        with HipLattice(lat.node_xyz[nodes], conn, lat.beam_radius[beams],
+                        pen.seg_len[beams], pen.seg_nsub[beams], self.young_modulus, self.poisson_ratio,
+                        pen_coef=self.penalization_coefficient, reorder=0,
+                        **({"precond": 5} if 6 * len(nodes) <= DDM_DENSE_MAX else {})) as dev:   # (see cell_device)
+            dev.assemble()
+            S = dev.schur(order, rtol=1e-13, max_iter=200000)
+            if not self.enable_gradient_computing:
+                return S, None
+            gl = []
+            for j, rj in enumerate(radii):
+                h = max(1e-8, 1e-6 * max(1.0, abs(rj)))
+                rp, rm = rj + h, max(1e-12, rj - h)
+                S_pm = []
+                for rv in (rp, rm):
+                    rad = lat.beam_radius[beams].copy()
+                    sel = lat.beam_type[beams] == j
+                    rad[sel] = rv * self._cell_gfac[c]
+                    dev.update_radii(rad)
+                    dev.assemble()
+                    S_pm.append(dev.schur(order, rtol=1e-13, max_iter=200000))
+                gl.append((S_pm[0] - S_pm[1]) / (rp - rm))
+            return S, gl
 
     def _surrogate_schur_complement_cells(self):
         """Surrogate branch of lattice_sim.py:846-919: one batched evaluation S(r) = B alpha(r) for the distinct

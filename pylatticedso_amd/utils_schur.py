@@ -56,7 +56,9 @@ def node_order_all_cells(lattice, tol=1e-9):
 
 
 def get_schur_complement(lattice, cell_index=None, rtol=1e-13, max_iter=200000):
-    """S = K_BB - K_BI K_II^-1 K_IB of one cell on its boundary nodes, (6 n_b, 6 n_b), node order as the reference."""
+    """S = K_BB - K_BI K_II^-1 K_IB of one cell on its boundary nodes, (6 n_b, 6 n_b), node order as the reference.
+    Exact dense condensation on the device (pl_schur_cells) when the cell fits that kernel; otherwise pl_schur, column by
+    column with the device PCG (rtol / max_iter apply to that path only)."""
     if cell_index is None and lattice.get_number_cells() > 1:
         raise ValueError("The lattice must contain only one cell for Schur complement calculation or specify a "
                          "cell_index.")
@@ -65,20 +67,45 @@ def get_schur_complement(lattice, cell_index=None, rtol=1e-13, max_iter=200000):
         # cell.points_cell / cell.beams_cell - struts shared with a neighbour included, with the radius and the
         # penalised end segments they have in the whole lattice); condensation on the cell's boundary nodes in
         # Cell.define_node_order_to_simulate order (utils_schur.py:36-41)
+        S = _exact_condensation(*_cell_arrays(lattice, int(cell_index)), lattice)
+        if S is not None:
+            return S
         dev, order = cell_device(lattice, int(cell_index))
         with dev:
             dev.assemble()
             return dev.schur(order, rtol=rtol, max_iter=max_iter)
     order = node_order_to_simulate(lattice, 0)
-    dev = lattice.device_model()
+    dev = lattice.device_model()          # (the lattice's own handle: callers manage it, as before)
+    if _batch_applies(lattice):
+        lat, pen = lattice.lattice, lattice.penalized
+        S = _exact_condensation(lat.node_xyz, lat.beam_conn, lat.beam_radius, pen.seg_len, pen.seg_nsub, order, lattice,
+                                pen_coef=lattice.penalization_coefficient)
+        if S is not None:
+            return S
     dev.assemble()
     return dev.schur(order, rtol=rtol, max_iter=max_iter)
 
 
-def cell_device(lattice, cell_index):
-    """(HipLattice of the sub-lattice made of one cell's struts and nodes, boundary nodes of that cell in the
-    reference's simulation order, numbered inside the sub-lattice)."""
-    from ._capi import HipLattice
+def _batch_applies(lattice):
+    """The batched condensation models plain struts: not the reference_compat rows nor strut multiplicities."""
+    return not getattr(lattice, "_compat_rows", False) and getattr(lattice, "beam_mult", None) is None
+
+
+def _exact_condensation(node_xyz, beam_conn, beam_radius, seg_len, seg_nsub, order, lattice, pen_coef=1.5):
+    """S of one cell by pl_schur_cells, or None when the cell is beyond that kernel's size."""
+    from . import _capi
+    if not _capi.schur_cells_fits(len(node_xyz), len(beam_conn), len(order)):
+        return None
+    S, info = _capi.schur_cells(node_xyz, beam_conn, order, beam_radius, seg_len, seg_nsub, lattice.young_modulus,
+                                lattice.poisson_ratio, pen_coef=pen_coef)
+    if info[0] != 0:
+        raise RuntimeError(f"Schur complement: the cell cannot be condensed (pl_schur_cells info {int(info[0])}: a "
+                           "mechanism or bad strut data)")
+    return S[0]
+
+
+def _cell_arrays(lattice, cell_index):
+    """The sub-lattice of cell_device as arrays: (node_xyz, beam_conn, beam_radius, seg_len, seg_nsub, boundary order)."""
     lat, pen = lattice.lattice, lattice.penalized
     if not 0 <= cell_index < lat.n_cells:
         raise IndexError("cell_index out of range")
@@ -88,12 +115,60 @@ def cell_device(lattice, cell_index):
                                       lat.beam_conn[struts].ravel()]))
     local = np.full(lat.n_nodes, -1, np.int64)
     local[nodes] = np.arange(len(nodes))
+    return (lat.node_xyz[nodes], local[lat.beam_conn[struts]], lat.beam_radius[struts], pen.seg_len[struts],
+            pen.seg_nsub[struts], local[node_order_to_simulate(lattice, cell_index)])
+
+
+def get_schur_complements_batch(lattice, radii_batch):
+    """Exact Schur complements of a one-cell lattice at every radius set of ``radii_batch`` ((n, n_geometries)), in one
+    device launch (pl_schur_cells): (n, 6 n_b, 6 n_b).  For each set the struts get the radii and the penalised segments
+    that ``reset_cell_with_new_radii`` would give them (the joint-penalisation lengths depend on the neighbours' radii);
+    the topology is the lattice's own.  The lattice itself is left unchanged."""
+    from dataclasses import replace
+    from . import _capi
+    from . import lattice_arrays as LA
+    if lattice.get_number_cells() != 1:
+        raise ValueError("get_schur_complements_batch needs a lattice of one cell")
+    radii_batch = np.asarray(radii_batch, dtype=float)
+    if radii_batch.ndim == 1:
+        radii_batch = radii_batch[:, None]
+    if radii_batch.ndim != 2 or radii_batch.shape[1] != len(lattice.radii):
+        raise ValueError(f"radius sets of {len(lattice.radii)} values expected, got shape {radii_batch.shape}")
+    lat = lattice.lattice
+    order = node_order_to_simulate(lattice, 0)
+    gfac = float(lattice._cell_gfac[0])
+    if not (_batch_applies(lattice) and _capi.schur_cells_fits(lat.n_nodes, lat.n_beams, len(order))):
+        raise NotImplementedError("get_schur_complements_batch: the cell is beyond the batched condensation "
+                                  "(use reset_cell_with_new_radii + get_schur_complement)")
+    rad = radii_batch[:, lat.beam_type] * gfac                   # (LA.generate: cell radii times the gradient factor)
+    slen, nsub = [], []
+    for r in rad:
+        if lattice.is_penalized:
+            lr = replace(lat, beam_radius=r)
+            pen = LA.penalize(lr, LA.compute_lzone(lr, bool(lattice.enable_periodicity)))
+        else:
+            pen = lattice.penalized
+        slen.append(pen.seg_len)
+        nsub.append(pen.seg_nsub)
+    S, info = _capi.schur_cells(lat.node_xyz, lat.beam_conn, order, rad, np.stack(slen), np.stack(nsub),
+                                lattice.young_modulus, lattice.poisson_ratio, pen_coef=lattice.penalization_coefficient)
+    bad = np.flatnonzero(info != 0)
+    if len(bad):
+        raise RuntimeError(f"get_schur_complements_batch: radius set {bad[0]} ({radii_batch[bad[0]].tolist()}) cannot be "
+                           f"condensed (pl_schur_cells info {int(info[bad[0]])})")
+    return S
+
+
+def cell_device(lattice, cell_index):
+    """(HipLattice of the sub-lattice made of one cell's struts and nodes, boundary nodes of that cell in the
+    reference's simulation order, numbered inside the sub-lattice)."""
+    from ._capi import HipLattice
+    xyz, conn, rad, seg_len, seg_nsub, order = _cell_arrays(lattice, cell_index)
     # one cell: a few hundred dofs - the dense factor of P K P as the preconditioner (precond = 5), so that each of the 6 n_b
     # condensation solves of pl_schur is one or two PCG steps instead of hundreds of Jacobi iterations
-    dev = HipLattice(lat.node_xyz[nodes], local[lat.beam_conn[struts]], lat.beam_radius[struts], pen.seg_len[struts],
-                     pen.seg_nsub[struts], lattice.young_modulus, lattice.poisson_ratio,
-                     **({"precond": 5} if 6 * len(nodes) <= 16384 else {}))
-    return dev, local[node_order_to_simulate(lattice, cell_index)]
+    dev = HipLattice(xyz, conn, rad, seg_len, seg_nsub, lattice.young_modulus, lattice.poisson_ratio,
+                     **({"precond": 5} if 6 * len(xyz) <= 16384 else {}))
+    return dev, order
 
 
 def define_path_schur_complement(lattice_object):
