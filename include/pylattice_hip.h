@@ -357,6 +357,26 @@ int pl_schur_cells(const pl_opts_t *o, int32_t n_inst, int32_t n_nodes, int32_t 
                    const double *seg_len /*[n_inst][3*n_beams]*/, const int32_t *seg_nsub /*[n_inst][3*n_beams]*/,
                    double *S /*[n_inst][6nb][6nb]*/, int32_t *info /*[n_inst]*/);
 
+/* The backward half of pl_schur_cells, same conventions (opts, shared beam_conn / boundary_nodes, per-instance geometry,
+ * info codes, size limits): from the boundary values u_b of every instance the displacement of the whole cell -
+ * u_full repeats u_b on the boundary nodes and holds -K_II^-1 K_IB u_b on the others (no load and no Dirichlet dof on
+ * interior nodes, as the DDM assumes) - the same for an adjoint field lam_b (NULL: lam = u), and per strut
+ * sens[b] = lam_e^T (dK_e/dr_b) u_e on the recovered fields (the quantity of pl_sens).  Summed over the struts of one
+ * radius parameter this is lam_b^T (dS/dr) u_b exactly, at fixed segment geometry.  u_b / lam_b rows follow
+ * boundary_nodes; u_full / lam_full are in the cell's own node order.  Any of u_full, lam_full, sens may be NULL (not
+ * all).  A cell without interior nodes is legal.  A failed instance (info != 0) gets NaN in its own outputs only. */
+int pl_cells_recover(const pl_opts_t *o, int32_t n_inst, int32_t n_nodes, int32_t n_beams,
+                     const int32_t *beam_conn /*[2*n_beams], shared*/, int32_t nb,
+                     const int32_t *boundary_nodes /*[nb], shared*/,
+                     const double *node_xyz /*[n_inst][3*n_nodes]*/, const double *beam_radius /*[n_inst][n_beams]*/,
+                     const double *seg_len /*[n_inst][3*n_beams]*/, const int32_t *seg_nsub /*[n_inst][3*n_beams]*/,
+                     const double *u_b /*[n_inst][6nb], boundary_nodes order*/,
+                     const double *lam_b /*[n_inst][6nb] or NULL: lam = u*/,
+                     double *u_full /*[n_inst][6*n_nodes], cell-local node order, or NULL*/,
+                     double *lam_full /*[n_inst][6*n_nodes] or NULL*/,
+                     double *sens /*[n_inst][n_beams]: lam_e^T (dK_e/dr_b) u_e, or NULL*/,
+                     int32_t *info /*[n_inst]*/);
+
 /* Debug / test access to the condensed per-strut records: rec[8*B] = (a, c, e1, e2, e3, dx, dy, dz). */
 int pl_get_records(pl_handle h, double *rec);
 

@@ -22,7 +22,7 @@ EXPORTS = ["pl_default_opts", "pl_opts_size", "pl_stats_size", "pl_abi_version",
            "pl_ddm_set_preconditioner", "pl_ddm_set_geometry", "pl_ddm_update_matrices", "pl_destroy", "pl_set_bc", "pl_set_periodic",
            "pl_update_radii", "pl_set_multiplicity", "pl_update_segments", "pl_assemble", "pl_assemble_bsr", "pl_get_bsr", "pl_spmv",
            "pl_spmv_free", "pl_spmv_bsr", "pl_solve", "pl_reactions", "pl_sens", "pl_energy", "pl_node_mod", "pl_schur",
-           "pl_schur_cells", "pl_get_records", "pl_time_kernel", "pl_algorithmic_bytes", "pl_forget_history", "pl_debug_spd_solve", "pl_dist_unique_id_bytes",
+           "pl_schur_cells", "pl_cells_recover", "pl_get_records", "pl_time_kernel", "pl_algorithmic_bytes", "pl_forget_history", "pl_debug_spd_solve", "pl_dist_unique_id_bytes",
            "pl_dist_unique_id", "pl_dist_loopback_id", "pl_dist_abort", "pl_dist_init", "pl_dist_set_peers", "pl_generate_lattice", "pl_lattice_fetch",
            "pl_lattice_free", "pl_penalize", "pl_boundary_index", "pl_boundary_index_rows"]
 
@@ -91,6 +91,7 @@ def load_library(path: str | None = None):
            "pl_spmv_free": [V, V, V], "pl_spmv_bsr": [V, V, V], "pl_solve": [V, D, I32, V, V],
            "pl_reactions": [V, V, V], "pl_sens": [V, V, V, V], "pl_energy": [V, V, V], "pl_node_mod": [V, V, V],
            "pl_schur": [V, V, I32, D, I32, V], "pl_schur_cells": [V, I32, I32, I32, V, I32, V, V, V, V, V, V, V],
+           "pl_cells_recover": [V, I32, I32, I32, V, I32, V, V, V, V, V, V, V, V, V, V, V],
            "pl_get_records": [V, V], "pl_time_kernel": [V, I32, I32, V],
            "pl_algorithmic_bytes": [V, V], "pl_forget_history": [V], "pl_debug_spd_solve": [I32, I32, V, V, V, V, I32], "pl_dist_unique_id_bytes": [], "pl_dist_unique_id": [V], "pl_dist_loopback_id": [V], "pl_dist_abort": [V],
            "pl_dist_init": [V, I32, I32, V, V, V, I32, I32], "pl_dist_set_peers": [V, V],
@@ -184,6 +185,22 @@ def schur_cells(node_xyz, beam_conn, boundary_nodes, beam_radius, seg_len, seg_n
     seg_nsub (B, 3) are either shared or given per instance with a leading n_inst axis.  Returns (S (n_inst, 6 n_b, 6 n_b),
     info (n_inst,) int32): info 0 = ok, k > 0 = Cholesky pivot k of K_II not positive, -1 = bad radius / segment data
     (S of such an instance is NaN)."""
+    xyz, conn, bn, rad, slen, nsub, n_inst = _cell_batch_arrays(node_xyz, beam_conn, boundary_nodes, beam_radius, seg_len,
+                                                                seg_nsub, n_inst)
+    B, N = len(conn), xyz.shape[1]
+    lib = load_library()
+    opts = default_opts(lib)
+    opts.young, opts.poisson, opts.kappa, opts.pen_coef, opts.device = young, poisson, kappa, pen_coef, device
+    m = 6 * len(bn)
+    S = np.empty((n_inst, m, m), np.float64)
+    info = np.empty(n_inst, np.int32)
+    _check(lib, lib.pl_schur_cells(C.byref(opts), n_inst, N, B, _ptr(conn), len(bn), _ptr(bn), _ptr(xyz), _ptr(rad),
+                                   _ptr(slen), _ptr(nsub), _ptr(S), _ptr(info)))
+    return S, info
+
+
+def _cell_batch_arrays(node_xyz, beam_conn, boundary_nodes, beam_radius, seg_len, seg_nsub, n_inst, extra_lead=()):
+    """The checked, broadcast arguments schur_cells and cells_recover share: (xyz, conn, bn, rad, slen, nsub, n_inst)."""
     conn = np.asarray(beam_conn)
     bn = np.asarray(boundary_nodes)
     if conn.ndim != 2 or conn.shape[1] != 2 or not np.issubdtype(conn.dtype, np.integer):
@@ -197,7 +214,7 @@ def schur_cells(node_xyz, beam_conn, boundary_nodes, beam_radius, seg_len, seg_n
     if xyz.ndim not in (2, 3) or xyz.shape[-1] != 3:
         raise ValueError("node_xyz must be (N, 3) or (n_inst, N, 3)")
     B, N = len(conn), xyz.shape[-2]
-    lead = [a.shape[0] for a, nd in ((xyz, 3), (rad, 2), (slen, 3), (nsub, 3)) if a.ndim == nd]
+    lead = [a.shape[0] for a, nd in ((xyz, 3), (rad, 2), (slen, 3), (nsub, 3)) if a.ndim == nd] + list(extra_lead)
     if n_inst is None:
         n_inst = max(lead) if lead else 1
     n_inst = int(n_inst)
@@ -209,15 +226,55 @@ def schur_cells(node_xyz, beam_conn, boundary_nodes, beam_radius, seg_len, seg_n
     nsub = _per_instance("seg_nsub", nsub.astype(np.int32, copy=False), (B, 3), n_inst)
     conn = np.ascontiguousarray(conn, dtype=np.int32)
     bn = np.ascontiguousarray(bn, dtype=np.int32)
+    return xyz, conn, bn, rad, slen, nsub, n_inst
+
+
+def cells_recover(node_xyz, beam_conn, boundary_nodes, beam_radius, seg_len, seg_nsub, u_b, young, poisson, lam_b=None,
+                  want=("u", "lam", "sens"), kappa=0.9, pen_coef=1.5, device=0):
+    """Cell interiors and exact strut sensitivities from boundary values, n_inst instances of one cell topology in one
+    launch (pl_cells_recover).
+
+    Geometry arguments as ``schur_cells``.  u_b (6 n_b,) / (n_b, 6) or with a leading n_inst axis, rows in
+    boundary_nodes order; lam_b likewise, None: lam = u.  ``want`` chooses among "u" (u_full (n_inst, N, 6): u_b on the
+    boundary nodes, -K_II^-1 K_IB u_b on the others, in the cell's node order), "lam" (the same for lam_b) and "sens"
+    ((n_inst, B): lam_e^T (dK_e/dr_b) u_e).  Returns a dict with the wanted keys and "info" ((n_inst,) int32, codes of
+    ``schur_cells``; the outputs of a failed instance are NaN)."""
+    want = (want,) if isinstance(want, str) else tuple(want)
+    if not want or any(w not in ("u", "lam", "sens") for w in want):
+        raise ValueError('want must be a non-empty subset of ("u", "lam", "sens")')
+    bn = np.asarray(boundary_nodes)
+    m = 6 * (len(bn) if bn.ndim == 1 else 0)
+
+    def boundary_values(name, v):
+        v = np.asarray(v, dtype=np.float64)
+        if v.ndim >= 2 and v.shape[-2:] == (m // 6, 6):
+            v = v.reshape(v.shape[:-2] + (m,))
+        if v.ndim not in (1, 2) or v.shape[-1] != m:
+            raise ValueError(f"{name} must have {m} values per instance, got shape {v.shape}")
+        return v
+
+    ub = boundary_values("u_b", u_b)
+    lb = None if lam_b is None else boundary_values("lam_b", lam_b)
+    lead = [v.shape[0] for v in (ub, lb) if v is not None and v.ndim == 2]
+    xyz, conn, bn, rad, slen, nsub, n_inst = _cell_batch_arrays(node_xyz, beam_conn, boundary_nodes, beam_radius, seg_len,
+                                                                seg_nsub, None, lead)
+    ub = _per_instance("u_b", ub, (m,), n_inst)
+    lb = None if lb is None else _per_instance("lam_b", lb, (m,), n_inst)
+    B, N = len(conn), xyz.shape[1]
     lib = load_library()
     opts = default_opts(lib)
     opts.young, opts.poisson, opts.kappa, opts.pen_coef, opts.device = young, poisson, kappa, pen_coef, device
-    m = 6 * len(bn)
-    S = np.empty((n_inst, m, m), np.float64)
-    info = np.empty(n_inst, np.int32)
-    _check(lib, lib.pl_schur_cells(C.byref(opts), n_inst, N, B, _ptr(conn), len(bn), _ptr(bn), _ptr(xyz), _ptr(rad),
-                                   _ptr(slen), _ptr(nsub), _ptr(S), _ptr(info)))
-    return S, info
+    out = {"info": np.empty(n_inst, np.int32)}
+    if "u" in want:
+        out["u"] = np.empty((n_inst, N, 6), np.float64)
+    if "lam" in want:
+        out["lam"] = np.empty((n_inst, N, 6), np.float64)
+    if "sens" in want:
+        out["sens"] = np.empty((n_inst, B), np.float64)
+    _check(lib, lib.pl_cells_recover(C.byref(opts), n_inst, N, B, _ptr(conn), len(bn), _ptr(bn), _ptr(xyz), _ptr(rad),
+                                     _ptr(slen), _ptr(nsub), _ptr(ub), _ptr(lb), _ptr(out.get("u")), _ptr(out.get("lam")),
+                                     _ptr(out.get("sens")), _ptr(out["info"])))
+    return out
 
 
 class PlLatticeInfo(C.Structure):

@@ -1578,6 +1578,29 @@ int pl_schur(pl_handle h, const int32_t *boundary_nodes, int32_t nb, double rtol
   return PL_OK;
 }
 
+// PL_TIMING: HIP-event time of one launch on the null stream ("[<call>] kernel_hip_event <ms> ms", four decimals)
+struct KernelEventTimer {
+  const char *what;
+  bool on;
+  hipEvent_t e0 = nullptr, e1 = nullptr;
+  KernelEventTimer(const char *w, bool enabled) : what(w), on(enabled) {
+    if (on && (hipEventCreate(&e0) != hipSuccess || hipEventCreate(&e1) != hipSuccess)) on = false;
+    if (on) (void)hipEventRecord(e0, nullptr);
+  }
+  void stop() {
+    if (on) (void)hipEventRecord(e1, nullptr);
+  }
+  void report() {                                  // after the stream was synchronised
+    float ms = 0.0f;
+    if (on && hipEventElapsedTime(&ms, e0, e1) == hipSuccess)
+      std::fprintf(stderr, "[%s] %-28s %10.4f ms\n", what, "kernel_hip_event", (double)ms);
+  }
+  ~KernelEventTimer() {
+    if (e0) (void)hipEventDestroy(e0);
+    if (e1) (void)hipEventDestroy(e1);
+  }
+};
+
 int pl_schur_cells(const pl_opts_t *o, int32_t n_inst, int32_t n_nodes, int32_t n_beams, const int32_t *beam_conn,
                    int32_t nb, const int32_t *boundary_nodes, const double *node_xyz, const double *beam_radius,
                    const double *seg_len, const int32_t *seg_nsub, double *S, int32_t *info) {
@@ -1669,11 +1692,121 @@ int pl_schur_cells(const pl_opts_t *o, int32_t n_inst, int32_t n_nodes, int32_t 
   if (lds > 64 * 1024)
     PL_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&pl::k_schur_cells),
                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+  KernelEventTimer kernel_time("pl_schur_cells", stage.on);
   hipLaunchKernelGGL(pl::k_schur_cells, dim3((unsigned)n_inst), dim3(pl::kCondBlock), lds, nullptr, a);
+  kernel_time.stop();
   PL_HIP(hipGetLastError());
   PL_HIP(hipDeviceSynchronize());
+  kernel_time.report();
   stage.mark("kernel");
   PL_HIP(hipMemcpy(S, dS.p, dS.n * sizeof(double), hipMemcpyDeviceToHost));
+  PL_HIP(hipMemcpy(info, dinfo.p, ninst * sizeof(int32_t), hipMemcpyDeviceToHost));
+  stage.mark("download");
+  return PL_OK;
+}
+
+int pl_cells_recover(const pl_opts_t *o, int32_t n_inst, int32_t n_nodes, int32_t n_beams, const int32_t *beam_conn,
+                     int32_t nb, const int32_t *boundary_nodes, const double *node_xyz, const double *beam_radius,
+                     const double *seg_len, const int32_t *seg_nsub, const double *u_b, const double *lam_b,
+                     double *u_full, double *lam_full, double *sens, int32_t *info) {
+  if (!o || !beam_conn || !boundary_nodes || !node_xyz || !beam_radius || !seg_len || !seg_nsub || !u_b || !info)
+    return fail(PL_ERR_ARG, "pl_cells_recover: null argument");
+  if (!u_full && !lam_full && !sens) return fail(PL_ERR_ARG, "pl_cells_recover: no output asked for");
+  if (int rc_abi = check_opts_abi(o, "pl_cells_recover")) return rc_abi;
+  if (n_inst <= 0 || n_nodes <= 0 || n_beams <= 0 || nb <= 0 || nb > n_nodes)
+    return fail(PL_ERR_ARG, "pl_cells_recover: bad sizes");
+  const int32_t ni = n_nodes - nb;
+  if (nb > pl::kCondMaxBoundary || ni > pl::kCondMaxInterior || n_beams > pl::kCondMaxBeams)
+    return fail(PL_ERR_ARG, "pl_cells_recover: cell too large for the batched recovery (" + std::to_string(nb) +
+                                " boundary nodes, " + std::to_string(ni) + " interior nodes, " + std::to_string(n_beams) +
+                                " struts; at most " + std::to_string(pl::kCondMaxBoundary) + " / " +
+                                std::to_string(pl::kCondMaxInterior) + " / " + std::to_string(pl::kCondMaxBeams) + ")");
+  if (!(o->young > 0.0) || !(o->poisson > -1.0) || !(o->kappa > 0.0) || !(o->pen_coef > 0.0))
+    return fail(PL_ERR_ARG, "pl_cells_recover: bad material");
+  StageTimer stage("pl_cells_recover");
+  // slots as in pl_schur_cells: position in boundary_nodes, or -1 - rank among the other nodes (ascending node index)
+  std::vector<int32_t> slot((size_t)n_nodes, INT32_MIN);
+  for (int i = 0; i < nb; ++i) {
+    const int32_t v = boundary_nodes[i];
+    if (v < 0 || v >= n_nodes) return fail(PL_ERR_ARG, "pl_cells_recover: boundary node out of range");
+    if (slot[v] != INT32_MIN) return fail(PL_ERR_ARG, "pl_cells_recover: boundary node listed twice");
+    slot[v] = i;
+  }
+  for (int32_t v = 0, k = 0; v < n_nodes; ++v)
+    if (slot[v] == INT32_MIN) slot[v] = -1 - k++;
+  std::vector<int32_t> end_slot(2 * (size_t)n_beams);
+  for (int64_t h = 0; h < 2 * (int64_t)n_beams; ++h) {
+    const int32_t v = beam_conn[h];
+    if (v < 0 || v >= n_nodes) return fail(PL_ERR_ARG, "pl_cells_recover: strut end out of range");
+    if ((h & 1) && v == beam_conn[h - 1]) return fail(PL_ERR_ARG, "pl_cells_recover: strut with both ends on one node");
+    end_slot[h] = slot[v];
+  }
+  int ndev = 0;
+  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0)
+    return fail(PL_ERR_NODEVICE, "pl_cells_recover: no HIP device visible (libpylattice_hip has no CPU fallback)");
+  if (o->device < 0 || o->device >= ndev) return fail(PL_ERR_ARG, "pl_cells_recover: bad device ordinal");
+  const size_t lds = pl::recover_lds_doubles(n_beams, ni) * sizeof(double);   // at most 32 + 72 KiB
+  const int block = pl::recover_block(n_beams, ni);
+  stage.mark("validate");
+  PL_HIP(hipSetDevice(o->device));
+  const size_t m = 6 * (size_t)nb, n6 = 6 * (size_t)n_nodes, ninst = (size_t)n_inst;
+  DevBuf<int32_t> dconn, dslot, dnslot, dnsub, dinfo;
+  DevBuf<double> dxyz, drad, dlen, dub, dlb, duf, dlf, dsens;
+  PL_HIP(dconn.alloc(2 * (size_t)n_beams));
+  PL_HIP(dslot.alloc(2 * (size_t)n_beams));
+  PL_HIP(dnslot.alloc((size_t)n_nodes));
+  PL_HIP(dxyz.alloc(ninst * 3 * n_nodes));
+  PL_HIP(drad.alloc(ninst * n_beams));
+  PL_HIP(dlen.alloc(ninst * 3 * n_beams));
+  PL_HIP(dnsub.alloc(ninst * 3 * n_beams));
+  PL_HIP(dub.alloc(ninst * m));
+  if (lam_b) PL_HIP(dlb.alloc(ninst * m));
+  if (u_full) PL_HIP(duf.alloc(ninst * n6));
+  if (lam_full) PL_HIP(dlf.alloc(ninst * n6));
+  if (sens) PL_HIP(dsens.alloc(ninst * n_beams));
+  PL_HIP(dinfo.alloc(ninst));
+  PL_HIP(hipMemcpy(dconn.p, beam_conn, dconn.n * sizeof(int32_t), hipMemcpyHostToDevice));
+  PL_HIP(hipMemcpy(dslot.p, end_slot.data(), dslot.n * sizeof(int32_t), hipMemcpyHostToDevice));
+  PL_HIP(hipMemcpy(dnslot.p, slot.data(), dnslot.n * sizeof(int32_t), hipMemcpyHostToDevice));
+  PL_HIP(hipMemcpy(dxyz.p, node_xyz, dxyz.n * sizeof(double), hipMemcpyHostToDevice));
+  PL_HIP(hipMemcpy(drad.p, beam_radius, drad.n * sizeof(double), hipMemcpyHostToDevice));
+  PL_HIP(hipMemcpy(dlen.p, seg_len, dlen.n * sizeof(double), hipMemcpyHostToDevice));
+  PL_HIP(hipMemcpy(dnsub.p, seg_nsub, dnsub.n * sizeof(int32_t), hipMemcpyHostToDevice));
+  PL_HIP(hipMemcpy(dub.p, u_b, dub.n * sizeof(double), hipMemcpyHostToDevice));
+  if (lam_b) PL_HIP(hipMemcpy(dlb.p, lam_b, dlb.n * sizeof(double), hipMemcpyHostToDevice));
+  stage.mark("upload");
+  pl::RecoverArgs a;
+  a.n_nodes = n_nodes;
+  a.n_beams = n_beams;
+  a.nb = nb;
+  a.ni = ni;
+  a.conn = dconn.p;
+  a.end_slot = dslot.p;
+  a.node_slot = dnslot.p;
+  a.xyz = dxyz.p;
+  a.radius = drad.p;
+  a.seg_len = dlen.p;
+  a.seg_nsub = dnsub.p;
+  a.m = {o->young, o->young / (2.0 * (1.0 + o->poisson)), o->kappa, o->pen_coef};
+  a.u_b = dub.p;
+  a.lam_b = lam_b ? dlb.p : nullptr;
+  a.u_full = u_full ? duf.p : nullptr;
+  a.lam_full = lam_full ? dlf.p : nullptr;
+  a.sens = sens ? dsens.p : nullptr;
+  a.info = dinfo.p;
+  if (lds > 64 * 1024)
+    PL_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&pl::k_cells_recover),
+                               hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+  KernelEventTimer kernel_time("pl_cells_recover", stage.on);
+  hipLaunchKernelGGL(pl::k_cells_recover, dim3((unsigned)n_inst), dim3((unsigned)block), lds, nullptr, a);
+  kernel_time.stop();
+  PL_HIP(hipGetLastError());
+  PL_HIP(hipDeviceSynchronize());
+  kernel_time.report();
+  stage.mark("kernel");
+  if (u_full) PL_HIP(hipMemcpy(u_full, duf.p, duf.n * sizeof(double), hipMemcpyDeviceToHost));
+  if (lam_full) PL_HIP(hipMemcpy(lam_full, dlf.p, dlf.n * sizeof(double), hipMemcpyDeviceToHost));
+  if (sens) PL_HIP(hipMemcpy(sens, dsens.p, dsens.n * sizeof(double), hipMemcpyDeviceToHost));
   PL_HIP(hipMemcpy(info, dinfo.p, ninst * sizeof(int32_t), hipMemcpyDeviceToHost));
   stage.mark("download");
   return PL_OK;

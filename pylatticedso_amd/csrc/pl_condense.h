@@ -12,8 +12,14 @@
 //   5. S = K_BB - V_I^T V_J for the node-pair blocks of the panel pair, K_BB summed from the records by the block's
 //      owning thread; upper triangle computed, the lower one mirrored, so that S is exactly symmetric.
 // A bad instance (info != 0) writes NaN into its S and leaves the others alone.
+//
+// pl_cells_recover (k_cells_recover) is the backward half on the same factor: steps 1 - 3, then
+//   4'. g = K_IB u_b per interior node by its owning thread (the incident struts in strut order, tip_force);
+//   5'. L L^T w = -g, one wave per right-hand side (u, and lam when given), the vector in registers;
+//   6'. per strut lam_e^T (dK_e/dr) u_e on the recovered fields (strut_sens, the arithmetic of k_sens).
+// It holds no V panel: records + factor in LDS, the boundary values are read from global memory.
 #pragma once
-#include "pl_device.h"
+#include "pl_kernels.h"
 
 namespace pl {
 
@@ -90,52 +96,45 @@ __device__ __forceinline__ void cond_panel(const CondenseArgs &a, const Record *
   __syncthreads();
 }
 
-__global__ __launch_bounds__(kCondBlock) void k_schur_cells(CondenseArgs a) {
-  extern __shared__ __attribute__((aligned(16))) double cond_lds[];
-  __shared__ double diag0[6 * kCondMaxInterior];
-  __shared__ int status;
-  const int64_t inst = blockIdx.x;
-  const int B = a.n_beams, N = a.n_nodes, ni = a.ni, n6 = 6 * ni, m = 6 * a.nb;
-  const int npan = (a.nb + a.pw - 1) / a.pw, W = 6 * a.pw;
-  Record *rec = reinterpret_cast<Record *>(cond_lds);
-  double *L = cond_lds + 8 * (size_t)B;
-  double *VJ = L + (size_t)n6 * n6;
-  double *VI = npan > 1 ? VJ + (size_t)n6 * W : VJ;
-  double *S = a.S + inst * (size_t)m * m;
-  if (threadIdx.x == 0) status = 0;
-  __syncthreads();
-
-  // 1. records; -1 for a non-positive radius or segment count (or a strut without length)
-  const double *xyz = a.xyz + inst * 3 * (size_t)N;
+// Step 1: the strut records of instance inst into rec; *status = -1 for a non-positive radius or segment count (or a
+// strut without length).  The caller synchronises.
+__device__ __forceinline__ void cond_records(const int32_t *conn, const double *xyz_all, const double *radius,
+                                             const double *seg_len, const int32_t *seg_nsub, const Material &m,
+                                             int64_t inst, int N, int B, Record *rec, int *status) {
+  const double *xyz = xyz_all + inst * 3 * (size_t)N;
   for (int b = threadIdx.x; b < B; b += blockDim.x) {
-    const double r = a.radius[inst * B + b];
+    const double r = radius[inst * B + b];
     double len[3];
     int ns[3];
     bool ok = r > 0.0;
 #pragma unroll
     for (int k = 0; k < 3; ++k) {
-      len[k] = a.seg_len[inst * 3 * B + 3 * b + k];
-      ns[k] = a.seg_nsub[inst * 3 * B + 3 * b + k];
+      len[k] = seg_len[inst * 3 * B + 3 * b + k];
+      ns[k] = seg_nsub[inst * 3 * B + 3 * b + k];
       ok = ok && len[k] >= 0.0 && (len[k] == 0.0 || ns[k] >= 1);
     }
-    const int ia = a.conn[2 * b], ib = a.conn[2 * b + 1];
+    const int ia = conn[2 * b], ib = conn[2 * b + 1];
     const V3 d = {xyz[3 * ib] - xyz[3 * ia], xyz[3 * ib + 1] - xyz[3 * ia + 1], xyz[3 * ib + 2] - xyz[3 * ia + 2]};
     ok = ok && (len[0] + len[1] + len[2]) > 0.0 && dot(d, d) > 0.0;
     if (ok)
-      rec[b] = make_record(scalars_from_flex(strut_flexibility(r, len, ns, a.m)), d);
+      rec[b] = make_record(scalars_from_flex(strut_flexibility(r, len, ns, m)), d);
     else
-      status = -1;
+      *status = -1;
   }
-  __syncthreads();
-  int st = status;
+}
 
+// Steps 2 and 3 (st == 0 on entry, else nothing is done): lower triangle of K_II into L, its Cholesky factor in place.
+// Returns the status: 0, or pivot k + 1 when it is not positive (a mechanism, a floating interior node).
+__device__ __forceinline__ int cond_factor(const Record *rec, const int32_t *end_slot, int B, int ni, double *L,
+                                           double *diag0, int *status, int st) {
+  const int n6 = 6 * ni;
   // 2. lower triangle of K_II (block rows p >= q)
   if (st == 0) {
     for (int t = threadIdx.x; t < ni * ni; t += blockDim.x) {
       const int p = t / ni, q = t - p * ni;
       if (q > p) continue;
       double K[36];
-      cond_node_block(rec, a.end_slot, B, -1 - p, -1 - q, K);
+      cond_node_block(rec, end_slot, B, -1 - p, -1 - q, K);
 #pragma unroll
       for (int e = 0; e < 36; ++e) {
         const int i = 6 * p + e / 6, j = 6 * q + e % 6;
@@ -151,12 +150,12 @@ __global__ __launch_bounds__(kCondBlock) void k_schur_cells(CondenseArgs a) {
       if (threadIdx.x == 0) {
         const double d = L[(size_t)k * n6 + k];
         if (!(diag0[k] > 0.0) || !(d > 1e-14 * diag0[k]))
-          status = k + 1;
+          *status = k + 1;
         else
           L[(size_t)k * n6 + k] = sqrt(d);
       }
       __syncthreads();
-      st = status;
+      st = *status;
       if (st != 0) break;
       const double lkk = L[(size_t)k * n6 + k];
       for (int i = k + 1 + threadIdx.x; i < n6; i += blockDim.x) L[(size_t)i * n6 + k] /= lkk;
@@ -169,6 +168,28 @@ __global__ __launch_bounds__(kCondBlock) void k_schur_cells(CondenseArgs a) {
       __syncthreads();
     }
   }
+  return st;
+}
+
+__global__ __launch_bounds__(kCondBlock) void k_schur_cells(CondenseArgs a) {
+  extern __shared__ __attribute__((aligned(16))) double cond_lds[];
+  __shared__ double diag0[6 * kCondMaxInterior];
+  __shared__ int status;
+  const int64_t inst = blockIdx.x;
+  const int B = a.n_beams, N = a.n_nodes, ni = a.ni, n6 = 6 * ni, m = 6 * a.nb;
+  const int npan = (a.nb + a.pw - 1) / a.pw, W = 6 * a.pw;
+  Record *rec = reinterpret_cast<Record *>(cond_lds);
+  double *L = cond_lds + 8 * (size_t)B;
+  double *VJ = L + (size_t)n6 * n6;
+  double *VI = npan > 1 ? VJ + (size_t)n6 * W : VJ;
+  double *S = a.S + inst * (size_t)m * m;
+  if (threadIdx.x == 0) status = 0;
+  __syncthreads();
+
+  // 1. - 3. records, K_II, its Cholesky factor
+  cond_records(a.conn, a.xyz, a.radius, a.seg_len, a.seg_nsub, a.m, inst, N, B, rec, &status);
+  __syncthreads();
+  const int st = cond_factor(rec, a.end_slot, B, ni, L, diag0, &status, status);
   if (threadIdx.x == 0) a.info[inst] = st;
   if (st != 0) {
     const double nan = __builtin_nan("");
@@ -201,6 +222,162 @@ __global__ __launch_bounds__(kCondBlock) void k_schur_cells(CondenseArgs a) {
         }
       }
       __syncthreads();   // VI is refilled by the next panel
+    }
+  }
+}
+
+// ---------------------------------------------------------------------------------------------------------
+// pl_cells_recover
+// ---------------------------------------------------------------------------------------------------------
+struct RecoverArgs {
+  int32_t n_nodes, n_beams, nb, ni;
+  const int32_t *conn;           // [2 B] shared
+  const int32_t *end_slot;       // [2 B] as CondenseArgs
+  const int32_t *node_slot;      // [n_nodes] slot of every node
+  const double *xyz, *radius, *seg_len;
+  const int32_t *seg_nsub;
+  Material m;
+  const double *u_b, *lam_b;     // [n_inst][6 nb]; lam_b may be null (lam = u)
+  double *u_full, *lam_full;     // [n_inst][6 n_nodes] or null
+  double *sens;                  // [n_inst][B] or null
+  int32_t *info;                 // [n_inst]
+};
+
+// LDS of one workgroup in doubles: records and K_II / its factor
+__host__ __device__ inline size_t recover_lds_doubles(int n_beams, int ni) {
+  return 8 * (size_t)n_beams + 36 * (size_t)ni * ni;
+}
+
+// Workgroup size: the widest loops are the trailing update of the factor ((6 ni)^2 entries) and the struts
+inline int recover_block(int n_beams, int ni) {
+  const int work = n_beams > 9 * ni * ni ? n_beams : 9 * ni * ni;
+  return work <= 64 ? 64 : work <= 128 ? 128 : kCondBlock;
+}
+
+// Values of the node with slot s: boundary values from vb, interior ones from w (zero when w is null)
+__device__ __forceinline__ void cond_node_values(int s, const double *vb, const double *w, V3 &u, V3 &t) {
+  if (s >= 0)
+    load6(vb + 6 * s, u, t);
+  else if (w)
+    load6(w + 6 * (-1 - s), u, t);
+  else
+    u = t = V3{0.0, 0.0, 0.0};
+}
+
+__global__ __launch_bounds__(kCondBlock) void k_cells_recover(RecoverArgs a) {
+  extern __shared__ __attribute__((aligned(16))) double cond_lds[];
+  __shared__ double diag0[6 * kCondMaxInterior];
+  __shared__ __attribute__((aligned(16))) double W[2][6 * kCondMaxInterior];
+  __shared__ int status;
+  const int64_t inst = blockIdx.x;
+  const int B = a.n_beams, N = a.n_nodes, ni = a.ni, n6 = 6 * ni, m = 6 * a.nb;
+  const int nrhs = a.lam_b ? 2 : 1;
+  Record *rec = reinterpret_cast<Record *>(cond_lds);
+  double *L = cond_lds + 8 * (size_t)B;
+  if (threadIdx.x == 0) status = 0;
+  __syncthreads();
+  cond_records(a.conn, a.xyz, a.radius, a.seg_len, a.seg_nsub, a.m, inst, N, B, rec, &status);
+  __syncthreads();
+  const int st = cond_factor(rec, a.end_slot, B, ni, L, diag0, &status, status);
+  if (threadIdx.x == 0) a.info[inst] = st;
+  double *uf = a.u_full ? a.u_full + inst * 6 * (size_t)N : nullptr;
+  double *lf = a.lam_full ? a.lam_full + inst * 6 * (size_t)N : nullptr;
+  double *sens = a.sens ? a.sens + inst * (size_t)B : nullptr;
+  if (st != 0) {
+    const double nan = __builtin_nan("");
+    for (int t = threadIdx.x; t < 6 * N; t += blockDim.x) {
+      if (uf) uf[t] = nan;
+      if (lf) lf[t] = nan;
+    }
+    if (sens)
+      for (int b = threadIdx.x; b < B; b += blockDim.x) sens[b] = nan;
+    return;
+  }
+  const double *vb[2] = {a.u_b + inst * (size_t)m, a.lam_b ? a.lam_b + inst * (size_t)m : nullptr};
+
+  // 4'. W = -K_IB v_b: the owning thread of (right-hand side, interior node) sums the incident struts in strut order
+  for (int t = threadIdx.x; t < nrhs * ni; t += blockDim.x) {
+    const int r = t / ni, p = t - r * ni;
+    V3 gF = {0.0, 0.0, 0.0}, gM = {0.0, 0.0, 0.0};
+    for (int b = 0; b < B; ++b) {
+      const int sa = a.end_slot[2 * b], sb = a.end_slot[2 * b + 1];
+      if (sa != -1 - p && sb != -1 - p) continue;
+      V3 uA, tA, uB, tB, F, M;
+      cond_node_values(sa, vb[r], nullptr, uA, tA);
+      cond_node_values(sb, vb[r], nullptr, uB, tB);
+      if (sb == -1 - p)
+        tip_force(rec[b], uA, tA, uB, tB, F, M);
+      else
+        tip_force(reversed(rec[b]), uB, tB, uA, tA, F, M);
+      gF = gF + F;
+      gM = gM + M;
+    }
+    double *w = W[r] + 6 * p;
+    w[0] = -gF.x; w[1] = -gF.y; w[2] = -gF.z;
+    w[3] = -gM.x; w[4] = -gM.y; w[5] = -gM.z;
+  }
+  __syncthreads();
+
+  // 5'. L L^T w = W: one wave per right-hand side, entries k and k + 64 of the vector in the registers of lane k
+  if (n6 > 0) {
+    const int lane = threadIdx.x & (kWave - 1), wave = threadIdx.x / kWave, nwave = blockDim.x / kWave;
+    for (int r = wave; r < nrhs; r += nwave) {
+      double *w = W[r];
+      double x0 = lane < n6 ? w[lane] : 0.0, x1 = lane + kWave < n6 ? w[lane + kWave] : 0.0;
+      for (int k = 0; k < n6; ++k) {             // L y = w by rows: y_k = (w_k - L[k, :k] . y[:k]) / L_kk
+        const double *Lk = L + (size_t)k * n6;
+        double part = 0.0;
+        if (lane < k) part = Lk[lane] * x0;
+        if (lane + kWave < k) part += Lk[lane + kWave] * x1;
+        const double s = wave_sum(part);
+        if (lane == (k & (kWave - 1))) {
+          if (k < kWave) x0 = (x0 - s) / Lk[k];
+          else x1 = (x1 - s) / Lk[k];
+        }
+      }
+      for (int k = n6 - 1; k >= 0; --k) {        // L^T x = y by columns of L^T = rows of L
+        const double *Lk = L + (size_t)k * n6;
+        const double xk = __shfl(k < kWave ? x0 : x1, k & (kWave - 1)) / Lk[k];
+        if (lane == (k & (kWave - 1))) {
+          if (k < kWave) x0 = xk;
+          else x1 = xk;
+        }
+        if (lane < k) x0 -= Lk[lane] * xk;
+        if (lane + kWave < k) x1 -= Lk[lane + kWave] * xk;
+      }
+      if (lane < n6) w[lane] = x0;
+      if (lane + kWave < n6) w[lane + kWave] = x1;
+    }
+  }
+  __syncthreads();
+
+  // the whole fields, cell-local node order
+  for (int t = threadIdx.x; t < 6 * N; t += blockDim.x) {
+    const int s = a.node_slot[t / 6], k = t % 6;
+    if (uf) uf[t] = s >= 0 ? vb[0][6 * s + k] : W[0][6 * (-1 - s) + k];
+    if (lf) lf[t] = s >= 0 ? vb[nrhs - 1][6 * s + k] : W[nrhs - 1][6 * (-1 - s) + k];
+  }
+
+  // 6'. per-strut sensitivities on the recovered fields
+  if (sens) {
+    const double *xyz = a.xyz + inst * 3 * (size_t)N;
+    for (int b = threadIdx.x; b < B; b += blockDim.x) {
+      const int ia = a.conn[2 * b], ib = a.conn[2 * b + 1];
+      const int sa = a.end_slot[2 * b], sb = a.end_slot[2 * b + 1];
+      const V3 d = {xyz[3 * ib] - xyz[3 * ia], xyz[3 * ib + 1] - xyz[3 * ia + 1], xyz[3 * ib + 2] - xyz[3 * ia + 2]};
+      double len[3];
+      int ns[3];
+#pragma unroll
+      for (int k = 0; k < 3; ++k) {
+        len[k] = a.seg_len[inst * 3 * B + 3 * b + k];
+        ns[k] = a.seg_nsub[inst * 3 * B + 3 * b + k];
+      }
+      V3 uA, tA, uB, tB, lA, mA, lB, mB;
+      cond_node_values(sa, vb[0], W[0], uA, tA);
+      cond_node_values(sb, vb[0], W[0], uB, tB);
+      cond_node_values(sa, vb[nrhs - 1], W[nrhs - 1], lA, mA);
+      cond_node_values(sb, vb[nrhs - 1], W[nrhs - 1], lB, mB);
+      sens[b] = strut_sens(a.radius[inst * B + b], len, ns, a.m, d, uA, tA, uB, tB, lA, mA, lB, mB);
     }
   }
 }

@@ -628,6 +628,19 @@ __global__ __launch_bounds__(kBlock) void k_compose_solution(int64_t n6, const u
 // ---------------------------------------------------------------------------------------------------------
 // Per-strut sensitivity s_b = lam_e^T (dK_e/dr) u_e and strain energy (one thread per strut, no scatter).
 // ---------------------------------------------------------------------------------------------------------
+// One strut: r its radius, d = x_B - x_A, (u, t) / (l, m) the translations and rotations of u / lam at its ends.
+__device__ __forceinline__ double strut_sens(double r, const double *len, const int *ns, const Material &m, V3 d,
+                                             V3 uA, V3 tA, V3 uB, V3 tB, V3 lA, V3 mA, V3 lB, V3 mB) {
+  const Flex f = strut_flexibility(r, len, ns, m);
+  const Record dr = make_record(dscalars_dr(f, r), d);
+  V3 F, M;
+  tip_force(dr, uA, tA, uB, tB, F, M);
+  // energy-conjugate pairing: lam_e . (dK u)_e = F.(dlu) + M.(dlth) with the SAME relative deformations of lam
+  const V3 dlu = lB - lA + cross(d, mA);
+  const V3 dlt = mB - mA;
+  return dot(F, dlu) + dot(M, dlt);
+}
+
 __global__ __launch_bounds__(kBlock) void k_sens(int64_t B, const double *__restrict__ xyz,
                                                  const int32_t *__restrict__ conn, const double *__restrict__ radius,
                                                  const double *__restrict__ seg_len,
@@ -642,20 +655,12 @@ __global__ __launch_bounds__(kBlock) void k_sens(int64_t B, const double *__rest
   const V3 d = {xyz[3 * ib] - xyz[3 * ia], xyz[3 * ib + 1] - xyz[3 * ia + 1], xyz[3 * ib + 2] - xyz[3 * ia + 2]};
   const double len[3] = {seg_len[3 * b], seg_len[3 * b + 1], seg_len[3 * b + 2]};
   const int ns[3] = {seg_nsub[3 * b], seg_nsub[3 * b + 1], seg_nsub[3 * b + 2]};
-  const double r = radius[b];
-  const Flex f = strut_flexibility(r, len, ns, m);
-  const Record dr = make_record(dscalars_dr(f, r), d);
-  V3 uA, tA, uB, tB, F, M;
+  V3 uA, tA, uB, tB, lA, mA, lB, mB;
   load6(u + 6 * ia, uA, tA);
   load6(u + 6 * ib, uB, tB);
-  tip_force(dr, uA, tA, uB, tB, F, M);
-  // energy-conjugate pairing: lam_e . (dK u)_e = F.(dlu) + M.(dlth) with the SAME relative deformations of lam
-  V3 lA, mA, lB, mB;
   load6(lam + 6 * ia, lA, mA);
   load6(lam + 6 * ib, lB, mB);
-  const V3 dlu = lB - lA + cross(d, mA);
-  const V3 dlt = mB - mA;
-  out[b] = dot(F, dlu) + dot(M, dlt);
+  out[b] = strut_sens(radius[b], len, ns, m, d, uA, tA, uB, tB, lA, mA, lB, mB);
 }
 
 // ---------------------------------------------------------------------------------------------------------

@@ -31,17 +31,40 @@ _DOF = {"X": 0, "Y": 1, "Z": 2, "RX": 3, "RY": 4, "RZ": 5}
 
 class LatticeOpti(LatticeSim):
     def __init__(self, name_file, mesh_trimmer=None, verbose: int = 0, convergence_plotting: bool = False,
-                 data_roots=None, reference_compat=None):
-        """``reference_compat`` (one switch with LatticeSim's): the reference's behaviour where it differs from the consistent
+                 data_roots=None, reference_compat=None, ddm_gradient=None):
+        """``ddm_gradient``: how the exact-DDM gradient is formed - "finite_difference" (default: central differences of
+        whole cell Schur complements, the reference's way) or "analytic" (exact cell matrices only: every cell is condensed
+        once, the adjoint and the state are recovered on the whole cell and the per-strut sensitivities summed,
+        LatticeSim.recover_cell_interiors).  None: the preset's
+        ``simulation_parameters.DDM.schur_complement_computation.gradient``, else "finite_difference".  The two agree to
+        the finite differences' own error when the preset has no radius gradient (``_cell_gfac`` = 1, every test and
+        timing of this repository).  With one they differ: the central differences perturb the representative's strut
+        radii as (r +- h) gfac[rep], so dS/dr already carries gfac[rep], and _ddm_cell_sensitivities multiplies by gfac[c]
+        once more (kept as it was: the default path is unchanged); the analytic mode applies the chain rule
+        d(strut radius)/d(cell radius) = gfac[c] once.
+
+        ``reference_compat`` (one switch with LatticeSim's): the reference's behaviour where it differs from the consistent
         one - its model of struts shared by several cells (lattice_sim.py docstring here), and for the "linear"
         parameterisation its gradient exactly as it computes it (lattice_opti.py:787-841, 719-720) instead of the
         derivative of the objective (see calculate_gradient)."""
-        info = open_lattice_parameters(name_file).get("optimization_informations", {})
+        params = open_lattice_parameters(name_file)
+        info = params.get("optimization_informations", {})
         # lattice_opti.py:96-103: simulation_type "DDM" runs every equilibrium through solve_DDM with the cell Schur
         # complements (exact or surrogate) and contracts their derivatives dS/dr for the gradient
         self._ddm_mode = info.get("simulation_type", None) == "DDM"
-        super().__init__(name_file, mesh_trimmer, verbose, self._ddm_mode, data_roots=data_roots,
-                         reference_compat=reference_compat)
+        comp = ((params.get("simulation_parameters", {}).get("DDM") or {}).get("schur_complement_computation") or {})
+        if ddm_gradient is None:
+            ddm_gradient = comp.get("gradient", "finite_difference") if self._ddm_mode else "finite_difference"
+        if ddm_gradient not in ("finite_difference", "analytic"):
+            raise ValueError('ddm_gradient must be "finite_difference" or "analytic"')
+        if ddm_gradient == "analytic" and not self._ddm_mode:
+            raise ValueError('ddm_gradient="analytic" applies to simulation_type "DDM" only (the FEM gradient is analytic '
+                             "already)")
+        if ddm_gradient == "analytic" and comp.get("type", None) != "exact":
+            raise ValueError('ddm_gradient="analytic" needs exact Schur complements '
+                             '(schur_complement_computation.type = "exact"): a surrogate has no strut model to differentiate')
+        super().__init__(params, mesh_trimmer, verbose, self._ddm_mode, data_roots=data_roots,
+                         reference_compat=reference_compat, ddm_gradient=ddm_gradient)
         self.solution = None
         self.actual_objective = None
         self.denorm_objective = None
@@ -380,10 +403,12 @@ class LatticeOpti(LatticeSim):
         """(C, G):  lam_c^T (dS_c/dr_j) u_c per cell and geometry, u_c / lam_c on the cell's boundary nodes in
         Cell.define_node_order_to_simulate order (lattice_opti.py:746-760, 866-890)."""
         self._flush_schur()
-        if self.schur_gradients is None:
+        analytic = self.ddm_gradient == "analytic"
+        if self.schur_gradients is None and not analytic:
             raise RuntimeError("Schur complement gradients are not available: enable_gradient_computing must be true")
         cb = self.cell_boundary_nodes()
         U = self.displacement_vector[cb].reshape(len(cb), -1)
+        lam_nodes = None                          # (rows x 6) adjoint; None: the state itself
         if self.objective_type == "compliance":
             Lam = U
         elif self.objective_type == "displacement":
@@ -393,12 +418,22 @@ class LatticeOpti(LatticeSim):
             sign = -1.0 if self.objective_function == "max" else 1.0
             for d in self.objectif_data["DOF"]:
                 q[nodes, _DOF[d]] += sign / cnt
-            Lam = self._ddm_adjoint(q)[cb].reshape(len(cb), -1)
+            lam_nodes = self._ddm_adjoint(q)
+            Lam = lam_nodes[cb].reshape(len(cb), -1)
         elif self.objective_type == "displacement_ratio":
-            Lam = self._ddm_adjoint(self._ratio_terms()[2])[cb].reshape(len(cb), -1)
+            lam_nodes = self._ddm_adjoint(self._ratio_terms()[2])
+            Lam = lam_nodes[cb].reshape(len(cb), -1)
         else:
             raise NotImplementedError(f"Gradient for objective '{self.objective_type}' not implemented yet.")
         G = len(self.geom_types)
+        if analytic:
+            # lam_c^T (dS_c/dr_j) u_c = sum over the cell's struts of type j of lam_e^T (dK_e/dr) u_e, u and lam recovered on
+            # the whole cell (E = [I; -K_II^-1 K_IB]: dS/dr = E^T (dK/dr) E at fixed segment geometry) - no step length
+            self.recover_cell_interiors(lam=lam_nodes, want_sens=True)
+            btype = self.lattice.beam_type
+            s_cell = np.stack([np.bincount(btype[beams], weights=s, minlength=G)[:G]
+                               for beams, s in self.cell_strut_sens])
+            return s_cell * self._cell_gfac[:, None]
         GA = getattr(self, "_schur_gradients_array", None)
         if GA is not None and GA.shape[1] == G:
             # every cell at once: t = dS[idx[c], j] u_c (batched matrix-vector products), then lam_c . t  (a design with one

@@ -83,10 +83,18 @@ class LatticeSim(LatticeViews):
     _design_mult_note_done = False      # the "strut copies" warning is given once per process
 
     def __init__(self, name_file, mesh_trimmer=None, verbose: int = 0,
-                 enable_domain_decomposition_solver: bool = False, data_roots=None, reference_compat=None):
+                 enable_domain_decomposition_solver: bool = False, data_roots=None, reference_compat=None,
+                 ddm_gradient="finite_difference"):
         """Same arguments as the reference (lattice_sim.py:44-47) plus ``data_roots``: extra directories in which the
-        reduced-basis files of the surrogate DDM modes are looked up (the reference finds them in its own checkout), and
-        ``reference_compat`` (module docstring; None = environment PYLATTICE_REFERENCE_COMPAT, else False)."""
+        reduced-basis files of the surrogate DDM modes are looked up (the reference finds them in its own checkout),
+        ``reference_compat`` (module docstring; None = environment PYLATTICE_REFERENCE_COMPAT, else False) and
+        ``ddm_gradient``: what the exact branch of calculate_schur_complement_cells builds when
+        ``enable_gradient_computing`` is on - "finite_difference": the central differences dS/dr of every representative
+        (the reference's way); "analytic": nothing beyond the matrices, the sensitivities come from
+        recover_cell_interiors (LatticeOpti)."""
+        if ddm_gradient not in ("finite_difference", "analytic"):
+            raise ValueError('ddm_gradient must be "finite_difference" or "analytic"')
+        self.ddm_gradient = ddm_gradient
         if mesh_trimmer is not None:
             raise NotImplementedError("mesh_trimmer is outside the accelerated path")
         if reference_compat is None:
@@ -112,6 +120,7 @@ class LatticeSim(LatticeViews):
         self.iteration = 0
         self.enable_gradient_computing = False     # lattice_sim.py:114: also keep dS/dr per unique cell
         self.schur_gradients = None                # [n_S] lists of dS/dr_j
+        self._schur_cell_data = None               # [n_S] strut data every exact cell matrix was condensed from
         self.schur_surrogate = None
         if self.domain_decomposition_solver:
             if self.type_schur_complement_computation == "FE2":
@@ -629,6 +638,7 @@ class LatticeSim(LatticeViews):
         if S.ndim == 2:
             S = S[None]
         self.schur_complements = S
+        self._schur_cell_data = None       # (calculate_schur_complement_cells sets it again for its own matrices)
         self.cell_schur_index = (np.zeros(self.lattice.n_cells, np.int32) if cell_index is None
                                  else np.asarray(cell_index, np.int32))
         dev = self._ddm_device
@@ -663,7 +673,8 @@ class LatticeSim(LatticeViews):
                 groups[k] = len(reps)
                 reps.append(c)
             idx[c] = groups[k]
-        mats, grads = [None] * len(reps), [None] * len(reps)
+        mats, grads, data = [None] * len(reps), [None] * len(reps), [None] * len(reps)
+        fd_gradients = self._schur_fd_gradients()
         by_topology = {}
         for q, c in enumerate(reps):
             beams = lat.cell_beam_idx[lat.cell_beam_ptr[c]:lat.cell_beam_ptr[c + 1]]
@@ -673,6 +684,10 @@ class LatticeSim(LatticeViews):
             conn, order = remap[lat.beam_conn[beams]], remap[cb[c]]
             key = (len(nodes), conn.tobytes(), order.tobytes())
             by_topology.setdefault(key, []).append((q, c, beams, nodes, conn, order))
+            # what recover_cell_interiors sends for every cell that uses this matrix
+            data[q] = {"cell": c, "key": key, "conn": conn, "order": order, "xyz": lat.node_xyz[nodes].copy(),
+                       "radius": lat.beam_radius[beams].copy(), "seg_len": pen.seg_len[beams].copy(),
+                       "seg_nsub": pen.seg_nsub[beams].copy()}
         for (n_nodes, _, _), members in by_topology.items():
             _, _, beams0, _, conn, order = members[0]
             if not _capi.schur_cells_fits(n_nodes, len(beams0), len(order)):
@@ -686,7 +701,7 @@ class LatticeSim(LatticeViews):
             for q, c, beams, nodes, _, _ in members:
                 base = lat.beam_radius[beams]
                 variants = [base]
-                if self.enable_gradient_computing:
+                if fd_gradients:
                     for j, rj in enumerate(par[c]):
                         h = max(1e-8, 1e-6 * max(1.0, abs(rj)))
                         rp, rm = rj + h, max(1e-12, rj - h)
@@ -710,12 +725,17 @@ class LatticeSim(LatticeViews):
             per = len(variants)                   # instances per representative (the same for every member)
             for i, (q, c, *_rest) in enumerate(members):
                 mats[q] = S[i * per]
-                if self.enable_gradient_computing:
+                if fd_gradients:
                     st = steps[i * len(par[c]):(i + 1) * len(par[c])]
                     grads[q] = [(S[i * per + 1 + 2 * j] - S[i * per + 2 + 2 * j]) / st[j] for j in range(len(par[c]))]
-        self.schur_gradients = grads if self.enable_gradient_computing else None
+        self.schur_gradients = grads if fd_gradients else None
         self._schur_gradients_array = None
         self.set_schur_complements(np.stack(mats), idx)
+        self._schur_cell_data = data
+
+    def _schur_fd_gradients(self):
+        """Whether the exact branch also builds the central differences dS/dr (gradients on, not the analytic mode)."""
+        return bool(self.enable_gradient_computing) and self.ddm_gradient != "analytic"
 
     def _schur_cell_by_columns(self, c, beams, nodes, conn, order, radii):
         """Exact Schur complement (and, with gradients on, its central differences) of cell c by pl_schur: one PCG solve
@@ -728,7 +748,7 @@ class LatticeSim(LatticeViews):
                         **({"precond": 5} if 6 * len(nodes) <= DDM_DENSE_MAX else {})) as dev:   # (see cell_device)
             dev.assemble()
             S = dev.schur(order, rtol=1e-13, max_iter=200000)
-            if not self.enable_gradient_computing:
+            if not self._schur_fd_gradients():
                 return S, None
             gl = []
             for j, rj in enumerate(radii):
@@ -779,6 +799,123 @@ class LatticeSim(LatticeViews):
     def get_schur_complement_from_reduced_basis(self, geometric_params):
         """lattice_sim.py:979-1018."""
         return self.get_schur_complement_from_reduced_basis_batch([list(geometric_params)])[0]
+
+    # ------------------------------------------------------------------------------------------------
+    # Backward half of the exact DDM: cell interiors and exact strut sensitivities (pl_cells_recover)
+    # ------------------------------------------------------------------------------------------------
+    @timing.category("simulation")
+    @timing.timeit
+    def recover_cell_interiors(self, lam=None, want_sens=False):
+        """Fill the interior rows of ``displacement_vector`` from its cell-boundary rows: u_I = -K_II^-1 K_IB u_B per cell
+        (no load and no Dirichlet dof on interior nodes, as the DDM assumes).  The cells of one topology (connectivity +
+        boundary order) go to the device in ONE call (pl_cells_recover), each with the strut data of its REPRESENTATIVE -
+        the cell its Schur complement was condensed from - so that the recovered field belongs to the operator
+        ``solve_DDM`` solved: u_full^T K u_full = u_B^T S u_B per cell.  With one radius set per cell this is the cell's
+        own data and the field is the FEM field.  Cells beyond the kernel's size are solved one by one on a handle.
+
+        ``lam`` (rows x 6, like ``displacement_vector``; None: lam = u): a second field recovered the same way from its
+        boundary rows, for the sensitivities.  ``want_sens``: return the per-strut sensitivities
+        lam_e^T (dK_e/dr) u_e as an (n_beams,) array on the lattice's strut indices (a strut held by several cells gets
+        their sum); per cell they stay in ``cell_strut_sens`` as (strut indices, values).  Summed over the struts of one
+        radius parameter of a cell they are lam_B^T (dS/dr) u_B, exactly and at fixed segment geometry.  They are
+        derivatives with respect to the STRUT radius; a preset radius gradient (``_cell_gfac``) is the caller's chain
+        rule."""
+        from . import _capi
+        if self.type_schur_complement_computation != "exact":
+            raise NotImplementedError("recover_cell_interiors: surrogate Schur complements have no strut model behind "
+                                      "their matrices; only the exact mode can recover cell interiors")
+        if getattr(self, "_compat_rows", False):
+            raise NotImplementedError("recover_cell_interiors: not available with reference_compat rows")
+        data = self._schur_cell_data
+        if data is None or self.cell_schur_index is None:
+            raise ValueError("recover_cell_interiors: the cell matrices were not condensed by "
+                             "calculate_schur_complement_cells() (set_schur_complements() installs matrices only)")
+        lat, pen = self.lattice, self.penalized
+        cb = self.cell_boundary_nodes()
+        U = self.displacement_vector
+        lam = None if lam is None else np.asarray(lam, dtype=float).reshape(U.shape)
+        groups = {}
+        for c in range(lat.n_cells):
+            beams = lat.cell_beam_idx[lat.cell_beam_ptr[c]:lat.cell_beam_ptr[c + 1]]
+            nodes = np.unique(lat.beam_conn[beams])
+            conn, order = np.searchsorted(nodes, lat.beam_conn[beams]), np.searchsorted(nodes, cb[c])
+            key = (len(nodes), conn.tobytes(), order.tobytes())
+            src = data[self.cell_schur_index[c]]
+            if src["key"] != key:
+                # struts or nodes numbered differently from the representative's: the cell's own strut data
+                src = {"xyz": lat.node_xyz[nodes], "radius": lat.beam_radius[beams], "seg_len": pen.seg_len[beams],
+                       "seg_nsub": pen.seg_nsub[beams]}
+            groups.setdefault(key, []).append((c, beams, nodes, conn, order, src))
+        want = ("u", "sens") if want_sens else ("u",)
+        sens = np.zeros(lat.n_beams) if want_sens else None
+        self.cell_strut_sens = [None] * lat.n_cells if want_sens else None
+        for (n_nodes, _, _), members in groups.items():
+            _, beams0, _, conn, order, _ = members[0]
+            ub = np.stack([U[cb[m[0]]].reshape(-1) for m in members])
+            lb = None if lam is None else np.stack([lam[cb[m[0]]].reshape(-1) for m in members])
+            if _capi.schur_cells_fits(n_nodes, len(beams0), len(order)):
+                out = _capi.cells_recover(np.stack([m[5]["xyz"] for m in members]), conn, order,
+                                          np.stack([m[5]["radius"] for m in members]),
+                                          np.stack([m[5]["seg_len"] for m in members]),
+                                          np.stack([m[5]["seg_nsub"] for m in members]), ub, self.young_modulus,
+                                          self.poisson_ratio, lam_b=lb, want=want,
+                                          pen_coef=self.penalization_coefficient)
+                bad = np.flatnonzero(out["info"] != 0)
+                if len(bad):
+                    raise RuntimeError(f"recover_cell_interiors: cell {members[bad[0]][0]} cannot be recovered "
+                                       f"(pl_cells_recover info {int(out['info'][bad[0]])}: a mechanism or bad strut data)")
+            else:
+                res = [self._recover_cell_by_solve(m[5], conn, order, ub[i], None if lb is None else lb[i], want_sens)
+                       for i, m in enumerate(members)]
+                out = {"u": np.stack([r[0] for r in res])}
+                if want_sens:
+                    out["sens"] = np.stack([r[2] for r in res])
+            interior = np.setdiff1d(np.arange(n_nodes), order)
+            for i, (c, beams, nodes, *_rest) in enumerate(members):
+                U[nodes[interior]] = out["u"][i][interior]
+                if want_sens:
+                    self.cell_strut_sens[c] = (beams, out["sens"][i])
+                    np.add.at(sens, beams, out["sens"][i])
+        return sens
+
+    def _recover_cell_by_solve(self, src, conn, order, ub, lb, want_sens):
+        """recover_cell_interiors for one cell beyond the batched kernel's size: a handle of the cell's struts with every
+        boundary dof fixed at its value, one solve per field, then pl_sens (the pattern of _schur_cell_by_columns).
+        Returns (u_full, lam_full or None, sens or None)."""
+        from ._capi import HipLattice
+        n = len(src["xyz"])
+        fixed = np.zeros((n, 6), bool)
+        fixed[order] = True
+        with HipLattice(src["xyz"], conn, src["radius"], src["seg_len"], src["seg_nsub"], self.young_modulus,
+                        self.poisson_ratio, pen_coef=self.penalization_coefficient, reorder=0,
+                        **({"precond": 5} if 6 * n <= DDM_DENSE_MAX else {})) as dev:
+            fields = []
+            for vb in (ub,) if lb is None else (ub, lb):
+                ubar = np.zeros((n, 6))
+                ubar[order] = np.asarray(vb).reshape(-1, 6)
+                if not ubar.any():
+                    fields.append(ubar)
+                    continue
+                dev.set_bc(fixed, ubar, None)
+                dev.assemble()
+                fields.append(dev.solve(rtol=1e-13, max_iter=200000)[0])
+            s = None
+            if want_sens:
+                dev.assemble()
+                s = dev.sens(fields[0], None if lb is None else fields[1])
+        return fields[0], (None if lb is None else fields[1]), s
+
+    def ddm_result_model(self):
+        """What ``solve_FEM_FenicsX`` hands back as its model, for a DDM result whose interiors were recovered
+        (``solve_DDM(recover_interior=True)``): the whole field ``u``, the lattice and an assembled handle of its struts -
+        what ``exportSimulationResults`` and the per-strut post-processing read."""
+        from .utils_simulation import FullScaleLatticeSimulation
+        dev = self.device_model()
+        dev.update_radii(self.lattice.beam_radius)       # (a design loop in DDM mode changes radii without a new handle)
+        dev.assemble()
+        model = FullScaleLatticeSimulation(self, dev)
+        model.u = model._u_solver = self.displacement_vector.copy()
+        return model
 
     def ddm_model(self):
         from ._capi import HipLattice
@@ -889,11 +1026,15 @@ class LatticeSim(LatticeViews):
 
     @timing.category("simulation")
     @timing.timeit
-    def solve_DDM(self):
+    def solve_DDM(self, recover_interior=False):
         """Domain-decomposition solve on the cell-boundary nodes (lattice_sim.py:1111-1176): right-hand side
         b = f_free - (S u_imposed)_free, plain CG with the reference's parameters (tol 1e-6, alpha clamp 100,
         max_iterations from the preset), results written back to displacement_vector; returns
-        (xsol, info, global_displacement_index, b) or four None when b == 0."""
+        (xsol, info, global_displacement_index, b) or four None when b == 0.
+
+        ``recover_interior`` (exact Schur complements only): afterwards fill the interior nodes of every cell too
+        (recover_cell_interiors), so that what the FEM path offers after a solve - the penalisation-point rows, per-strut
+        results, the VTU export - works on the result."""
         if not self.domain_decomposition_solver:
             raise ValueError("LatticeSim was not created with enable_domain_decomposition_solver=True")
         dev = self.ddm_model()
@@ -938,6 +1079,19 @@ class LatticeSim(LatticeViews):
                   f"{st['rel_residual']:.2e}).")
         self.displacement_vector[bn] = u
         self.reaction_force_vector[bn] = dev.reactions(u)
+        if recover_interior:
+            self.recover_cell_interiors()
+            if self.is_penalized:
+                # penalisation points: back-substituted now, on a handle of the struts as they are at this moment (a
+                # deferred evaluation could meet radii or segments changed since the solve)
+                from ._capi import HipLattice
+                lat, pen = self.lattice, self.penalized
+                with HipLattice(lat.node_xyz, lat.beam_conn, lat.beam_radius, pen.seg_len, pen.seg_nsub,
+                                self.young_modulus, self.poisson_ratio, pen_coef=self.penalization_coefficient) as fem:
+                    fem.assemble()
+                    per_strut = fem.node_mod(self.displacement_vector)
+                self._node_mod_pending, self._node_mod_stale = None, False
+                self.set_node_mod_displacement(per_strut)
         xsol, idx = self.get_global_displacement()
         return xsol, info, self.global_displacement_index, b[~fixed]
 
