@@ -341,6 +341,30 @@ int pl_energy(pl_handle h, const double *u, double *energy);
  * (schur_complement.py:75-147).  S is [6*nb x 6*nb] row-major. */
 int pl_schur(pl_handle h, const int32_t *boundary_nodes, int32_t nb, double rtol, int32_t max_iter, double *S);
 
+/* ---- several right-hand sides on one operator, one Jacobi-PCG pass (round 8) -------------------------------------------
+ * The reference factorises once and back-substitutes per column (PETSc LU: simulation_base.py:501-511,
+ * schur_complement.py:75-147, homogenization_cell.py:256-331); here all columns iterate in lock step and every launch
+ * carries all of them.  Single-GPU FEM handles (not pl_create_ddm, not pl_dist_init), fp64, Jacobi preconditioner, x0 = 0:
+ * the handle's multi-level / dense preconditioner, node elimination and warm start are ignored, and its single-column state
+ * (solution of the last pl_solve, warm-start history, statistics) is left untouched.  Periodic constraints of
+ * pl_set_periodic are honoured.  A column that has converged, or whose p^T K p is not positive, is frozen while the
+ * others go on.  n_rhs < 1 or > PL_MULTI_MAX is PL_ERR_ARG. */
+#define PL_MULTI_MAX 64
+/* y_j = K x_j (masked != 0: P K P x_j, x_j zeroed on fixed dofs first), j < n_rhs; x, y: [n_rhs][6N] host arrays. */
+int pl_spmv_multi(pl_handle h, int32_t n_rhs, int masked, const double *x, double *y);
+/* K u_j = f_j under the Dirichlet MASK of the last pl_set_bc, with per-column prescribed values ubar[n_rhs][6N]
+ * (read where fixed; NULL = 0) and loads f[n_rhs][6N] (NULL = 0).  u[n_rhs][6N] gets the full fields.
+ * stats: NULL or n_rhs entries, struct_size set by the caller in each; iterations / converged / rel_residual / b_norm
+ * per column, ms_solve = the whole call.  PL_ERR_NOCONV when any column missed rtol (all outputs still written). */
+int pl_solve_multi(pl_handle h, int32_t n_rhs, const double *ubar, const double *f, double rtol, int32_t max_iter,
+                   double *u, pl_stats_t *stats);
+/* pl_schur by column blocks: the unit boundary displacements are generated, solved (the loop of pl_solve_multi) and
+ * contracted to S on the device, `block` columns at a time (0 = the library's choice, <= PL_MULTI_MAX); only S comes
+ * back.  Same S, row order and meaning of rtol / max_iter as pl_schur.  The handle's boundary data (pl_set_bc) are not
+ * touched: the boundary mask of the condensation lives in the call's own workspace. */
+int pl_schur_block(pl_handle h, const int32_t *boundary_nodes, int32_t nb, double rtol, int32_t max_iter,
+                   int32_t block, double *S);
+
 /* The same condensation, exact and batched, without a handle: n_inst small lattices of ONE topology (a unit cell at
  * several radius sets - the exact DDM mode, Schur datasets), each condensed by a dense Cholesky of K_II in one workgroup
  * of a single launch.  Material, pen_coef and device come from o (stamped by pl_default_opts; the solver fields are

@@ -22,6 +22,7 @@ EXPORTS = ["pl_default_opts", "pl_opts_size", "pl_stats_size", "pl_abi_version",
            "pl_ddm_set_preconditioner", "pl_ddm_set_geometry", "pl_ddm_update_matrices", "pl_destroy", "pl_set_bc", "pl_set_periodic",
            "pl_update_radii", "pl_set_multiplicity", "pl_update_segments", "pl_assemble", "pl_assemble_bsr", "pl_get_bsr", "pl_spmv",
            "pl_spmv_free", "pl_spmv_bsr", "pl_solve", "pl_reactions", "pl_sens", "pl_energy", "pl_node_mod", "pl_schur",
+           "pl_spmv_multi", "pl_solve_multi", "pl_schur_block",
            "pl_schur_cells", "pl_cells_recover", "pl_get_records", "pl_time_kernel", "pl_algorithmic_bytes", "pl_forget_history", "pl_debug_spd_solve", "pl_dist_unique_id_bytes",
            "pl_dist_unique_id", "pl_dist_loopback_id", "pl_dist_abort", "pl_dist_init", "pl_dist_set_peers", "pl_generate_lattice", "pl_lattice_fetch",
            "pl_lattice_free", "pl_penalize", "pl_boundary_index", "pl_boundary_index_rows"]
@@ -90,7 +91,9 @@ def load_library(path: str | None = None):
            "pl_assemble_bsr": [V, I32, V, V], "pl_get_bsr": [V, V, V, V], "pl_spmv": [V, V, V],
            "pl_spmv_free": [V, V, V], "pl_spmv_bsr": [V, V, V], "pl_solve": [V, D, I32, V, V],
            "pl_reactions": [V, V, V], "pl_sens": [V, V, V, V], "pl_energy": [V, V, V], "pl_node_mod": [V, V, V],
-           "pl_schur": [V, V, I32, D, I32, V], "pl_schur_cells": [V, I32, I32, I32, V, I32, V, V, V, V, V, V, V],
+           "pl_schur": [V, V, I32, D, I32, V], "pl_spmv_multi": [V, I32, I32, V, V],
+           "pl_solve_multi": [V, I32, V, V, D, I32, V, V], "pl_schur_block": [V, V, I32, D, I32, I32, V],
+           "pl_schur_cells": [V, I32, I32, I32, V, I32, V, V, V, V, V, V, V],
            "pl_cells_recover": [V, I32, I32, I32, V, I32, V, V, V, V, V, V, V, V, V, V, V],
            "pl_get_records": [V, V], "pl_time_kernel": [V, I32, I32, V],
            "pl_algorithmic_bytes": [V, V], "pl_forget_history": [V], "pl_debug_spd_solve": [I32, I32, V, V, V, V, I32], "pl_dist_unique_id_bytes": [], "pl_dist_unique_id": [V], "pl_dist_loopback_id": [V], "pl_dist_abort": [V],
@@ -157,6 +160,9 @@ def debug_spd_solve(A, b, device=0, fp32_factor=False):
     _check(lib, lib.pl_debug_spd_solve(device, len(b), _ptr(A), _ptr(b), _ptr(x), C.byref(q), int(bool(fp32_factor))))
     return x, q.value
 
+
+# columns one pl_spmv_multi / pl_solve_multi call takes (PL_MULTI_MAX of include/pylattice_hip.h)
+MULTI_MAX = 64
 
 # what one workgroup of pl_schur_cells holds (include/pylattice_hip.h): larger cells go through pl_schur
 SCHUR_CELLS_MAX_BOUNDARY, SCHUR_CELLS_MAX_INTERIOR, SCHUR_CELLS_MAX_BEAMS = 32, 16, 512
@@ -591,11 +597,63 @@ class HipLattice:
         _check(self._lib, self._lib.pl_energy(self._h, _ptr(u), C.byref(e)))
         return e.value
 
-    def schur(self, boundary_nodes, rtol=1e-12, max_iter=20000):
+    def schur(self, boundary_nodes, rtol=1e-12, max_iter=20000, block=None):
+        """Schur complement on the listed nodes.  block = None: pl_schur, one solve per boundary dof; an int: pl_schur_block,
+        `block` columns per PCG pass, generated and contracted on the device (0 = the library's choice)."""
         bn = np.ascontiguousarray(boundary_nodes, dtype=np.int32)
         S = np.empty((6 * len(bn), 6 * len(bn)), np.float64)
-        _check(self._lib, self._lib.pl_schur(self._h, _ptr(bn), len(bn), float(rtol), int(max_iter), _ptr(S)))
+        if block is None:
+            _check(self._lib, self._lib.pl_schur(self._h, _ptr(bn), len(bn), float(rtol), int(max_iter), _ptr(S)))
+        else:
+            _check(self._lib, self._lib.pl_schur_block(self._h, _ptr(bn), len(bn), float(rtol), int(max_iter), int(block),
+                                                       _ptr(S)))
         return S
+
+    # -- several right-hand sides in one pass -------------------------------------------------------------
+    def _columns(self, name, a, k=None):
+        """a as a contiguous (k, 6 N) array: (k, N, 6), (k, 6 N), or one column (N, 6) / (6 N,)."""
+        n6 = 6 * self.n_nodes
+        a = np.asarray(a, dtype=np.float64)
+        if a.shape in ((self.n_nodes, 6), (n6,)):
+            a = a.reshape(1, n6)
+        elif a.ndim == 3 and a.shape[1:] == (self.n_nodes, 6):
+            a = a.reshape(a.shape[0], n6)
+        elif not (a.ndim == 2 and a.shape[1] == n6):
+            raise ValueError(f"{name} must have shape (k, {self.n_nodes}, 6) or (k, {n6}), got {a.shape}")
+        if not 1 <= a.shape[0] <= MULTI_MAX:
+            raise ValueError(f"{name}: 1 ... {MULTI_MAX} columns per call, got {a.shape[0]}")
+        if k is not None and a.shape[0] != k:
+            raise ValueError(f"{name} has {a.shape[0]} columns, {k} expected")
+        return np.ascontiguousarray(a)
+
+    def spmv_multi(self, X, masked=False):
+        """Y[j] = K X[j] for k columns in one launch (pl_spmv_multi); masked: P K P X[j] under the mask of set_bc.
+        X (k, N, 6) or (k, 6 N); returns (k, N, 6)."""
+        x = self._columns("X", X)
+        y = np.empty_like(x)
+        _check(self._lib, self._lib.pl_spmv_multi(self._h, x.shape[0], int(bool(masked)), _ptr(x), _ptr(y)))
+        return y.reshape(x.shape[0], self.n_nodes, 6)
+
+    def solve_multi(self, ubar=None, f=None, rtol=1e-8, max_iter=20000, raise_on_noconv=True):
+        """K u_j = f_j for k columns in one Jacobi-PCG pass under the Dirichlet mask of the last set_bc (pl_solve_multi):
+        ubar (k, N, 6) prescribed values (read where fixed; None = 0), f (k, N, 6) loads (None = 0), at least one of them.
+        Returns (U (k, N, 6), [stats of every column]).  The handle's single-column state is not touched."""
+        if ubar is None and f is None:
+            raise ValueError("solve_multi needs ubar or f (they give the number of columns)")
+        ub = None if ubar is None else self._columns("ubar", ubar)
+        ff = None if f is None else self._columns("f", f, None if ub is None else ub.shape[0])
+        k = (ub if ub is not None else ff).shape[0]
+        u = np.empty((k, 6 * self.n_nodes), np.float64)
+        st = (PlStats * k)()
+        for s in st:
+            s.struct_size = C.sizeof(PlStats)
+        rc = self._lib.pl_solve_multi(self._h, k, _ptr(ub), _ptr(ff), float(rtol), int(max_iter), _ptr(u), st)
+        keys = [n for n, _ in PlStats._fields_ if n not in ("reserved", "reserved_i", "struct_size")]
+        stats = [{n: getattr(s, n) for n in keys} for s in st]
+        if rc in (PL_OK, PL_ERR_NOCONV):
+            _timing.device("pl_solve_multi: PCG (HIP events)", st[0].ms_solve)
+        _check(self._lib, rc, allow=() if raise_on_noconv else (PL_ERR_NOCONV,))
+        return u.reshape(k, self.n_nodes, 6), stats
 
     # -- measurement ------------------------------------------------------------------------------------
     def time_kernel(self, which, reps=20):
@@ -660,7 +718,7 @@ class HipLattice:
 # the reference wraps every hot-path method in @timing.category(..) @timing.timeit; here the
 # C-ABI calls are the hot path: host wall clock per call, plus the device's own HIP-event times (see solve)
 for _name in ("assemble", "assemble_bsr", "get_bsr", "solve", "set_bc", "spmv", "spmv_free", "spmv_bsr", "reactions",
-              "sens", "energy", "schur", "update_radii", "update_segments", "records"):
+              "sens", "energy", "schur", "spmv_multi", "solve_multi", "update_radii", "update_segments", "records"):
     _f = getattr(HipLattice, _name, None)
     if _f is not None:
         _f._timing_category = "hip"

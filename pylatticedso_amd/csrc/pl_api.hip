@@ -2,6 +2,7 @@
 // pl_context.h (handle state) <- pl_ops.h (operator launches) <- pl_assembly.h <- pl_solver.h <- this file.
 #include "pl_solver.h"
 #include "pl_condense.h"
+#include "pl_multi.h"
 
 
 // ==========================================================================================================
@@ -1575,6 +1576,151 @@ int pl_schur(pl_handle h, const int32_t *boundary_nodes, int32_t nb, double rtol
     for (int i = 0; i < m; ++i) S[(size_t)i * m + j] = R[6 * (size_t)boundary_nodes[i / 6] + (i % 6)];
     ubar[dofj] = 0.0;
   }
+  return PL_OK;
+}
+
+// ---- several right-hand sides in one pass (pl_multi.h) ---------------------------------------------------------------
+int pl_spmv_multi(pl_handle h, int32_t n_rhs, int masked, const double *x, double *y) {
+  if (!valid(h) || !x || !y) return fail(PL_ERR_ARG, "pl_spmv_multi: null argument");
+  if (n_rhs < 1 || n_rhs > PL_MULTI_MAX) return fail(PL_ERR_ARG, "pl_spmv_multi: n_rhs must be 1 ... PL_MULTI_MAX");
+  if (int rc = multi_check_handle(h, "pl_spmv_multi", masked != 0)) return rc;
+  PL_HIP(hipSetDevice(h->opt.device));
+  const MultiShape s = multi_shape(h, n_rhs);
+  MultiWs *w = nullptr;
+  if (int rc = multi_ws(h, s, false, &w)) return rc;
+  if (int rc = multi_upload(h, w, s, x, w->F.p, masked ? -1 : 0)) return rc;
+  const bool timing = std::getenv("PL_TIMING") != nullptr;
+  if (timing) PL_HIP(hipEventRecord(h->ev0, h->stream));
+  if (int rc = launch_spmv_multi(h, s, h->fixedbits.p, w->F.p, w->U.p, masked != 0, nullptr)) return rc;
+  if (timing) {
+    PL_HIP(hipEventRecord(h->ev1, h->stream));
+    PL_HIP(hipEventSynchronize(h->ev1));
+    float ms = 0.f;
+    PL_HIP(hipEventElapsedTime(&ms, h->ev0, h->ev1));
+    std::fprintf(stderr, "[pl_spmv_multi] %-28s %10.4f ms\n", "kernel_hip_event", (double)ms);
+  }
+  return multi_download(h, w, s, w->U.p, y);
+}
+
+namespace {
+// per-column statistics from the status block of pcg_solve_multi; returns the number of columns that missed rtol
+int multi_stats(const MultiShape &s, const double *status, double rtol, double ms, pl_stats_t *stats, bool *bad_number) {
+  int missed = 0;
+  for (int j = 0; j < s.n_rhs; ++j) {
+    const double rr = status[pl::M_ST_RR * s.ncol + j], bb = status[pl::M_ST_BB * s.ncol + j];
+    const bool conv = rr <= rtol * rtol * bb;
+    if (!std::isfinite(rr) || !std::isfinite(bb)) *bad_number = true;
+    if (!conv) ++missed;
+    if (stats) {
+      pl_stats_t st{};
+      st.struct_size = (uint32_t)sizeof(pl_stats_t);
+      st.iterations = (int32_t)status[pl::M_ST_ITER * s.ncol + j];
+      st.converged = conv ? 1 : 0;
+      st.rel_residual = bb > 0.0 ? std::sqrt(rr / bb) : 0.0;
+      st.b_norm = std::sqrt(bb);
+      st.ms_solve = ms;
+      st.precond_used = 1.0;
+      st.kp_form = 5.0;
+      st.info = conv ? 0.0 : 1.0;
+      stats[j] = st;
+    }
+  }
+  return missed;
+}
+}  // namespace
+
+int pl_solve_multi(pl_handle h, int32_t n_rhs, const double *ubar, const double *f, double rtol, int32_t max_iter, double *u,
+                   pl_stats_t *stats) {
+  if (!valid(h) || !u) return fail(PL_ERR_ARG, "pl_solve_multi: null argument");
+  if (n_rhs < 1 || n_rhs > PL_MULTI_MAX) return fail(PL_ERR_ARG, "pl_solve_multi: n_rhs must be 1 ... PL_MULTI_MAX");
+  if (!(rtol > 0.0) || max_iter <= 0) return fail(PL_ERR_ARG, "pl_solve_multi: rtol and max_iter must be positive");
+  if (stats)
+    for (int j = 0; j < n_rhs; ++j)
+      if (stats[j].struct_size != sizeof(pl_stats_t))
+        return fail(PL_ERR_ARG, "pl_solve_multi: stats[" + std::to_string(j) + "].struct_size is " + std::to_string(stats[j].struct_size) +
+                                    ", this library's pl_stats_t has " + std::to_string(sizeof(pl_stats_t)) + " bytes");
+  if (int rc = multi_check_handle(h, "pl_solve_multi", true)) return rc;
+  PL_HIP(hipSetDevice(h->opt.device));
+  const MultiShape s = multi_shape(h, n_rhs);
+  MultiWs *w = nullptr;
+  if (int rc = multi_ws(h, s, true, &w)) return rc;
+  if (int rc = multi_upload(h, w, s, ubar, w->UB.p, 1)) return rc;
+  if (f)
+    if (int rc = multi_upload(h, w, s, f, w->F.p, 0)) return rc;
+  std::vector<double> status((size_t)pl::M_ST_COUNT * s.ncol);
+  PL_HIP(hipEventRecord(h->ev0, h->stream));
+  if (int rc = pcg_solve_multi(h, w, s, h->fixedbits.p, f ? (const double *)w->F.p : (const double *)nullptr, rtol, max_iter,
+                               status.data()))
+    return rc;
+  PL_HIP(hipEventRecord(h->ev1, h->stream));
+  PL_HIP(hipStreamSynchronize(h->stream));
+  float ms = 0.f;
+  PL_HIP(hipEventElapsedTime(&ms, h->ev0, h->ev1));
+  if (int rc = multi_download(h, w, s, w->U.p, u)) return rc;
+  bool bad = false;
+  const int missed = multi_stats(s, status.data(), rtol, ms, stats, &bad);
+  if (bad) return fail(PL_ERR_NAN, "pl_solve_multi: NaN/Inf in a residual norm");
+  if (missed) return fail(PL_ERR_NOCONV, "pl_solve_multi: " + std::to_string(missed) + " column(s) did not reach rtol within max_iter");
+  return PL_OK;
+}
+
+int pl_schur_block(pl_handle h, const int32_t *boundary_nodes, int32_t nb, double rtol, int32_t max_iter, int32_t block,
+                   double *S) {
+  if (!valid(h) || !boundary_nodes || !S || nb <= 0) return fail(PL_ERR_ARG, "pl_schur_block: bad argument");
+  if (block < 0 || block > PL_MULTI_MAX) return fail(PL_ERR_ARG, "pl_schur_block: block must be 0 ... PL_MULTI_MAX");
+  if (!(rtol > 0.0) || max_iter <= 0) return fail(PL_ERR_ARG, "pl_schur_block: rtol and max_iter must be positive");
+  if (int rc = multi_check_handle(h, "pl_schur_block", false)) return rc;
+  const int64_t N = h->N;
+  for (int i = 0; i < nb; ++i)
+    if (boundary_nodes[i] < 0 || boundary_nodes[i] >= N) return fail(PL_ERR_ARG, "pl_schur_block: node index out of range");
+  PL_HIP(hipSetDevice(h->opt.device));
+  const int m = nb * 6;
+  if (block == 0) block = kSchurBlockDefault;
+  block = std::min(block, m);
+  // The boundary mask, the unit displacements and the Jacobi inverse live in the workspace: the handle's own boundary data
+  // (pl_set_bc) are never touched, so there is nothing to restore.
+  std::vector<int32_t> inv((size_t)N), bdev((size_t)nb);
+  for (int64_t i = 0; i < N; ++i) inv[(size_t)h->perm[i]] = (int32_t)i;          // caller node -> device node
+  std::vector<uint8_t> bits((size_t)N, 0);
+  for (int i = 0; i < nb; ++i) {
+    bdev[(size_t)i] = inv[(size_t)boundary_nodes[i]];
+    bits[(size_t)bdev[(size_t)i]] = 0x3f;
+  }
+  const MultiShape s0 = multi_shape(h, block);
+  MultiWs *w = nullptr;
+  if (int rc = multi_ws(h, s0, true, &w)) return rc;
+  if (w->fixedbits.n < (size_t)N) PL_HIP(w->fixedbits.alloc((size_t)N));
+  if (w->bnodes.n < (size_t)nb) PL_HIP(w->bnodes.alloc((size_t)nb));
+  if (w->S.n < (size_t)m * m) PL_HIP(w->S.alloc((size_t)m * m));
+  PL_HIP(hipMemcpyAsync(w->fixedbits.p, bits.data(), (size_t)N, hipMemcpyHostToDevice, h->stream));
+  PL_HIP(hipMemcpyAsync(w->bnodes.p, bdev.data(), (size_t)nb * sizeof(int32_t), hipMemcpyHostToDevice, h->stream));
+  PL_HIP(hipStreamSynchronize(h->stream));      // (bits / bdev are pageable host memory)
+  // Column j of S = reaction on the boundary dofs when boundary dof j = 1, the other boundary dofs = 0 and the interior is
+  // in equilibrium (as pl_schur)
+  std::vector<double> status((size_t)pl::M_ST_COUNT * PL_MULTI_MAX);
+  int rc = PL_OK, missed = 0;
+  bool bad = false;
+  for (int j0 = 0; j0 < m && rc == PL_OK; j0 += block) {
+    const int n = std::min(block, m - j0);
+    const MultiShape s = multi_shape(h, n);
+    const size_t bytes = (size_t)s.ncb * s.stride * sizeof(double);
+    if (hipMemsetAsync(w->UB.p, 0, bytes, h->stream) != hipSuccess) { rc = fail(PL_ERR_HIP, "pl_schur_block: memset failed"); break; }
+    hipLaunchKernelGGL(pl::k_multi_unit_ubar, dim3(grid_for(n)), dim3(pl::kBlock), 0, h->stream, n, j0, (const int32_t *)w->bnodes.p,
+                       w->UB.p, s.KB, s.stride);
+    rc = pcg_solve_multi(h, w, s, w->fixedbits.p, nullptr, rtol, max_iter, status.data());
+    if (rc) break;
+    missed += multi_stats(s, status.data(), rtol, 0.0, nullptr, &bad);
+    rc = launch_spmv_multi(h, s, w->fixedbits.p, w->U.p, w->AP.p, false, nullptr);     // reactions R_j = K u_j
+    if (rc) break;
+    hipLaunchKernelGGL(pl::k_multi_schur_rows, dim3(grid_for((int64_t)m * n)), dim3(pl::kBlock), 0, h->stream, m, n, j0,
+                       (const int32_t *)w->bnodes.p, (const double *)w->AP.p, w->S.p, s.KB, s.stride);
+  }
+  if (rc) return rc;
+  PL_HIP(hipGetLastError());
+  PL_HIP(hipMemcpyAsync(S, w->S.p, (size_t)m * m * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+  PL_HIP(hipStreamSynchronize(h->stream));
+  if (bad) return fail(PL_ERR_NAN, "pl_schur_block: NaN/Inf in a residual norm");
+  if (missed) return fail(PL_ERR_NOCONV, "pl_schur_block: " + std::to_string(missed) + " column(s) did not reach rtol within max_iter");
   return PL_OK;
 }
 

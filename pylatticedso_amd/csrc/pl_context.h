@@ -11,6 +11,7 @@
 #include <cstdio>
 #include <cstring>
 #include <functional>
+#include <memory>
 #include <numeric>
 #include <string>
 #include <vector>
@@ -260,6 +261,7 @@ struct pl_context {
   DevBuf<double> sens_out;     // [B] per-strut sensitivities of pl_sens (kept: a design loop calls it every iteration)
   DevBuf<double> usol;         // composed solution of the last pl_solve (pl_sens with u = NULL reads it)
   bool usol_valid = false;
+  std::shared_ptr<void> multi_ws;   // workspace of the multi-column calls (pl_multi.h), created by the first of them
 
   ~pl_context() {
     if (ev0) (void)hipEventDestroy(ev0);

@@ -81,7 +81,7 @@ class HomogenizedCell:
     """Mirror of the reference's ``HomogenizedCell`` results interface: ``homogenizeMatrix``, ``orthotropicMatrix``,
     ``saveDataToExport`` (six total displacement fields, (N, 6) each), ``get_S_orthotropic`` and the print helpers."""
 
-    def __init__(self, lattice, device=None, solver="device", rtol=1e-13):
+    def __init__(self, lattice, device=None, solver="device", rtol=1e-13, batched=False):
         if lattice.get_number_cells() > 1:
             raise ValueError("The lattice must contain only one cell for homogenization.")
         if solver not in ("device", "host"):
@@ -90,6 +90,9 @@ class HomogenizedCell:
         self.BeamModel = self
         self.solver = solver
         self.rtol = rtol
+        # batched (device solver only): the six macro strains as six columns of ONE spmv_multi / solve_multi / spmv_multi
+        # round trip instead of six set_bc + solve + spmv loops (opt-in)
+        self.batched = bool(batched)
         self.pcg_iterations = []
         self.device = device if device is not None else lattice.device_model(precond=1)
         self.homogenizeMatrix = None
@@ -201,6 +204,24 @@ class HomogenizedCell:
         b = self._boundary
         return R[b, :3].T @ self.lattice.lattice.node_xyz[b]
 
+    def _solve_six_batched(self, W):
+        """The six fluctuation fields of W (6, N, 6) in one pass: loads -Q K w_k from one spmv_multi, one solve_multi under
+        the anchor mask and the periodic constraints, the six reactions K (w_k + u_k) from one spmv_multi."""
+        dev = self.device
+        if not getattr(self, "_periodic_set", False):
+            dev.set_periodic(self._master)
+            self._periodic_set = True
+        fixed = np.zeros((dev.n_nodes, 6), bool)
+        fixed[self._anchor_group(), :3] = True
+        KW = dev.spmv_multi(W)
+        F = np.stack([self._group_average(-kw) for kw in KW])
+        F[:, fixed] = 0.0
+        dev.set_bc(fixed)                       # the mask only: loads and prescribed values travel per column
+        U, stats = dev.solve_multi(None, F, rtol=self.rtol, max_iter=200000)
+        self.pcg_iterations.extend(int(st["iterations"]) for st in stats)
+        U_tot = W + U
+        return U_tot, dev.spmv_multi(U_tot)
+
     def solve_full_homogenization(self):
         if self._master is None:
             self.periodic_boundary_condition()
@@ -208,7 +229,16 @@ class HomogenizedCell:
             self.apply_dirichlet_for_homogenization()
         xyz = self.lattice.lattice.node_xyz
         columns, self.saveDataToExport = [], []
-        for case in range(1, 7):
+        if self.batched and self.solver == "device":
+            W = np.stack([imposed_displacement(case, xyz) for case in range(1, 7)])
+            U_tot, R = self._solve_six_batched(W)
+            b = self._boundary
+            for k in range(6):
+                s = R[k][b, :3].T @ xyz[b]
+                columns.append(np.array([s[i][j] for i, j in _VOIGT]))
+                self.saveDataToExport.append(U_tot[k])
+            self.generalizedStress = R[5]
+        for case in ([] if columns else range(1, 7)):
             w = imposed_displacement(case, xyz)
             u_tot = w + self.solve_multiple_linear_problem(w)
             s = self.calculate_macro_stress(u_tot)

@@ -31,7 +31,7 @@ _DOF = {"X": 0, "Y": 1, "Z": 2, "RX": 3, "RY": 4, "RZ": 5}
 
 class LatticeOpti(LatticeSim):
     def __init__(self, name_file, mesh_trimmer=None, verbose: int = 0, convergence_plotting: bool = False,
-                 data_roots=None, reference_compat=None, ddm_gradient=None):
+                 data_roots=None, reference_compat=None, ddm_gradient=None, paired_adjoint=False):
         """``ddm_gradient``: how the exact-DDM gradient is formed - "finite_difference" (default: central differences of
         whole cell Schur complements, the reference's way) or "analytic" (exact cell matrices only: every cell is condensed
         once, the adjoint and the state are recovered on the whole cell and the per-strut sensitivities summed,
@@ -42,6 +42,10 @@ class LatticeOpti(LatticeSim):
         radii as (r +- h) gfac[rep], so dS/dr already carries gfac[rep], and _ddm_cell_sensitivities multiplies by gfac[c]
         once more (kept as it was: the default path is unchanged); the analytic mode applies the chain rule
         d(strut radius)/d(cell radius) = gfac[c] once.
+
+        ``paired_adjoint`` (FEM mode, displacement / displacement_ratio objectives; opt-in): the gradient solves the state and
+        its adjoint right-hand sides as the columns of ONE pl_solve_multi pass under the equilibrium's Dirichlet mask instead
+        of one pl_solve per right-hand side with the boundary data re-installed in between.
 
         ``reference_compat`` (one switch with LatticeSim's): the reference's behaviour where it differs from the consistent
         one - its model of struts shared by several cells (lattice_sim.py docstring here), and for the "linear"
@@ -65,6 +69,7 @@ class LatticeOpti(LatticeSim):
                              '(schur_complement_computation.type = "exact"): a surrogate has no strut model to differentiate')
         super().__init__(params, mesh_trimmer, verbose, self._ddm_mode, data_roots=data_roots,
                          reference_compat=reference_compat, ddm_gradient=ddm_gradient)
+        self.paired_adjoint = bool(paired_adjoint)
         self.solution = None
         self.actual_objective = None
         self.denorm_objective = None
@@ -363,10 +368,46 @@ class LatticeOpti(LatticeSim):
         dev.set_bc(fixed, self._model._ubar, self._model._f)     # restore the equilibrium problem
         return lam
 
+    def _paired_state_adjoints(self, qs):
+        """The state and the adjoints of the loads qs as the columns of one solve_multi under the equilibrium's mask:
+        column 0 carries the prescribed values and loads of the equilibrium, the others zero values and their q on the
+        free dofs.  Returns (u, [lam ...])."""
+        dev = self.device_model()
+        fixed = np.asarray(self._model._fixed, dtype=bool).reshape(-1, 6)
+        ubar = np.zeros((1 + len(qs),) + fixed.shape)
+        ubar[0] = np.asarray(self._model._ubar).reshape(fixed.shape)
+        f = np.stack([np.asarray(self._model._f, dtype=float).reshape(fixed.shape)] +
+                     [np.where(fixed, 0.0, np.asarray(q).reshape(fixed.shape)) for q in qs])
+        U, _ = dev.solve_multi(ubar, f, rtol=1e-10, max_iter=200000)
+        return U[0], list(U[1:])
+
+    def _unit_mean_load(self, nodes, dofs):
+        """d(mean displacement over nodes x dofs)/du as a nodal field."""
+        q = np.zeros_like(self._model.u)
+        for k in dofs:
+            np.add.at(q, (np.asarray(nodes, dtype=np.int64), k), 1.0 / (len(nodes) * len(dofs)))
+        return q
+
     def strut_sensitivities(self):
         """s_b such that d(objective)/d r_b = −s_b at fixed segment geometry (compliance: s_b = u_eᵀ ∂K_e/∂r u_e)."""
         dev = self.device_model()
         u = self._model.u
+        if self.paired_adjoint and self.objective_type == "displacement":
+            nodes = self._objective_nodes(self.objectif_data["Surface"])
+            sign = -1.0 if self.objective_function == "max" else 1.0
+            q = sign * self._unit_mean_load(nodes, [_DOF[d] for d in self.objectif_data["DOF"]])
+            u2, (lam,) = self._paired_state_adjoints([q])
+            return dev.sens(u2, lam)
+        if self.paired_adjoint and self.objective_type == "displacement_ratio":
+            # q = -u_in e_out - u_out e_in is linear in two loads that do not depend on the state: three columns
+            bd = self.boundary_conditions
+            bd = bd["Force"] if bd.get("Force", None) is not None else bd["Displacement"]
+            u_in, u_out, _ = self._ratio_terms()
+            e_out = self._unit_mean_load(self._objective_nodes(self.objectif_data["Surface"]),
+                                         [_DOF[d] for d in self.objectif_data["DOF"]])
+            e_in = self._unit_mean_load(self._objective_nodes(bd["Load"]["Surface"]), [_DOF[d] for d in bd["Load"]["DOF"]])
+            u2, (l_out, l_in) = self._paired_state_adjoints([e_out, e_in])
+            return dev.sens(u2, -u_in * l_out - u_out * l_in)
         if self.objective_type == "compliance":
             lam = u
             if np.any(self._model._ubar != 0.0):      # prescribed displacements: the adjoint is not u itself

@@ -737,9 +737,15 @@ class LatticeSim(LatticeViews):
         """Whether the exact branch also builds the central differences dS/dr (gradients on, not the analytic mode)."""
         return bool(self.enable_gradient_computing) and self.ddm_gradient != "analytic"
 
+    # Opt-in for cells beyond the batched kernels' size: an int makes _schur_cell_by_columns condense that many columns per
+    # PCG pass (pl_schur_block; 0 = the library's choice) and _recover_cell_by_solve solve u and lam as two columns of one
+    # pl_solve_multi.  None: one pl_solve per column / field.
+    schur_column_block = None
+
     def _schur_cell_by_columns(self, c, beams, nodes, conn, order, radii):
         """Exact Schur complement (and, with gradients on, its central differences) of cell c by pl_schur: one PCG solve
         per boundary dof on a handle of the cell's struts - for cells beyond the batched kernel's size."""
+        blk = self.schur_column_block
         from ._capi import HipLattice
         lat, pen = self.lattice, self.penalized
         with HipLattice(lat.node_xyz[nodes], conn, lat.beam_radius[beams],
@@ -747,7 +753,7 @@ class LatticeSim(LatticeViews):
                         pen_coef=self.penalization_coefficient, reorder=0,
                         **({"precond": 5} if 6 * len(nodes) <= DDM_DENSE_MAX else {})) as dev:   # (see cell_device)
             dev.assemble()
-            S = dev.schur(order, rtol=1e-13, max_iter=200000)
+            S = dev.schur(order, rtol=1e-13, max_iter=200000, block=blk)
             if not self._schur_fd_gradients():
                 return S, None
             gl = []
@@ -761,7 +767,7 @@ class LatticeSim(LatticeViews):
                     rad[sel] = rv * self._cell_gfac[c]
                     dev.update_radii(rad)
                     dev.assemble()
-                    S_pm.append(dev.schur(order, rtol=1e-13, max_iter=200000))
+                    S_pm.append(dev.schur(order, rtol=1e-13, max_iter=200000, block=blk))
                 gl.append((S_pm[0] - S_pm[1]) / (rp - rm))
             return S, gl
 
@@ -890,7 +896,15 @@ class LatticeSim(LatticeViews):
                         self.poisson_ratio, pen_coef=self.penalization_coefficient, reorder=0,
                         **({"precond": 5} if 6 * n <= DDM_DENSE_MAX else {})) as dev:
             fields = []
-            for vb in (ub,) if lb is None else (ub, lb):
+            if self.schur_column_block is not None:      # u and lam as the columns of one pass
+                ubar = np.zeros((1 if lb is None else 2, n, 6))
+                ubar[0, order] = np.asarray(ub).reshape(-1, 6)
+                if lb is not None:
+                    ubar[1, order] = np.asarray(lb).reshape(-1, 6)
+                dev.set_bc(fixed)
+                dev.assemble()
+                fields = list(dev.solve_multi(ubar, None, rtol=1e-13, max_iter=200000)[0])
+            for vb in () if fields else ((ub,) if lb is None else (ub, lb)):
                 ubar = np.zeros((n, 6))
                 ubar[order] = np.asarray(vb).reshape(-1, 6)
                 if not ubar.any():

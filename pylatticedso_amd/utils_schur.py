@@ -55,10 +55,11 @@ def node_order_all_cells(lattice, tol=1e-9):
     return nodes[order].reshape(C, counts[0]).astype(np.int64)
 
 
-def get_schur_complement(lattice, cell_index=None, rtol=1e-13, max_iter=200000):
+def get_schur_complement(lattice, cell_index=None, rtol=1e-13, max_iter=200000, column_block=None):
     """S = K_BB - K_BI K_II^-1 K_IB of one cell on its boundary nodes, (6 n_b, 6 n_b), node order as the reference.
     Exact dense condensation on the device (pl_schur_cells) when the cell fits that kernel; otherwise pl_schur, column by
-    column with the device PCG (rtol / max_iter apply to that path only)."""
+    column with the device PCG (rtol / max_iter apply to that path only).  column_block = an int: that path condenses
+    `column_block` columns per PCG pass instead (pl_schur_block; 0 = the library's choice)."""
     if cell_index is None and lattice.get_number_cells() > 1:
         raise ValueError("The lattice must contain only one cell for Schur complement calculation or specify a "
                          "cell_index.")
@@ -73,7 +74,7 @@ def get_schur_complement(lattice, cell_index=None, rtol=1e-13, max_iter=200000):
         dev, order = cell_device(lattice, int(cell_index))
         with dev:
             dev.assemble()
-            return dev.schur(order, rtol=rtol, max_iter=max_iter)
+            return dev.schur(order, rtol=rtol, max_iter=max_iter, block=column_block)
     order = node_order_to_simulate(lattice, 0)
     dev = lattice.device_model()          # (the lattice's own handle: callers manage it, as before)
     if _batch_applies(lattice):
@@ -83,7 +84,7 @@ def get_schur_complement(lattice, cell_index=None, rtol=1e-13, max_iter=200000):
         if S is not None:
             return S
     dev.assemble()
-    return dev.schur(order, rtol=rtol, max_iter=max_iter)
+    return dev.schur(order, rtol=rtol, max_iter=max_iter, block=column_block)
 
 
 def _batch_applies(lattice):
