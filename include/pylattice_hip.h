@@ -333,6 +333,41 @@ int pl_sens(pl_handle h, const double *u, const double *lam, double *dCdr);
  * segment gives the end node's own values. */
 int pl_node_mod(pl_handle h, const double *u, double *out);
 
+/* ---- strut section forces, von Mises stress and its p-norm aggregate (round 9) ---------------------------------------------
+ * Replaces generalized_stress = C eps (simulation_base.py:116-125), calculate_forces / calculate_moments and
+ * extract_stress_field (simulation_base.py:776-806), which prints the maximum.  Single-GPU FEM handles after pl_assemble
+ * (PL_ERR_STATE on pl_create_ddm / pl_dist_init handles and before assembly).  u[6N]; NULL = the solution of the last
+ * pl_solve of this handle, still on the device (as pl_sens).  All outputs in the caller's strut and node numbering.
+ *
+ * A strut carries no span load: the axial force N = F.t, the shear force V = |F - N t| and the torque T = M.t are constant
+ * along it, the bending moment Mb(s) = |M(s) - T t| is the norm of a linear function of the arclength and peaks at a
+ * segment end.  Stations per strut, in the direction beam_conn[2b] -> beam_conn[2b+1], laid out [A, q1, q2, B]:
+ *   where = 0: A = end beam_conn[2b] (radius of the first present segment of seg_len), q1 / q2 = the junctions behind the
+ *              penalised segment at point1 / in front of the one at point2 (radius: the smaller of the two adjacent segments',
+ *              i.e. r), B = end beam_conn[2b+1] (radius of the last present segment).  A junction whose segment is absent
+ *              is absent.  Penalised segments have radius pen_coef * r, the middle one r.
+ *   where = 1: slots 1 and 2 = the two ends of the MIDDLE segment, both with radius r (the penalised joint zones are a
+ *              stiffness device, not a place to read stresses); slots 0 and 3 absent; no station on a strut without a middle
+ *              segment.
+ * An absent station is NaN in `station` and contributes to no sum.  Circular section of radius R (S = pi R^2, I = pi R^4 / 4,
+ * J = 2 I):  sigma = |N| / S + Mb R / I,  tau = |T| R / J,  sigma_vm = sqrt(sigma^2 + 3 tau^2); V is reported but does not
+ * enter (the transverse shear stress vanishes at the fibre where bending peaks).
+ * Multiplicity (pl_set_multiplicity): the record's force is shared by its k parallel copies - N, V, T, Mb and the stresses are
+ * those of ONE copy (F / k, M / k), and a copy counts once in the aggregate below, not k times.
+ * PL_ERR_ARG: where not 0 / 1, every output pointer NULL. */
+int pl_stress(pl_handle h, const double *u /*[6N] or NULL*/, int32_t where,
+              double *station /*[B][4][5] = N, V, T, Mb, sigma_vm per station, or NULL*/,
+              double *peak /*[B] max sigma_vm over the strut's stations (0 if none), or NULL*/);
+/* Phi_p = (sum over the present stations of sigma_vm^p)^(1/p), p >= 1 (PL_ERR_ARG below 1): an upper bound of
+ * sigma_max = max sigma_vm that tends to it with p; evaluated as sigma_max (sum (sigma_vm / sigma_max)^p)^(1/p), so no power
+ * overflows; Phi = 0 and zero derivatives when sigma_max = 0.  dphi_du[6N] = dPhi/du at fixed radii, dphi_dr[B] = dPhi/dr_b at
+ * fixed u and segment geometry - through the strut record AND through the section constants S, I, J (R = r or pen_coef r).
+ * Derivatives of |N|, |T|, Mb at exactly zero are taken as zero.  Both reductions run in two stages in a fixed order and
+ * dphi_du is gathered per node without atomics: two calls with the same inputs return the same bits in every output.
+ * Any output may be NULL, not all. */
+int pl_stress_pnorm(pl_handle h, const double *u /*[6N] or NULL*/, int32_t where, double p, double *phi, double *sigma_max,
+                    double *dphi_du /*[6N] or NULL*/, double *dphi_dr /*[B] or NULL*/);
+
 /* Strain energy 1/2 u^T K u (LatticeOpti.compute_compliance, lattice_opti.py:645-663 uses u^T K u). */
 int pl_energy(pl_handle h, const double *u, double *energy);
 

@@ -22,6 +22,7 @@ EXPORTS = ["pl_default_opts", "pl_opts_size", "pl_stats_size", "pl_abi_version",
            "pl_ddm_set_preconditioner", "pl_ddm_set_geometry", "pl_ddm_update_matrices", "pl_destroy", "pl_set_bc", "pl_set_periodic",
            "pl_update_radii", "pl_set_multiplicity", "pl_update_segments", "pl_assemble", "pl_assemble_bsr", "pl_get_bsr", "pl_spmv",
            "pl_spmv_free", "pl_spmv_bsr", "pl_solve", "pl_reactions", "pl_sens", "pl_energy", "pl_node_mod", "pl_schur",
+           "pl_stress", "pl_stress_pnorm",
            "pl_spmv_multi", "pl_solve_multi", "pl_schur_block",
            "pl_schur_cells", "pl_cells_recover", "pl_get_records", "pl_time_kernel", "pl_algorithmic_bytes", "pl_forget_history", "pl_debug_spd_solve", "pl_dist_unique_id_bytes",
            "pl_dist_unique_id", "pl_dist_loopback_id", "pl_dist_abort", "pl_dist_init", "pl_dist_set_peers", "pl_generate_lattice", "pl_lattice_fetch",
@@ -91,6 +92,7 @@ def load_library(path: str | None = None):
            "pl_assemble_bsr": [V, I32, V, V], "pl_get_bsr": [V, V, V, V], "pl_spmv": [V, V, V],
            "pl_spmv_free": [V, V, V], "pl_spmv_bsr": [V, V, V], "pl_solve": [V, D, I32, V, V],
            "pl_reactions": [V, V, V], "pl_sens": [V, V, V, V], "pl_energy": [V, V, V], "pl_node_mod": [V, V, V],
+           "pl_stress": [V, V, I32, V, V], "pl_stress_pnorm": [V, V, I32, D, V, V, V, V],
            "pl_schur": [V, V, I32, D, I32, V], "pl_spmv_multi": [V, I32, I32, V, V],
            "pl_solve_multi": [V, I32, V, V, D, I32, V, V], "pl_schur_block": [V, V, I32, D, I32, I32, V],
            "pl_schur_cells": [V, I32, I32, I32, V, I32, V, V, V, V, V, V, V],
@@ -366,6 +368,7 @@ class HipLattice:
         self._radius = _f64(beam_radius, self.n_beams)
         self._seg_len = _f64(seg_len, 3 * self.n_beams)
         self._seg_nsub = np.ascontiguousarray(seg_nsub, dtype=np.int32).reshape(-1)
+        self._material = (float(young), float(poisson), float(kappa), float(pen_coef))
         mesh = PlMesh(self.n_nodes, self.n_beams, _ptr(self.node_xyz), _ptr(self.beam_conn), _ptr(self._radius),
                       _ptr(self._seg_len), _ptr(self._seg_nsub))
         opts = default_opts(self._lib)
@@ -591,6 +594,42 @@ class HipLattice:
         _check(self._lib, self._lib.pl_node_mod(self._h, _ptr(u), _ptr(out)))
         return out
 
+    def stress(self, u=None, where=0):
+        """Section forces and von Mises stress at the stations [A, q1, q2, B] of every strut (pl_stress): dict with N, V, T,
+        Mb, sigma_vm of shape (B, 4) (NaN at absent stations) and peak (B,).  u = None: the solution of the last solve().
+        where = 0: all stations, 1: the two ends of the middle segment only."""
+        u = None if u is None else _f64(np.asarray(u).reshape(-1), 6 * self.n_nodes)
+        st = np.empty((self.n_beams, 4, 5), np.float64)
+        peak = np.empty(self.n_beams, np.float64)
+        _check(self._lib, self._lib.pl_stress(self._h, _ptr(u), int(where), _ptr(st), _ptr(peak)))
+        out = {name: st[:, :, i] for i, name in enumerate(("N", "V", "T", "Mb", "sigma_vm"))}
+        out["peak"] = peak
+        return out
+
+    def stress_pnorm(self, p, u=None, where=0, want_grad=True):
+        """(phi, sigma_max, dphi_du (N, 6), dphi_dr (B,)) of the p-norm aggregate of sigma_vm over the stations
+        (pl_stress_pnorm); the two derivatives are None with want_grad=False.  dphi_dr: at fixed u and segment geometry."""
+        u = None if u is None else _f64(np.asarray(u).reshape(-1), 6 * self.n_nodes)
+        phi, smax = C.c_double(), C.c_double()
+        du = np.empty((self.n_nodes, 6), np.float64) if want_grad else None
+        dr = np.empty(self.n_beams, np.float64) if want_grad else None
+        _check(self._lib, self._lib.pl_stress_pnorm(self._h, _ptr(u), int(where), float(p), C.byref(phi), C.byref(smax),
+                                                    _ptr(du), _ptr(dr)))
+        return phi.value, smax.value, du, dr
+
+    def stress_host(self, u, where=0):
+        """The numpy restatement of ``stress`` (stress_host.strut_stress) on this handle's records and segment data."""
+        from . import stress_host as SH
+        return SH.strut_stress(self.records(), self.beam_conn, self._radius, self._seg_len, u, self._material[3],
+                               self._mult, where)
+
+    def stress_pnorm_host(self, p, u, where=0, want_grad=True):
+        """The numpy restatement of ``stress_pnorm`` (stress_host.stress_pnorm)."""
+        from . import stress_host as SH
+        E, nu, kappa, pen = self._material
+        return SH.stress_pnorm(self.records(), self.n_nodes, self.beam_conn, self._radius, self._seg_len, self._seg_nsub,
+                               u, p, E, nu, kappa, pen, self._mult, where, want_grad)
+
     def energy(self, u):
         u = _f64(np.asarray(u).reshape(-1), 6 * self.n_nodes)
         e = C.c_double()
@@ -718,7 +757,7 @@ class HipLattice:
 # the reference wraps every hot-path method in @timing.category(..) @timing.timeit; here the
 # C-ABI calls are the hot path: host wall clock per call, plus the device's own HIP-event times (see solve)
 for _name in ("assemble", "assemble_bsr", "get_bsr", "solve", "set_bc", "spmv", "spmv_free", "spmv_bsr", "reactions",
-              "sens", "energy", "schur", "spmv_multi", "solve_multi", "update_radii", "update_segments", "records"):
+              "sens", "stress", "stress_pnorm", "energy", "schur", "spmv_multi", "solve_multi", "update_radii", "update_segments", "records"):
     _f = getattr(HipLattice, _name, None)
     if _f is not None:
         _f._timing_category = "hip"

@@ -3,6 +3,7 @@
 #include "pl_solver.h"
 #include "pl_condense.h"
 #include "pl_multi.h"
+#include "pl_stress.h"
 
 
 // ==========================================================================================================
@@ -1523,6 +1524,135 @@ int pl_node_mod(pl_handle h, const double *u, double *out) {
   PL_HIP(hipMemcpyAsync(tmp.data(), dev.p, tmp.size() * sizeof(double), hipMemcpyDeviceToHost, h->stream));
   PL_HIP(hipStreamSynchronize(h->stream));
   for (int64_t b = 0; b < h->B; ++b) std::memcpy(out + 12 * (size_t)h->bperm[b], &tmp[12 * (size_t)b], 12 * sizeof(double));
+  return PL_OK;
+}
+
+namespace {
+// what pl_stress and pl_stress_pnorm share: the checks, and u on the device (tmp, or the last solution)
+int stress_begin(pl_handle h, const char *who, const double *u, int32_t where, const double **u_dev) {
+  if (!valid(h)) return fail(PL_ERR_ARG, std::string(who) + ": null handle");
+  if (h->opkind != 0) return fail(PL_ERR_STATE, std::string(who) + ": not available on a DDM handle");
+  if (h->dist.active) return fail(PL_ERR_STATE, std::string(who) + ": not available on a multi-GPU handle");
+  if (!h->assembled) return fail(PL_ERR_STATE, std::string(who) + ": call pl_assemble first");
+  if (where != 0 && where != 1) return fail(PL_ERR_ARG, std::string(who) + ": where must be 0 (all stations) or 1 (middle segment)");
+  if (!u && !(h->usol.p && h->usol_valid))
+    return fail(PL_ERR_STATE, std::string(who) + ": u = NULL needs a pl_solve on this handle first");
+  PL_HIP(hipSetDevice(h->opt.device));
+  *u_dev = h->usol.p;
+  if (u) {
+    std::vector<double> stage;
+    if (int rc = upload6(h, u, h->tmp.p, stage)) return rc;
+    *u_dev = h->tmp.p;
+  }
+  return PL_OK;
+}
+// kernel time of a stress call on stderr when PL_TIMING is set (tools/time_stress.py), as pl_spmv_multi does
+struct StressTimer {
+  pl_handle h;
+  const char *who;
+  bool on;
+  StressTimer(pl_handle h_, const char *w) : h(h_), who(w), on(std::getenv("PL_TIMING") != nullptr) {
+    if (on) (void)hipEventRecord(h->ev0, h->stream);
+  }
+  void stop() {
+    if (!on) return;
+    float ms = 0.f;
+    if (hipEventRecord(h->ev1, h->stream) == hipSuccess && hipEventSynchronize(h->ev1) == hipSuccess &&
+        hipEventElapsedTime(&ms, h->ev0, h->ev1) == hipSuccess)
+      std::fprintf(stderr, "[%s] %-28s %10.4f ms\n", who, "kernel_hip_event", (double)ms);
+  }
+};
+}  // namespace
+
+int pl_stress(pl_handle h, const double *u, int32_t where, double *station, double *peak) {
+  const double *u_dev = nullptr;
+  if (int rc = stress_begin(h, "pl_stress", u, where, &u_dev)) return rc;
+  if (!station && !peak) return fail(PL_ERR_ARG, "pl_stress: every output pointer is NULL");
+  const int64_t B = h->B;
+  DevBuf<double> d_station;
+  if (station) PL_HIP(d_station.alloc((size_t)B * 20));
+  if (peak && !h->st_dr.p) PL_HIP(h->st_dr.alloc((size_t)B));
+  StressTimer timer(h, "pl_stress");
+  hipLaunchKernelGGL(pl::k_stress_stations, dim3(grid_for(B)), dim3(pl::kBlock), 0, h->stream, B, h->conn.p, h->rec.p,
+                     h->radius.p, h->seg_len.p, h->mult.p, h->mat.pen, (int)where, u_dev, d_station.p,
+                     peak ? h->st_dr.p : (double *)nullptr, (double *)nullptr, (double *)nullptr);
+  PL_HIP(hipGetLastError());
+  timer.stop();
+  if (station) {
+    std::vector<double> tmp((size_t)B * 20);
+    PL_HIP(hipMemcpyAsync(tmp.data(), d_station.p, tmp.size() * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+    PL_HIP(hipStreamSynchronize(h->stream));
+    pl::parallel_for(B, [&](int64_t b0, int64_t b1, unsigned) {
+      for (int64_t b = b0; b < b1; ++b) std::memcpy(station + 20 * (size_t)h->bperm[b], &tmp[20 * (size_t)b], 20 * sizeof(double));
+    }, 1 << 14);
+  }
+  if (peak) {
+    double *stg = nullptr;
+    if (int rc = stagingB(h, &stg)) return rc;
+    PL_HIP(hipMemcpyAsync(stg, h->st_dr.p, B * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+    PL_HIP(hipStreamSynchronize(h->stream));
+    pl::parallel_for(B, [&](int64_t b0, int64_t b1, unsigned) {
+      for (int64_t b = b0; b < b1; ++b) peak[h->bperm[b]] = stg[b];
+    }, 1 << 16);
+  }
+  return PL_OK;
+}
+
+int pl_stress_pnorm(pl_handle h, const double *u, int32_t where, double p, double *phi, double *sigma_max, double *dphi_du,
+                    double *dphi_dr) {
+  const double *u_dev = nullptr;
+  if (int rc = stress_begin(h, "pl_stress_pnorm", u, where, &u_dev)) return rc;
+  if (!(p >= 1.0) || !std::isfinite(p)) return fail(PL_ERR_ARG, "pl_stress_pnorm: p must be >= 1");
+  if (!phi && !sigma_max && !dphi_du && !dphi_dr) return fail(PL_ERR_ARG, "pl_stress_pnorm: every output pointer is NULL");
+  const int64_t B = h->B, N = h->N;
+  const unsigned grid = grid_for(B);
+  if (!h->st_vm4.p) PL_HIP(h->st_vm4.alloc((size_t)B * 4));
+  if (!h->st_part.p) PL_HIP(h->st_part.alloc(std::max<size_t>(grid, 1)));
+  if (!h->st_red.p) PL_HIP(h->st_red.alloc(4));
+  const bool grad = dphi_du || dphi_dr;
+  if (grad && !h->st_G.p) PL_HIP(h->st_G.alloc((size_t)B * 6));
+  if (dphi_dr && !h->st_dr.p) PL_HIP(h->st_dr.alloc((size_t)B));
+  StressTimer timer(h, "pl_stress_pnorm");
+  hipLaunchKernelGGL(pl::k_stress_stations, dim3(grid), dim3(pl::kBlock), 0, h->stream, B, h->conn.p, h->rec.p, h->radius.p,
+                     h->seg_len.p, h->mult.p, h->mat.pen, (int)where, u_dev, (double *)nullptr, (double *)nullptr,
+                     h->st_vm4.p, h->st_part.p);
+  hipLaunchKernelGGL(pl::k_stress_fold<true>, dim3(1), dim3(pl::kBlock), 0, h->stream, (int64_t)grid, h->st_part.p, p,
+                     h->st_red.p);
+  hipLaunchKernelGGL(pl::k_stress_psum, dim3(grid), dim3(pl::kBlock), 0, h->stream, B, h->st_vm4.p, h->st_red.p, p,
+                     h->st_part.p);
+  hipLaunchKernelGGL(pl::k_stress_fold<false>, dim3(1), dim3(pl::kBlock), 0, h->stream, (int64_t)grid, h->st_part.p, p,
+                     h->st_red.p);
+  if (grad) {
+    if (dphi_dr)
+      hipLaunchKernelGGL(pl::k_stress_grad<true>, dim3(grid), dim3(pl::kBlock), 0, h->stream, B, h->conn.p, h->rec.p,
+                         h->radius.p, h->seg_len.p, h->seg_nsub.p, h->mult.p, h->mat, (int)where, p, u_dev, h->st_red.p,
+                         h->st_G.p, h->st_dr.p);
+    else
+      hipLaunchKernelGGL(pl::k_stress_grad<false>, dim3(grid), dim3(pl::kBlock), 0, h->stream, B, h->conn.p, h->rec.p,
+                         h->radius.p, h->seg_len.p, h->seg_nsub.p, h->mult.p, h->mat, (int)where, p, u_dev, h->st_red.p,
+                         h->st_G.p, (double *)nullptr);
+    if (dphi_du)   // (tmp2 is free: u sits in tmp or usol)
+      hipLaunchKernelGGL(pl::k_stress_gather, dim3(grid_for(N)), dim3(pl::kBlock), 0, h->stream, N, pl::kWave / h->lpn,
+                         h->slice_ptr.p, h->ent.p, h->rec.p, h->st_G.p, h->tmp2.p);
+  }
+  PL_HIP(hipGetLastError());
+  timer.stop();
+  double red[3] = {0, 0, 0};
+  PL_HIP(hipMemcpyAsync(red, h->st_red.p, sizeof(red), hipMemcpyDeviceToHost, h->stream));
+  PL_HIP(hipStreamSynchronize(h->stream));
+  if (sigma_max) *sigma_max = red[0];
+  if (phi) *phi = red[2];
+  if (dphi_du)
+    if (int rc = download6(h, h->tmp2.p, dphi_du)) return rc;
+  if (dphi_dr) {
+    double *stg = nullptr;
+    if (int rc = stagingB(h, &stg)) return rc;
+    PL_HIP(hipMemcpyAsync(stg, h->st_dr.p, B * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+    PL_HIP(hipStreamSynchronize(h->stream));
+    pl::parallel_for(B, [&](int64_t b0, int64_t b1, unsigned) {
+      for (int64_t b = b0; b < b1; ++b) dphi_dr[h->bperm[b]] = stg[b];
+    }, 1 << 16);
+  }
   return PL_OK;
 }
 

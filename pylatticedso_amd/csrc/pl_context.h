@@ -262,6 +262,9 @@ struct pl_context {
   DevBuf<double> usol;         // composed solution of the last pl_solve (pl_sens with u = NULL reads it)
   bool usol_valid = false;
   std::shared_ptr<void> multi_ws;   // workspace of the multi-column calls (pl_multi.h), created by the first of them
+  // pl_stress / pl_stress_pnorm (pl_stress.h), allocated by the first call: per-station sigma_vm [B][4], block partials of the
+  // two reductions, (sigma_max, p-sum, Phi_p), per-strut dPhi/d(du, dth) [B][6] and dPhi/dr [B]
+  DevBuf<double> st_vm4, st_part, st_red, st_G, st_dr;
 
   ~pl_context() {
     if (ev0) (void)hipEventDestroy(ev0);

@@ -56,6 +56,9 @@ class LatticeOpti(LatticeSim):
         # lattice_opti.py:96-103: simulation_type "DDM" runs every equilibrium through solve_DDM with the cell Schur
         # complements (exact or surrogate) and contracts their derivatives dS/dr for the gradient
         self._ddm_mode = info.get("simulation_type", None) == "DDM"
+        if self._ddm_mode and "max_stress" in (info.get("constraints") or {}):
+            raise NotImplementedError('the "max_stress" constraint needs simulation_type "FEM": strut stresses on the '
+                                      "recovered interiors of DDM cells are not implemented")
         comp = ((params.get("simulation_parameters", {}).get("DDM") or {}).get("schur_complement_computation") or {})
         if ddm_gradient is None:
             ddm_gradient = comp.get("gradient", "finite_difference") if self._ddm_mode else "finite_difference"
@@ -90,6 +93,9 @@ class LatticeOpti(LatticeSim):
                          "parameters": [], "timestamp": []}
         lat = self.lattice
         self._get_optimization_parameters(name_file)
+        self._last_stress = None
+        if "max_stress" in self.constraints_dict:
+            self._history["max_stress"] = []
         self._set_number_parameters_optimization()
         # strut -> (cell, type) of the LAST cell that holds it: Cell.change_beam_radius (cell.py:896-917) is called
         # cell after cell, so a strut shared by several cells ends with the last one's radius
@@ -494,14 +500,23 @@ class LatticeOpti(LatticeSim):
         """Raw gradient in the reference's sign convention (lattice_opti.py:735-907): sum over the struts driven by
         each parameter of λ_eᵀ (∂K_e/∂r) u_e (FEM) or over the cells of λ_cᵀ (∂S_c/∂r) u_c (DDM), chained through
         Cell.get_radius and the parameterisation."""
-        lat = self.lattice
-        G = len(self.geom_types)
         if self._ddm_mode:
             s_cell = self._ddm_cell_sensitivities()
         else:
-            s = self.strut_sensitivities()
-            s_cell = np.zeros((lat.n_cells, G))
-            np.add.at(s_cell, (self._beam_cell, lat.beam_type), s * self._cell_gfac[self._beam_cell])
+            s_cell = self._strut_to_cell(self.strut_sensitivities())
+        return self._chain_cell_sensitivities(s_cell, self.reference_compat)
+
+    def _strut_to_cell(self, s):
+        """(C, G) sums of a per-strut derivative over the struts every (cell, geometry) radius drives, times the cells'
+        gradient factor (Cell.get_radius)."""
+        lat = self.lattice
+        s_cell = np.zeros((lat.n_cells, len(self.geom_types)))
+        np.add.at(s_cell, (self._beam_cell, lat.beam_type), s * self._cell_gfac[self._beam_cell])
+        return s_cell
+
+    def _chain_cell_sensitivities(self, s_cell, reference_chain=False):
+        """(C, G) derivatives with respect to the cell radii -> the parameterisation's variables (physical units; the
+        normalisation of the variables is the caller's).  reference_chain: the reference's own chain rule for "linear"."""
         t = self.optimization_parameters["type"]
         if t == "unit_cell":
             return s_cell.ravel()
@@ -509,7 +524,7 @@ class LatticeOpti(LatticeSim):
             if self.optimization_parameters.get("hybrid", False):
                 return s_cell.sum(axis=0)
             return np.array([s_cell.sum()])
-        if t == "linear" and self.reference_compat:
+        if t == "linear" and reference_chain:
             # The reference's chain rule, verbatim in effect (lattice_opti.py:787-841): slopes are de-normalised like
             # radii (clamped into [r_min, r_max]), the "unclamped radius" r = sum a_k c_k + d is formed with the ABSOLUTE
             # cell-centre coordinates and only decides which cells count; d r / d a_k = c_k, d r / d d = 1.  This is not
@@ -580,6 +595,46 @@ class LatticeOpti(LatticeSim):
         self.set_optimization_parameters(r)
         return self.relative_density() - float(self.constraints_dict["relative_density"]["value"])
 
+    # -- stress constraint (FEM mode): p-norm of the strut von Mises stresses, pl_stress_pnorm -----------------------------
+    def _stress_settings(self):
+        c = self.constraints_dict["max_stress"]
+        return float(c["value"]), float(c.get("p", 8)), int(c.get("where", 1))
+
+    def strut_stress_aggregate(self, want_grad=False):
+        """(Phi_p, sigma_max, dPhi/du, dPhi/dr at fixed u) of the current equilibrium with the constraint's p and where."""
+        _, p, where = self._stress_settings()
+        out = self.device_model().stress_pnorm(p, self._model.u, where=where, want_grad=want_grad)
+        self._last_stress = (out[0], out[1])
+        return out
+
+    def stress_constraint(self, r):
+        """Phi_p / s_allow - 1 (<= 0 when feasible; Phi_p >= the largest von Mises stress of any strut station)."""
+        self.set_optimization_parameters(r)
+        if not self._sim_is_current:
+            self._simulate_lattice_equilibrium()
+        return self.strut_stress_aggregate()[0] / self._stress_settings()[0] - 1.0
+
+    def stress_constraint_gradient(self, r):
+        """d(stress_constraint)/d(theta): dPhi/dr_b = dPhi/dr_b at fixed u - lam^T (dK/dr_b) u with K lam = dPhi/du on the free
+        dofs (lam = 0 on prescribed ones, which take no load), chained through Cell.get_radius and the parameterisation
+        as the objective's gradient is."""
+        self.set_optimization_parameters(r)
+        if not self._sim_is_current:
+            self._simulate_lattice_equilibrium()
+        s_allow = self._stress_settings()[0]
+        _, _, dphi_du, dphi_dr = self.strut_stress_aggregate(want_grad=True)
+        lam = self._adjoint(dphi_du)
+        s = dphi_dr - self.device_model().sens(self._model.u, lam)
+        g = self._chain_cell_sensitivities(self._strut_to_cell(s))
+        scale = np.ones(self.number_parameters)          # d(physical variable)/d(theta)
+        if self.enable_normalization:
+            span = self.max_radius - self.min_radius
+            if self.optimization_parameters["type"] == "linear":
+                scale[-1] = span                          # the slopes act on the physical radius directly
+            else:
+                scale[:] = span
+        return g * scale / s_allow
+
     # -- driver (SciPy SLSQP, as the reference) ---------------------------------------------------------------------
     def _initialize_optimization_solver(self):
         from scipy.optimize import Bounds
@@ -604,6 +659,8 @@ class LatticeOpti(LatticeSim):
         self._history["objective_norm"].append(self.actual_objective)
         self._history["objective"].append(self.denorm_objective)
         self._history["relative_density"].append(self.relative_density())
+        if "max_stress" in self._history:
+            self._history["max_stress"].append(None if self._last_stress is None else self._last_stress[1])
         self._history["parameters"].append(list(map(float, r)))
         self._history["timestamp"].append(time.time())
 
@@ -620,6 +677,9 @@ class LatticeOpti(LatticeSim):
             mode = self.constraints_dict["relative_density"].get("mode", "upper")
             lb, ub = {"upper": (-np.inf, 0.0), "lower": (0.0, np.inf), "eq": (0.0, 0.0)}.get(mode, (-np.inf, 0.0))
             self.constraints.append(NonlinearConstraint(self.density_constraint, lb, ub))
+        if "max_stress" in self.constraints_dict:
+            jac = {"jac": self.stress_constraint_gradient} if self.enable_gradient_computing else {}
+            self.constraints.append(NonlinearConstraint(self.stress_constraint, -np.inf, 0.0, **jac))
         kw = dict(fun=self.objective, x0=self.initial_parameters, method="SLSQP", bounds=self.bounds,
                   constraints=self.constraints, callback=self.callback_function,
                   options={"maxiter": self.optim_max_iteration, "ftol": self.optim_ftol, "disp": self.optim_disp,

@@ -619,6 +619,24 @@ class LatticeSim(LatticeViews):
                                       pen_coef=self.penalization_coefficient, **kw)
         return self._device
 
+    def strut_stress(self, where=0):
+        """Section forces and von Mises stress of every strut for the displacements of the last solve_FEM_FenicsX, on the
+        device (pl_stress; the reference: generalized_stress / calculate_forces / calculate_moments,
+        simulation_base.py:116-174): dict with N, V, T, Mb, sigma_vm of shape (n_beams, 4) - the stations [A, q1, q2, B] of
+        every strut, NaN where absent - and peak (n_beams,).  where = 1: the two ends of the un-penalised middle segment only."""
+        if self._device is None or getattr(self, "_compat_rows", False):
+            raise RuntimeError("strut_stress needs a solve_FEM_FenicsX on this lattice first (default strut model; the "
+                               "reference_compat model has no device stress pass)")
+        # (LatticeOpti solves adjoint systems on the same handle: its equilibrium field is passed explicitly; otherwise the
+        #  solution of the last solve is still on the device)
+        model = getattr(self, "_model", None)
+        return self._device.stress(None if model is None else model._u_solver, where=where)
+
+    def max_strut_stress(self, where=0):
+        """Largest von Mises stress of any strut station (what the reference's extract_stress_field prints,
+        simulation_base.py:776-806)."""
+        return float(self.strut_stress(where)["peak"].max())
+
     # ------------------------------------------------------------------------------------------------
     # Domain decomposition (lattice_sim.py:846-919, 1111-1252)
     # ------------------------------------------------------------------------------------------------

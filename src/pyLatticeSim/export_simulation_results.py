@@ -102,6 +102,28 @@ class exportSimulationResults:
         """Cell field "Moment" = (M_t, M_a1, M_a2) at the segment mid-points (reference :94-107, calculate_moments :169-174)."""
         self._cell_fields[f"Moment_{case}" if case else "Moment"] = self._section_forces(FE_result)[1]
 
+    def export_stress(self, where: int = 0):
+        """Cell fields "sigma_vm" and "N" per exported segment, from the device stress pass (pl_stress): the larger von Mises
+        stress of the stations at the segment's two ends and the strut's axial force (the reference prints the maximum of
+        its stress field only, extract_stress_field simulation_base.py:776-806).  Not part of full_export."""
+        from pylatticedso_amd.views import _tables
+        t = _tables(self.model.lattice)
+        st = self.model.device.stress(np.asarray(self.model.u, dtype=float), where=where)
+        par, part = t.beam_parent, t.beam_part
+        vm = st["sigma_vm"][par]                                     # (segments, 4): stations [A, q1, q2, B] of the strut
+        ends = {-1: (0, 3), 0: (0, 1), 1: (1, 2), 2: (2, 3)}
+        out = np.full(len(par), np.nan)
+        for code, (i, j) in ends.items():
+            sel = part == code
+            a, b = vm[sel, i], vm[sel, j]
+            if code == 1:                                            # a middle segment that starts / ends on a lattice node
+                a = np.where(np.isnan(a), vm[sel, 0], a)
+                b = np.where(np.isnan(b), vm[sel, 3], b)
+            out[sel] = np.fmax(a, b)
+        self._cell_fields["sigma_vm"] = out
+        N = st["N"]                                                  # constant along a strut: its first present station
+        self._cell_fields["N"] = np.where(np.isnan(N[:, 0]), N[:, 1], N[:, 0])[par]
+
     def full_export(self, case: int = 0):
         self.export_displacement_rotation(case)
         self.export_reaction_force()
@@ -176,7 +198,7 @@ class exportSimulationResults:
                      + arr(t.beam_mod.astype(int), "beam_mod", 1, "Int64")
                      + arr(sim.lattice.beam_type[t.beam_parent], "type_beam", 1, "Int64"))
             for name, a in self._cell_fields.items():
-                fh.write(arr(a, name, 3))
+                fh.write(arr(a, name, 3 if np.ndim(a) > 1 else 1))
             fh.write("</CellData>\n</Piece>\n</UnstructuredGrid>\n</VTKFile>\n")
         self.pvd_path = os.path.join(self.out_dir, f"{stem}.pvd")
         with open(self.pvd_path, "w") as fh:
