@@ -368,6 +368,29 @@ int pl_stress(pl_handle h, const double *u /*[6N] or NULL*/, int32_t where,
 int pl_stress_pnorm(pl_handle h, const double *u /*[6N] or NULL*/, int32_t where, double p, double *phi, double *sigma_max,
                     double *dphi_du /*[6N] or NULL*/, double *dphi_dr /*[B] or NULL*/);
 
+/* ---- Euler buckling utilisation of the struts and its p-norm aggregate (round 10) -------------------------------------------
+ * The other way a slender strut fails.  Same handles, same u (NULL = last pl_solve) and same numbering rules as pl_stress.
+ * Per strut b: N = F.t / k, the signed axial force of ONE copy (tension > 0) - exactly the N of pl_stress, k the multiplicity
+ * of pl_set_multiplicity; compressive force P = max(0, -N).
+ * Buckling length l:  length = 0: the node-to-node length |d|;  length = 1: the middle segment seg_len[3b+1] (the penalised
+ * joint zones are rigid ends, the view where = 1 takes for stresses) - a strut without a middle segment is then absent: NaN in
+ * util, n_axial and n_crit, and it enters no sum.
+ * Critical load with the un-penalised radius r, I = pi r^4 / 4, S = pi r^2:  N_E = pi^2 E I / (k_eff l)^2 (k_eff = 1
+ * pinned-pinned, 0.5 clamped-clamped);  shear = 0: N_cr = N_E;  shear = 1: the Engesser load of a Timoshenko column,
+ * N_cr = N_E / (1 + N_E / (kappa G S)), G = E / (2 (1 + nu)); E, nu, kappa of the handle.
+ * Utilisation util = beta = P / N_cr >= 0: buckling is predicted at beta >= 1; a strut in tension has beta = 0 exactly.
+ * PL_ERR_ARG: length not 0 / 1, shear not 0 / 1, k_eff <= 0 or not finite, every output pointer NULL. */
+int pl_buckling(pl_handle h, const double *u /*[6N] or NULL*/, int32_t length, double k_eff, int32_t shear,
+                double *util /*[B] or NULL*/, double *n_axial /*[B] signed, one copy, or NULL*/, double *n_crit /*[B] or NULL*/);
+/* B_p = (sum over the present struts of beta^p)^(1/p), p >= 1 (PL_ERR_ARG below 1), evaluated as
+ * beta_max (sum (beta / beta_max)^p)^(1/p) so that no power overflows; util_max = beta_max; B_p = 0 and zero derivatives when
+ * beta_max = 0; the derivative of max(0, -N) at N = 0 is taken as zero.  dbp_du[6N] = dB/du at fixed radii, dbp_dr[B] = dB/dr_b
+ * at fixed u and segment geometry - through the strut record AND through N_cr(r).  Two-stage reductions in a fixed order and a
+ * per-node gather without atomics: two calls with the same inputs return the same bits in every output.
+ * Any output may be NULL, not all. */
+int pl_buckling_pnorm(pl_handle h, const double *u /*[6N] or NULL*/, int32_t length, double k_eff, int32_t shear, double p,
+                      double *bp, double *util_max, double *dbp_du /*[6N] or NULL*/, double *dbp_dr /*[B] or NULL*/);
+
 /* Strain energy 1/2 u^T K u (LatticeOpti.compute_compliance, lattice_opti.py:645-663 uses u^T K u). */
 int pl_energy(pl_handle h, const double *u, double *energy);
 

@@ -22,7 +22,7 @@ EXPORTS = ["pl_default_opts", "pl_opts_size", "pl_stats_size", "pl_abi_version",
            "pl_ddm_set_preconditioner", "pl_ddm_set_geometry", "pl_ddm_update_matrices", "pl_destroy", "pl_set_bc", "pl_set_periodic",
            "pl_update_radii", "pl_set_multiplicity", "pl_update_segments", "pl_assemble", "pl_assemble_bsr", "pl_get_bsr", "pl_spmv",
            "pl_spmv_free", "pl_spmv_bsr", "pl_solve", "pl_reactions", "pl_sens", "pl_energy", "pl_node_mod", "pl_schur",
-           "pl_stress", "pl_stress_pnorm",
+           "pl_stress", "pl_stress_pnorm", "pl_buckling", "pl_buckling_pnorm",
            "pl_spmv_multi", "pl_solve_multi", "pl_schur_block",
            "pl_schur_cells", "pl_cells_recover", "pl_get_records", "pl_time_kernel", "pl_algorithmic_bytes", "pl_forget_history", "pl_debug_spd_solve", "pl_dist_unique_id_bytes",
            "pl_dist_unique_id", "pl_dist_loopback_id", "pl_dist_abort", "pl_dist_init", "pl_dist_set_peers", "pl_generate_lattice", "pl_lattice_fetch",
@@ -93,6 +93,7 @@ def load_library(path: str | None = None):
            "pl_spmv_free": [V, V, V], "pl_spmv_bsr": [V, V, V], "pl_solve": [V, D, I32, V, V],
            "pl_reactions": [V, V, V], "pl_sens": [V, V, V, V], "pl_energy": [V, V, V], "pl_node_mod": [V, V, V],
            "pl_stress": [V, V, I32, V, V], "pl_stress_pnorm": [V, V, I32, D, V, V, V, V],
+           "pl_buckling": [V, V, I32, D, I32, V, V, V], "pl_buckling_pnorm": [V, V, I32, D, I32, D, V, V, V, V],
            "pl_schur": [V, V, I32, D, I32, V], "pl_spmv_multi": [V, I32, I32, V, V],
            "pl_solve_multi": [V, I32, V, V, D, I32, V, V], "pl_schur_block": [V, V, I32, D, I32, I32, V],
            "pl_schur_cells": [V, I32, I32, I32, V, I32, V, V, V, V, V, V, V],
@@ -630,6 +631,41 @@ class HipLattice:
         return SH.stress_pnorm(self.records(), self.n_nodes, self.beam_conn, self._radius, self._seg_len, self._seg_nsub,
                                u, p, E, nu, kappa, pen, self._mult, where, want_grad)
 
+    def buckling(self, u=None, length=1, k_eff=1.0, shear=0):
+        """Euler buckling utilisation of every strut (pl_buckling): dict with util = max(0, -N) / N_cr, n_axial (signed N of
+        one copy) and n_crit, each (B,).  u = None: the solution of the last solve().  length = 0: node-to-node buckling
+        length, 1: the middle segment (NaN on a strut without one); k_eff: effective-length factor; shear = 1: Engesser."""
+        u = None if u is None else _f64(np.asarray(u).reshape(-1), 6 * self.n_nodes)
+        out = {name: np.empty(self.n_beams, np.float64) for name in ("util", "n_axial", "n_crit")}
+        _check(self._lib, self._lib.pl_buckling(self._h, _ptr(u), int(length), float(k_eff), int(shear), _ptr(out["util"]),
+                                                _ptr(out["n_axial"]), _ptr(out["n_crit"])))
+        return out
+
+    def buckling_pnorm(self, p, u=None, length=1, k_eff=1.0, shear=0, want_grad=True):
+        """(bp, util_max, dbp_du (N, 6), dbp_dr (B,)) of the p-norm aggregate of the utilisations (pl_buckling_pnorm); the
+        two derivatives are None with want_grad=False.  dbp_dr: at fixed u and segment geometry."""
+        u = None if u is None else _f64(np.asarray(u).reshape(-1), 6 * self.n_nodes)
+        bp, bmax = C.c_double(), C.c_double()
+        du = np.empty((self.n_nodes, 6), np.float64) if want_grad else None
+        dr = np.empty(self.n_beams, np.float64) if want_grad else None
+        _check(self._lib, self._lib.pl_buckling_pnorm(self._h, _ptr(u), int(length), float(k_eff), int(shear), float(p),
+                                                      C.byref(bp), C.byref(bmax), _ptr(du), _ptr(dr)))
+        return bp.value, bmax.value, du, dr
+
+    def buckling_host(self, u, length=1, k_eff=1.0, shear=0):
+        """The numpy restatement of ``buckling`` (buckling_host.strut_buckling) on this handle's records and segment data."""
+        from . import buckling_host as BH
+        E, nu, kappa, _ = self._material
+        return BH.strut_buckling(self.records(), self.beam_conn, self._radius, self._seg_len, u, E, nu, kappa, self._mult,
+                                 length, k_eff, shear)
+
+    def buckling_pnorm_host(self, p, u, length=1, k_eff=1.0, shear=0, want_grad=True):
+        """The numpy restatement of ``buckling_pnorm`` (buckling_host.buckling_pnorm)."""
+        from . import buckling_host as BH
+        E, nu, kappa, pen = self._material
+        return BH.buckling_pnorm(self.records(), self.n_nodes, self.beam_conn, self._radius, self._seg_len, self._seg_nsub,
+                                 u, p, E, nu, kappa, pen, self._mult, length, k_eff, shear, want_grad)
+
     def energy(self, u):
         u = _f64(np.asarray(u).reshape(-1), 6 * self.n_nodes)
         e = C.c_double()
@@ -757,7 +793,7 @@ class HipLattice:
 # the reference wraps every hot-path method in @timing.category(..) @timing.timeit; here the
 # C-ABI calls are the hot path: host wall clock per call, plus the device's own HIP-event times (see solve)
 for _name in ("assemble", "assemble_bsr", "get_bsr", "solve", "set_bc", "spmv", "spmv_free", "spmv_bsr", "reactions",
-              "sens", "stress", "stress_pnorm", "energy", "schur", "spmv_multi", "solve_multi", "update_radii", "update_segments", "records"):
+              "sens", "stress", "stress_pnorm", "buckling", "buckling_pnorm", "energy", "schur", "spmv_multi", "solve_multi", "update_radii", "update_segments", "records"):
     _f = getattr(HipLattice, _name, None)
     if _f is not None:
         _f._timing_category = "hip"

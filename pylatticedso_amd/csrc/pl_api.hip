@@ -4,6 +4,7 @@
 #include "pl_condense.h"
 #include "pl_multi.h"
 #include "pl_stress.h"
+#include "pl_buckling.h"
 
 
 // ==========================================================================================================
@@ -1653,6 +1654,106 @@ int pl_stress_pnorm(pl_handle h, const double *u, int32_t where, double p, doubl
       for (int64_t b = b0; b < b1; ++b) dphi_dr[h->bperm[b]] = stg[b];
     }, 1 << 16);
   }
+  return PL_OK;
+}
+
+namespace {
+// what pl_buckling and pl_buckling_pnorm share: the argument checks, then those of the stress pass and u on the device
+int buckling_begin(pl_handle h, const char *who, const double *u, int32_t length, double k_eff, int32_t shear,
+                   const double **u_dev) {
+  if (!valid(h)) return fail(PL_ERR_ARG, std::string(who) + ": null handle");
+  if (length != 0 && length != 1)
+    return fail(PL_ERR_ARG, std::string(who) + ": length must be 0 (node to node) or 1 (middle segment)");
+  if (shear != 0 && shear != 1) return fail(PL_ERR_ARG, std::string(who) + ": shear must be 0 (Euler) or 1 (Engesser)");
+  if (!(k_eff > 0.0) || !std::isfinite(k_eff)) return fail(PL_ERR_ARG, std::string(who) + ": k_eff must be positive and finite");
+  return stress_begin(h, who, u, 0, u_dev);
+}
+// one [B] array from the device to the caller's strut numbering
+int download_struts(pl_handle h, const double *dev, double *host) {
+  double *stg = nullptr;
+  if (int rc = stagingB(h, &stg)) return rc;
+  PL_HIP(hipMemcpyAsync(stg, dev, h->B * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+  PL_HIP(hipStreamSynchronize(h->stream));
+  pl::parallel_for(h->B, [&](int64_t b0, int64_t b1, unsigned) {
+    for (int64_t b = b0; b < b1; ++b) host[h->bperm[b]] = stg[b];
+  }, 1 << 16);
+  return PL_OK;
+}
+}  // namespace
+
+int pl_buckling(pl_handle h, const double *u, int32_t length, double k_eff, int32_t shear, double *util, double *n_axial,
+                double *n_crit) {
+  const double *u_dev = nullptr;
+  if (int rc = buckling_begin(h, "pl_buckling", u, length, k_eff, shear, &u_dev)) return rc;
+  if (!util && !n_axial && !n_crit) return fail(PL_ERR_ARG, "pl_buckling: every output pointer is NULL");
+  const int64_t B = h->B;
+  if (!h->st_vm4.p) PL_HIP(h->st_vm4.alloc((size_t)B * 4));   // rows 0..2 of [4][B]: beta, N, N_cr
+  double *d_util = h->st_vm4.p, *d_n = h->st_vm4.p + B, *d_cr = h->st_vm4.p + 2 * B;
+  StressTimer timer(h, "pl_buckling");
+  hipLaunchKernelGGL(pl::k_buckling_util, dim3(grid_for(B)), dim3(pl::kBlock), 0, h->stream, B, h->conn.p, h->rec.p,
+                     h->radius.p, h->seg_len.p, h->mult.p, h->mat, (int)length, k_eff, (int)shear, u_dev,
+                     util ? d_util : (double *)nullptr, n_axial ? d_n : (double *)nullptr,
+                     n_crit ? d_cr : (double *)nullptr, (double *)nullptr);
+  PL_HIP(hipGetLastError());
+  timer.stop();
+  if (util)
+    if (int rc = download_struts(h, d_util, util)) return rc;
+  if (n_axial)
+    if (int rc = download_struts(h, d_n, n_axial)) return rc;
+  if (n_crit)
+    if (int rc = download_struts(h, d_cr, n_crit)) return rc;
+  return PL_OK;
+}
+
+int pl_buckling_pnorm(pl_handle h, const double *u, int32_t length, double k_eff, int32_t shear, double p, double *bp,
+                      double *util_max, double *dbp_du, double *dbp_dr) {
+  const double *u_dev = nullptr;
+  if (int rc = buckling_begin(h, "pl_buckling_pnorm", u, length, k_eff, shear, &u_dev)) return rc;
+  if (!(p >= 1.0) || !std::isfinite(p)) return fail(PL_ERR_ARG, "pl_buckling_pnorm: p must be >= 1");
+  if (!bp && !util_max && !dbp_du && !dbp_dr) return fail(PL_ERR_ARG, "pl_buckling_pnorm: every output pointer is NULL");
+  const int64_t B = h->B, N = h->N;
+  const unsigned grid = grid_for(B);
+  // the stress pass's work arrays serve here too (one stream, every call ends with its downloads): beta in st_vm4
+  if (!h->st_vm4.p) PL_HIP(h->st_vm4.alloc((size_t)B * 4));
+  if (!h->st_part.p) PL_HIP(h->st_part.alloc(std::max<size_t>(grid, 1)));
+  if (!h->st_red.p) PL_HIP(h->st_red.alloc(4));
+  const bool grad = dbp_du || dbp_dr;
+  if (grad && !h->st_G.p) PL_HIP(h->st_G.alloc((size_t)B * 6));
+  if (dbp_dr && !h->st_dr.p) PL_HIP(h->st_dr.alloc((size_t)B));
+  StressTimer timer(h, "pl_buckling_pnorm");
+  hipLaunchKernelGGL(pl::k_buckling_util, dim3(grid), dim3(pl::kBlock), 0, h->stream, B, h->conn.p, h->rec.p, h->radius.p,
+                     h->seg_len.p, h->mult.p, h->mat, (int)length, k_eff, (int)shear, u_dev, h->st_vm4.p, (double *)nullptr,
+                     (double *)nullptr, h->st_part.p);
+  hipLaunchKernelGGL(pl::k_stress_fold<true>, dim3(1), dim3(pl::kBlock), 0, h->stream, (int64_t)grid, h->st_part.p, p,
+                     h->st_red.p);
+  hipLaunchKernelGGL(pl::k_buckling_psum, dim3(grid), dim3(pl::kBlock), 0, h->stream, B, h->st_vm4.p, h->st_red.p, p,
+                     h->st_part.p);
+  hipLaunchKernelGGL(pl::k_stress_fold<false>, dim3(1), dim3(pl::kBlock), 0, h->stream, (int64_t)grid, h->st_part.p, p,
+                     h->st_red.p);
+  if (grad) {
+    if (dbp_dr)
+      hipLaunchKernelGGL(pl::k_buckling_grad<true>, dim3(grid), dim3(pl::kBlock), 0, h->stream, B, h->conn.p, h->rec.p,
+                         h->radius.p, h->seg_len.p, h->seg_nsub.p, h->mult.p, h->mat, (int)length, k_eff, (int)shear, p, u_dev,
+                         h->st_red.p, h->st_G.p, h->st_dr.p);
+    else
+      hipLaunchKernelGGL(pl::k_buckling_grad<false>, dim3(grid), dim3(pl::kBlock), 0, h->stream, B, h->conn.p, h->rec.p,
+                         h->radius.p, h->seg_len.p, h->seg_nsub.p, h->mult.p, h->mat, (int)length, k_eff, (int)shear, p, u_dev,
+                         h->st_red.p, h->st_G.p, (double *)nullptr);
+    if (dbp_du)   // (tmp2 is free: u sits in tmp or usol)
+      hipLaunchKernelGGL(pl::k_stress_gather, dim3(grid_for(N)), dim3(pl::kBlock), 0, h->stream, N, pl::kWave / h->lpn,
+                         h->slice_ptr.p, h->ent.p, h->rec.p, h->st_G.p, h->tmp2.p);
+  }
+  PL_HIP(hipGetLastError());
+  timer.stop();
+  double red[3] = {0, 0, 0};
+  PL_HIP(hipMemcpyAsync(red, h->st_red.p, sizeof(red), hipMemcpyDeviceToHost, h->stream));
+  PL_HIP(hipStreamSynchronize(h->stream));
+  if (util_max) *util_max = red[0];
+  if (bp) *bp = red[2];
+  if (dbp_du)
+    if (int rc = download6(h, h->tmp2.p, dbp_du)) return rc;
+  if (dbp_dr)
+    if (int rc = download_struts(h, h->st_dr.p, dbp_dr)) return rc;
   return PL_OK;
 }
 

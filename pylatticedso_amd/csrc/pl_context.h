@@ -264,6 +264,7 @@ struct pl_context {
   std::shared_ptr<void> multi_ws;   // workspace of the multi-column calls (pl_multi.h), created by the first of them
   // pl_stress / pl_stress_pnorm (pl_stress.h), allocated by the first call: per-station sigma_vm [B][4], block partials of the
   // two reductions, (sigma_max, p-sum, Phi_p), per-strut dPhi/d(du, dth) [B][6] and dPhi/dr [B]
+  // (pl_buckling / pl_buckling_pnorm, pl_buckling.h, use the same arrays: st_vm4 as [4][B] with beta, N, N_cr in rows 0..2)
   DevBuf<double> st_vm4, st_part, st_red, st_G, st_dr;
 
   ~pl_context() {

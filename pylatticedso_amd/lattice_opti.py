@@ -59,6 +59,9 @@ class LatticeOpti(LatticeSim):
         if self._ddm_mode and "max_stress" in (info.get("constraints") or {}):
             raise NotImplementedError('the "max_stress" constraint needs simulation_type "FEM": strut stresses on the '
                                       "recovered interiors of DDM cells are not implemented")
+        if self._ddm_mode and "buckling" in (info.get("constraints") or {}):
+            raise NotImplementedError('the "buckling" constraint needs simulation_type "FEM": strut forces on the '
+                                      "recovered interiors of DDM cells are not implemented")
         comp = ((params.get("simulation_parameters", {}).get("DDM") or {}).get("schur_complement_computation") or {})
         if ddm_gradient is None:
             ddm_gradient = comp.get("gradient", "finite_difference") if self._ddm_mode else "finite_difference"
@@ -96,6 +99,9 @@ class LatticeOpti(LatticeSim):
         self._last_stress = None
         if "max_stress" in self.constraints_dict:
             self._history["max_stress"] = []
+        self._last_buckling = None
+        if "buckling" in self.constraints_dict:
+            self._history["max_buckling"] = []
         self._set_number_parameters_optimization()
         # strut -> (cell, type) of the LAST cell that holds it: Cell.change_beam_radius (cell.py:896-917) is called
         # cell after cell, so a strut shared by several cells ends with the last one's radius
@@ -623,8 +629,14 @@ class LatticeOpti(LatticeSim):
             self._simulate_lattice_equilibrium()
         s_allow = self._stress_settings()[0]
         _, _, dphi_du, dphi_dr = self.strut_stress_aggregate(want_grad=True)
-        lam = self._adjoint(dphi_du)
-        s = dphi_dr - self.device_model().sens(self._model.u, lam)
+        return self._aggregate_gradient(dphi_du, dphi_dr) / s_allow
+
+    def _aggregate_gradient(self, dq_du, dq_dr):
+        """dq/d(theta) of a scalar q(u(r), r) of the equilibrium from its partial derivatives: dq/dr_b = dq/dr_b at fixed u -
+        lam^T (dK/dr_b) u with K lam = dq/du on the free dofs, through _strut_to_cell, the parameterisation's chain and the
+        normalisation of the variables."""
+        lam = self._adjoint(dq_du)
+        s = dq_dr - self.device_model().sens(self._model.u, lam)
         g = self._chain_cell_sensitivities(self._strut_to_cell(s))
         scale = np.ones(self.number_parameters)          # d(physical variable)/d(theta)
         if self.enable_normalization:
@@ -633,7 +645,38 @@ class LatticeOpti(LatticeSim):
                 scale[-1] = span                          # the slopes act on the physical radius directly
             else:
                 scale[:] = span
-        return g * scale / s_allow
+        return g * scale
+
+    # -- buckling constraint (FEM mode): p-norm of the struts' Euler utilisations, pl_buckling_pnorm ------------------------
+    def _buckling_settings(self):
+        c = self.constraints_dict["buckling"]
+        return float(c.get("value", 1.0)), float(c.get("p", 8)), dict(length=int(c.get("length", 1)),
+                                                                        k_eff=float(c.get("k_eff", 1.0)),
+                                                                        shear=int(c.get("shear", 0)))
+
+    def strut_buckling_aggregate(self, want_grad=False):
+        """(B_p, util_max, dB/du, dB/dr at fixed u) of the current equilibrium with the constraint's p and column model."""
+        _, p, kw = self._buckling_settings()
+        out = self.device_model().buckling_pnorm(p, self._model.u, want_grad=want_grad, **kw)
+        self._last_buckling = (out[0], out[1])
+        return out
+
+    def buckling_constraint(self, r):
+        """B_p / beta_allow - 1 (<= 0 when feasible; B_p >= the largest utilisation max(0, -N) / N_cr of any strut)."""
+        self.set_optimization_parameters(r)
+        if not self._sim_is_current:
+            self._simulate_lattice_equilibrium()
+        return self.strut_buckling_aggregate()[0] / self._buckling_settings()[0] - 1.0
+
+    def buckling_constraint_gradient(self, r):
+        """d(buckling_constraint)/d(theta) by the adjoint chain of stress_constraint_gradient: dB/dr_b at fixed u -
+        lam^T (dK/dr_b) u with K lam = dB/du on the free dofs."""
+        self.set_optimization_parameters(r)
+        if not self._sim_is_current:
+            self._simulate_lattice_equilibrium()
+        b_allow = self._buckling_settings()[0]
+        _, _, dbp_du, dbp_dr = self.strut_buckling_aggregate(want_grad=True)
+        return self._aggregate_gradient(dbp_du, dbp_dr) / b_allow
 
     # -- driver (SciPy SLSQP, as the reference) ---------------------------------------------------------------------
     def _initialize_optimization_solver(self):
@@ -661,6 +704,8 @@ class LatticeOpti(LatticeSim):
         self._history["relative_density"].append(self.relative_density())
         if "max_stress" in self._history:
             self._history["max_stress"].append(None if self._last_stress is None else self._last_stress[1])
+        if "max_buckling" in self._history:
+            self._history["max_buckling"].append(None if self._last_buckling is None else self._last_buckling[1])
         self._history["parameters"].append(list(map(float, r)))
         self._history["timestamp"].append(time.time())
 
@@ -680,6 +725,9 @@ class LatticeOpti(LatticeSim):
         if "max_stress" in self.constraints_dict:
             jac = {"jac": self.stress_constraint_gradient} if self.enable_gradient_computing else {}
             self.constraints.append(NonlinearConstraint(self.stress_constraint, -np.inf, 0.0, **jac))
+        if "buckling" in self.constraints_dict:
+            jac = {"jac": self.buckling_constraint_gradient} if self.enable_gradient_computing else {}
+            self.constraints.append(NonlinearConstraint(self.buckling_constraint, -np.inf, 0.0, **jac))
         kw = dict(fun=self.objective, x0=self.initial_parameters, method="SLSQP", bounds=self.bounds,
                   constraints=self.constraints, callback=self.callback_function,
                   options={"maxiter": self.optim_max_iteration, "ftol": self.optim_ftol, "disp": self.optim_disp,

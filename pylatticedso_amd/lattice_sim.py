@@ -637,6 +637,24 @@ class LatticeSim(LatticeViews):
         simulation_base.py:776-806)."""
         return float(self.strut_stress(where)["peak"].max())
 
+    def strut_buckling(self, length=1, k_eff=1.0, shear=0):
+        """Euler buckling utilisation of every strut for the displacements of the last solve_FEM_FenicsX, on the device
+        (pl_buckling): dict with util = max(0, -N) / N_cr (buckling predicted at 1; 0 in tension), n_axial (signed axial force
+        of one copy) and n_crit, each (n_beams,).  length = 1: the un-penalised middle segment is the buckling length (NaN on a
+        strut without one), 0: the node-to-node length; k_eff: effective-length factor (1 pinned-pinned, 0.5 clamped-clamped);
+        shear = 1: Engesser's shear-reduced load."""
+        if self._device is None or getattr(self, "_compat_rows", False):
+            raise RuntimeError("strut_buckling needs a solve_FEM_FenicsX on this lattice first (default strut model; the "
+                               "reference_compat model has no device buckling pass)")
+        model = getattr(self, "_model", None)       # (as strut_stress: LatticeOpti's equilibrium field is passed explicitly)
+        return self._device.buckling(None if model is None else model._u_solver, length=length, k_eff=k_eff, shear=shear)
+
+    def max_strut_buckling(self, length=1, k_eff=1.0, shear=0):
+        """Largest buckling utilisation of any present strut (0 when no strut is compressed or none is present)."""
+        util = self.strut_buckling(length, k_eff, shear)["util"]
+        util = util[~np.isnan(util)]                 # (length = 1: struts without a middle segment are absent)
+        return float(util.max()) if util.size else 0.0
+
     # ------------------------------------------------------------------------------------------------
     # Domain decomposition (lattice_sim.py:846-919, 1111-1252)
     # ------------------------------------------------------------------------------------------------
