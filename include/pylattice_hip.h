@@ -423,6 +423,37 @@ int pl_solve_multi(pl_handle h, int32_t n_rhs, const double *ubar, const double 
 int pl_schur_block(pl_handle h, const int32_t *boundary_nodes, int32_t nb, double rtol, int32_t max_iter,
                    int32_t block, double *S);
 
+/* ---- global linear buckling (csrc/pl_geom.h) --------------------------------------------------------
+ * With u the equilibrium of the applied loads: the smallest lambda > 0 with (K + lambda K_g(u)) phi = 0, K_g the geometric
+ * stiffness of the struts' axial forces in u - the load factor at which cells or the whole lattice buckle together, which the
+ * per-strut check of pl_buckling does not see.  Limits: single-GPU FEM handles only (the cases of pl_spmv_multi).  K_g takes
+ * each strut as ONE Hermite-cubic element between its two lattice nodes, loaded by the record's total axial force: penalised
+ * end zones and sub-element counts do not enter, a strut buckling between its own two joints cannot be represented and is
+ * over-estimated (pl_buckling covers that failure).  Linearised prebuckling only.  A spectrum dominated by tension
+ * (|mu_min| >> mu_max, mu = 1 / lambda) converges slowly under the shift of the iteration; it stays correct, and max_outer
+ * bounds it. */
+/* y_j = K_g(u) x_j (masked != 0: P K_g P x_j), j < n_rhs <= PL_MULTI_MAX; u[6N] or NULL = solution of the last
+ * pl_solve; x, y: [n_rhs][6N] host arrays.  Test hook and building block. */
+int pl_geom_spmv_multi(pl_handle h, const double *u, int32_t n_rhs, int masked, const double *x, double *y);
+/* The n_modes smallest POSITIVE load factors of (K + lambda K_g(u)) phi = 0 on the free dofs of the last pl_set_bc,
+ * ascending, and their modes (0 on fixed dofs, phi_i^T K phi_j = delta_ij, largest component positive).
+ * Shifted block subspace iteration on G phi = mu K phi, G = -K_g, with n_sub columns (a multiple of 4 in 4 ... 32; 0 =
+ * max(8, 2 n_modes rounded up to a multiple of 4)), 1 <= n_modes <= n_sub / 2; every outer step solves its n_sub columns in
+ * one Jacobi-PCG pass (rtol, max_iter as pl_solve_multi) and ends with a Rayleigh-Ritz step on products that are applied,
+ * so the Ritz values are true Rayleigh quotients.  It stops when the n_modes largest Ritz values have changed by less than
+ * tol relatively between two steps (values below 1e-10 of the largest magnitude count as zero).
+ * Fewer than n_modes positive factors may exist (every strut in tension, u = 0): n_found says how many were found, the rest
+ * of every output is NaN, and the call returns PL_OK.  PL_ERR_NOCONV when max_outer is reached (outputs still written).
+ * PL_ERR_STATE in the cases of pl_spmv_multi, on a handle with pl_set_periodic constraints, before pl_set_bc, and for
+ * u = NULL without a pl_solve; PL_ERR_ARG for bad sizes or null outputs.  The handle's single-column state (last solution,
+ * warm-start history, statistics) is left untouched. */
+int pl_buckling_modes(pl_handle h, const double *u /*[6N] or NULL*/, int32_t n_modes, int32_t n_sub,
+                      double rtol, int32_t max_iter,      /* inner PCG, as pl_solve_multi */
+                      double tol, int32_t max_outer,      /* outer: largest relative change of the wanted Ritz values */
+                      double *load_factor /*[n_modes]*/, double *modes /*[n_modes][6N] or NULL*/,
+                      double *residual /*[n_modes] or NULL: |K phi + lambda K_g phi| / |K phi|, free dofs*/,
+                      int32_t *n_found, int32_t *outer_iterations);
+
 /* The same condensation, exact and batched, without a handle: n_inst small lattices of ONE topology (a unit cell at
  * several radius sets - the exact DDM mode, Schur datasets), each condensed by a dense Cholesky of K_II in one workgroup
  * of a single launch.  Material, pen_coef and device come from o (stamped by pl_default_opts; the solver fields are

@@ -23,7 +23,7 @@ EXPORTS = ["pl_default_opts", "pl_opts_size", "pl_stats_size", "pl_abi_version",
            "pl_update_radii", "pl_set_multiplicity", "pl_update_segments", "pl_assemble", "pl_assemble_bsr", "pl_get_bsr", "pl_spmv",
            "pl_spmv_free", "pl_spmv_bsr", "pl_solve", "pl_reactions", "pl_sens", "pl_energy", "pl_node_mod", "pl_schur",
            "pl_stress", "pl_stress_pnorm", "pl_buckling", "pl_buckling_pnorm",
-           "pl_spmv_multi", "pl_solve_multi", "pl_schur_block",
+           "pl_spmv_multi", "pl_solve_multi", "pl_schur_block", "pl_geom_spmv_multi", "pl_buckling_modes",
            "pl_schur_cells", "pl_cells_recover", "pl_get_records", "pl_time_kernel", "pl_algorithmic_bytes", "pl_forget_history", "pl_debug_spd_solve", "pl_dist_unique_id_bytes",
            "pl_dist_unique_id", "pl_dist_loopback_id", "pl_dist_abort", "pl_dist_init", "pl_dist_set_peers", "pl_generate_lattice", "pl_lattice_fetch",
            "pl_lattice_free", "pl_penalize", "pl_boundary_index", "pl_boundary_index_rows"]
@@ -96,6 +96,8 @@ def load_library(path: str | None = None):
            "pl_buckling": [V, V, I32, D, I32, V, V, V], "pl_buckling_pnorm": [V, V, I32, D, I32, D, V, V, V, V],
            "pl_schur": [V, V, I32, D, I32, V], "pl_spmv_multi": [V, I32, I32, V, V],
            "pl_solve_multi": [V, I32, V, V, D, I32, V, V], "pl_schur_block": [V, V, I32, D, I32, I32, V],
+           "pl_geom_spmv_multi": [V, V, I32, I32, V, V],
+           "pl_buckling_modes": [V, V, I32, I32, D, I32, D, I32, V, V, V, V, V],
            "pl_schur_cells": [V, I32, I32, I32, V, I32, V, V, V, V, V, V, V],
            "pl_cells_recover": [V, I32, I32, I32, V, I32, V, V, V, V, V, V, V, V, V, V, V],
            "pl_get_records": [V, V], "pl_time_kernel": [V, I32, I32, V],
@@ -730,6 +732,56 @@ class HipLattice:
         _check(self._lib, rc, allow=() if raise_on_noconv else (PL_ERR_NOCONV,))
         return u.reshape(k, self.n_nodes, 6), stats
 
+    # -- global linear buckling ---------------------------------------------------------------------------
+    def geom_spmv_multi(self, X, u=None, masked=False):
+        """Y[j] = K_g(u) X[j] for k columns in one launch (pl_geom_spmv_multi), K_g the geometric stiffness of the struts'
+        axial forces in u (None: the solution of the last solve()); masked: P K_g P X[j] under the mask of set_bc.
+        X (k, N, 6) or (k, 6 N); returns (k, N, 6)."""
+        x = self._columns("X", X)
+        u = None if u is None else _f64(np.asarray(u).reshape(-1), 6 * self.n_nodes)
+        y = np.empty_like(x)
+        _check(self._lib, self._lib.pl_geom_spmv_multi(self._h, _ptr(u), x.shape[0], int(bool(masked)), _ptr(x), _ptr(y)))
+        return y.reshape(x.shape[0], self.n_nodes, 6)
+
+    def buckling_modes(self, n_modes=4, u=None, n_sub=0, rtol=1e-10, max_iter=200000, tol=1e-9, max_outer=200,
+                       raise_on_noconv=True):
+        """The n_modes smallest positive load factors of (K + lambda K_g(u)) phi = 0 on the free dofs of set_bc and their
+        modes (pl_buckling_modes): dict with load_factor (n_modes,) ascending, modes (n_modes, N, 6) (phi^T K phi = 1,
+        largest component positive), residual (n_modes,), n_found and outer_iterations; entries beyond n_found are NaN.
+        u = None: the solution of the last solve().  n_sub: columns of the subspace iteration (0 = the library's choice);
+        rtol, max_iter: its inner PCG; tol, max_outer: its stopping rule."""
+        u = None if u is None else _f64(np.asarray(u).reshape(-1), 6 * self.n_nodes)
+        n_modes = int(n_modes)
+        lam = np.empty(max(n_modes, 0), np.float64)
+        modes = np.empty((max(n_modes, 0), self.n_nodes, 6), np.float64)
+        res = np.empty(max(n_modes, 0), np.float64)
+        found, outer = C.c_int32(), C.c_int32()
+        rc = self._lib.pl_buckling_modes(self._h, _ptr(u), n_modes, int(n_sub), float(rtol), int(max_iter), float(tol),
+                                         int(max_outer), _ptr(lam), _ptr(modes), _ptr(res), C.byref(found), C.byref(outer))
+        _check(self._lib, rc, allow=() if raise_on_noconv else (PL_ERR_NOCONV,))
+        return {"load_factor": lam, "modes": modes, "residual": res, "n_found": found.value,
+                "outer_iterations": outer.value}
+
+    def geom_spmv_multi_host(self, X, u, masked=False, fixed=None):
+        """The numpy restatement of ``geom_spmv_multi`` (geometric_host.geometric_apply) on this handle's records; the
+        masked product needs the mask ``fixed`` (N, 6) that was given to set_bc."""
+        from . import geometric_host as GH
+        if masked and fixed is None:
+            raise ValueError("the masked product needs the mask given to set_bc")
+        x = self._columns("X", X).reshape(-1, self.n_nodes, 6)
+        return GH.geometric_apply(self.records(), self.beam_conn, u, x, fixed if masked else None)
+
+    def buckling_modes_host(self, u, fixed, n_modes=4, n_sub=0, tol=1e-9, max_outer=200, dense=False):
+        """The scipy restatement of ``buckling_modes`` on this handle's records: geometric_host.buckling_modes_subspace
+        (exact solves), or buckling_modes_dense with dense=True.  fixed (N, 6): the mask that was given to set_bc."""
+        from . import geometric_host as GH
+        rec = self.records()
+        K = GH.elastic_matrix(rec, self.beam_conn, self.n_nodes)
+        Kg = GH.geometric_matrix(rec, self.beam_conn, u, self.n_nodes)
+        if dense:
+            return GH.buckling_modes_dense(K, Kg, fixed, n_modes)
+        return GH.buckling_modes_subspace(K, Kg, fixed, n_modes, n_sub, tol, max_outer)
+
     # -- measurement ------------------------------------------------------------------------------------
     def time_kernel(self, which, reps=20):
         ms = C.c_double()
@@ -793,7 +845,7 @@ class HipLattice:
 # the reference wraps every hot-path method in @timing.category(..) @timing.timeit; here the
 # C-ABI calls are the hot path: host wall clock per call, plus the device's own HIP-event times (see solve)
 for _name in ("assemble", "assemble_bsr", "get_bsr", "solve", "set_bc", "spmv", "spmv_free", "spmv_bsr", "reactions",
-              "sens", "stress", "stress_pnorm", "buckling", "buckling_pnorm", "energy", "schur", "spmv_multi", "solve_multi", "update_radii", "update_segments", "records"):
+              "sens", "stress", "stress_pnorm", "buckling", "buckling_pnorm", "energy", "schur", "spmv_multi", "solve_multi", "geom_spmv_multi", "buckling_modes", "update_radii", "update_segments", "records"):
     _f = getattr(HipLattice, _name, None)
     if _f is not None:
         _f._timing_category = "hip"

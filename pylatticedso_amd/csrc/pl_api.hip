@@ -5,6 +5,7 @@
 #include "pl_multi.h"
 #include "pl_stress.h"
 #include "pl_buckling.h"
+#include "pl_geom.h"
 
 
 // ==========================================================================================================
@@ -1952,6 +1953,192 @@ int pl_schur_block(pl_handle h, const int32_t *boundary_nodes, int32_t nb, doubl
   PL_HIP(hipStreamSynchronize(h->stream));
   if (bad) return fail(PL_ERR_NAN, "pl_schur_block: NaN/Inf in a residual norm");
   if (missed) return fail(PL_ERR_NOCONV, "pl_schur_block: " + std::to_string(missed) + " column(s) did not reach rtol within max_iter");
+  return PL_OK;
+}
+
+// ---- global linear buckling (pl_geom.h) --------------------------------------------------------------------------------
+namespace {
+// what the two geometric calls share after their argument checks: the handle checks and the geometric records of u
+int geom_begin(pl_handle h, const char *who, const double *u, bool need_bc, GeomWs **g) {
+  if (int rc = multi_check_handle(h, who, need_bc)) return rc;
+  if (!u && !(h->usol.p && h->usol_valid))
+    return fail(PL_ERR_STATE, std::string(who) + ": u = NULL needs a pl_solve on this handle first");
+  PL_HIP(hipSetDevice(h->opt.device));
+  const double *u_dev = h->usol.p;
+  if (u) {
+    std::vector<double> stage;
+    if (int rc = upload6(h, u, h->tmp.p, stage)) return rc;
+    u_dev = h->tmp.p;
+  }
+  if (int rc = geom_ws(h, g)) return rc;
+  return launch_geom_records(h, *g, u_dev);
+}
+}  // namespace
+
+int pl_geom_spmv_multi(pl_handle h, const double *u, int32_t n_rhs, int masked, const double *x, double *y) {
+  if (!valid(h) || !x || !y) return fail(PL_ERR_ARG, "pl_geom_spmv_multi: null argument");
+  if (n_rhs < 1 || n_rhs > PL_MULTI_MAX) return fail(PL_ERR_ARG, "pl_geom_spmv_multi: n_rhs must be 1 ... PL_MULTI_MAX");
+  GeomWs *g = nullptr;
+  if (int rc = geom_begin(h, "pl_geom_spmv_multi", u, masked != 0, &g)) return rc;
+  const MultiShape s = multi_shape(h, n_rhs);
+  MultiWs *w = nullptr;
+  if (int rc = multi_ws(h, s, false, &w)) return rc;
+  if (int rc = multi_upload(h, w, s, x, w->F.p, masked ? -1 : 0)) return rc;
+  const bool timing = std::getenv("PL_TIMING") != nullptr;
+  if (timing) PL_HIP(hipEventRecord(h->ev0, h->stream));
+  if (int rc = launch_geom_multi(h, g, s, w->F.p, w->U.p, masked != 0)) return rc;
+  if (timing) {
+    PL_HIP(hipEventRecord(h->ev1, h->stream));
+    PL_HIP(hipEventSynchronize(h->ev1));
+    float ms = 0.f;
+    PL_HIP(hipEventElapsedTime(&ms, h->ev0, h->ev1));
+    std::fprintf(stderr, "[pl_geom_spmv_multi] %-28s %10.4f ms\n", "kernel_hip_event", (double)ms);
+  }
+  return multi_download(h, w, s, w->U.p, y);
+}
+
+int pl_buckling_modes(pl_handle h, const double *u, int32_t n_modes, int32_t n_sub, double rtol, int32_t max_iter, double tol,
+                      int32_t max_outer, double *load_factor, double *modes, double *residual, int32_t *n_found,
+                      int32_t *outer_iterations) {
+  if (!valid(h) || !load_factor || !n_found || !outer_iterations) return fail(PL_ERR_ARG, "pl_buckling_modes: null argument");
+  if (n_sub == 0) n_sub = std::max(8, (2 * std::max(n_modes, 1) + 3) / 4 * 4);
+  if (n_sub < 4 || n_sub > 32 || n_sub % 4 != 0) return fail(PL_ERR_ARG, "pl_buckling_modes: n_sub must be a multiple of 4 in 4 ... 32 (or 0)");
+  if (n_modes < 1 || n_modes > n_sub / 2) return fail(PL_ERR_ARG, "pl_buckling_modes: n_modes must be 1 ... n_sub / 2");
+  if (!(rtol > 0.0) || max_iter <= 0) return fail(PL_ERR_ARG, "pl_buckling_modes: rtol and max_iter must be positive");
+  if (!(tol > 0.0) || max_outer <= 0) return fail(PL_ERR_ARG, "pl_buckling_modes: tol and max_outer must be positive");
+  if (valid(h) && h->n_per_groups > 0)
+    return fail(PL_ERR_STATE, "pl_buckling_modes: not available with periodic constraints (pl_set_periodic)");
+  GeomWs *g = nullptr;
+  if (int rc = geom_begin(h, "pl_buckling_modes", u, true, &g)) return rc;
+  const int64_t N = h->N, n6 = N * 6;
+  const MultiShape s = multi_shape(h, n_sub);     // KB = 4, ncol = n_sub
+  const int n = s.ncol;
+  MultiWs *w = nullptr;
+  if (int rc = multi_ws(h, s, true, &w)) return rc;
+  const unsigned nchunk = std::min(grid_stream(n6), 512u);
+  if (int rc = geom_ws_modes(h, g, s, nchunk)) return rc;
+  const size_t vec_bytes = (size_t)s.ncb * s.stride * sizeof(double);
+  const bool timing = std::getenv("PL_TIMING") != nullptr;
+  const auto t_begin = std::chrono::steady_clock::now();
+  PL_HIP(hipMemcpyAsync(g->perm.p, h->perm.data(), (size_t)N * sizeof(int32_t), hipMemcpyHostToDevice, h->stream));
+  PL_HIP(hipStreamSynchronize(h->stream));       // (perm is pageable host memory)
+  PL_HIP(hipMemsetAsync(w->UB.p, 0, vec_bytes, h->stream));     // zero prescribed values in every solve
+  const dim3 gs(grid_stream(n6), (unsigned)s.ncb);
+  hipLaunchKernelGGL((pl::k_geom_start<4>), gs, dim3(pl::kBlock), 0, h->stream, n6, (const int32_t *)g->perm.p,
+                     (const uint8_t *)h->fixedbits.p, g->Y.p, s.stride);
+  PL_HIP(hipGetLastError());
+
+  const double ninf = -std::numeric_limits<double>::infinity();
+  std::vector<double> Mh((size_t)2 * n * n), mu, Cm, cur(n_modes, ninf), prev(n_modes, ninf);
+  std::vector<double> status((size_t)pl::M_ST_COUNT * s.ncol);
+  double mu_low = 0.0, ztol = 0.0, ms_solve = 0.0;
+  int rank = 0, outer = 0;
+  bool converged = false;
+  // Rayleigh-Ritz on span(Y) with products that are applied: X <- Y C, K X <- (K Y) C, K_g X <- (K_g Y) C
+  auto ritz = [&]() -> int {
+    if (int rc = launch_spmv_multi(h, s, h->fixedbits.p, g->Y.p, g->KY.p, true, nullptr)) return rc;
+    if (int rc = launch_geom_multi(h, g, s, g->Y.p, g->GY.p, true)) return rc;
+    if (int rc = launch_gram(h, g, s, nchunk, g->Y.p, g->KY.p, g->M.p)) return rc;
+    if (int rc = launch_gram(h, g, s, nchunk, g->Y.p, g->GY.p, g->M.p + (size_t)n * n)) return rc;
+    PL_HIP(hipMemcpyAsync(Mh.data(), g->M.p, Mh.size() * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+    PL_HIP(hipStreamSynchronize(h->stream));
+    for (double v : Mh)
+      if (!std::isfinite(v)) return fail(PL_ERR_NAN, "pl_buckling_modes: NaN/Inf in a projected matrix");
+    std::vector<double> Km(Mh.begin(), Mh.begin() + (size_t)n * n), Gm((size_t)n * n);
+    for (size_t q = 0; q < Gm.size(); ++q) Gm[q] = -Mh[(size_t)n * n + q];      // G = -K_g
+    rank = ritz_host(n, Km, Gm, mu, Cm);
+    PL_HIP(hipMemcpyAsync(g->C.p, Cm.data(), Cm.size() * sizeof(double), hipMemcpyHostToDevice, h->stream));
+    PL_HIP(hipStreamSynchronize(h->stream));     // (Cm is pageable host memory)
+    if (int rc = launch_combine(h, g, s, g->Y.p, g->X.p)) return rc;
+    if (int rc = launch_combine(h, g, s, g->KY.p, g->KX.p)) return rc;
+    if (int rc = launch_combine(h, g, s, g->GY.p, g->GX.p)) return rc;
+    double scale = 0.0;
+    for (int j = 0; j < rank; ++j) scale = std::max(scale, std::fabs(mu[j]));
+    ztol = 1e-10 * scale;
+    prev = cur;
+    for (int j = 0; j < n_modes; ++j) cur[j] = j < rank ? (std::fabs(mu[j]) <= ztol ? 0.0 : mu[j]) : ninf;
+    if (rank > 0) mu_low = std::min(mu_low, mu[rank - 1]);
+    return PL_OK;
+  };
+  if (int rc = ritz()) return rc;                 // K-orthonormalises the start vectors
+  while (rank > 0) {
+    if (outer == max_outer) break;
+    const double sigma = std::max(0.0, -mu_low);
+    // Y = K^-1 (G X) + sigma X: one multi-column solve with K_g X as loads, W = K^-1 K_g X = -K^-1 G X
+    const auto t0 = std::chrono::steady_clock::now();
+    if (int rc = pcg_solve_multi(h, w, s, h->fixedbits.p, g->GX.p, rtol, max_iter, status.data())) return rc;
+    ms_solve += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    hipLaunchKernelGGL(pl::k_multi_axpby, dim3(grid_stream((int64_t)s.ncb * s.stride / 2)), dim3(pl::kBlock), 0, h->stream,
+                       (int64_t)s.ncb * s.stride / 2, -1.0, (const double *)w->U.p, sigma, (const double *)g->X.p, g->Y.p);
+    PL_HIP(hipGetLastError());
+    if (int rc = ritz()) return rc;
+    ++outer;
+    double change = 0.0;
+    for (int j = 0; j < n_modes; ++j) {
+      if (cur[j] == prev[j]) continue;
+      change = std::max(change, (cur[j] != 0.0 && std::isfinite(cur[j]) && std::isfinite(prev[j]))
+                                    ? std::fabs(cur[j] - prev[j]) / std::fabs(cur[j])
+                                    : std::numeric_limits<double>::infinity());
+    }
+    if (change < tol) { converged = true; break; }
+  }
+  if (rank == 0) converged = true;                // G vanishes on the free dofs: no factor exists
+  int found = 0;
+  while (found < n_modes && cur[found] > 0.0) ++found;
+  *n_found = found;
+  *outer_iterations = outer;
+  const double nan = std::numeric_limits<double>::quiet_NaN();
+  for (int j = 0; j < n_modes; ++j) load_factor[j] = j < found ? 1.0 / cur[j] : nan;
+  if (residual)
+    for (int j = 0; j < n_modes; ++j) residual[j] = nan;
+  if (modes) std::fill(modes, modes + (size_t)n_modes * n6, nan);
+  if (found > 0 && (modes || residual)) {
+    MultiShape sd = s;                            // the column blocks that hold the found modes
+    sd.n_rhs = found;
+    sd.ncb = (found + s.KB - 1) / s.KB;
+    std::vector<double> own;
+    double *phi = modes;
+    if (!phi) {
+      own.resize((size_t)found * n6);
+      phi = own.data();
+    }
+    if (int rc = multi_download(h, w, sd, g->X.p, phi)) return rc;
+    if (residual) {
+      std::vector<double> Kp((size_t)found * n6), Gp((size_t)found * n6);
+      if (int rc = multi_download(h, w, sd, g->KX.p, Kp.data())) return rc;
+      if (int rc = multi_download(h, w, sd, g->GX.p, Gp.data())) return rc;
+      for (int j = 0; j < found; ++j) {
+        double rr = 0.0, kk = 0.0;
+        const double lam = load_factor[j];
+        for (int64_t e = 0; e < n6; ++e) {
+          const double k = Kp[(size_t)j * n6 + e], r = k + lam * Gp[(size_t)j * n6 + e];
+          rr += r * r;
+          kk += k * k;
+        }
+        residual[j] = std::sqrt(rr / kk);
+      }
+    }
+    if (modes)
+      for (int j = 0; j < found; ++j) {           // largest component positive
+        double *p = modes + (size_t)j * n6;
+        int64_t big = 0;
+        for (int64_t e = 1; e < n6; ++e)
+          if (std::fabs(p[e]) > std::fabs(p[big])) big = e;
+        if (p[big] < 0.0)
+          for (int64_t e = 0; e < n6; ++e) p[e] = -p[e];
+      }
+  }
+  if (timing) {
+    PL_HIP(hipStreamSynchronize(h->stream));
+    const double ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_begin).count();
+    std::fprintf(stderr, "[pl_buckling_modes] %-28s %10.4f ms\n", "whole_call_host_clock", ms);
+    std::fprintf(stderr, "[pl_buckling_modes] %-28s %10d\n", "outer_steps", outer);
+    if (outer > 0) {
+      std::fprintf(stderr, "[pl_buckling_modes] %-28s %10.4f ms\n", "outer_step_mean_host_clock", ms / outer);
+      std::fprintf(stderr, "[pl_buckling_modes] %-28s %10.4f ms\n", "inner_solve_mean_host_clock", ms_solve / outer);
+    }
+  }
+  if (!converged) return fail(PL_ERR_NOCONV, "pl_buckling_modes: max_outer reached before the Ritz values settled");
   return PL_OK;
 }
 

@@ -655,6 +655,22 @@ class LatticeSim(LatticeViews):
         util = util[~np.isnan(util)]                 # (length = 1: struts without a middle segment are absent)
         return float(util.max()) if util.size else 0.0
 
+    def global_buckling(self, n_modes=4, **kw):
+        """Global linear buckling for the displacements of the last solve_FEM_FenicsX, on the device (pl_buckling_modes):
+        the n_modes smallest positive factors lambda by which the applied loads may grow before cells or the whole lattice
+        buckle together, (K + lambda K_g(u)) phi = 0, and their modes.  Every strut enters K_g as one element between its two
+        joints: a strut buckling on its own is the business of ``strut_buckling``.  Keyword arguments (n_sub, rtol, max_iter,
+        tol, max_outer) go to ``HipLattice.buckling_modes``.  Sets ``buckling_load_factors`` (n_modes,) and
+        ``buckling_modes`` (n_modes, n_nodes, 6) - NaN beyond the factors that exist - and returns the device call's dict."""
+        if self._device is None or getattr(self, "_compat_rows", False):
+            raise RuntimeError("global_buckling needs a solve_FEM_FenicsX on this lattice first (default strut model; the "
+                               "reference_compat model has no device buckling pass)")
+        model = getattr(self, "_model", None)       # (as strut_stress: LatticeOpti's equilibrium field is passed explicitly)
+        out = self._device.buckling_modes(n_modes, None if model is None else model._u_solver, **kw)
+        self.buckling_load_factors = out["load_factor"]
+        self.buckling_modes = out["modes"]
+        return out
+
     # ------------------------------------------------------------------------------------------------
     # Domain decomposition (lattice_sim.py:846-919, 1111-1252)
     # ------------------------------------------------------------------------------------------------
