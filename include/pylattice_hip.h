@@ -493,6 +493,16 @@ int pl_cells_recover(const pl_opts_t *o, int32_t n_inst, int32_t n_nodes, int32_
 /* Debug / test access to the condensed per-strut records: rec[8*B] = (a, c, e1, e2, e3, dx, dy, dz). */
 int pl_get_records(pl_handle h, double *rec);
 
+/* Debug / test access to the solver's partition, caller's node numbering; any pointer may be NULL; -1 where absent.
+ * The spans of the preconditioner's modes are sets of nodes, so a host restatement of M^-1 (oracle/precond_oracle.py) needs
+ * exactly this and nothing else of the solver's state.  [n_nodes] each.
+ * FEM handles: tile_of_node = the K*p tile (the tile level's blocks), agg_of_node = the aggregate of the dense level
+ * (precond 2 / 3 / 4), local_agg_of_node = the aggregate of the rank-local level (precond 4), eliminated = 1 on the nodes
+ * opts.condense takes out of the CG (chosen by pl_set_bc, valid after pl_assemble; which solver forms honour it:
+ * pl_stats_t.condensed_nodes).  DDM handles after pl_ddm_set_geometry: agg_of_node = the aggregate of precond = 4. */
+int pl_debug_partition(pl_handle h, int32_t *tile_of_node, int32_t *agg_of_node, int32_t *local_agg_of_node,
+                       uint8_t *eliminated);
+
 /* Measurement hooks (bench.py): run `reps` launches of one kernel on the handle's stream between two HIP
  * events and return the average milliseconds.  which: 0 = K*p (PCG operator), 1 = record build,
  * 2 = BSR fill, 3 = one full PCG iteration, 4 = BSR SpMV; on a multi-GPU handle also 5 = the interface all-reduce of

@@ -24,7 +24,7 @@ EXPORTS = ["pl_default_opts", "pl_opts_size", "pl_stats_size", "pl_abi_version",
            "pl_spmv_free", "pl_spmv_bsr", "pl_solve", "pl_reactions", "pl_sens", "pl_energy", "pl_node_mod", "pl_schur",
            "pl_stress", "pl_stress_pnorm", "pl_buckling", "pl_buckling_pnorm",
            "pl_spmv_multi", "pl_solve_multi", "pl_schur_block", "pl_geom_spmv_multi", "pl_buckling_modes",
-           "pl_schur_cells", "pl_cells_recover", "pl_get_records", "pl_time_kernel", "pl_algorithmic_bytes", "pl_forget_history", "pl_debug_spd_solve", "pl_dist_unique_id_bytes",
+           "pl_schur_cells", "pl_cells_recover", "pl_get_records", "pl_debug_partition", "pl_time_kernel", "pl_algorithmic_bytes", "pl_forget_history", "pl_debug_spd_solve", "pl_dist_unique_id_bytes",
            "pl_dist_unique_id", "pl_dist_loopback_id", "pl_dist_abort", "pl_dist_init", "pl_dist_set_peers", "pl_generate_lattice", "pl_lattice_fetch",
            "pl_lattice_free", "pl_penalize", "pl_boundary_index", "pl_boundary_index_rows"]
 
@@ -100,7 +100,7 @@ def load_library(path: str | None = None):
            "pl_buckling_modes": [V, V, I32, I32, D, I32, D, I32, V, V, V, V, V],
            "pl_schur_cells": [V, I32, I32, I32, V, I32, V, V, V, V, V, V, V],
            "pl_cells_recover": [V, I32, I32, I32, V, I32, V, V, V, V, V, V, V, V, V, V, V],
-           "pl_get_records": [V, V], "pl_time_kernel": [V, I32, I32, V],
+           "pl_get_records": [V, V], "pl_debug_partition": [V, V, V, V, V], "pl_time_kernel": [V, I32, I32, V],
            "pl_algorithmic_bytes": [V, V], "pl_forget_history": [V], "pl_debug_spd_solve": [I32, I32, V, V, V, V, I32], "pl_dist_unique_id_bytes": [], "pl_dist_unique_id": [V], "pl_dist_loopback_id": [V], "pl_dist_abort": [V],
            "pl_dist_init": [V, I32, I32, V, V, V, I32, I32], "pl_dist_set_peers": [V, V],
            "pl_generate_lattice": [I64, V, V, V, I32, I32, V, V, V, V], "pl_lattice_fetch": [V] * 12,
@@ -546,6 +546,18 @@ class HipLattice:
         rec = np.empty((self.n_beams, 8), np.float64)
         _check(self._lib, self._lib.pl_get_records(self._h, _ptr(rec)))
         return rec
+
+    def partition(self):
+        """The solver's partition in the caller's node numbering (pl_debug_partition): dict of (N,) arrays - ``tile`` (K*p
+        tile = block of the tile level), ``agg`` (aggregate of the dense level), ``local_agg`` (aggregate of the rank-local
+        level of precond = 4), int32 with -1 where the handle has no such level, and ``eliminated`` (bool: nodes that
+        opts.condense takes out of the CG; after assemble()).  A DDM handle with node positions reports the aggregates of
+        its precond = 4 in ``agg``."""
+        n = self.n_nodes
+        tile, agg, loc = np.empty(n, np.int32), np.empty(n, np.int32), np.empty(n, np.int32)
+        elim = np.empty(n, np.uint8)
+        _check(self._lib, self._lib.pl_debug_partition(self._h, _ptr(tile), _ptr(agg), _ptr(loc), _ptr(elim)))
+        return {"tile": tile, "agg": agg, "local_agg": loc, "eliminated": elim.astype(bool)}
 
     # -- operator ---------------------------------------------------------------------------------------
     def _vec_op(self, fn, x):

@@ -2386,6 +2386,46 @@ int pl_get_records(pl_handle h, double *rec) {
   return PL_OK;
 }
 
+int pl_debug_partition(pl_handle h, int32_t *tile_of_node, int32_t *agg_of_node, int32_t *local_agg_of_node,
+                       uint8_t *eliminated) {
+  if (!valid(h)) return fail(PL_ERR_ARG, "pl_debug_partition: null handle");
+  PL_HIP(hipSetDevice(h->opt.device));
+  const int64_t N = h->N;
+  std::vector<int32_t> tmp((size_t)N);
+  // device array (device numbering) -> caller numbering; absent: -1 everywhere
+  auto fetch = [&](const int32_t *dev, int32_t *out) -> int {
+    if (!out) return PL_OK;
+    if (!dev) {
+      std::fill(out, out + N, -1);
+      return PL_OK;
+    }
+    PL_HIP(hipMemcpy(tmp.data(), dev, (size_t)N * sizeof(int32_t), hipMemcpyDeviceToHost));
+    for (int64_t i = 0; i < N; ++i) out[h->perm[i]] = tmp[(size_t)i];
+    return PL_OK;
+  };
+  if (tile_of_node) {
+    std::fill(tile_of_node, tile_of_node + N, -1);
+    if (h->opkind == 0)
+      for (size_t t = 0; t + 1 < h->h_tile_start.size(); ++t)
+        for (int32_t i = h->h_tile_start[t]; i < h->h_tile_start[t + 1]; ++i) tile_of_node[h->perm[i]] = (int32_t)t;
+  }
+  int rc = fetch(h->opkind == 1 ? (h->dd2_plan ? (const int32_t *)h->dd2_agg.p : (const int32_t *)nullptr)
+                                : (h->coarse.enabled ? (const int32_t *)h->coarse.agg_of_node.p : (const int32_t *)nullptr),
+                 agg_of_node);
+  if (rc) return rc;
+  rc = fetch(h->coarseL.enabled ? (const int32_t *)h->coarseL.agg_of_node.p : (const int32_t *)nullptr, local_agg_of_node);
+  if (rc) return rc;
+  if (eliminated) {
+    std::fill(eliminated, eliminated + N, (uint8_t)0);
+    if (h->n_cond > 0 && h->cond_ready && h->cflag.p) {
+      std::vector<uint8_t> flag((size_t)N);
+      PL_HIP(hipMemcpy(flag.data(), h->cflag.p, (size_t)N, hipMemcpyDeviceToHost));
+      for (int64_t i = 0; i < N; ++i) eliminated[h->perm[i]] = flag[(size_t)i];
+    }
+  }
+  return PL_OK;
+}
+
 int pl_algorithmic_bytes(pl_handle h, double *out3) {
   if (!valid(h) || !out3) return fail(PL_ERR_ARG, "pl_algorithmic_bytes: null argument");
   // SURVEY.md 8(d) with the storage widths the next pl_solve really uses: records are fp64 in every mode (w = 8); the PCG

@@ -940,9 +940,12 @@ int pcg_solve_cg1(pl_context *c, const double *f_dev, const double *Kubar_dev, d
   std::vector<double> h_hist(chunk);
   int k = 0, next = chunk, k_prev = 0;
   double rr_prev = bb;
-  // hist[k] = ||r_k||^2, the residual BEFORE update k (it is reduced together with that iteration's other sums)
-  while (k < max_iter + 1) {
-    const int todo = std::min(next, max_iter + 1 - k);
+  // hist[k] = ||r_k||^2, the residual BEFORE update k (it is reduced together with that iteration's other sums).  Exactly
+  // max_iter updates are applied: the residual after the last one is read from the block the next update would have used
+  // (until this was counted right the loop ran max_iter + 1 updates to learn it, and a solve that hit max_iter handed back
+  // x_(max_iter + 1) under iterations = max_iter: tests/test_gpu_precond.py)
+  while (k < max_iter) {
+    const int todo = std::min(next, max_iter - k);
     for (int j = 0; j < todo; ++j) {
       const int it = k + j, cur = it & 1, nxt = (it + 1) & 1;
       if (tm12) PL_CG1_UPD(false, 12, cur, nxt, it);
@@ -977,7 +980,20 @@ int pcg_solve_cg1(pl_context *c, const double *f_dev, const double *Kubar_dev, d
       k_prev = k;
     }
   }
-  if (!st->converged) st->iterations = std::min(k, max_iter);
+  if (!st->converged) {
+    double h_rr[pl::kSlots], rr = 0.0;       // ||r_k||^2 after update k - 1: slot 2 of the reduced block of iteration k
+    PL_HIP(hipMemcpyAsync(h_rr, blk[k & 1] + ncp + 2 * pl::kSlots, sizeof(h_rr), hipMemcpyDeviceToHost, c->stream));
+    PL_HIP(hipStreamSynchronize(c->stream));
+    for (int q = 0; q < pl::kSlots; ++q) rr += h_rr[q];
+    if (std::isnan(rr) || std::isinf(rr)) return fail(PL_ERR_NAN, "NaN/Inf in the PCG residual");
+    st->rel_residual = std::sqrt(rr / bb);
+    st->iterations = k;
+    if (rr <= thresh) {
+      st->converged = 1;
+      st->info = 0.0;
+      st->stop_reason = 0.0;
+    }
+  }
 #undef PL_CG1_UPD
   return PL_OK;
 }
