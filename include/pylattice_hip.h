@@ -516,6 +516,16 @@ int pl_time_kernel(pl_handle h, int which, int reps, double *avg_ms);
  * storage widths the next pl_solve uses: strut records and the explicit K are fp64 in every mode, the PCG vectors are 4 bytes
  * wide where opts.precision stores them in fp32 (precision 1: all of them; 2: p and K*p). */
 int pl_algorithmic_bytes(pl_handle h, double *out3);
+/* What the vector kernels of the multi-level PCG read per node on this handle (node words): instead of
+ * 24 bytes of Jacobi weights, 12 bytes of lever arm and the Dirichlet bits, one 4-byte word {rx, ry, rz, class} where the
+ * lattice allows it.  The two halves are independent:
+ *   classes_on  1 if the last pl_assemble found at most 256 distinct rows {six fp32 weights, Dirichlet bits} and every node
+ *               matched its row bit for bit (0: too many, an attempt skipped after earlier failures, no assembly yet)
+ *   n_classes   rows counted by the last attempt (may exceed 256 when classes_on = 0; 0 when no attempt was made)
+ *   bytes_on    1 if every lever arm is a signed byte in units of 2^-byte_exp, exactly (decided at pl_create)
+ *   byte_exp    that exponent, 0 .. 8; -1 when bytes_on = 0
+ * Any pointer may be null.  Everything is 0 / -1 with PL_NODE_WORDS=0, on multi-GPU handles and with precond = 4. */
+int pl_node_words_info(pl_handle h, int *classes_on, int *n_classes, int *bytes_on, int *byte_exp);
 /* Forget what earlier solves taught this handle: the iteration count that places the first look at the residual history of
  * the next solve (pl_solve) and the previous solution a warm start would begin from.  bench.py uses it
  * to report the cold value of a loop of identical solves beside the ordinary one. */

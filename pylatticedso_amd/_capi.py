@@ -24,7 +24,7 @@ EXPORTS = ["pl_default_opts", "pl_opts_size", "pl_stats_size", "pl_abi_version",
            "pl_spmv_free", "pl_spmv_bsr", "pl_solve", "pl_reactions", "pl_sens", "pl_energy", "pl_node_mod", "pl_schur",
            "pl_stress", "pl_stress_pnorm", "pl_buckling", "pl_buckling_pnorm",
            "pl_spmv_multi", "pl_solve_multi", "pl_schur_block", "pl_geom_spmv_multi", "pl_buckling_modes",
-           "pl_schur_cells", "pl_cells_recover", "pl_get_records", "pl_debug_partition", "pl_time_kernel", "pl_algorithmic_bytes", "pl_forget_history", "pl_debug_spd_solve", "pl_dist_unique_id_bytes",
+           "pl_schur_cells", "pl_cells_recover", "pl_get_records", "pl_debug_partition", "pl_time_kernel", "pl_algorithmic_bytes", "pl_node_words_info", "pl_forget_history", "pl_debug_spd_solve", "pl_dist_unique_id_bytes",
            "pl_dist_unique_id", "pl_dist_loopback_id", "pl_dist_abort", "pl_dist_init", "pl_dist_set_peers", "pl_generate_lattice", "pl_lattice_fetch",
            "pl_lattice_free", "pl_penalize", "pl_boundary_index", "pl_boundary_index_rows"]
 
@@ -101,7 +101,7 @@ def load_library(path: str | None = None):
            "pl_schur_cells": [V, I32, I32, I32, V, I32, V, V, V, V, V, V, V],
            "pl_cells_recover": [V, I32, I32, I32, V, I32, V, V, V, V, V, V, V, V, V, V, V],
            "pl_get_records": [V, V], "pl_debug_partition": [V, V, V, V, V], "pl_time_kernel": [V, I32, I32, V],
-           "pl_algorithmic_bytes": [V, V], "pl_forget_history": [V], "pl_debug_spd_solve": [I32, I32, V, V, V, V, I32], "pl_dist_unique_id_bytes": [], "pl_dist_unique_id": [V], "pl_dist_loopback_id": [V], "pl_dist_abort": [V],
+           "pl_algorithmic_bytes": [V, V], "pl_node_words_info": [V, V, V, V, V], "pl_forget_history": [V], "pl_debug_spd_solve": [I32, I32, V, V, V, V, I32], "pl_dist_unique_id_bytes": [], "pl_dist_unique_id": [V], "pl_dist_loopback_id": [V], "pl_dist_abort": [V],
            "pl_dist_init": [V, I32, I32, V, V, V, I32, I32], "pl_dist_set_peers": [V, V],
            "pl_generate_lattice": [I64, V, V, V, I32, I32, V, V, V, V], "pl_lattice_fetch": [V] * 12,
            "pl_lattice_free": [V], "pl_penalize": [I64, V, V, V, D, V, V, V],
@@ -799,6 +799,13 @@ class HipLattice:
         ms = C.c_double()
         _check(self._lib, self._lib.pl_time_kernel(self._h, int(which), int(reps), C.byref(ms)))
         return ms.value
+
+    def node_words_info(self):
+        """What the PCG vector kernels read per node on this handle: {"classes": bool, "n_classes": int, "bytes": bool,
+        "byte_exp": int} (pl_node_words_info)."""
+        v = [C.c_int() for _ in range(4)]
+        _check(self._lib, self._lib.pl_node_words_info(self._h, *[C.byref(x) for x in v]))
+        return {"classes": bool(v[0].value), "n_classes": v[1].value, "bytes": bool(v[2].value), "byte_exp": v[3].value}
 
     def algorithmic_bytes(self):
         out = (C.c_double * 3)()

@@ -929,6 +929,7 @@ void pl_destroy(pl_handle h) {
   pl::dist_destroy(h->dist);
   if (h->pal_host_flags != h->pal_fallback_flags) (void)hipHostFree(h->pal_host_flags);
   if (h->cls_host_flag) (void)hipHostFree(h->cls_host_flag);
+  if (h->dcl_host_flags) (void)hipHostFree(h->dcl_host_flags);
   delete h;
 }
 
@@ -973,6 +974,7 @@ int pl_set_bc(pl_handle h, const uint8_t *fixed, const double *ubar, const doubl
   h->have_bc = true;
   h->coarse.n_fix = -1;
   h->coarseL.n_fix = -1;
+  h->coarse.dcl_ready = false;     // (the classes of the Jacobi weights carry the mask: rebuilt with dinv32 below / in pl_assemble)
   {
     int rcs = select_condensed(h, bits);
     if (rcs) return rcs;
@@ -1002,11 +1004,14 @@ int pl_set_bc(pl_handle h, const uint8_t *fixed, const double *ubar, const doubl
     if (rc) return rc;
     rc = launch_dinv32(h);
     if (rc) return rc;
+    rc = launch_node_classes(h, h->stream, false);      // (dinv32 was written just above)
+    if (rc) return rc;
     rc = agree_condensed(h);
     if (rc) return rc;
     rc = launch_condensed_blocks(h, h->stream);
     if (rc) return rc;
     PL_HIP(hipStreamSynchronize(h->stream));
+    finish_node_classes(h);
     {
       const bool keep = h->pal_ready;        // (the record palette is untouched by a new mask)
       finish_condensed_classes(h);
@@ -1075,6 +1080,7 @@ int pl_update_radii(pl_handle h, const double *beam_radius) {
   PL_HIP(hipMemcpyAsync(h->radius.p, stg, h->B * sizeof(double), hipMemcpyHostToDevice, h->stream));
   PL_HIP(hipStreamSynchronize(h->stream));
   h->assembled = false;
+  h->coarse.dcl_ready = false;     // the Jacobi weights are stale, and their classes with them
   h->have_bsr = false;
   return PL_OK;
 }
@@ -1094,6 +1100,7 @@ int pl_set_multiplicity(pl_handle h, const double *beam_mult) {
     PL_HIP(hipMemcpy(h->mult.p, m.data(), h->B * sizeof(double), hipMemcpyHostToDevice));
   }
   h->assembled = false;
+  h->coarse.dcl_ready = false;     // the Jacobi weights are stale, and their classes with them
   h->have_bsr = false;
   return PL_OK;
 }
@@ -1111,6 +1118,7 @@ int pl_update_segments(pl_handle h, const double *seg_len, const int32_t *seg_ns
   PL_HIP(hipMemcpy(h->seg_len.p, sl.data(), 3 * h->B * sizeof(double), hipMemcpyHostToDevice));
   PL_HIP(hipMemcpy(h->seg_nsub.p, sn.data(), 3 * h->B * sizeof(int32_t), hipMemcpyHostToDevice));
   h->assembled = false;
+  h->coarse.dcl_ready = false;     // the Jacobi weights are stale, and their classes with them
   h->have_bsr = false;
   return PL_OK;
 }
@@ -1290,17 +1298,36 @@ int pl_assemble(pl_handle h) {
     rc = fem_factor_dense(h);
     if (rc) return rc;
   }
-  rc = build_coarse(h, h->coarse.enabled && h->have_bc ? std::function<void(int)>(queue_fill) : std::function<void(int)>());
+  // The classes of the Jacobi weights (node words) run on the side stream, behind the diagonal - but their launches are
+  // QUEUED only here, from the callback at the head of the chain, when the front of the chain is already queued on the main
+  // stream: queued ahead of it they held the host back and the chain started 100 us later (profiles/README.md,
+  // r12_node_words_timeline).  ev_join moves behind them, so that everything that waits for the side stream waits for them.
+  bool dcl_queued = false;
+  int rc_dcl = PL_OK;
+  auto beside_chain = [&](int phase) {
+    if (!dcl_queued) {
+      dcl_queued = true;
+      rc_dcl = launch_node_classes(h, h->side, true);
+      if (!rc_dcl && hipEventRecord(h->ev_join, h->side) != hipSuccess)
+        rc_dcl = fail(PL_ERR_HIP, "pl_assemble: event record failed");
+    }
+    queue_fill(phase);
+  };
+  rc = build_coarse(h, h->coarse.enabled && h->have_bc ? std::function<void(int)>(beside_chain) : std::function<void(int)>());
   if (rc) return rc;
+  if (rc_dcl) return rc_dcl;
   queue_fill(1);                                 // (no dense level: queue it now)
   if (rc_fill) return rc_fill;
   PL_HIP(hipStreamWaitEvent(h->stream, h->ev_join, 0));
-  rc = launch_dinv32(h);
-  if (rc) return rc;
+  if (!h->dcl_pending) {      // (a queued classification has written dinv32 itself, on the side stream, and verified against it)
+    rc = launch_dinv32(h);
+    if (rc) return rc;
+  }
   PL_HIP(hipEventRecord(h->ev1, h->stream));
   PL_HIP(hipStreamSynchronize(h->stream));
   finish_palette(h);
   finish_condensed_classes(h);
+  finish_node_classes(h);
   // the factorisation has consumed A_c: zero it now, behind the caller's back, instead of at the head of the next
   // assembly's critical chain (34 MB; it would sit in front of the coarse assembly there)
   for (pl::Coarse *cs : {&h->coarse, &h->coarseL})
@@ -2556,6 +2583,19 @@ int pl_time_kernel(pl_handle h, int which, int reps, double *avg_ms) {
   float ms = 0.f;
   PL_HIP(hipEventElapsedTime(&ms, h->ev0, h->ev1));
   *avg_ms = (double)ms / reps;
+  return PL_OK;
+}
+
+int pl_node_words_info(pl_handle h, int *classes_on, int *n_classes, int *bytes_on, int *byte_exp) {
+  if (!valid(h)) return fail(PL_ERR_ARG, "pl_node_words_info: null handle");
+  const pl::Coarse &cs = h->coarse;
+  const bool words = node_words_apply(h);      // (the predicate of the solver's launch helper)
+  const bool cls = words && h->assembled && cs.dcl_ready;
+  const bool bytes = words && cs.rel_e >= 0;
+  if (classes_on) *classes_on = cls ? 1 : 0;
+  if (n_classes) *n_classes = h->assembled ? cs.dcl_classes : 0;
+  if (bytes_on) *bytes_on = bytes ? 1 : 0;
+  if (byte_exp) *byte_exp = bytes ? cs.rel_e : -1;
   return PL_OK;
 }
 

@@ -185,6 +185,73 @@ int launch_dinv32(pl_context *c) {
   return PL_OK;
 }
 
+// Classes of the Jacobi weights for the node words (Coarse::nword): queued on `st` behind the kernel that wrote dinv32, read
+// back into pinned memory; finish_node_classes (after a sync) reads the verdict.  Single-GPU handles only: with a
+// communicator the diagonal is final only after its all-reduce on the main stream.
+// convert = true: dinv32 is written here first, from dinv, on the same stream (pl_assemble, where the diagonal is final once
+// k_diag_gather has run on a single-GPU handle and nothing touches dinv afterwards); the caller then skips launch_dinv32.
+// The classes are hashed from and verified against dinv32 ITSELF, the array the kernels would otherwise read.
+// Which handles read node words at all: the same test in the solver's launch helper and in pl_node_words_info.
+inline bool node_words_apply(const pl_context *c) {
+  return c->coarse.enabled && c->coarse.nword.p && !c->dist.active && !c->coarseL.ready;
+}
+int launch_node_classes(pl_context *c, hipStream_t st, bool convert) {
+  pl::Coarse &cs = c->coarse;
+  cs.dcl_ready = false;
+  cs.dcl_classes = 0;
+  c->dcl_pending = false;
+  if (!cs.enabled || !cs.nword.p || !cs.dcl_table || !c->have_bc || c->dist.active || c->coarseL.enabled)
+    return PL_OK;
+  if (c->dcl_skip_left > 0) {       // (back-off after failed attempts, as launch_palette)
+    c->dcl_skip_left--;
+    return PL_OK;
+  }
+  if (!c->dcl_keys.p) {
+    PL_HIP(c->dcl_keys.alloc(pl::kDclSlots));
+    PL_HIP(c->dcl_owner.alloc(pl::kDclSlots));
+    PL_HIP(c->dcl_dense_of_slot.alloc(pl::kDclSlots));
+    PL_HIP(c->dcl_flags.alloc(2));
+    PL_HIP(c->dcl_slot.alloc((size_t)c->N));
+    void *pinned = nullptr;
+    PL_HIP(hipHostMalloc(&pinned, 2 * sizeof(int), hipHostMallocDefault));
+    c->dcl_host_flags = static_cast<int *>(pinned);
+  }
+  c->dcl_host_flags[0] = 1;
+  c->dcl_host_flags[1] = 0;
+  PL_HIP(hipMemsetAsync(c->dcl_keys.p, 0xFF, pl::kDclSlots * sizeof(unsigned long long), st));
+  PL_HIP(hipMemsetAsync(c->dcl_owner.p, 0x7F, pl::kDclSlots * sizeof(int), st));
+  PL_HIP(hipMemsetAsync(c->dcl_dense_of_slot.p, 0xFF, pl::kDclSlots * sizeof(int), st));
+  PL_HIP(hipMemsetAsync(c->dcl_flags.p, 0, 2 * sizeof(int), st));
+  const dim3 g(grid_for(c->N)), blk(pl::kBlock);
+  if (convert)
+    hipLaunchKernelGGL(pl::k_to_float, dim3(grid_for(c->N * 6)), blk, 0, st, c->N * 6, c->dinv.p, cs.dinv32);
+  hipLaunchKernelGGL(pl::k_dcl_insert, g, blk, 0, st, c->N, (const float *)cs.dinv32, (const uint8_t *)c->fixedbits.p,
+                     c->dcl_keys.p, c->dcl_owner.p, c->dcl_slot.p, c->dcl_flags.p);
+  hipLaunchKernelGGL(pl::k_dcl_publish, g, blk, 0, st, c->N, (const float *)cs.dinv32, (const uint8_t *)c->fixedbits.p,
+                     (const int *)c->dcl_owner.p, (const uint16_t *)c->dcl_slot.p, c->dcl_dense_of_slot.p, cs.dcl_table,
+                     c->dcl_flags.p);
+  hipLaunchKernelGGL(pl::k_dcl_verify, g, blk, 0, st, c->N, (const float *)cs.dinv32, (const uint8_t *)c->fixedbits.p,
+                     (const uint16_t *)c->dcl_slot.p, (const int *)c->dcl_dense_of_slot.p, (const uint32_t *)cs.dcl_table,
+                     cs.nword.p, c->dcl_flags.p);
+  PL_HIP(hipGetLastError());
+  PL_HIP(hipMemcpyAsync(c->dcl_host_flags, c->dcl_flags.p, 2 * sizeof(int), hipMemcpyDeviceToHost, st));
+  c->dcl_pending = true;
+  return PL_OK;
+}
+void finish_node_classes(pl_context *c) {
+  if (!c->dcl_pending) return;
+  c->dcl_pending = false;
+  pl::Coarse &cs = c->coarse;
+  cs.dcl_classes = c->dcl_host_flags[1];
+  cs.dcl_ready = c->dcl_host_flags[0] == 0 && cs.dcl_classes > 0 && cs.dcl_classes <= pl::kDclMax;
+  if (cs.dcl_ready) {
+    c->dcl_fail_streak = 0;
+  } else {          // the next 1, 3, 7, 15 assemblies go without an attempt (graded design loops)
+    c->dcl_fail_streak = std::min(c->dcl_fail_streak + 1, 4);
+    c->dcl_skip_left = (1 << c->dcl_fail_streak) - 1;
+  }
+}
+
 // The rank-local levels (tile blocks on several GPUs, local dense level) see shared nodes as constrained.
 int launch_local_mask(pl_context *c) {
   if (!c->coarse.enabled || !(c->dist.active || c->coarseL.enabled)) return PL_OK;

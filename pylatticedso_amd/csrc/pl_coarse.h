@@ -22,14 +22,24 @@
 
 #include <algorithm>
 #include <cstdint>
+#include <cstdlib>
 #include <vector>
 
 #include "pl_dense.h"
 #include "pl_kernels.h"
+#include "pl_nodeword.h"
 #include "pl_tile.h"
 
 namespace pl {
 
+constexpr int kDclMax = 256;        // classes of Jacobi weights a node word can name (one byte)
+constexpr int kDclSlots = 4096;     // hash slots of their table (k_dcl_insert)
+// PL_NODE_WORDS=0: the vector kernels of the PCG read dinv32 / rel32 / fixedbits as before node words existed (A/B switch,
+// read at pl_create: a handle created under it has no words, whatever the variable says later)
+inline bool node_words_enabled() {
+  const char *e = std::getenv("PL_NODE_WORDS");
+  return !(e && e[0] == '0');
+}
 
 struct Coarse {
   bool enabled = false;     // topology prepared (pl_create)
@@ -75,6 +85,16 @@ struct Coarse {
   // of 24 (+ the reference point): the same numbers, bit for bit (rel_exact; checked node by node in coarse_setup)
   TBuf<float> rel32;
   bool rel_exact = false;
+  // Node words (pl_nodeword.h): {rx, ry, rz, class} in 4 bytes per node instead of rel32 (12) + dinv32 (24) + fixedbits (1).
+  // The two halves are independent.  rel_e >= 0: the lever arms are signed bytes in units of 2^-rel_e, decided once in
+  // coarse_setup (geometry and partition only).  dcl_ready: byte 3 indexes dcl_table, the distinct rows {six fp32 Jacobi
+  // weights, Dirichlet bits} of the current assembly (k_dcl_*; at most kDclMax of them, else the handle keeps dinv32).
+  // nword.p == nullptr: PL_NODE_WORDS=0, a rank-local level, or no lever arms to look at - today's path throughout.
+  TBuf<uint32_t> nword;
+  int rel_e = -1;
+  bool dcl_ready = false;
+  int dcl_classes = 0;
+  uint32_t *dcl_table = nullptr;             // [kDclMax][8]: d0 .. d5 as float bits, the node's fixedbits, padding
   // struts inside one aggregate that touch a Dirichlet dof (the only non-crossing struts with coarse energy);
   // rebuilt on the device after every pl_set_bc
   TBuf<int32_t> fix_list;
@@ -83,7 +103,7 @@ struct Coarse {
   ~Coarse() {
     for (void *q : {(void *)Ac, (void *)Lf, (void *)W, (void *)Wt, (void *)Dinv, (void *)rc, (void *)yc, (void *)tv,
                     (void *)info, (void *)Bt_inv, (void *)yt, (void *)fix_count, (void *)dinv32, (void *)bar,
-                    (void *)Bt_raw, (void *)Bt_rawA, (void *)Ainv})
+                    (void *)Bt_raw, (void *)Bt_rawA, (void *)Ainv, (void *)dcl_table})
       if (q) (void)hipFree(q);
   }
 };
@@ -171,6 +191,20 @@ inline int coarse_setup(Coarse &c, const std::vector<int32_t> &tile_start, const
         if (c.rel32.upload(rel) != hipSuccess) return 1;
         c.rel_exact = true;
       }
+    }
+    // ... and as three signed bytes where they are small multiples of a power of two (pl_nodeword.h): bit for bit again.
+    // The words are allocated either way - their fourth byte, the class of the Jacobi weights, does not need the other three.
+    c.rel_e = -1;
+    if (!local && xyz_dev_order && node_words_enabled()) {
+      std::vector<double> d((size_t)N * 3);
+      for (int64_t i = 0; i < N; ++i)
+        for (int k = 0; k < 3; ++k) d[3 * (size_t)i + k] = xyz_dev_order[3 * i + k] - cen[3 * (size_t)agg_of_node[i] + k];
+      std::vector<uint32_t> words;
+      int e = -1;
+      if (pack_rel_bytes(d.data(), (size_t)N, words, e)) c.rel_e = e;
+      else words.assign((size_t)N, 0u);
+      if (c.nword.upload(words) != hipSuccess) return 1;
+      if (hipMalloc((void **)&c.dcl_table, (size_t)kDclMax * 8 * sizeof(uint32_t)) != hipSuccess) return 2;
     }
   }
   c.n_agg = n_agg;
@@ -969,6 +1003,13 @@ __global__ __launch_bounds__(kBlock) void k_to_float(int64_t n, const double *__
   if (i < n) y[i] = (float)x[i];
 }
 
+// a node's lever arm from the three signed bytes of its word (Coarse::nword), in units of rscale = 2^-e: exact
+__device__ __forceinline__ void nword_rel(uint32_t w, double rscale, double &rx, double &ry, double &rz) {
+  rx = (double)((int)(w << 24) >> 24) * rscale;
+  ry = (double)((int)(w << 16) >> 24) * rscale;
+  rz = (double)((int)(w << 8) >> 24) * rscale;
+}
+
 // PT = storage type of the search direction p and of Ap, RT = of the iterate x and the residual r (double / float:
 // opts.precision).  Every sum is accumulated in fp64 whatever the storage.
 // TM = modes of the tile level: 6, or 12 (rigid + uniform strains, single-GPU handles: Coarse::tile_modes)
@@ -993,7 +1034,10 @@ __global__ __launch_bounds__(kBlock) void k_pcg_update_tile(const int32_t *__res
                                                             double *__restrict__ rcL, int ncp,
                                                             const uint8_t *__restrict__ skip_rows /* may be null */,
                                                             int cm = 6 /* modes per aggregate of the dense level */,
-                                                            const float *__restrict__ rel32 = nullptr /* Coarse::rel32 */) {
+                                                            const float *__restrict__ rel32 = nullptr /* Coarse::rel32 */,
+                                                            const uint32_t *__restrict__ nword = nullptr /* Coarse::nword */,
+                                                            const uint32_t *__restrict__ dtab = nullptr /* class table, or null */,
+                                                            double rscale = 0.0 /* 2^-rel_e, or 0: no lever-arm bytes */) {
   __shared__ double red[32][4 * kBlock / kWave];   // one partial per row of 16 lanes (row_sums)
   if constexpr (!MULTI) {
     w = nullptr;
@@ -1045,7 +1089,10 @@ __global__ __launch_bounds__(kBlock) void k_pcg_update_tile(const int32_t *__res
     if (skip_rows && skip_rows[i]) continue;    // eliminated node (opts.condense): not an unknown of this CG
     // (x += alpha p is done by k_pcg_direction_coarse, which reads p anyway: one vector pass less per iteration)
     double av[6], dv[6], rv[6];
-    const float2 *d2 = reinterpret_cast<const float2 *>(dinv32 + 6 * (int64_t)i);
+    const uint32_t nw = nword ? nword[i] : 0u;
+    // D^-1: the node's 24 bytes, or the row of its class (the same address in nearly every lane: one cache line)
+    const float2 *d2 = dtab ? reinterpret_cast<const float2 *>(dtab + 8 * (nw >> 24))
+                            : reinterpret_cast<const float2 *>(dinv32 + 6 * (int64_t)i);
 #pragma unroll
     for (int k = 0; k < 3; ++k) {
       const double2 aa = load_pair(Ap, 3 * (int64_t)i + k), rr = load_pair(r, 3 * (int64_t)i + k);
@@ -1068,7 +1115,9 @@ __global__ __launch_bounds__(kBlock) void k_pcg_update_tile(const int32_t *__res
       for (int k = 0; k < 6; ++k) wt[k] = w[6 * (int64_t)i + k];
     }
     double rx, ry, rz;
-    if (rel32) {          // the same three numbers as 12 bytes (exact by construction: Coarse::rel_exact)
+    if (rscale != 0.0) {  // ... as three bytes of the node word (exact by construction: Coarse::rel_e)
+      nword_rel(nw, rscale, rx, ry, rz);
+    } else if (rel32) {   // the same three numbers as 12 bytes (exact by construction: Coarse::rel_exact)
       rx = (double)rel32[3 * (int64_t)i];
       ry = (double)rel32[3 * (int64_t)i + 1];
       rz = (double)rel32[3 * (int64_t)i + 2];
@@ -1387,6 +1436,118 @@ __global__ __launch_bounds__(kBlock) void k_cls_verify(int64_t nc, const double 
   }
   if (!(diff <= 1e-10 * scale)) flags[0] = 1;
 }
+// ---- classes of nodes with the same Jacobi weights (node words, Coarse::nword): a class is the exact bit pattern of the
+// node's six fp32 weights plus its Dirichlet bits.  Same scheme once more: hash -> claim a slot (one probe per wave and
+// distinct key: half a million nodes share nine classes at 50^3 Octet) -> the owner takes a dense id and publishes its row
+// -> every node compares itself with its row, word by word, and only then writes the id into byte 3 of its word.
+__device__ __forceinline__ void dcl_row(const float *__restrict__ dinv32, const uint8_t *__restrict__ fixedbits, int64_t i,
+                                        uint32_t v[7]) {
+#pragma unroll
+  for (int k = 0; k < 6; ++k) v[k] = __float_as_uint(dinv32[6 * i + k]);
+  v[6] = fixedbits[i];
+}
+__device__ __forceinline__ unsigned long long dcl_hash(const uint32_t v[7]) {
+  unsigned long long h = 0x9E3779B97F4A7C15ull;
+#pragma unroll
+  for (int k = 0; k < 7; ++k) {
+    h = (h ^ v[k]) * 0xBF58476D1CE4E5B9ull;
+    h ^= h >> 29;
+  }
+  h *= 0x94D049BB133111EBull;
+  h ^= h >> 32;
+  return h == ~0ull ? 0 : h;
+}
+__device__ __forceinline__ int dcl_probe(unsigned long long h, unsigned long long *__restrict__ keys,
+                                         int *__restrict__ owner, int i) {
+  unsigned slot = (unsigned)(h >> 52) & (unsigned)(kDclSlots - 1);
+  for (int probe = 0; probe < 32; ++probe) {
+    unsigned long long cur = __hip_atomic_load(keys + slot, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    if (cur == ~0ull) cur = atomicCAS(keys + slot, ~0ull, h);
+    if (cur == ~0ull || cur == h) {
+      if (i < __hip_atomic_load(owner + slot, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) atomicMin(owner + slot, i);
+      return (int)slot;
+    }
+    slot = (slot + 1) & (unsigned)(kDclSlots - 1);
+  }
+  return -1;
+}
+// flags[0]: the classes do not hold (table full, too many classes, a node differs from its row); flags[1]: classes
+__global__ __launch_bounds__(kBlock) void k_dcl_insert(int64_t N, const float *__restrict__ dinv,
+                                                       const uint8_t *__restrict__ fixedbits,
+                                                       unsigned long long *__restrict__ keys, int *__restrict__ owner,
+                                                       uint16_t *__restrict__ slot_of_node, int *__restrict__ flags) {
+  const int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+  const bool valid = i < N;
+  uint32_t v[7] = {0, 0, 0, 0, 0, 0, 0};
+  if (valid) dcl_row(dinv, fixedbits, i, v);
+  const unsigned long long h = valid ? dcl_hash(v) : 0ull;
+  const int lane = threadIdx.x & 63;
+  int found = -2;                                   // -2: not settled yet, -1: table full
+  unsigned long long todo = __ballot(valid);
+  for (int round = 0; round < 12 && todo; ++round) {
+    const int leader = __ffsll((long long)todo) - 1;
+    const unsigned long long hl =
+        ((unsigned long long)(unsigned)__builtin_amdgcn_readlane((int)(h >> 32), leader) << 32) |
+        (unsigned long long)(unsigned)__builtin_amdgcn_readlane((int)(h & 0xFFFFFFFFull), leader);
+    const unsigned long long same = __ballot(valid && found == -2 && h == hl);
+    int sl = 0;
+    if (lane == leader) sl = dcl_probe(h, keys, owner, (int)i);   // the lowest lane of the group: its smallest node
+    sl = __builtin_amdgcn_readlane(sl, leader);
+    if ((same >> lane) & 1ull) found = sl;
+    todo &= ~same;
+  }
+  if (valid && found == -2) found = dcl_probe(h, keys, owner, (int)i);
+  if (valid) {
+    if (found < 0) flags[0] = 1;
+    slot_of_node[i] = (uint16_t)(found < 0 ? 0 : found);
+  }
+}
+__global__ __launch_bounds__(kBlock) void k_dcl_publish(int64_t N, const float *__restrict__ dinv,
+                                                        const uint8_t *__restrict__ fixedbits,
+                                                        const int *__restrict__ owner,
+                                                        const uint16_t *__restrict__ slot_of_node,
+                                                        int *__restrict__ dense_of_slot, uint32_t *__restrict__ table,
+                                                        int *__restrict__ flags) {
+  const int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+  if (i >= N) return;
+  const int slot = slot_of_node[i];
+  if (owner[slot] != (int)i) return;
+  const int d = atomicAdd(flags + 1, 1);
+  if (d >= kDclMax) {
+    flags[0] = 1;
+    return;                                         // (dense_of_slot stays -1)
+  }
+  uint32_t v[7];
+  dcl_row(dinv, fixedbits, i, v);
+#pragma unroll
+  for (int k = 0; k < 7; ++k) table[8 * d + k] = v[k];
+  table[8 * d + 7] = 0u;
+  dense_of_slot[slot] = d;
+}
+__global__ __launch_bounds__(kBlock) void k_dcl_verify(int64_t N, const float *__restrict__ dinv,
+                                                       const uint8_t *__restrict__ fixedbits,
+                                                       const uint16_t *__restrict__ slot_of_node,
+                                                       const int *__restrict__ dense_of_slot,
+                                                       const uint32_t *__restrict__ table, uint32_t *__restrict__ nword,
+                                                       int *__restrict__ flags) {
+  const int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+  if (i >= N) return;
+  const int d = dense_of_slot[slot_of_node[i]];
+  if (d < 0 || d >= kDclMax) {
+    flags[0] = 1;
+    return;
+  }
+  uint32_t v[7];
+  dcl_row(dinv, fixedbits, i, v);
+  bool same = true;
+#pragma unroll
+  for (int k = 0; k < 7; ++k) same = same && table[8 * d + k] == v[k];
+  if (!same) {
+    flags[0] = 1;
+    return;
+  }
+  nword[i] = (nword[i] & 0x00FFFFFFu) | ((uint32_t)d << 24);
+}
 // r_v <- r_v - y_v on the rows of the nodes that stay (the load the eliminated nodes pass on to them); the rows of the
 // eliminated nodes keep their own right-hand side b_c for the back-substitution at the end
 template <typename VT>
@@ -1440,7 +1601,10 @@ __global__ __launch_bounds__(kBlock) void k_pcg_direction_coarse(const int32_t *
                                                                  double *__restrict__ rcL, int ncpL,
                                                                  const uint8_t *__restrict__ zero_rows /* may be null */,
                                                                  int cm = 6,
-                                                                 const float *__restrict__ rel32 = nullptr /* Coarse::rel32 */) {
+                                                                 const float *__restrict__ rel32 = nullptr /* Coarse::rel32 */,
+                                                                 const uint32_t *__restrict__ nword = nullptr,
+                                                                 const uint32_t *__restrict__ dtab = nullptr,
+                                                                 double rscale = 0.0 /* as in k_pcg_update_tile */) {
   if constexpr (!MULTI) shared = nullptr;
   if constexpr (!MULTI || !LOCAL) aggL_of_tile = nullptr;
   double old, rz_new, pap;
@@ -1510,8 +1674,11 @@ __global__ __launch_bounds__(kBlock) void k_pcg_direction_coarse(const int32_t *
     // eliminated node: not an unknown of this CG (its row of p is rewritten by the first pass of every product, which
     // takes the old content as zero: k_spmv_tile<.., kEndsCondensedSolve>)
     if (zero_rows && zero_rows[i]) continue;
+    const uint32_t nw = nword ? nword[i] : 0u;
     double rx, ry, rz;
-    if (rel32) {
+    if (rscale != 0.0) {
+      nword_rel(nw, rscale, rx, ry, rz);
+    } else if (rel32) {
       rx = (double)rel32[3 * i];
       ry = (double)rel32[3 * i + 1];
       rz = (double)rel32[3 * i + 2];
@@ -1550,8 +1717,9 @@ __global__ __launch_bounds__(kBlock) void k_pcg_direction_coarse(const int32_t *
       zc[4] += L[4];
       zc[5] += L[5];
     }
-    const unsigned fb = fixedbits[i];
-    const float2 *d2 = reinterpret_cast<const float2 *>(dinv32 + 6 * i);
+    const uint32_t *row = dtab ? dtab + 8 * (nw >> 24) : nullptr;        // (the class row carries the Dirichlet bits too)
+    const unsigned fb = dtab ? row[6] : (unsigned)fixedbits[i];
+    const float2 *d2 = dtab ? reinterpret_cast<const float2 *>(row) : reinterpret_cast<const float2 *>(dinv32 + 6 * i);
 #pragma unroll
     for (int q = 0; q < 3; ++q) {
       const double2 rr = load_pair(r, 3 * i + q);
@@ -1593,7 +1761,10 @@ __global__ __launch_bounds__(kBlock) void k_pcg_direction_flat(int64_t N, const 
                                                                double *__restrict__ rc, int ncp,
                                                                const int32_t *__restrict__ keep /* may be null */,
                                                                int cm, const uint8_t *__restrict__ shared /* may be null */,
-                                                               const float *__restrict__ rel32 = nullptr /* Coarse::rel32 */) {
+                                                               const float *__restrict__ rel32 = nullptr /* Coarse::rel32 */,
+                                                               const uint32_t *__restrict__ nword = nullptr,
+                                                               const uint32_t *__restrict__ dtab = nullptr,
+                                                               double rscale = 0.0 /* as in k_pcg_update_tile */) {
   // keep: with node elimination (opts.condense) N counts the nodes that stay unknowns and keep[] lists them - the lanes
   // map onto those only (a flag test per node left half of the lanes of a BCC lattice idle: 80 us for 1.03 M kept nodes at
   // 100^3 against 26 us for 0.5 M nodes of the Octet lattice)
@@ -1642,8 +1813,11 @@ __global__ __launch_bounds__(kBlock) void k_pcg_direction_flat(int64_t N, const 
 #pragma unroll
     for (int m = 0; m < TM; ++m) C[m] += w[m];
   }
+  const uint32_t nw = nword ? nword[i] : 0u;
   double rx, ry, rz;
-  if (rel32) {
+  if (rscale != 0.0) {
+    nword_rel(nw, rscale, rx, ry, rz);
+  } else if (rel32) {
     rx = (double)rel32[3 * i];
     ry = (double)rel32[3 * i + 1];
     rz = (double)rel32[3 * i + 2];
@@ -1661,8 +1835,9 @@ __global__ __launch_bounds__(kBlock) void k_pcg_direction_flat(int64_t N, const 
   }
   double z0 = q == 0 ? zc[0] : (q == 1 ? zc[2] : zc[4]);
   double z1 = q == 0 ? zc[1] : (q == 1 ? zc[3] : zc[5]);
-  const unsigned fb = fixedbits[i];
-  const float2 dd = reinterpret_cast<const float2 *>(dinv32)[pair];
+  const uint32_t *row = dtab ? dtab + 8 * (nw >> 24) : nullptr;          // (the class row carries the Dirichlet bits too)
+  const unsigned fb = dtab ? row[6] : (unsigned)fixedbits[i];
+  const float2 dd = dtab ? reinterpret_cast<const float2 *>(row)[q] : reinterpret_cast<const float2 *>(dinv32)[pair];
   const double2 rr = load_pair(r, pair);
   double2 pp = load_pair(p, pair);
   double2 xx = load_pair(x, pair);

@@ -222,6 +222,14 @@ struct pl_context {
   DevBuf<double> cls_table;
   int *cls_host_flag = nullptr;       // pinned
   bool cls_ready = false;
+  // classes of nodes with the same Jacobi weights (node words of the PCG vector kernels: Coarse::nword, k_dcl_*); an attempt
+  // that fails (a graded lattice: more than kDclMax classes) is not repeated at once, as with the record palette
+  DevBuf<unsigned long long> dcl_keys;
+  DevBuf<int> dcl_owner, dcl_dense_of_slot, dcl_flags;
+  DevBuf<uint16_t> dcl_slot;
+  int *dcl_host_flags = nullptr;      // pinned [2]: failed, classes
+  int dcl_fail_streak = 0, dcl_skip_left = 0;
+  bool dcl_pending = false;           // an attempt is queued: finish_node_classes reads its verdict
   // short form of the iteration on small lattices (pl_small.h): second p buffer, ring of four scalar sets, two r_c buffers
   DevBuf<double> p2, small_scal, small_rc;
   bool small_use = false;    // the running solve takes the short form (solver_plan)
