@@ -508,7 +508,8 @@ int pl_debug_partition(pl_handle h, int32_t *tile_of_node, int32_t *agg_of_node,
  * 2 = BSR fill, 3 = one full PCG iteration, 4 = BSR SpMV; on a multi-GPU handle also 5 = the interface all-reduce of
  * one K*p (staging kernels + RCCL) and 6 = the coarse-residual all-reduce - collective calls, every rank must make them.
  * With the multi-level PCG: 7 = K*p on fp32-stored vectors, 8 = one iteration of the fp32 inner PCG (precision 1),
- * 9 = one iteration of the mixed PCG (precision 2); 10 = the operator exactly as the next pl_solve applies it (BOTH passes
+ * 9 = one iteration of the mixed PCG (precision 2) - 8 and 9 call the solver's own iteration, so they apply the operator
+ * as the handle's plan does (both passes where it eliminates nodes); 10 = the operator exactly as the next pl_solve applies it (BOTH passes
  * under node elimination, fp32-stored operands in the fp32 solver modes) - what a roofline of "K*p" must be priced with;
  * 11 = one whole PCG iteration exactly as the next pl_solve runs it (storage width and node elimination of its plan). */
 int pl_time_kernel(pl_handle h, int which, int reps, double *avg_ms);

@@ -1,5 +1,5 @@
 // libpylattice_hip.so - the C ABI declared in include/pylattice_hip.h (gfx950 / MI355X).  One translation unit:
-// pl_context.h (handle state) <- pl_ops.h (operator launches) <- pl_assembly.h <- pl_solver.h <- this file.
+// pl_context.h (handle state) <- pl_ops.h (operator launches) <- pl_assembly.h <- pl_solver.h (+ pl_warm.h, pl_schedule.h) <- this file.
 #include "pl_solver.h"
 #include "pl_condense.h"
 #include "pl_multi.h"
@@ -2500,6 +2500,8 @@ int pl_time_kernel(pl_handle h, int which, int reps, double *avg_ms) {
                        reinterpret_cast<float *>(h->z.p));
     PL_HIP(hipMemsetAsync(h->tmp.p, 0, n6 * sizeof(double), h->stream));
   }
+  float *p32 = reinterpret_cast<float *>(h->z.p), *Ap32 = p32 + n6;             // (ids 7 to 11)
+  float *x32 = reinterpret_cast<float *>(h->tmp.p), *r32 = x32 + n6;
   auto one = [&](int k) -> int {
     switch (which) {
       case 0: return launch_spmv(h, h->p.p, h->Ap.p, true, h->scal.p + pl::S_PAP * pl::kSlots);
@@ -2521,51 +2523,20 @@ int pl_time_kernel(pl_handle h, int which, int reps, double *avg_ms) {
         if (!h->dist.active || !h->coarse.ready) return fail(PL_ERR_STATE, "pl_time_kernel: 6 needs a coarse level");
         return pl::dist_sum_scalars(h->dist, h->coarse.tv, h->coarse.ncp, h->stream)
                    ? fail(PL_ERR_HIP, "RCCL all-reduce failed") : PL_OK;
-      case 7:   // K*p on fp32-stored vectors (the operator of opts.precision = 1 / 2)
+      case 7:   // K*p on fp32-stored vectors (the operator of opts.precision = 1 / 2), without node elimination
       case 8:   // one whole iteration of the fp32 inner PCG (precision = 1)
-      case 9: { // one whole iteration of the mixed PCG (precision = 2: p, K*p fp32; x, r fp64)
+      case 9:   // one whole iteration of the mixed PCG (precision = 2: p, K*p fp32; x, r fp64)
         if (!(h->coarse.ready && h->tile.ready && choose_kernel(h) == 3))
           return fail(PL_ERR_STATE, "pl_time_kernel: 7/8/9 need the multi-level PCG on the tile kernel");
-        float *p32 = reinterpret_cast<float *>(h->z.p), *Ap32 = p32 + n6;
-        double *cur = h->scal.p + (k & 1) * pl::S_COUNT * pl::kSlots, *nxt = h->scal.p + ((k + 1) & 1) * pl::S_COUNT * pl::kSlots;
-        int r7 = launch_spmv_f32(h, p32, Ap32, true, cur + pl::S_PAP * pl::kSlots);
-        if (r7 || which == 7) return r7;
-        if (which == 8) {
-          float *x32 = reinterpret_cast<float *>(h->tmp.p), *r32 = x32 + n6;
-          return pcg_tail_coarse_t<float, float>(h, cur, nxt, k, p32, (const float *)Ap32, x32, r32);
-        }
-        return pcg_tail_coarse_t<float, double>(h, cur, nxt, k, p32, (const float *)Ap32, h->x.p, h->r.p);
-      }
-      case 10: {   // the operator exactly as the next pl_solve applies it: both passes under node elimination, fp32-stored
-                   // operands in the fp32 solver modes
-        if (mp_applies(h)) {
-          float *p32 = reinterpret_cast<float *>(h->z.p), *Ap32 = p32 + n6;
-          if (h->cond_use) {
-            int r0 = launch_spmv_f32(h, p32, p32, false, nullptr, nullptr, pl::kEndsCondensedSolve);
-            return r0 ? r0 : launch_spmv_f32(h, p32, Ap32, true, h->scal.p + pl::S_PAP * pl::kSlots, h->maskC.p, pl::kEndsOthers);
-          }
-          return launch_spmv_f32(h, p32, Ap32, true, h->scal.p + pl::S_PAP * pl::kSlots);
-        }
-        if (h->cond_use) {
-          int r0 = launch_spmv(h, h->p.p, h->p.p, false, nullptr, nullptr, pl::kEndsCondensedSolve);
-          return r0 ? r0 : launch_spmv(h, h->p.p, h->Ap.p, true, h->scal.p + pl::S_PAP * pl::kSlots, h->maskC.p, pl::kEndsOthers);
-        }
-        return launch_spmv(h, h->p.p, h->Ap.p, true, h->scal.p + pl::S_PAP * pl::kSlots);
-      }
-      case 11: {   // one whole iteration exactly as the next pl_solve runs it (storage width and node elimination of its plan)
-        if (!(mp_applies(h) && h->opt.precision == 1)) return pcg_iteration(h, k);
-        float *p32 = reinterpret_cast<float *>(h->z.p), *Ap32 = p32 + n6;
-        float *x32 = reinterpret_cast<float *>(h->tmp.p), *r32 = x32 + n6;
-        double *cur = h->scal.p + (k & 1) * pl::S_COUNT * pl::kSlots, *nxt = h->scal.p + ((k + 1) & 1) * pl::S_COUNT * pl::kSlots;
-        int r11;
-        if (h->cond_use) {
-          r11 = launch_spmv_f32(h, p32, p32, false, nullptr, nullptr, pl::kEndsCondensedSolve);
-          if (!r11) r11 = launch_spmv_f32(h, p32, Ap32, true, cur + pl::S_PAP * pl::kSlots, h->maskC.p, pl::kEndsOthers);
-        } else {
-          r11 = launch_spmv_f32(h, p32, Ap32, true, cur + pl::S_PAP * pl::kSlots);
-        }
-        return r11 ? r11 : pcg_tail_coarse_t<float, float>(h, cur, nxt, k, p32, (const float *)Ap32, x32, r32);
-      }
+        if (which == 7) return launch_spmv_f32(h, p32, Ap32, true, h->scal.p + pl::S_PAP * pl::kSlots);
+        return which == 8 ? mp_iteration<float>(h, k, k, p32, Ap32, x32, r32)
+                          : mp_iteration<double>(h, k, k, p32, Ap32, h->x.p, h->r.p);
+      case 10:   // the operator exactly as the next pl_solve applies it: both passes under node elimination, fp32-stored
+                 // operands in the fp32 solver modes
+        return mp_applies(h) ? apply_operator<float>(h, p32, Ap32, h->scal.p + pl::S_PAP * pl::kSlots)
+                             : apply_operator<double>(h, h->p.p, h->Ap.p, h->scal.p + pl::S_PAP * pl::kSlots);
+      case 11:   // one whole iteration exactly as the next pl_solve runs it (storage width and node elimination of its plan)
+        return mp_applies(h) && h->opt.precision == 1 ? mp_iteration<float>(h, k, k, p32, Ap32, x32, r32) : pcg_iteration(h, k);
       default: return fail(PL_ERR_ARG, "pl_time_kernel: unknown kernel id");
     }
   };

@@ -241,6 +241,22 @@ int launch_spmv_f32(pl_context *c, const float *x, float *y, bool masked, double
   return tile_spmv<float>(c, mk, x, y, dot_dev, ends, true);
 }
 
+// The operator as the next solve applies it (solver_plan has set c->cond_use): Ap = S p, dot_dev += p . S p (may be null).
+// With node elimination S p takes two passes: the eliminated nodes take their equilibrium position under p (their rows of p
+// are 0 on entry; fused with the 6 x 6 solves, every tile writes -K_cc^-1 (K p_v)_c into the p rows of its eliminated
+// nodes), then the ordinary product with their rows masked like Dirichlet rows.
+template <typename VT>
+int spmv_as_stored(pl_context *c, const VT *x, VT *y, bool masked, double *dot_dev, const uint8_t *maskbits, int ends) {
+  if constexpr (sizeof(VT) == 4) return launch_spmv_f32(c, x, y, masked, dot_dev, maskbits, ends);
+  else return launch_spmv(c, x, y, masked, dot_dev, maskbits, ends);
+}
+template <typename VT>
+int apply_operator(pl_context *c, VT *p, VT *Ap, double *dot_dev) {
+  if (!c->cond_use) return spmv_as_stored<VT>(c, p, Ap, true, dot_dev, nullptr, pl::kEndsAll);
+  const int rc = spmv_as_stored<VT>(c, p, p, false, nullptr, nullptr, pl::kEndsCondensedSolve);
+  return rc ? rc : spmv_as_stored<VT>(c, p, Ap, true, dot_dev, c->maskC.p, pl::kEndsOthers);
+}
+
 // residual history + (reference-CG mode) direction norm, solution norm and step length of every iteration
 int ensure_hist(pl_context *c, int cap) {
   if (cap <= c->hist_cap) return PL_OK;

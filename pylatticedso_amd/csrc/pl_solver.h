@@ -1,85 +1,132 @@
 // PCG solvers of libpylattice_hip: ordinary multi-level / Jacobi / reference-CG loop, single-reduction form
 // (Chronopoulos-Gear), fp32 solver modes.
 #pragma once
+#include <type_traits>
+
 #include "pl_assembly.h"
+#include "pl_schedule.h"
+#include "pl_warm.h"
 
 namespace {
 
-// Warm start (opts.warm_start, design loops): p <- the previous converged solution of this handle with the eliminated nodes'
-// rows zeroed, then r -= (operator p), x = p on the rows that are unknowns of the CG.
-__global__ __launch_bounds__(pl::kBlock) void k_warm_mask(int64_t N, const uint8_t *__restrict__ cflag /* may be null */,
-                                                         const uint8_t *__restrict__ fixed, double *__restrict__ p) {
-  const int64_t t = (int64_t)blockIdx.x * pl::kBlock + threadIdx.x;
-  if (t < 6 * N && ((cflag && cflag[t / 6]) || fixed[t])) p[t] = 0.0;     // (the Dirichlet set may have changed since)
+int read_slots(pl_context *c, const double *dev, double *sum) {
+  double h[pl::kSlots];
+  PL_HIP(hipMemcpyAsync(h, dev, sizeof(h), hipMemcpyDeviceToHost, c->stream));
+  PL_HIP(hipStreamSynchronize(c->stream));
+  *sum = 0.0;
+  for (int k = 0; k < pl::kSlots; ++k) *sum += h[k];
+  return PL_OK;
 }
-// opts.warm_start = 2: p <- 2 x_prev - x_prev2, the linear extrapolation of the last two solutions of a design loop
-__global__ __launch_bounds__(pl::kBlock) void k_warm_extrapolate(int64_t n6, const double *__restrict__ a /* x_prev */,
-                                                                 const double *__restrict__ b /* x_prev2 */, double *__restrict__ p) {
-  const int64_t t = (int64_t)blockIdx.x * pl::kBlock + threadIdx.x;
-  if (t < n6) p[t] = 2.0 * a[t] - b[t];
+
+// Start of every solve: ||b||^2 from its slots, the stats of a solve that has not iterated yet.  *zero: the right-hand side
+// is zero (or NaN) - the solve is over and the return value is its result.
+int solve_begin(pl_context *c, const double *bb_slots, pl_stats_t *st, double *bb, bool *zero) {
+  *zero = false;
+  const int rc = read_slots(c, bb_slots, bb);
+  if (rc) return rc;
+  st->b_norm = std::sqrt(*bb);
+  st->iterations = 0;
+  st->converged = 0;
+  st->rel_residual = 0.0;
+  if (*bb > 0.0) return PL_OK;
+  *zero = true;
+  st->converged = 1;
+  return std::isnan(*bb) ? fail(PL_ERR_NAN, "NaN in the right-hand side") : PL_OK;
 }
-__global__ __launch_bounds__(pl::kBlock) void k_warm_extrapolate2(int64_t n6, const double *__restrict__ a, const double *__restrict__ b,
-                                                                  const double *__restrict__ c3, double *__restrict__ p) {
-  const int64_t t = (int64_t)blockIdx.x * pl::kBlock + threadIdx.x;
-  if (t < n6) p[t] = 3.0 * (a[t] - b[t]) + c3[t];
+
+inline void converged_at(pl_stats_t *st, int iterations, double stop_reason) {
+  st->converged = 1;
+  st->iterations = iterations;
+  st->info = 0.0;
+  st->stop_reason = stop_reason;
 }
-// opts.warm_start = 4 (Galerkin start): out[i] += v_i . Ap for the m stored vectors, out[m] += vj . r - rows that are unknowns
-// of the CG only (not eliminated, not constrained: v is masked, Ap is masked)
-constexpr int kWarmMax = pl_context::kWarmMax;
-struct WarmVecs {
-  const double *v[kWarmMax];
+
+// ----------------------------------------------------------------------------------------------------------
+// Launches of the iteration's tail kernels: every kernel's argument list is written once, in its launch_* function, and the
+// compile-time variant is chosen by one of the two dispatchers below, which hand it to a generic lambda as constants.
+// ----------------------------------------------------------------------------------------------------------
+template <int V>
+using Int = std::integral_constant<int, V>;
+
+// f(tm): modes of the tile level, 6 or 12
+template <typename F>
+inline void with_tile_modes(const pl_context *c, F &&f) {
+  if (tile_modes_now(c) == 12) f(Int<12>{});
+  else f(Int<6>{});
+}
+// f(tm, multi, local): MULTI = several ranks or a rank-local dense level, LOCAL = the rank-local level (k_pcg_update_tile)
+template <typename F>
+inline void with_tail_variant(const pl_context *c, F &&f) {
+  with_tile_modes(c, [&](auto tm) {
+    if (c->coarseL.ready) f(tm, std::true_type{}, std::true_type{});
+    else if (c->dist.active) f(tm, std::true_type{}, std::false_type{});
+    else f(tm, std::false_type{}, std::false_type{});
+  });
+}
+
+// Lever arms as exact floats where the lattice allows it (Coarse::rel32) and the node words (Coarse::nword): the class table
+// of the Jacobi weights and / or the lever arms as bytes, whichever this handle has; neither (or PL_NODE_WORDS=0 at
+// pl_create: no words): null, and the kernels read what they always read
+struct NodeWords {
+  const float *rel32;
+  const uint32_t *nword, *dtab;
+  double rscale;
 };
-struct WarmCoef {
-  double c[kWarmMax];
-};
-__global__ __launch_bounds__(pl::kBlock) void k_warm_dots(int64_t N, int m, WarmVecs V, int j, const uint8_t *__restrict__ cflag,
-                                                          const double *__restrict__ Ap, const double *__restrict__ r,
-                                                          double *__restrict__ out /* [m + 1] */) {
-  __shared__ double red[kWarmMax + 1][pl::kBlock / pl::kWave];
-  double acc[kWarmMax + 1];
-#pragma unroll
-  for (int i = 0; i <= kWarmMax; ++i) acc[i] = 0.0;
-  for (int64_t t = (int64_t)blockIdx.x * pl::kBlock + threadIdx.x; t < 6 * N; t += (int64_t)gridDim.x * pl::kBlock) {
-    if (cflag && cflag[t / 6]) continue;
-    const double a = Ap[t];
-#pragma unroll
-    for (int i = 0; i < kWarmMax; ++i)
-      if (i < m) acc[i] += V.v[i][t] * a;
-    acc[kWarmMax] += V.v[j][t] * r[t];
-  }
-  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-#pragma unroll
-  for (int i = 0; i <= kWarmMax; ++i) {
-    const double s = pl::wave_sum(acc[i]);
-    if (lane == 0) red[i][wv] = s;
-  }
-  __syncthreads();
-  if (threadIdx.x <= kWarmMax) {
-    double s = 0.0;
-    for (int w = 0; w < pl::kBlock / pl::kWave; ++w) s += red[threadIdx.x][w];
-    const int i = threadIdx.x;
-    if (i < m) unsafeAtomicAdd(out + i, s);
-    else if (i == kWarmMax) unsafeAtomicAdd(out + m, s);
-  }
+inline NodeWords node_words_of(const pl_context *c) {
+  const pl::Coarse &cs = c->coarse;
+  const bool words = node_words_apply(c);
+  NodeWords nw;
+  nw.rel32 = cs.rel_exact ? (const float *)cs.rel32.p : (const float *)nullptr;
+  nw.dtab = words && cs.dcl_ready ? (const uint32_t *)cs.dcl_table : (const uint32_t *)nullptr;
+  nw.rscale = words && cs.rel_e >= 0 ? std::ldexp(1.0, -cs.rel_e) : 0.0;
+  nw.nword = (nw.dtab || nw.rscale != 0.0) ? (const uint32_t *)cs.nword.p : (const uint32_t *)nullptr;
+  return nw;
 }
-// p = sum_i c_i v_i
-__global__ __launch_bounds__(pl::kBlock) void k_warm_combine(int64_t n6, int m, WarmVecs V, WarmCoef C, double *__restrict__ p) {
-  const int64_t t = (int64_t)blockIdx.x * pl::kBlock + threadIdx.x;
-  if (t >= n6) return;
-  double s = 0.0;
-#pragma unroll
-  for (int i = 0; i < kWarmMax; ++i)
-    if (i < m) s += C.c[i] * V.v[i][t];
-  p[t] = s;
+
+// r -= alpha Ap with the scalars of `scal`, restriction into rc_out, tile solve (the rank-local level has its own reference
+// points)
+template <typename PT, typename RT, int TM, bool MULTI, bool LOCAL>
+void launch_update_tile(pl_context *c, Int<TM>, std::bool_constant<MULTI>, std::bool_constant<LOCAL>, const PT *Ap, RT *r,
+                        double *scal, double *rc_out, const NodeWords &nw) {
+  pl::Coarse &cs = c->coarse, &cl = c->coarseL;
+  hipLaunchKernelGGL((pl::k_pcg_update_tile<PT, RT, TM, MULTI, LOCAL>), dim3((unsigned)cs.n_tiles), dim3(cs.vblock), 0,
+                     c->stream, c->tile.tile_start.p, cs.agg_of_tile.p, cs.cen.p, c->xyz.p, Ap, cs.dinv32,
+                     c->dist.active ? (const double *)c->dist.weight.p : (const double *)nullptr, r, scal, rc_out,
+                     cs.tile_level ? (const double *)cs.Bt_inv : (const double *)nullptr, cs.yt,
+                     LOCAL ? (const int32_t *)cl.agg_of_tile.p : (const int32_t *)nullptr,
+                     LOCAL ? (const double *)cl.cen.p : (const double *)nullptr,
+                     MULTI ? (const uint8_t *)c->sharedbits.p : (const uint8_t *)nullptr, LOCAL ? cl.rc : (double *)nullptr,
+                     cs.ncp, c->cond_use ? (const uint8_t *)c->cflag.p : (const uint8_t *)nullptr, cs.cm, nw.rel32, nw.nword,
+                     nw.dtab, nw.rscale);
 }
-__global__ __launch_bounds__(pl::kBlock) void k_warm_apply(int64_t N, const uint8_t *__restrict__ cflag /* may be null */,
-                                                          const double *__restrict__ Ap, const double *__restrict__ p,
-                                                          double *__restrict__ r, double *__restrict__ x) {
-  const int64_t t = (int64_t)blockIdx.x * pl::kBlock + threadIdx.x;
-  if (t >= 6 * N) return;
-  if (cflag && cflag[t / 6]) return;
-  r[t] -= Ap[t];
-  x[t] = p[t];
+template <typename PT, typename RT, int TM, bool MULTI, bool LOCAL>
+void launch_direction_coarse(pl_context *c, Int<TM>, std::bool_constant<MULTI>, std::bool_constant<LOCAL>, PT *p, RT *x,
+                             const RT *r, double *cur, double *nxt, int hist_slot, const NodeWords &nw) {
+  pl::Coarse &cs = c->coarse, &cl = c->coarseL;
+  hipLaunchKernelGGL((pl::k_pcg_direction_coarse<PT, RT, TM, MULTI, LOCAL>), dim3((unsigned)cs.n_tiles), dim3(cs.vblock), 0,
+                     c->stream, c->tile.tile_start.p, r, cs.dinv32, c->xyz.p, cs.agg_of_tile.p, cs.cen.p, cs.yc,
+                     cs.tile_level ? (const double *)cs.yt : (const double *)nullptr, c->fixedbits.p, p, x, cur, nxt,
+                     c->hist.p, hist_slot, cs.rc, cs.ncp,
+                     LOCAL ? (const int32_t *)cl.agg_of_tile.p : (const int32_t *)nullptr,
+                     LOCAL ? (const double *)cl.cen.p : (const double *)nullptr,
+                     LOCAL ? (const double *)cl.yc : (const double *)nullptr,
+                     MULTI ? (const uint8_t *)c->sharedbits.p : (const uint8_t *)nullptr, LOCAL ? cl.rc : (double *)nullptr,
+                     LOCAL ? cl.ncp : 0, c->cond_use ? (const uint8_t *)c->cflag.p : (const uint8_t *)nullptr, cs.cm,
+                     nw.rel32, nw.nword, nw.dtab, nw.rscale);
+}
+// the same direction on a flat mapping, contiguous per wave (no rank-local level)
+template <typename PT, typename RT, int TM>
+void launch_direction_flat(pl_context *c, Int<TM>, PT *p, RT *x, const RT *r, double *cur, double *nxt, int hist_slot,
+                           const NodeWords &nw) {
+  pl::Coarse &cs = c->coarse;
+  const int64_t n_flat = c->cond_use ? c->N - c->n_cond : c->N;       // nodes that are unknowns of this CG
+  hipLaunchKernelGGL((pl::k_pcg_direction_flat<PT, RT, TM>), dim3((unsigned)((3 * n_flat + pl::kBlock - 1) / pl::kBlock)),
+                     dim3(pl::kBlock), 0, c->stream, n_flat, cs.tile_of_node.p, r, cs.dinv32, c->xyz.p, cs.agg_of_tile.p,
+                     cs.cen.p, cs.yc, cs.tile_level ? (const double *)cs.yt : (const double *)nullptr, c->fixedbits.p, p, x,
+                     cur, nxt, c->hist.p, hist_slot, cs.rc, cs.ncp,
+                     c->cond_use ? (const int32_t *)c->ckeep.p : (const int32_t *)nullptr, cs.cm,
+                     c->dist.active ? (const uint8_t *)c->sharedbits.p : (const uint8_t *)nullptr, nw.rel32, nw.nword, nw.dtab,
+                     nw.rscale);
 }
 
 // Everything of a two-level PCG iteration after K*p: update + restriction, coarse solve, new direction.
@@ -87,33 +134,8 @@ template <typename PT, typename RT>
 int pcg_tail_coarse_t(pl_context *c, double *cur, double *nxt, int hist_slot, PT *p, const PT *Ap, RT *x, RT *r) {
   pl::Coarse &cs = c->coarse, &cl = c->coarseL;
   const bool useL = cl.ready;
-#define PL_UPD(TM, MULTI, LOCAL)                                                                                    \
-  hipLaunchKernelGGL((pl::k_pcg_update_tile<PT, RT, TM, MULTI, LOCAL>), dim3((unsigned)cs.n_tiles), dim3(cs.vblock), \
-                     0, c->stream,                                                                                   \
-                     c->tile.tile_start.p, cs.agg_of_tile.p, cs.cen.p, c->xyz.p, Ap, cs.dinv32,                       \
-                     c->dist.active ? (const double *)c->dist.weight.p : (const double *)nullptr, r, cur,             \
-                     cs.rc, cs.tile_level ? (const double *)cs.Bt_inv : (const double *)nullptr, cs.yt,               \
-                     useL ? (const int32_t *)cl.agg_of_tile.p : (const int32_t *)nullptr, cl.cen.p,                   \
-                     (c->dist.active || useL) ? (const uint8_t *)c->sharedbits.p : (const uint8_t *)nullptr, cl.rc,   \
-                     cs.ncp, c->cond_use ? (const uint8_t *)c->cflag.p : (const uint8_t *)nullptr, cs.cm, rel32,   \
-                     nword, dtab, rscale)
-  // lever arms as exact floats where the lattice allows it (Coarse::rel32); the rank-local level has its own reference points
-  const float *rel32 = cs.rel_exact ? (const float *)cs.rel32.p : (const float *)nullptr;
-  // node words (Coarse::nword): the class table of the Jacobi weights and / or the lever arms as bytes, whichever this
-  // handle has; neither (or PL_NODE_WORDS=0 at pl_create: no words): null, and the kernels read what they always read
-  const bool words = node_words_apply(c);
-  const uint32_t *dtab = words && cs.dcl_ready ? (const uint32_t *)cs.dcl_table : (const uint32_t *)nullptr;
-  const double rscale = words && cs.rel_e >= 0 ? std::ldexp(1.0, -cs.rel_e) : 0.0;
-  const uint32_t *nword = (dtab || rscale != 0.0) ? (const uint32_t *)cs.nword.p : (const uint32_t *)nullptr;
-  if (useL) {
-    if (tile_modes_now(c) == 12) PL_UPD(12, true, true);
-    else PL_UPD(6, true, true);
-  } else if (c->dist.active) {
-    if (tile_modes_now(c) == 12) PL_UPD(12, true, false);
-    else PL_UPD(6, true, false);
-  } else if (tile_modes_now(c) == 12) PL_UPD(12, false, false);
-  else PL_UPD(6, false, false);
-#undef PL_UPD
+  const NodeWords nw = node_words_of(c);
+  with_tail_variant(c, [&](auto tm, auto multi, auto local) { launch_update_tile(c, tm, multi, local, Ap, r, cur, cs.rc, nw); });
   if (useL)   // rank-local level: y_L is never communicated, but its share of r.z, r_L . A_L^-1 r_L, is a per-rank
               // partial sum: it joins the r.D^-1 r slots BEFORE they travel in the collective below
     pl::coarse_apply(cl, cl.rc, cl.tv, cl.yc, cs.rc + cs.ncp + pl::kSlots, (const double *)nullptr, c->stream);
@@ -122,40 +144,14 @@ int pcg_tail_coarse_t(pl_context *c, double *cur, double *nxt, int hist_slot, PT
       return fail(PL_ERR_HIP, "RCCL all-reduce of the coarse residual failed");
   }
   pl::coarse_apply(cs, cs.rc, cs.tv, cs.yc, cur + pl::S_RZ_NEW * pl::kSlots, cs.rc + cs.ncp + pl::kSlots, c->stream);
-#define PL_DIR(TM, MULTI, LOCAL)                                                                                         \
-  hipLaunchKernelGGL((pl::k_pcg_direction_coarse<PT, RT, TM, MULTI, LOCAL>), dim3((unsigned)cs.n_tiles), dim3(cs.vblock), \
-                     0, c->stream,                                                                                        \
-                     c->tile.tile_start.p, (const RT *)r, cs.dinv32, c->xyz.p, cs.agg_of_tile.p, cs.cen.p, cs.yc,         \
-                     cs.tile_level ? (const double *)cs.yt : (const double *)nullptr, c->fixedbits.p, p, x, cur, nxt,     \
-                     c->hist.p, hist_slot, cs.rc, cs.ncp,                                                                \
-                     useL ? (const int32_t *)cl.agg_of_tile.p : (const int32_t *)nullptr, cl.cen.p, cl.yc,                \
-                     (c->dist.active || useL) ? (const uint8_t *)c->sharedbits.p : (const uint8_t *)nullptr, cl.rc,       \
-                     cl.ncp, c->cond_use ? (const uint8_t *)c->cflag.p : (const uint8_t *)nullptr, cs.cm, rel32,         \
-                     nword, dtab, rscale)
-  const int64_t n_flat = c->cond_use ? c->N - c->n_cond : c->N;       // nodes that are unknowns of this CG
-#define PL_DIRF(TM)                                                                                                      \
-  hipLaunchKernelGGL((pl::k_pcg_direction_flat<PT, RT, TM>), dim3((unsigned)((3 * n_flat + pl::kBlock - 1) / pl::kBlock)), \
-                     dim3(pl::kBlock), 0, c->stream, n_flat, cs.tile_of_node.p, (const RT *)r, cs.dinv32, c->xyz.p,       \
-                     cs.agg_of_tile.p, cs.cen.p, cs.yc, cs.tile_level ? (const double *)cs.yt : (const double *)nullptr,  \
-                     c->fixedbits.p, p, x, cur, nxt, c->hist.p, hist_slot, cs.rc, cs.ncp,                                \
-                     c->cond_use ? (const int32_t *)c->ckeep.p : (const int32_t *)nullptr, cs.cm,                        \
-                     c->dist.active ? (const uint8_t *)c->sharedbits.p : (const uint8_t *)nullptr, rel32, nword, dtab,   \
-                     rscale)
-  // flat mapping, contiguous per wave: fp64 p without a rank-local level (measured on one box, 50^3 Octet: 26.2 -> 24.5 us;
+  // flat mapping: fp64 p without a rank-local level (measured on one box, 50^3 Octet: 26.2 -> 24.5 us;
   // fp32 p / fp64 r the same either way, fp32 p / fp32 r 19.0 -> 22.0 us - 8-byte loads per lane are too few in flight)
-  if (!useL && sizeof(PT) == 8) {
-    if (tile_modes_now(c) == 12) PL_DIRF(12);
-    else PL_DIRF(6);
-  } else if (useL) {
-    if (tile_modes_now(c) == 12) PL_DIR(12, true, true);
-    else PL_DIR(6, true, true);
-  } else if (c->dist.active) {
-    if (tile_modes_now(c) == 12) PL_DIR(12, true, false);
-    else PL_DIR(6, true, false);
-  } else if (tile_modes_now(c) == 12) PL_DIR(12, false, false);
-  else PL_DIR(6, false, false);
-#undef PL_DIRF
-#undef PL_DIR
+  if (!useL && sizeof(PT) == 8)
+    with_tile_modes(c, [&](auto tm) { launch_direction_flat(c, tm, p, x, (const RT *)r, cur, nxt, hist_slot, nw); });
+  else
+    with_tail_variant(c, [&](auto tm, auto multi, auto local) {
+      launch_direction_coarse(c, tm, multi, local, p, x, (const RT *)r, cur, nxt, hist_slot, nw);
+    });
   PL_HIP(hipGetLastError());
   return PL_OK;
 }
@@ -211,32 +207,24 @@ int small_prepare(pl_context *c) {
 
 // update (r -= alpha Ap with the scalars of set k, restriction into the r_c buffer of parity k + 1, tile solve) and the
 // z-kernel of iteration k (k = -1: the pass that prepares iteration 0, alpha = 0; its history entry goes to hist_slot)
-int small_tail(pl_context *c, int k, int hist_slot) {
+template <int TM>
+void launch_small_z(pl_context *c, Int<TM>, int k, int hist_slot) {
   pl::Coarse &cs = c->coarse;
-  const uint8_t *skip = c->cond_use ? (const uint8_t *)c->cflag.p : (const uint8_t *)nullptr;
-  const double *Bt = cs.tile_level ? (const double *)cs.Bt_inv : (const double *)nullptr;
-  double *rc_new = small_rc(c, k + 1), *rc_old = small_rc(c, k);
-#define PL_SUPD(TM)                                                                                                         \
-  hipLaunchKernelGGL((pl::k_pcg_update_tile<double, double, TM, false, false>), dim3((unsigned)cs.n_tiles), dim3(cs.vblock),  \
-                     0, c->stream, c->tile.tile_start.p, cs.agg_of_tile.p, cs.cen.p, c->xyz.p, (const double *)c->Ap.p,     \
-                     cs.dinv32, (const double *)nullptr, c->r.p, small_set(c, k), rc_new, Bt, cs.yt,                        \
-                     (const int32_t *)nullptr, (const double *)nullptr, (const uint8_t *)nullptr, (double *)nullptr, cs.ncp, \
-                     skip, cs.cm)
-#define PL_SZ(TM)                                                                                                           \
-  hipLaunchKernelGGL((pl::k_small_z<TM>), dim3((unsigned)cs.n_tiles), dim3(cs.vblock), 0, c->stream, c->tile.tile_start.p,  \
-                     cs.agg_of_tile.p, cs.cen.p, c->xyz.p, (const double *)c->r.p, cs.dinv32, c->fixedbits.p, skip,         \
-                     (const float *)cs.Ainv, cs.ncp, cs.cm, (const double *)rc_new, rc_old,                                 \
-                     cs.tile_level ? (const double *)cs.yt : (const double *)nullptr, c->z.p, small_set(c, k + 1),          \
-                     small_set(c, k + 2), c->hist.p, hist_slot)
-  if (tile_modes_now(c) == 12) {
-    PL_SUPD(12);
-    PL_SZ(12);
-  } else {
-    PL_SUPD(6);
-    PL_SZ(6);
-  }
-#undef PL_SUPD
-#undef PL_SZ
+  hipLaunchKernelGGL((pl::k_small_z<TM>), dim3((unsigned)cs.n_tiles), dim3(cs.vblock), 0, c->stream, c->tile.tile_start.p,
+                     cs.agg_of_tile.p, cs.cen.p, c->xyz.p, (const double *)c->r.p, cs.dinv32, c->fixedbits.p,
+                     c->cond_use ? (const uint8_t *)c->cflag.p : (const uint8_t *)nullptr, (const float *)cs.Ainv, cs.ncp, cs.cm,
+                     (const double *)small_rc(c, k + 1), small_rc(c, k),
+                     cs.tile_level ? (const double *)cs.yt : (const double *)nullptr, c->z.p, small_set(c, k + 1),
+                     small_set(c, k + 2), c->hist.p, hist_slot);
+}
+int small_tail(pl_context *c, int k, int hist_slot) {
+  // (one rank, no rank-local level: small_wanted; the short form reads neither exact lever arms nor node words)
+  const NodeWords none = {(const float *)nullptr, (const uint32_t *)nullptr, (const uint32_t *)nullptr, 0.0};
+  with_tile_modes(c, [&](auto tm) {
+    launch_update_tile(c, tm, std::false_type{}, std::false_type{}, (const double *)c->Ap.p, c->r.p, small_set(c, k),
+                       small_rc(c, k + 1), none);
+    launch_small_z(c, tm, k, hist_slot);
+  });
   PL_HIP(hipGetLastError());
   return PL_OK;
 }
@@ -258,7 +246,7 @@ int small_iteration(pl_context *c, int k) {
   const void *tab = stream_form ? (const void *)c->tile.dir_table.p : (const void *)c->pal_dense.p;
   const int n_tab = stream_form ? c->tile.n_dir : c->pal_entries;
   const pl::Rec5 *r5 = stream_form ? reinterpret_cast<const pl::Rec5 *>(c->rec5.p) : (const pl::Rec5 *)nullptr;
-  if (c->cond_use) {
+  if (c->cond_use) {   // (the first pass of S p with the direction formed in the kernel, the second as in apply_operator)
     const pl::CondSolve cs = cond_solve(c, pl::kEndsCondensedSolve);
     if (!pl::launch_tile_spmv_lds_defer(c->tile, vw, tab, n_tab, r5, nullptr, df.p_new, nullptr, c->stream,
                                         pl::kEndsCondensedSolve, c->cflag.p, cs, df))
@@ -296,19 +284,9 @@ int pcg_iteration(pl_context *c, int k) {
   const int64_t n6 = c->N * 6;
   const int set = pl::S_COUNT * pl::kSlots;
   double *cur = c->scal.p + (k & 1) * set, *nxt = c->scal.p + ((k + 1) & 1) * set;
-  if (c->cond_use) {
-    // S p: the condensed nodes take their equilibrium position under p (first pass, their rows of p are 0 on entry),
-    // then the ordinary product with their rows masked like Dirichlet rows (second pass, with p.Ap)
-    // (first pass fused with the 6 x 6 solves: every tile writes -K_cc^-1 (K p_v)_c into the p rows of its condensed nodes)
-    int rc = launch_spmv(c, c->p.p, c->p.p, false, nullptr, nullptr, pl::kEndsCondensedSolve);
-    if (rc) return rc;
-    rc = launch_spmv(c, c->p.p, c->Ap.p, true, cur + pl::S_PAP * pl::kSlots, c->maskC.p, pl::kEndsOthers);
-    if (rc) return rc;
-    return pcg_tail_coarse(c, cur, nxt, k);
-  }
-  int rc = launch_spmv(c, c->p.p, c->Ap.p, true, cur + pl::S_PAP * pl::kSlots);
+  int rc = apply_operator(c, c->p.p, c->Ap.p, cur + pl::S_PAP * pl::kSlots);
   if (rc) return rc;
-  if (c->coarse.ready) return pcg_tail_coarse(c, cur, nxt, k);
+  if (c->coarse.ready) return pcg_tail_coarse(c, cur, nxt, k);      // (node elimination: with the multi-level PCG only)
   periodic_average(c, c->Ap.p);        // (periodic constraints: the operator is Q K Q; p.Kp above is already p.QKQp)
   // reference-CG mode (conjugate_gradient_solver.py:79-109): every restart_every-th iteration the direction is rebuilt
   // on the PREVIOUS z (with a preconditioner; kept in tmp) or on the updated residual (without one: z aliases r there)
@@ -328,57 +306,42 @@ int pcg_iteration(pl_context *c, int k) {
   const int hcap = ref ? c->hist_cap : 0;
   int *stop = c->stop_use ? c->stop_flag.p : (int *)nullptr;     // (DDM handles: the device stops itself, k_pcg_direction)
   const double stop_mintol = ref ? c->opt.mintol : 0.0;
+  const double *pn_upd = ref ? pn : (const double *)nullptr;
+  const auto update = [&] {            // x += alpha p, r -= alpha Ap, z = D^-1 r (DDM: dinv = 0 leaves z = 0, r.z = 0)
+    const auto kern = ref ? pl::k_pcg_update<true> : pl::k_pcg_update<false>;
+    hipLaunchKernelGGL(kern, dim3(grid_stream(n6 / 2)), dim3(pl::kBlock), 0, c->stream, n6, c->p.p, c->Ap.p, c->dinv.p,
+                       c->x.p, c->r.p, c->z.p, cur, c->opt.alpha_max, pn_upd, (const int *)stop);
+  };
+  const auto direction = [&]() -> int {
+    hipLaunchKernelGGL(pl::k_pcg_direction, dim3(grid_stream(n6 / 2)), dim3(pl::kBlock), 0, c->stream, n6, c->z.p,
+                       c->p.p, cur, nxt, c->hist.p, k, psrc, hcap, stop, c->stop_thresh, stop_mintol);
+    PL_HIP(hipGetLastError());
+    return PL_OK;
+  };
   if (c->dd2_ready) {                  // two-level DDM preconditioner: update and restriction in one pass over the aggregates
     const uint8_t *fx = c->have_bc ? (const uint8_t *)c->fixed.p : (const uint8_t *)nullptr;
-    const dim3 g((unsigned)(c->dd2_n_agg * pl::kDdmSplit));
-    if (ref)
-      hipLaunchKernelGGL(pl::k_ddm_update_restrict<true>, g, dim3(pl::kBlock), 0, c->stream, c->dd2_ptr.p, c->dd2_nodes.p,
-                         (const double *)c->dd2_cen.p, (const double *)c->dd2_xyz.p, fx, (const double *)c->p.p,
-                         (const double *)c->Ap.p, c->x.p, c->r.p, cur, c->opt.alpha_max, pn, (const int *)stop, c->dd2.rc);
-    else
-      hipLaunchKernelGGL(pl::k_ddm_update_restrict<false>, g, dim3(pl::kBlock), 0, c->stream, c->dd2_ptr.p, c->dd2_nodes.p,
-                         (const double *)c->dd2_cen.p, (const double *)c->dd2_xyz.p, fx, (const double *)c->p.p,
-                         (const double *)c->Ap.p, c->x.p, c->r.p, cur, c->opt.alpha_max, (const double *)nullptr,
-                         (const int *)stop, c->dd2.rc);
+    const auto kern = ref ? pl::k_ddm_update_restrict<true> : pl::k_ddm_update_restrict<false>;
+    hipLaunchKernelGGL(kern, dim3((unsigned)(c->dd2_n_agg * pl::kDdmSplit)), dim3(pl::kBlock), 0, c->stream, c->dd2_ptr.p,
+                       c->dd2_nodes.p, (const double *)c->dd2_cen.p, (const double *)c->dd2_xyz.p, fx, (const double *)c->p.p,
+                       (const double *)c->Ap.p, c->x.p, c->r.p, cur, c->opt.alpha_max, pn_upd, (const int *)stop, c->dd2.rc);
     ddm_precondition(c, cur + pl::S_RZ_NEW * pl::kSlots, true);
-    hipLaunchKernelGGL(pl::k_pcg_direction, dim3(grid_stream(n6 / 2)), dim3(pl::kBlock), 0, c->stream, n6, c->z.p,
-                       c->p.p, cur, nxt, c->hist.p, k, psrc, hcap, stop, c->stop_thresh, stop_mintol);
-    PL_HIP(hipGetLastError());
-    return PL_OK;
+    return direction();
   }
-  if (c->dd_ready || c->dd_blocks) {   // DDM with the factorised assembled matrix / its node blocks: update leaves z = 0,
-                                       // r.z = 0; then z = G^-1 r
-    if (ref)
-      hipLaunchKernelGGL(pl::k_pcg_update<true>, dim3(grid_stream(n6 / 2)), dim3(pl::kBlock), 0, c->stream, n6, c->p.p,
-                         c->Ap.p, c->dinv.p, c->x.p, c->r.p, c->z.p, cur, c->opt.alpha_max, pn, (const int *)stop);
-    else
-      hipLaunchKernelGGL(pl::k_pcg_update<false>, dim3(grid_stream(n6 / 2)), dim3(pl::kBlock), 0, c->stream, n6, c->p.p,
-                         c->Ap.p, c->dinv.p, c->x.p, c->r.p, c->z.p, cur, c->opt.alpha_max, (const double *)nullptr,
-                         (const int *)stop);
+  if (c->dd_ready || c->dd_blocks) {   // DDM with the factorised assembled matrix / its node blocks: then z = G^-1 r
+    update();
     ddm_precondition(c, cur + pl::S_RZ_NEW * pl::kSlots);
-    hipLaunchKernelGGL(pl::k_pcg_direction, dim3(grid_stream(n6 / 2)), dim3(pl::kBlock), 0, c->stream, n6, c->z.p,
-                       c->p.p, cur, nxt, c->hist.p, k, psrc, hcap, stop, c->stop_thresh, stop_mintol);
-    PL_HIP(hipGetLastError());
-    return PL_OK;
+    return direction();
   }
   if (c->dist.active) {
     pl::launch_pcg_update_weighted(n6, c->p.p, c->Ap.p, c->dinv.p, c->dist.weight.p, c->x.p, c->r.p, c->z.p, cur,
                                    c->stream);
     if (pl::dist_sum_scalars(c->dist, cur + pl::S_RZ_NEW * pl::kSlots, 2 * pl::kSlots, c->stream))
       return fail(PL_ERR_HIP, "RCCL all-reduce of the PCG scalars failed");
-  } else if (ref) {
-    hipLaunchKernelGGL(pl::k_pcg_update<true>, dim3(grid_stream(n6 / 2)), dim3(pl::kBlock), 0, c->stream, n6, c->p.p,
-                       c->Ap.p, c->dinv.p, c->x.p, c->r.p, c->z.p, cur, c->opt.alpha_max, pn, (const int *)stop);
   } else {
-    hipLaunchKernelGGL(pl::k_pcg_update<false>, dim3(grid_stream(n6 / 2)), dim3(pl::kBlock), 0, c->stream, n6, c->p.p,
-                       c->Ap.p, c->dinv.p, c->x.p, c->r.p, c->z.p, cur, c->opt.alpha_max, (const double *)nullptr,
-                       (const int *)stop);
+    update();
   }
   periodic_average(c, c->z.p);         // z = Q D^-1 r (r.z was summed with the un-averaged D^-1 r: the same number, r = Q r)
-  hipLaunchKernelGGL(pl::k_pcg_direction, dim3(grid_stream(n6 / 2)), dim3(pl::kBlock), 0, c->stream, n6, c->z.p,
-                     c->p.p, cur, nxt, c->hist.p, k, psrc, hcap, stop, c->stop_thresh, stop_mintol);
-  PL_HIP(hipGetLastError());
-  return PL_OK;
+  return direction();
 }
 
 // The PCG loop as one persistent launch (pl_persist.h): x, r hold the initial iterate and residual on entry, the result on exit.
@@ -446,28 +409,22 @@ int persist_solve(pl_context *c, double thresh, double bb, int max_iter, pl_stat
   const size_t lds = ((size_t)12 * a.stride + (size_t)2 * a.n_tab * (stream_form ? 2 : pl::kPalLdsChunks) + (size_t)2 * cs.ncp +
                       (size_t)G * pl::kPersistRed) * sizeof(double) + ((size_t)c->ps_n_agg + 1 + G + 2) * sizeof(int32_t);
   if (lds > 150 * 1024) return fail(PL_ERR_STATE, "persistent PCG: the tile state does not fit the LDS");
-  const bool tm12 = tile_modes_now(c) == 12;
-#define PL_PS3(R, TM, NC)                                                                                               \
-  do {                                                                                                                  \
-    PL_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&pl::k_persist_cg1<R, TM, NC>),                           \
-                               hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));                                   \
-    hipLaunchKernelGGL((pl::k_persist_cg1<R, TM, NC>), dim3((unsigned)G), dim3(pl::kPersistBlock), lds, c->stream, a); \
-  } while (0)
-#define PL_PS(R, TM)                                                                   \
-  do {                                                                                 \
-    if (cs.ncp <= 2 * pl::kPersistBlock) PL_PS3(R, TM, 2);                             \
-    else if (cs.ncp <= 3 * pl::kPersistBlock) PL_PS3(R, TM, 3);                        \
-    else PL_PS3(R, TM, 4);                                                             \
-  } while (0)
-  if (stream_form) {
-    if (tm12) PL_PS(pl::kRecCompact, 12);
-    else PL_PS(pl::kRecCompact, 6);
-  } else {
-    if (tm12) PL_PS(pl::kRecPalette, 12);
-    else PL_PS(pl::kRecPalette, 6);
-  }
-#undef PL_PS
-#undef PL_PS3
+  hipError_t attr = hipSuccess;
+  const auto launch = [&](auto rec, auto tm, auto nc) {
+    const auto kern = &pl::k_persist_cg1<decltype(rec)::value, decltype(tm)::value, decltype(nc)::value>;
+    attr = hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    if (attr == hipSuccess) hipLaunchKernelGGL(kern, dim3((unsigned)G), dim3(pl::kPersistBlock), lds, c->stream, a);
+  };
+  with_tile_modes(c, [&](auto tm) {
+    const auto columns = [&](auto rec) {      // columns of A_c^-1 per thread
+      if (cs.ncp <= 2 * pl::kPersistBlock) launch(rec, tm, Int<2>{});
+      else if (cs.ncp <= 3 * pl::kPersistBlock) launch(rec, tm, Int<3>{});
+      else launch(rec, tm, Int<4>{});
+    };
+    if (stream_form) columns(Int<pl::kRecCompact>{});
+    else columns(Int<pl::kRecPalette>{});
+  });
+  PL_HIP(attr);
   PL_HIP(hipGetLastError());
   unsigned tail[3] = {0, 0, 0};
   PL_HIP(hipMemcpyAsync(tail, c->ps_flags.p + 2 * G, sizeof(tail), hipMemcpyDeviceToHost, c->stream));
@@ -495,12 +452,9 @@ int persist_solve(pl_context *c, double thresh, double bb, int max_iter, pl_stat
   return PL_OK;
 }
 
-// Solve P K P x = rhs (device rhs already masked), x0 = 0.  Result in c->x.  Returns iterations through stats.
-int pcg_solve(pl_context *c, const double *f_dev, const double *Kubar_dev, double rtol, int max_iter,
-              pl_stats_t *st) {
+// r0 = P (f - K ubar), x = 0, z0 = p0 = D^-1 r0 (G^-1 r0 on DDM handles), ||b||^2 and r0.z0 into scalar set 0
+int pcg_init(pl_context *c, const double *f_dev, const double *Kubar_dev, bool sum_rz) {
   const int64_t n6 = c->N * 6;
-  int rc = ensure_hist(c, max_iter + 1);
-  if (rc) return rc;
   PL_HIP(hipMemsetAsync(c->scal.p, 0, 2 * pl::S_COUNT * pl::kSlots * sizeof(double), c->stream));
   if (c->dist.active)
     pl::launch_pcg_init_weighted(n6, f_dev, Kubar_dev, c->fixed.p, c->dinv.p, c->dist.weight.p, c->x.p, c->r.p,
@@ -510,203 +464,58 @@ int pcg_solve(pl_context *c, const double *f_dev, const double *Kubar_dev, doubl
                        c->fixed.p, c->dinv.p, c->x.p, c->r.p, c->z.p, c->p.p, c->scal.p);
   PL_HIP(hipGetLastError());
   if (c->dist.active) {
-    if (pl::dist_sum_scalars(c->dist, c->scal.p + pl::S_RZ_OLD * pl::kSlots, pl::kSlots, c->stream) ||
+    if ((sum_rz && pl::dist_sum_scalars(c->dist, c->scal.p + pl::S_RZ_OLD * pl::kSlots, pl::kSlots, c->stream)) ||
         pl::dist_sum_scalars(c->dist, c->scal.p + pl::S_BB * pl::kSlots, pl::kSlots, c->stream))
       return fail(PL_ERR_HIP, "RCCL all-reduce of the initial PCG scalars failed");
   }
-  if (c->n_per_groups > 0) {   // periodic constraints: b is Q b (the caller's part), z0 = Q D^-1 r0, p0 = z0
-    periodic_average(c, c->z.p);
-    PL_HIP(hipMemcpyAsync(c->p.p, c->z.p, n6 * sizeof(double), hipMemcpyDeviceToDevice, c->stream));
-  }
-  if (c->dd_ready || c->dd_blocks) {   // z0 = p0 = G^-1 r0, rz_old = r0.z0 (k_pcg_init ran with dinv = 0)
-    ddm_precondition(c, c->scal.p + pl::S_RZ_OLD * pl::kSlots);
-    PL_HIP(hipMemcpyAsync(c->p.p, c->z.p, n6 * sizeof(double), hipMemcpyDeviceToDevice, c->stream));
-  }
-  if (c->cond_use) {   // (decided by solver_plan: never with a K*p kernel that ignores the elimination masks)
-    // start from the iterate whose condensed nodes are in equilibrium: x_c = K_cc^-1 r_c, r <- r - K x (rows of the
-    // condensed nodes become exactly 0 and stay 0: every later step keeps them in equilibrium)
-    // t_c = K_cc^-1 b_c (rows of z, zero elsewhere), r_v -= (K t)_v: the load the eliminated nodes pass on.  Their own
-    // rows of r keep b_c, their rows of x stay 0 until the back-substitution after the loop.
-    PL_HIP(hipMemsetAsync(c->z.p, 0, n6 * sizeof(double), c->stream));
-    hipLaunchKernelGGL(pl::k_condense_solve<double>, dim3(grid_for(c->n_cond * 6)), dim3(pl::kBlock), 0, c->stream,
-                       c->n_cond, c->cnodes.p, cinv(c), ccls(c), (const double *)c->r.p, c->z.p, 1.0);
-    rc = launch_spmv(c, c->z.p, c->tmp2.p, true, nullptr, c->maskC.p, pl::kEndsOthers);
-    if (rc) return rc;
-    hipLaunchKernelGGL(pl::k_condense_subtract<double>, dim3(grid_for(n6)), dim3(pl::kBlock), 0, c->stream, c->N, c->cflag.p,
-                       (const double *)c->tmp2.p, c->r.p);
-    PL_HIP(hipGetLastError());
-  }
-  const bool warm = c->opt.warm_start >= 1 && c->coarse.ready && !c->dist.active;
-  if (warm && c->xprev.p && c->xprev_valid) {
-    // x0 = the previous solution: r0 = b - S x0 through the same operator the iterations apply (with node elimination: first
-    // pass fills the eliminated rows of p, second pass takes the others); the tail below then builds z0, p0 from r0
-    bool combined = false;
-    if (c->opt.warm_start == 4 && c->gh_count >= 1) {
-      // Galerkin start: the combination x0 = sum c_i v_i of the handle's last m solutions that is nearest to the solution
-      // of the CURRENT system in its energy norm, (V^T S V) c = V^T b.  It contains the previous solution and both
-      // extrapolations as candidates, and - a projection - can do no worse than any of them.  m applications of the operator,
-      // m + 1 dot products each, one look at m^2 + m numbers on the host.
-      static const int want = [] { const char *e = std::getenv("PL_WARM_VECTORS"); const int v = e ? std::atoi(e) : 6;       // (configs[3]: 183 / 170 / 160 / 155 iterations per solve with 3 / 4 / 6 / 8)
-                                   return std::max(2, std::min(kWarmMax, v)); }();
-      const int m = std::min(want, 1 + c->gh_count);
-      const uint8_t *cf = c->cond_use ? (const uint8_t *)c->cflag.p : (const uint8_t *)nullptr;
-      WarmVecs V;
-      for (int i = 0; i < kWarmMax; ++i) V.v[i] = nullptr;
-      for (int i = 0; i < m; ++i) {
-        const double *src = i == 0 ? c->xprev.p
-                                   : c->gh[(c->gh_head - (i - 1) + 2 * (kWarmMax - 1)) % (kWarmMax - 1)].p;
-        if (!c->gw[i].p || c->gw[i].n < (size_t)n6) PL_HIP(c->gw[i].alloc(n6));
-        PL_HIP(hipMemcpyAsync(c->gw[i].p, src, n6 * sizeof(double), hipMemcpyDeviceToDevice, c->stream));
-        hipLaunchKernelGGL(k_warm_mask, dim3(grid_for(n6)), dim3(pl::kBlock), 0, c->stream, c->N, cf, (const uint8_t *)c->fixed.p,
-                           c->gw[i].p);
-        V.v[i] = c->gw[i].p;
-      }
-      constexpr int kRow = kWarmMax + 1;
-      if (!c->gw_dots.p) PL_HIP(c->gw_dots.alloc(kWarmMax * kRow));
-      PL_HIP(hipMemsetAsync(c->gw_dots.p, 0, kWarmMax * kRow * sizeof(double), c->stream));
-      for (int j = 0; j < m; ++j) {
-        // (with node elimination the first pass writes the eliminated rows of its operand: on a copy, the dots skip those rows)
-        PL_HIP(hipMemcpyAsync(c->p.p, c->gw[j].p, n6 * sizeof(double), hipMemcpyDeviceToDevice, c->stream));
-        if (c->cond_use) {
-          rc = launch_spmv(c, c->p.p, c->p.p, false, nullptr, nullptr, pl::kEndsCondensedSolve);
-          if (rc) return rc;
-          rc = launch_spmv(c, c->p.p, c->Ap.p, true, nullptr, c->maskC.p, pl::kEndsOthers);
-        } else {
-          rc = launch_spmv(c, c->p.p, c->Ap.p, true, nullptr);
-        }
-        if (rc) return rc;
-        hipLaunchKernelGGL(k_warm_dots, dim3(grid_stream(n6)), dim3(pl::kBlock), 0, c->stream, c->N, m, V, j, cf,
-                           (const double *)c->Ap.p, (const double *)c->r.p, c->gw_dots.p + kRow * j);
-      }
-      double hd[kWarmMax * kRow];
-      PL_HIP(hipMemcpyAsync(hd, c->gw_dots.p, sizeof(hd), hipMemcpyDeviceToHost, c->stream));
-      PL_HIP(hipStreamSynchronize(c->stream));
-      // G[i][j] = hd[kRow j + i] (symmetrised), g[j] = hd[kRow j + m]; Cholesky with a relative pivot floor: vectors that add
-      // nothing new (a stalled design path) are dropped
-      double G[kWarmMax][kWarmMax], g[kWarmMax], L[kWarmMax][kWarmMax] = {}, y[kWarmMax] = {};
-      WarmCoef cc;
-      for (int i = 0; i < kWarmMax; ++i) cc.c[i] = 0.0;
-      bool ok = true, used[kWarmMax] = {};
-      for (int i = 0; i < m; ++i) {
-        g[i] = hd[kRow * i + m];
-        for (int j = 0; j < m; ++j) G[i][j] = 0.5 * (hd[kRow * j + i] + hd[kRow * i + j]);
-        if (!(G[i][i] > 0.0) || !std::isfinite(G[i][i]) || !std::isfinite(g[i])) ok = false;
-      }
-      if (ok) {
-        for (int j = 0; j < m; ++j) {            // (in the order newest first: the newest vector is always kept)
-          double d = G[j][j];
-          for (int k = 0; k < j; ++k)
-            if (used[k]) d -= L[j][k] * L[j][k];
-          if (!(d > 1e-10 * G[j][j])) continue;
-          used[j] = true;
-          L[j][j] = std::sqrt(d);
-          for (int i = j + 1; i < m; ++i) {
-            double v = G[i][j];
-            for (int k = 0; k < j; ++k)
-              if (used[k]) v -= L[i][k] * L[j][k];
-            L[i][j] = v / L[j][j];
-          }
-        }
-        for (int i = 0; i < m; ++i) {
-          if (!used[i]) continue;
-          double v = g[i];
-          for (int k = 0; k < i; ++k)
-            if (used[k]) v -= L[i][k] * y[k];
-          y[i] = v / L[i][i];
-        }
-        for (int i = m - 1; i >= 0; --i) {
-          if (!used[i]) continue;
-          double v = y[i];
-          for (int k = i + 1; k < m; ++k)
-            if (used[k]) v -= L[k][i] * cc.c[k];
-          cc.c[i] = v / L[i][i];
-        }
-        for (int i = 0; i < m; ++i)
-          if (!std::isfinite(cc.c[i])) ok = false;
-      }
-      if (ok) {
-        hipLaunchKernelGGL(k_warm_combine, dim3(grid_for(n6)), dim3(pl::kBlock), 0, c->stream, n6, m, V, cc, c->p.p);
-        combined = true;
-      }
-    }
-    if (combined) {
-      // (p holds the combination of masked vectors)
-    } else if (c->opt.warm_start == 3 && c->xprev2_valid && c->xprev3_valid)
-      hipLaunchKernelGGL(k_warm_extrapolate2, dim3(grid_for(n6)), dim3(pl::kBlock), 0, c->stream, n6, (const double *)c->xprev.p,
-                         (const double *)c->xprev2.p, (const double *)c->xprev3.p, c->p.p);
-    else if ((c->opt.warm_start == 2 || c->opt.warm_start == 3) && c->xprev2.p && c->xprev2_valid)
-      hipLaunchKernelGGL(k_warm_extrapolate, dim3(grid_for(n6)), dim3(pl::kBlock), 0, c->stream, n6, (const double *)c->xprev.p,
-                         (const double *)c->xprev2.p, c->p.p);
-    else
-      PL_HIP(hipMemcpyAsync(c->p.p, c->xprev.p, n6 * sizeof(double), hipMemcpyDeviceToDevice, c->stream));
-    hipLaunchKernelGGL(k_warm_mask, dim3(grid_for(n6)), dim3(pl::kBlock), 0, c->stream, c->N,
-                       c->cond_use ? (const uint8_t *)c->cflag.p : (const uint8_t *)nullptr, (const uint8_t *)c->fixed.p, c->p.p);
-    if (c->cond_use) {
-      rc = launch_spmv(c, c->p.p, c->p.p, false, nullptr, nullptr, pl::kEndsCondensedSolve);
-      if (rc) return rc;
-      rc = launch_spmv(c, c->p.p, c->Ap.p, true, nullptr, c->maskC.p, pl::kEndsOthers);
-    } else {
-      rc = launch_spmv(c, c->p.p, c->Ap.p, true, nullptr);
-    }
-    if (rc) return rc;
-    hipLaunchKernelGGL(k_warm_apply, dim3(grid_for(n6)), dim3(pl::kBlock), 0, c->stream, c->N,
-                       c->cond_use ? (const uint8_t *)c->cflag.p : (const uint8_t *)nullptr, (const double *)c->Ap.p,
-                       (const double *)c->p.p, c->r.p, c->x.p);
-    PL_HIP(hipGetLastError());
-  }
-  if (c->persist_use) {
-    // (the persistent launch builds u0 = M^-1 r0 itself)
-  } else if (c->small_use) {
-    // short form: z0 = M^-1 r0 and r0.z0 through the tail of an iteration "-1" (alpha = 0: set -1 of the ring is zero);
-    // iteration 0 then forms p0 = z0 + 0 p_old in its K*p launch
-    rc = small_prepare(c);
+  return PL_OK;
+}
+
+// Node elimination, before the loop: start from the iterate whose eliminated nodes are in equilibrium.  t_c = K_cc^-1 b_c
+// (rows of the zeroed t, zero elsewhere), r_v -= (K t)_v: the load the eliminated nodes pass on.  Their own rows of r keep
+// b_c (every later step keeps them in equilibrium), their rows of x stay 0 until the back-substitution after the loop.
+template <typename T>
+int condense_prologue(pl_context *c, T *r, T *t, T *Kt) {
+  hipLaunchKernelGGL(pl::k_condense_solve<T>, dim3(grid_for(c->n_cond * 6)), dim3(pl::kBlock), 0, c->stream, c->n_cond,
+                     c->cnodes.p, cinv(c), ccls(c), (const T *)r, t, 1.0);
+  const int rc = spmv_as_stored<T>(c, t, Kt, true, nullptr, c->maskC.p, pl::kEndsOthers);
+  if (rc) return rc;
+  hipLaunchKernelGGL(pl::k_condense_subtract<T>, dim3(grid_for(c->N * 6)), dim3(pl::kBlock), 0, c->stream, c->N, c->cflag.p,
+                     (const T *)Kt, r);
+  PL_HIP(hipGetLastError());
+  return PL_OK;
+}
+// ... and after it: x_c = K_cc^-1 (b_c - (K [x_v ; 0])_c)
+template <typename T>
+int condense_backsubst(pl_context *c, T *x, const T *r, T *Kx) {
+  const int rc = spmv_as_stored<T>(c, x, Kx, false, nullptr, nullptr, pl::kEndsCondensed);
+  if (rc) return rc;
+  hipLaunchKernelGGL(pl::k_condense_backsubst<T>, dim3(grid_for(c->n_cond * 6)), dim3(pl::kBlock), 0, c->stream, c->n_cond,
+                     c->cnodes.p, cinv(c), ccls(c), r, (const T *)Kx, x);
+  PL_HIP(hipGetLastError());
+  return PL_OK;
+}
+
+// z0 = M^-1 r0 and r0.z0 of the multi-level forms, through the tail of an iteration "-1" (alpha = 0); its history entry
+// goes to slot max_iter.  (The persistent launch builds u0 = M^-1 r0 itself.)
+int pcg_first_direction(pl_context *c, int max_iter) {
+  const int64_t n6 = c->N * 6;
+  if (c->persist_use || !(c->small_use || c->coarse.ready)) return PL_OK;
+  if (c->small_use) {   // set -1 of the ring is zero; iteration 0 then forms p0 = z0 + 0 p_old in its K*p launch
+    const int rc = small_prepare(c);
     if (rc) return rc;
     PL_HIP(hipMemsetAsync(c->Ap.p, 0, n6 * sizeof(double), c->stream));
-    rc = small_tail(c, -1, max_iter);
-    if (rc) return rc;
-  } else if (c->coarse.ready) {
-    // z0 = M^-1 r0 needs the coarse solve: run the tail of an iteration "-1" with p = 0, alpha = 0 (p.Ap = 0) on
-    // scalar set 1; its direction kernel leaves p = z0 and rz_old = r0.z0 in set 0, where iteration 0 starts.
-    const int set = pl::S_COUNT * pl::kSlots;
-    PL_HIP(hipMemsetAsync(c->p.p, 0, n6 * sizeof(double), c->stream));
-    PL_HIP(hipMemsetAsync(c->Ap.p, 0, n6 * sizeof(double), c->stream));
-    rc = pcg_tail_coarse(c, c->scal.p + set, c->scal.p, max_iter);
-    if (rc) return rc;
+    return small_tail(c, -1, max_iter);
   }
-  double h_scal[pl::kSlots];
-  PL_HIP(hipMemcpyAsync(h_scal, c->scal.p + pl::S_BB * pl::kSlots, sizeof(h_scal), hipMemcpyDeviceToHost,
-                        c->stream));
-  PL_HIP(hipStreamSynchronize(c->stream));
-  double bb = 0.0;
-  for (int k = 0; k < pl::kSlots; ++k) bb += h_scal[k];
-  st->b_norm = std::sqrt(bb);
-  st->iterations = 0;
-  st->converged = 0;
-  st->rel_residual = 0.0;
-  if (!(bb > 0.0)) {   // zero right-hand side -> zero solution (a warm start above may have put the previous one into x)
-    st->converged = 1;
-    PL_HIP(hipMemsetAsync(c->x.p, 0, n6 * sizeof(double), c->stream));
-    PL_HIP(hipStreamSynchronize(c->stream));
-    return std::isnan(bb) ? fail(PL_ERR_NAN, "NaN in the right-hand side") : PL_OK;
-  }
-  const double thresh = rtol * rtol * bb;
-  if (c->persist_use) {
-    rc = persist_solve(c, thresh, bb, max_iter, st);
-    if (rc) return rc;
-    c->last_iterations = st->converged ? st->iterations : 0;
-    if (c->opt.warm_start == 1 && st->converged) {      // keep the solution for the next solve (as below)
-      if (!c->xprev.p) PL_HIP(c->xprev.alloc(n6));
-      PL_HIP(hipMemcpyAsync(c->xprev.p, c->x.p, n6 * sizeof(double), hipMemcpyDeviceToDevice, c->stream));
-      c->xprev_valid = true;
-    }
-    return PL_OK;
-  }
-  // The host looks at the residual history every `chunk` iterations.  With the default (check_every = 0) the chunk
-  // adapts: 32 while far from the threshold, then what the observed decay rate predicts is still needed - a fixed
-  // chunk overshoots by 16 iterations on average, 8 % of a 200-iteration solve.  (Every rank of a multi-GPU run sees
-  // the same all-reduced history, hence takes the same decisions.)
-  const bool adaptive = c->opt.check_every <= 0;
-  const int chunk = adaptive ? 32 : c->opt.check_every;
+  // p = 0 (p.Ap = 0) on scalar set 1: the direction kernel leaves p = z0 and rz_old = r0.z0 in set 0, where iteration 0 starts
+  PL_HIP(hipMemsetAsync(c->p.p, 0, n6 * sizeof(double), c->stream));
+  PL_HIP(hipMemsetAsync(c->Ap.p, 0, n6 * sizeof(double), c->stream));
+  return pcg_tail_coarse(c, c->scal.p + pl::S_COUNT * pl::kSlots, c->scal.p, max_iter);
+}
+
+// The iterations of pcg_solve: chunks of the look schedule (pl_schedule.h), the residual history read after each.
+// *done: iterations the device has run.
+int pcg_loop(pl_context *c, double thresh, double bb, int max_iter, pl_stats_t *st, int *done) {
   const bool ref = ref_cg(c) && !c->dist.active && !c->coarse.ready;
   const int hcap = c->hist_cap;
   // DDM handles: the device applies the stopping rules itself and freezes the iterate (k_pcg_direction), so the host may
@@ -717,25 +526,19 @@ int pcg_solve(pl_context *c, const double *f_dev, const double *Kubar_dev, doubl
     PL_HIP(hipMemsetAsync(c->stop_flag.p, 0, sizeof(int), c->stream));
     c->stop_thresh = thresh;
   }
-  // A design loop solves a slowly changing system over and over: the iteration count of the previous converged solve on
-  // this handle (identical on every rank) is where the first look at the history is worth taking - three iterations
-  // before it - instead of every 32 iterations on the way there (each look drains the stream: 30-50 us).
-  // ... and a handle preconditioned by a dense FACTOR of its own matrix (precond = 5; the assembled Schur matrix of a DDM handle,
-  // precond = 2) converges in one or two steps: look after two (32 queued iterations of a 9-node cell were 0.5 ms of the 0.57 ms
-  // a column of pl_schur took)
-  const bool direct = adaptive && c->dd_ready;
-  const int first = direct ? std::min(2, max_iter)
-                           : ((adaptive && !ref && c->last_iterations > 40) ? std::min(c->last_iterations - 3, max_iter) : chunk);
-  const int hbuf = std::max(chunk, first);
+  pl::LookParams lp{c->opt.check_every, max_iter, thresh, bb};
+  lp.dd_ready = c->dd_ready;
+  lp.ref_cg = ref;
+  lp.last_iterations = c->last_iterations;
+  pl::LookSchedule look(lp);
+  const int hbuf = look.max_chunk();
   std::vector<double> h_hist(hbuf), h_pp(ref ? hbuf : 0), h_xx(ref ? hbuf : 0), h_al(ref ? hbuf : 0);
   st->info = 1.0;
-  int k = 0, next = first;
-  double rr_prev = bb;
-  int k_prev = 0;
+  int k = 0;
   while (k < max_iter) {
-    const int todo = std::min(next, max_iter - k);
+    const int todo = look.todo(k);
     for (int j = 0; j < todo; ++j) {
-      rc = pcg_iteration(c, k + j);
+      const int rc = pcg_iteration(c, k + j);
       if (rc) return rc;
     }
     PL_HIP(hipMemcpyAsync(h_hist.data(), c->hist.p + k, todo * sizeof(double), hipMemcpyDeviceToHost, c->stream));
@@ -749,75 +552,81 @@ int pcg_solve(pl_context *c, const double *f_dev, const double *Kubar_dev, doubl
       const double rr = h_hist[j];
       if (std::isnan(rr) || std::isinf(rr)) return fail(PL_ERR_NAN, "NaN/Inf in the PCG residual");
       if (!st->converged) st->rel_residual = std::sqrt(rr / bb);
-      if (rr <= thresh && !st->converged) {
-        st->converged = 1;
-        st->iterations = k + j + 1;
-        st->info = 0.0;
-        st->stop_reason = 0.0;
-      }
+      if (rr <= thresh && !st->converged) converged_at(st, k + j + 1, 0.0);
       if (ref && !st->converged) {
         // conjugate_gradient_solver.py:102-109, in its order: the direction-norm stop, then the "tiny step" flag
-        if (c->opt.mintol > 0.0 && std::sqrt(h_pp[j]) < c->opt.mintol * (std::sqrt(h_xx[j]) + 1e-12)) {
-          st->converged = 1;
-          st->iterations = k + j + 1;
-          st->info = 0.0;
-          st->stop_reason = 1.0;
-        } else if (h_al[j] < 1e-6) {
-          st->info = 2.0;
-        }
+        if (c->opt.mintol > 0.0 && std::sqrt(h_pp[j]) < c->opt.mintol * (std::sqrt(h_xx[j]) + 1e-12)) converged_at(st, k + j + 1, 1.0);
+        else if (h_al[j] < 1e-6) st->info = 2.0;
       }
       if (st->converged && c->stop_use) break;     // (the device stopped there too: later slots of the history are not written)
     }
     k += todo;
     if (st->converged) break;
-    if (adaptive) {
-      const double rr_end = h_hist[todo - 1];
-      next = direct && k < 16 ? 2 : chunk;
-      if (rr_end < rr_prev && rr_end > thresh) {
-        const double per_it = std::log(rr_end / rr_prev) / (double)(k - k_prev);      // < 0
-        const double need = std::log(thresh / rr_end) / per_it;
-        if (need < 2.0 * chunk) next = std::max(2, std::min(chunk, (int)std::ceil(0.75 * need)));
-      }
-      rr_prev = rr_end;
-      k_prev = k;
-    }
+    look.missed(k, h_hist[todo - 1]);
   }
   if (!st->converged) st->iterations = k;
+  *done = k;
+  return PL_OK;
+}
+
+// Solve P K P x = rhs (device rhs already masked), x0 = 0.  Result in c->x.  Returns iterations through stats.
+int pcg_solve(pl_context *c, const double *f_dev, const double *Kubar_dev, double rtol, int max_iter,
+              pl_stats_t *st) {
+  const int64_t n6 = c->N * 6;
+  int rc = ensure_hist(c, max_iter + 1);
+  if (rc) return rc;
+  rc = pcg_init(c, f_dev, Kubar_dev, true);
+  if (rc) return rc;
+  if (c->n_per_groups > 0) {   // periodic constraints: b is Q b (the caller's part), z0 = Q D^-1 r0, p0 = z0
+    periodic_average(c, c->z.p);
+    PL_HIP(hipMemcpyAsync(c->p.p, c->z.p, n6 * sizeof(double), hipMemcpyDeviceToDevice, c->stream));
+  }
+  if (c->dd_ready || c->dd_blocks) {   // z0 = p0 = G^-1 r0, rz_old = r0.z0 (k_pcg_init ran with dinv = 0)
+    ddm_precondition(c, c->scal.p + pl::S_RZ_OLD * pl::kSlots);
+    PL_HIP(hipMemcpyAsync(c->p.p, c->z.p, n6 * sizeof(double), hipMemcpyDeviceToDevice, c->stream));
+  }
+  if (c->cond_use) {   // (decided by solver_plan: never with a K*p kernel that ignores the elimination masks)
+    PL_HIP(hipMemsetAsync(c->z.p, 0, n6 * sizeof(double), c->stream));
+    rc = condense_prologue<double>(c, c->r.p, c->z.p, c->tmp2.p);
+    if (rc) return rc;
+  }
+  const bool warm = c->opt.warm_start >= 1 && c->coarse.ready && !c->dist.active;
+  if (warm && c->xprev.p && c->xprev_valid) {
+    rc = warm_start_apply(c);
+    if (rc) return rc;
+  }
+  rc = pcg_first_direction(c, max_iter);
+  if (rc) return rc;
+  double bb = 0.0;
+  bool zero = false;
+  rc = solve_begin(c, c->scal.p + pl::S_BB * pl::kSlots, st, &bb, &zero);
+  if (zero) {   // zero right-hand side -> zero solution (a warm start above may have put the previous one into x)
+    PL_HIP(hipMemsetAsync(c->x.p, 0, n6 * sizeof(double), c->stream));
+    PL_HIP(hipStreamSynchronize(c->stream));
+  }
+  if (rc || zero) return rc;
+  const double thresh = rtol * rtol * bb;
+  if (c->persist_use) {
+    rc = persist_solve(c, thresh, bb, max_iter, st);
+    if (rc) return rc;
+    c->last_iterations = st->converged ? st->iterations : 0;
+    // (as found: only warm_start = 1 keeps the solution here, although 2 to 4 reach this branch as well)
+    return c->opt.warm_start == 1 && st->converged ? warm_retain(c, false) : PL_OK;
+  }
+  int k = 0;
+  rc = pcg_loop(c, thresh, bb, max_iter, st, &k);
+  if (rc) return rc;
   c->last_iterations = st->converged ? st->iterations : 0;
   if (c->small_use) {
     rc = small_finish(c, k);
     if (rc) return rc;
     st->short_iteration_used = 1.0;
   }
-  if (c->cond_use) {   // eliminated nodes: x_c = K_cc^-1 (b_c - (K [x_v ; 0])_c)
-    rc = launch_spmv(c, c->x.p, c->tmp2.p, false, nullptr, nullptr, pl::kEndsCondensed);
+  if (c->cond_use) {
+    rc = condense_backsubst<double>(c, c->x.p, (const double *)c->r.p, c->tmp2.p);
     if (rc) return rc;
-    hipLaunchKernelGGL(pl::k_condense_backsubst<double>, dim3(grid_for(c->n_cond * 6)), dim3(pl::kBlock), 0, c->stream,
-                       c->n_cond, c->cnodes.p, cinv(c), ccls(c), (const double *)c->r.p, (const double *)c->tmp2.p, c->x.p);
-    PL_HIP(hipGetLastError());
   }
-  if (warm && st->converged) {      // keep the solution for the next solve (before the caller's download adds ubar)
-    if (c->opt.warm_start == 4 && c->xprev.p && c->xprev_valid) {     // the Galerkin start's ring takes the solution before
-      c->gh_head = (c->gh_head + 1) % (pl_context::kWarmMax - 1);
-      DevBuf<double> &slot = c->gh[c->gh_head];
-      if (!slot.p || slot.n < (size_t)n6) PL_HIP(slot.alloc(n6));
-      PL_HIP(hipMemcpyAsync(slot.p, c->xprev.p, n6 * sizeof(double), hipMemcpyDeviceToDevice, c->stream));
-      c->gh_count = std::min(c->gh_count + 1, pl_context::kWarmMax - 1);
-    } else if (c->opt.warm_start >= 2 && c->xprev.p && c->xprev_valid) {     // ... and the one(s) before it
-      if (c->opt.warm_start >= 3 && c->xprev2_valid) {
-        std::swap(c->xprev2.p, c->xprev3.p);
-        std::swap(c->xprev2.n, c->xprev3.n);
-        c->xprev3_valid = true;
-      }
-      std::swap(c->xprev.p, c->xprev2.p);
-      std::swap(c->xprev.n, c->xprev2.n);
-      c->xprev2_valid = true;
-    }
-    if (!c->xprev.p) PL_HIP(c->xprev.alloc(n6));
-    PL_HIP(hipMemcpyAsync(c->xprev.p, c->x.p, n6 * sizeof(double), hipMemcpyDeviceToDevice, c->stream));
-    c->xprev_valid = true;
-  }
-  return PL_OK;
+  return warm && st->converged ? warm_retain(c, true) : PL_OK;
 }
 
 // ----------------------------------------------------------------------------------------------------------
@@ -870,28 +679,24 @@ int pcg_solve_cg1(pl_context *c, const double *f_dev, const double *Kubar_dev, d
   const double *Bt = cs.tile_level ? (const double *)cs.Bt_inv : (const double *)nullptr;
   const double *yt = cs.tile_level ? (const double *)cs.yt : (const double *)nullptr;
   const dim3 gt((unsigned)cs.n_tiles), blkdim(cs.vblock);
-  const bool tm12 = tile_modes_now(c) == 12, cm12 = cs.cm == 12;     // (a 12-mode dense level needs the 12-mode tile level)
-  auto restrict_to = [&](const double *v, double *out) {
-    if (cm12)
-      hipLaunchKernelGGL(pl::k_cg1_restrict<12>, gt, blkdim, 0, c->stream, c->tile.tile_start.p, cs.agg_of_tile.p, cs.cen.p,
-                         c->xyz.p, v, wt, out);
-    else
-      hipLaunchKernelGGL(pl::k_cg1_restrict<6>, gt, blkdim, 0, c->stream, c->tile.tile_start.p, cs.agg_of_tile.p, cs.cen.p,
-                         c->xyz.p, v, wt, out);
+  const bool cm12 = cs.cm == 12;     // (a 12-mode dense level needs the 12-mode tile level)
+  const auto restrict_to = [&](const double *v, double *out) {
+    const auto kern = cm12 ? pl::k_cg1_restrict<12> : pl::k_cg1_restrict<6>;
+    hipLaunchKernelGGL(kern, gt, blkdim, 0, c->stream, c->tile.tile_start.p, cs.agg_of_tile.p, cs.cen.p, c->xyz.p, v, wt, out);
+  };
+  // x += alpha p, r -= alpha s with the recurrences of iteration `it` (INIT: the pass before iteration 0)
+  const auto update = [&](auto init, int cur, int nxt, int it) {
+    with_tile_modes(c, [&](auto tm) {
+      hipLaunchKernelGGL((pl::k_cg1_update<decltype(init)::value, decltype(tm)::value>), gt, blkdim, 0, c->stream,
+                         c->tile.tile_start.p, cs.agg_of_tile.p, cs.cen.p, c->xyz.p, (const double *)u, (const double *)w,
+                         cs.dinv32, wt, c->p.p, s, c->x.p, c->r.p, (const double *)blk[cur], (const double *)gc[cur],
+                         (const double *)stt[cur], stt[nxt], blk[nxt], Bt, cs.yt, shared, cs.rc, sc, ncp, c->hist.p, it);
+    });
   };
 
-  PL_HIP(hipMemsetAsync(c->scal.p, 0, 2 * pl::S_COUNT * pl::kSlots * sizeof(double), c->stream));
+  rc = pcg_init(c, f_dev, Kubar_dev, false);      // (the z / p the init kernel also writes are overwritten below)
+  if (rc) return rc;
   PL_HIP(hipMemsetAsync(c->cg1.p, 0, need * sizeof(double), c->stream));
-  // r0 = P (f - K ubar), x = 0, ||b||^2 (the z / p the init kernel also writes are overwritten below)
-  if (c->dist.active)
-    pl::launch_pcg_init_weighted(n6, f_dev, Kubar_dev, c->fixed.p, c->dinv.p, c->dist.weight.p, c->x.p, c->r.p,
-                                 c->z.p, c->p.p, c->scal.p, c->stream);
-  else
-    hipLaunchKernelGGL(pl::k_pcg_init, dim3(grid_stream(n6)), dim3(pl::kBlock), 0, c->stream, n6, f_dev, Kubar_dev,
-                       c->fixed.p, c->dinv.p, c->x.p, c->r.p, c->z.p, c->p.p, c->scal.p);
-  PL_HIP(hipGetLastError());
-  if (c->dist.active && pl::dist_sum_scalars(c->dist, c->scal.p + pl::S_BB * pl::kSlots, pl::kSlots, c->stream))
-    return fail(PL_ERR_HIP, "RCCL all-reduce of the initial PCG scalars failed");
   PL_HIP(hipMemsetAsync(c->p.p, 0, n6 * sizeof(double), c->stream));
   PL_HIP(hipMemsetAsync(s, 0, n6 * sizeof(double), c->stream));
   PL_HIP(hipMemsetAsync(cs.rc, 0, (size_t)ncp * sizeof(double), c->stream));
@@ -900,13 +705,11 @@ int pcg_solve_cg1(pl_context *c, const double *f_dev, const double *Kubar_dev, d
   auto second_half = [&](int k) -> int {
     const int cur = k & 1, nxt = (k + 1) & 1;
     pl::coarse_apply(cs, cs.rc, cs.tv, cs.yc, gc[nxt], (const double *)nullptr, c->stream);
-#define PL_CG1_PRE(TM)                                                                                                  \
-  hipLaunchKernelGGL(pl::k_cg1_precond<TM>, gt, blkdim, 0, c->stream, c->tile.tile_start.p, (const double *)c->r.p,     \
-                     cs.dinv32, c->xyz.p, cs.agg_of_tile.p, cs.cen.p, cs.yc, yt, c->fixedbits.p, shared, u,             \
-                     k >= 0 ? blk[cur] : (double *)nullptr, bs, k >= 0 ? gc[cur] : (double *)nullptr, cs.cm)
-    if (tm12) PL_CG1_PRE(12);
-    else PL_CG1_PRE(6);
-#undef PL_CG1_PRE
+    with_tile_modes(c, [&](auto tm) {
+      hipLaunchKernelGGL(pl::k_cg1_precond<decltype(tm)::value>, gt, blkdim, 0, c->stream, c->tile.tile_start.p,
+                         (const double *)c->r.p, cs.dinv32, c->xyz.p, cs.agg_of_tile.p, cs.cen.p, cs.yc, yt, c->fixedbits.p,
+                         shared, u, k >= 0 ? blk[cur] : (double *)nullptr, bs, k >= 0 ? gc[cur] : (double *)nullptr, cs.cm);
+    });
     int r2 = launch_spmv(c, u, w, true, blk[nxt] + ncp, nullptr, pl::kEndsAll, false);
     if (r2) return r2;
     restrict_to((const double *)w, blk[nxt]);
@@ -919,46 +722,30 @@ int pcg_solve_cg1(pl_context *c, const double *f_dev, const double *Kubar_dev, d
   restrict_to((const double *)c->r.p, cs.rc);
   if (c->dist.active && pl::dist_sum_scalars(c->dist, cs.rc, ncp, c->stream))
     return fail(PL_ERR_HIP, "RCCL all-reduce of the initial coarse residual failed");
-#define PL_CG1_UPD(INIT, TM, CUR, NXT, IT)                                                                                \
-  hipLaunchKernelGGL((pl::k_cg1_update<INIT, TM>), gt, blkdim, 0, c->stream, c->tile.tile_start.p, cs.agg_of_tile.p,     \
-                     cs.cen.p, c->xyz.p, (const double *)u, (const double *)w, cs.dinv32, wt, c->p.p, s, c->x.p, c->r.p, \
-                     (const double *)blk[CUR], (const double *)gc[CUR], (const double *)stt[CUR], stt[NXT], blk[NXT], Bt, \
-                     cs.yt, shared, cs.rc, sc, ncp, c->hist.p, IT)
-  if (tm12) PL_CG1_UPD(true, 12, 1, 0, -1);
-  else PL_CG1_UPD(true, 6, 1, 0, -1);
+  update(std::true_type{}, 1, 0, -1);
   rc = second_half(-1);
   if (rc) return rc;
 
-  double h_scal[pl::kSlots];
-  PL_HIP(hipMemcpyAsync(h_scal, c->scal.p + pl::S_BB * pl::kSlots, sizeof(h_scal), hipMemcpyDeviceToHost, c->stream));
-  PL_HIP(hipStreamSynchronize(c->stream));
   double bb = 0.0;
-  for (int k = 0; k < pl::kSlots; ++k) bb += h_scal[k];
-  st->b_norm = std::sqrt(bb);
-  st->iterations = 0;
-  st->converged = 0;
-  st->rel_residual = 0.0;
+  bool zero = false;
   st->info = 1.0;
-  if (!(bb > 0.0)) {
-    st->converged = 1;
-    return std::isnan(bb) ? fail(PL_ERR_NAN, "NaN in the right-hand side") : PL_OK;
-  }
+  rc = solve_begin(c, c->scal.p + pl::S_BB * pl::kSlots, st, &bb, &zero);
+  if (rc || zero) return rc;
   const double thresh = rtol * rtol * bb;
-  const bool adaptive = c->opt.check_every <= 0;
-  const int chunk = adaptive ? 32 : c->opt.check_every;
-  std::vector<double> h_hist(chunk);
-  int k = 0, next = chunk, k_prev = 0;
-  double rr_prev = bb;
+  pl::LookParams lp{c->opt.check_every, max_iter, thresh, bb};
+  lp.extra = 1;      // (the history lags one update behind)
+  pl::LookSchedule look(lp);
+  std::vector<double> h_hist(look.max_chunk());
+  int k = 0;
   // hist[k] = ||r_k||^2, the residual BEFORE update k (it is reduced together with that iteration's other sums).  Exactly
   // max_iter updates are applied: the residual after the last one is read from the block the next update would have used
   // (until this was counted right the loop ran max_iter + 1 updates to learn it, and a solve that hit max_iter handed back
   // x_(max_iter + 1) under iterations = max_iter: tests/test_gpu_precond.py)
   while (k < max_iter) {
-    const int todo = std::min(next, max_iter - k);
+    const int todo = look.todo(k);
     for (int j = 0; j < todo; ++j) {
-      const int it = k + j, cur = it & 1, nxt = (it + 1) & 1;
-      if (tm12) PL_CG1_UPD(false, 12, cur, nxt, it);
-      else PL_CG1_UPD(false, 6, cur, nxt, it);
+      const int it = k + j;
+      update(std::false_type{}, it & 1, (it + 1) & 1, it);
       rc = second_half(it);
       if (rc) return rc;
     }
@@ -968,26 +755,12 @@ int pcg_solve_cg1(pl_context *c, const double *f_dev, const double *Kubar_dev, d
       const double rr = h_hist[j];
       if (std::isnan(rr) || std::isinf(rr)) return fail(PL_ERR_NAN, "NaN/Inf in the PCG residual");
       if (!st->converged) st->rel_residual = std::sqrt(rr / bb);
-      if (rr <= thresh && !st->converged) {
-        st->converged = 1;
-        st->iterations = k + j;      // updates applied when this residual was reached (x has had a few more since)
-        st->info = 0.0;
-        st->stop_reason = 0.0;
-      }
+      // (iterations: updates applied when this residual was reached - x has had a few more since)
+      if (rr <= thresh && !st->converged) converged_at(st, k + j, 0.0);
     }
     k += todo;
     if (st->converged) break;
-    if (adaptive) {
-      const double rr_end = h_hist[todo - 1];
-      next = chunk;
-      if (rr_end < rr_prev && rr_end > thresh) {
-        const double per_it = std::log(rr_end / rr_prev) / (double)(k - k_prev);
-        const double need_it = std::log(thresh / rr_end) / per_it;
-        if (need_it < 2.0 * chunk) next = std::max(2, std::min(chunk, (int)std::ceil(0.75 * need_it) + 1));
-      }
-      rr_prev = rr_end;
-      k_prev = k;
-    }
+    look.missed(k, h_hist[todo - 1]);
   }
   if (!st->converged) {
     double h_rr[pl::kSlots], rr = 0.0;       // ||r_k||^2 after update k - 1: slot 2 of the reduced block of iteration k
@@ -997,13 +770,8 @@ int pcg_solve_cg1(pl_context *c, const double *f_dev, const double *Kubar_dev, d
     if (std::isnan(rr) || std::isinf(rr)) return fail(PL_ERR_NAN, "NaN/Inf in the PCG residual");
     st->rel_residual = std::sqrt(rr / bb);
     st->iterations = k;
-    if (rr <= thresh) {
-      st->converged = 1;
-      st->info = 0.0;
-      st->stop_reason = 0.0;
-    }
+    if (rr <= thresh) converged_at(st, k, 0.0);
   }
-#undef PL_CG1_UPD
   return PL_OK;
 }
 
@@ -1046,13 +814,15 @@ __global__ __launch_bounds__(pl::kBlock) void k_mp_accumulate(int64_t n6, const 
     x[i] += (double)x32[i];
 }
 
-int read_slots(pl_context *c, const double *dev, double *sum) {
-  double h[pl::kSlots];
-  PL_HIP(hipMemcpyAsync(h, dev, sizeof(h), hipMemcpyDeviceToHost, c->stream));
-  PL_HIP(hipStreamSynchronize(c->stream));
-  *sum = 0.0;
-  for (int k = 0; k < pl::kSlots; ++k) *sum += h[k];
-  return PL_OK;
+// One iteration of the inner PCG of the fp32 modes: the operator as the solve applies it, then the multi-level tail.  j:
+// iteration of this inner solve (parity of the scalar sets).  (precision = 2 never eliminates nodes: solver_plan leaves
+// cond_use false there.)
+template <typename RT>
+int mp_iteration(pl_context *c, int j, int hist_slot, float *p32, float *Ap32, RT *x, RT *r) {
+  const int set = pl::S_COUNT * pl::kSlots;
+  double *cur = c->scal.p + (j & 1) * set, *nxt = c->scal.p + ((j + 1) & 1) * set;
+  const int rc = apply_operator<float>(c, p32, Ap32, cur + pl::S_PAP * pl::kSlots);
+  return rc ? rc : pcg_tail_coarse_t<float, RT>(c, cur, nxt, hist_slot, p32, (const float *)Ap32, x, r);
 }
 
 template <typename RT>
@@ -1077,16 +847,9 @@ int pcg_solve_mp_t(pl_context *c, const double *f_dev, const double *Kubar_dev, 
   if (c->dist.active && pl::dist_sum_scalars(c->dist, aux, pl::kSlots, c->stream))
     return fail(PL_ERR_HIP, "RCCL all-reduce of ||b||^2 failed");
   double bb = 0.0;
-  rc = read_slots(c, aux, &bb);
-  if (rc) return rc;
-  st->b_norm = std::sqrt(bb);
-  st->iterations = 0;
-  st->converged = 0;
-  st->rel_residual = 0.0;
-  if (!(bb > 0.0)) {
-    st->converged = 1;
-    return std::isnan(bb) ? fail(PL_ERR_NAN, "NaN in the right-hand side") : PL_OK;
-  }
+  bool zero = false;
+  rc = solve_begin(c, aux, st, &bb, &zero);
+  if (rc || zero) return rc;
   const double thresh = rtol * rtol * bb;
   // an fp32 residual recurrence is trustworthy over ~4 decades: restart from the true residual after that
   static const double drop_env = [] { const char *e = std::getenv("PL_MP_DROP"); return e ? std::atof(e) : 0.0; }();
@@ -1096,6 +859,22 @@ int pcg_solve_mp_t(pl_context *c, const double *f_dev, const double *Kubar_dev, 
   //  7: 130 / 144 / 357 / 298,  8: 130 / 147 / 393 / 354;  fp64: 120 / 137 / 335 / -)
   static const double stage_max = [] { const char *e = std::getenv("PL_MP_STAGE"); return e ? std::atof(e) : 6.0; }();
   double rr_true = bb;
+  // r = P (f - K (ubar + x)) in fp64, rr_true = its squared norm (summed over the ranks; a warm start has one rank)
+  const auto true_residual = [&](const char *nan_message) -> int {
+    const int r2 = launch_spmv(c, c->x.p, c->tmp2.p, true, nullptr);
+    if (r2) return r2;
+    PL_HIP(hipMemsetAsync(aux, 0, pl::kSlots * sizeof(double), c->stream));
+    hipLaunchKernelGGL(k_mp_true_residual, dim3(grid_stream(n6)), dim3(pl::kBlock), 0, c->stream, n6, f_dev, Kubar_dev,
+                       (const double *)c->tmp2.p, c->fixed.p, w, c->r.p, aux);
+    PL_HIP(hipGetLastError());
+    if (c->dist.active && pl::dist_sum_scalars(c->dist, aux, pl::kSlots, c->stream))
+      return fail(PL_ERR_HIP, "RCCL all-reduce of the true residual failed");
+    const int r3 = read_slots(c, aux, &rr_true);
+    if (r3) return r3;
+    if (std::isnan(rr_true) || std::isinf(rr_true)) return fail(PL_ERR_NAN, nan_message);
+    st->rel_residual = std::sqrt(rr_true / bb);
+    return PL_OK;
+  };
   // warm start (mode 1, as pcg_solve): the refinement begins at the previous solution of this handle, masked with the
   // CURRENT Dirichlet set - the first inner solve then works on its true residual like every later one
   const bool warm = kAll32 && c->opt.warm_start >= 1 && !c->dist.active;     // (2 / 3: the previous solution here, no extrapolation)
@@ -1103,23 +882,15 @@ int pcg_solve_mp_t(pl_context *c, const double *f_dev, const double *Kubar_dev, 
     PL_HIP(hipMemcpyAsync(c->x.p, c->xprev.p, n6 * sizeof(double), hipMemcpyDeviceToDevice, c->stream));
     hipLaunchKernelGGL(k_warm_mask, dim3(grid_for(n6)), dim3(pl::kBlock), 0, c->stream, c->N, (const uint8_t *)nullptr,
                        (const uint8_t *)c->fixed.p, c->x.p);
-    rc = launch_spmv(c, c->x.p, c->tmp2.p, true, nullptr);
+    rc = true_residual("NaN/Inf in the warm-start residual");
     if (rc) return rc;
-    PL_HIP(hipMemsetAsync(aux, 0, pl::kSlots * sizeof(double), c->stream));
-    hipLaunchKernelGGL(k_mp_true_residual, dim3(grid_stream(n6)), dim3(pl::kBlock), 0, c->stream, n6, f_dev, Kubar_dev,
-                       (const double *)c->tmp2.p, c->fixed.p, w, c->r.p, aux);
-    PL_HIP(hipGetLastError());
-    rc = read_slots(c, aux, &rr_true);
-    if (rc) return rc;
-    if (std::isnan(rr_true) || std::isinf(rr_true)) return fail(PL_ERR_NAN, "NaN/Inf in the warm-start residual");
-    st->rel_residual = std::sqrt(rr_true / bb);
     if (rr_true <= thresh) {       // (the previous solution already solves this system)
       st->converged = 1;
       return PL_OK;
     }
   }
   int k = 0;                      // iterations over all inner solves
-  std::vector<double> h_hist(32);
+  std::vector<double> h_hist;
   for (int outer = 0; outer < 40 && k < max_iter; ++outer) {
     // ---- (re)start: p = M^-1 r through the tail of an iteration "-1" (alpha = 0) on scalar set 1
     PL_HIP(hipMemsetAsync(c->scal.p, 0, 2 * set * sizeof(double), c->stream));
@@ -1127,15 +898,9 @@ int pcg_solve_mp_t(pl_context *c, const double *f_dev, const double *Kubar_dev, 
       hipLaunchKernelGGL(k_mp_restart, dim3(grid_stream(n6)), dim3(pl::kBlock), 0, c->stream, n6, c->r.p,
                          reinterpret_cast<float *>(ri), reinterpret_cast<float *>(xi));
     PL_HIP(hipMemsetAsync(p32, 0, n6 * sizeof(float), c->stream));
-    if (kAll32 && c->cond_use) {
-      // node elimination inside the inner solve (as in pcg_solve): t_c = K_cc^-1 b_c in the rows of p32, r_v -= (K t)_v
-      float *r32 = reinterpret_cast<float *>(ri);
-      hipLaunchKernelGGL(pl::k_condense_solve<float>, dim3(grid_for(c->n_cond * 6)), dim3(pl::kBlock), 0, c->stream,
-                         c->n_cond, c->cnodes.p, cinv(c), ccls(c), (const float *)r32, p32, 1.0);
-      rc = launch_spmv_f32(c, p32, Ap32, true, nullptr, c->maskC.p, pl::kEndsOthers);
+    if (c->cond_use) {   // node elimination inside the inner solve (as in pcg_solve; precision = 1 only: solver_plan)
+      rc = condense_prologue<float>(c, reinterpret_cast<float *>(ri), p32, Ap32);
       if (rc) return rc;
-      hipLaunchKernelGGL(pl::k_condense_subtract<float>, dim3(grid_for(n6)), dim3(pl::kBlock), 0, c->stream, c->N,
-                         c->cflag.p, (const float *)Ap32, r32);
       PL_HIP(hipMemsetAsync(p32, 0, n6 * sizeof(float), c->stream));
     }
     PL_HIP(hipMemsetAsync(Ap32, 0, n6 * sizeof(float), c->stream));
@@ -1150,72 +915,37 @@ int pcg_solve_mp_t(pl_context *c, const double *f_dev, const double *Kubar_dev, 
       const int stages = std::max(1, (int)std::ceil(left / stage_max));
       stop = stages == 1 ? thresh : std::max(thresh, rr_true * std::pow(10.0, -left / stages));
     }
+    pl::LookSchedule look(pl::LookParams{0, max_iter, stop, rr_true, k});     // (always adaptive, whatever opts.check_every says)
+    h_hist.resize(look.max_chunk());
+    const int k0 = k;
     bool inner_done = false;
-    int j = 0, next = 32;
-    double rr_prev = rr_true;
-    int j_prev = 0;
     while (!inner_done && k < max_iter) {
-      const int todo = std::min(next, max_iter - k);
+      const int todo = look.todo(k);
       for (int q = 0; q < todo; ++q) {
-        double *cur = c->scal.p + ((j + q) & 1) * set, *nxt = c->scal.p + ((j + q + 1) & 1) * set;
-        if (kAll32 && c->cond_use) {
-          rc = launch_spmv_f32(c, p32, p32, false, nullptr, nullptr, pl::kEndsCondensedSolve);
-          if (rc) return rc;
-          rc = launch_spmv_f32(c, p32, Ap32, true, cur + pl::S_PAP * pl::kSlots, c->maskC.p, pl::kEndsOthers);
-        } else {
-          rc = launch_spmv_f32(c, p32, Ap32, true, cur + pl::S_PAP * pl::kSlots);
-        }
-        if (rc) return rc;
-        rc = pcg_tail_coarse_t<float, RT>(c, cur, nxt, k + q, p32, (const float *)Ap32, xi, ri);
+        rc = mp_iteration<RT>(c, k - k0 + q, k + q, p32, Ap32, xi, ri);
         if (rc) return rc;
       }
       PL_HIP(hipMemcpyAsync(h_hist.data(), c->hist.p + k, todo * sizeof(double), hipMemcpyDeviceToHost, c->stream));
       PL_HIP(hipStreamSynchronize(c->stream));
-      int used = todo;
-      for (int q = 0; q < todo; ++q) {
+      for (int q = 0; q < todo && !inner_done; ++q) {
         const double rr = h_hist[q];
         if (std::isnan(rr) || std::isinf(rr)) return fail(PL_ERR_NAN, "NaN/Inf in the PCG residual");
-        if (rr <= stop) { inner_done = true; used = q + 1; break; }
+        inner_done = rr <= stop;
       }
       // (the device has run the whole chunk: x holds the iterate after `todo` iterations, which is what is kept)
-      const double rr_end = h_hist[todo - 1];
-      j += todo;
       k += todo;
-      (void)used;
-      if (!inner_done) {
-        next = 32;
-        if (rr_end < rr_prev && rr_end > stop) {
-          const double per_it = std::log(rr_end / rr_prev) / (double)(j - j_prev);
-          const double need = std::log(stop / rr_end) / per_it;
-          if (need < 64.0) next = std::max(2, std::min(32, (int)std::ceil(0.75 * need)));
-        }
-        rr_prev = rr_end;
-        j_prev = j;
-      }
+      if (!inner_done) look.missed(k, h_hist[todo - 1]);
     }
     // ---- true residual of the accumulated solution
-    if (kAll32 && c->cond_use) {   // the eliminated nodes of this inner solve: x_c = K_cc^-1 (b_c - (K [x_v ; 0])_c)
-      float *x32 = reinterpret_cast<float *>(xi), *r32 = reinterpret_cast<float *>(ri);
-      rc = launch_spmv_f32(c, x32, Ap32, false, nullptr, nullptr, pl::kEndsCondensed);
+    if (c->cond_use) {   // the eliminated nodes of this inner solve
+      rc = condense_backsubst<float>(c, reinterpret_cast<float *>(xi), reinterpret_cast<const float *>(ri), Ap32);
       if (rc) return rc;
-      hipLaunchKernelGGL(pl::k_condense_backsubst<float>, dim3(grid_for(c->n_cond * 6)), dim3(pl::kBlock), 0, c->stream,
-                         c->n_cond, c->cnodes.p, cinv(c), ccls(c), (const float *)r32, (const float *)Ap32, x32);
     }
     if (kAll32)
       hipLaunchKernelGGL(k_mp_accumulate, dim3(grid_stream(n6)), dim3(pl::kBlock), 0, c->stream, n6,
                          reinterpret_cast<const float *>(xi), c->x.p);
-    rc = launch_spmv(c, c->x.p, c->tmp2.p, true, nullptr);
+    rc = true_residual("NaN/Inf in the true residual");
     if (rc) return rc;
-    PL_HIP(hipMemsetAsync(aux, 0, pl::kSlots * sizeof(double), c->stream));
-    hipLaunchKernelGGL(k_mp_true_residual, dim3(grid_stream(n6)), dim3(pl::kBlock), 0, c->stream, n6, f_dev, Kubar_dev,
-                       (const double *)c->tmp2.p, c->fixed.p, w, c->r.p, aux);
-    PL_HIP(hipGetLastError());
-    if (c->dist.active && pl::dist_sum_scalars(c->dist, aux, pl::kSlots, c->stream))
-      return fail(PL_ERR_HIP, "RCCL all-reduce of the true residual failed");
-    rc = read_slots(c, aux, &rr_true);
-    if (rc) return rc;
-    if (std::isnan(rr_true) || std::isinf(rr_true)) return fail(PL_ERR_NAN, "NaN/Inf in the true residual");
-    st->rel_residual = std::sqrt(rr_true / bb);
     st->restarts = (double)(outer + 1);     // restarts (inner solves) taken
     if (rr_true <= thresh * 1.0000001) {
       st->converged = 1;
@@ -1223,12 +953,8 @@ int pcg_solve_mp_t(pl_context *c, const double *f_dev, const double *Kubar_dev, 
     }
   }
   st->iterations = k;
-  if (warm && st->converged) {
-    if (!c->xprev.p) PL_HIP(c->xprev.alloc(n6));
-    PL_HIP(hipMemcpyAsync(c->xprev.p, c->x.p, n6 * sizeof(double), hipMemcpyDeviceToDevice, c->stream));
-    c->xprev_valid = true;
-  }
-  return PL_OK;
+  // (as found: every warm_start >= 1 is 1 here - no older solutions are kept)
+  return warm && st->converged ? warm_retain(c, false) : PL_OK;
 }
 
 }  // namespace
