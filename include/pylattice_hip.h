@@ -453,6 +453,28 @@ int pl_buckling_modes(pl_handle h, const double *u /*[6N] or NULL*/, int32_t n_m
                       double *load_factor /*[n_modes]*/, double *modes /*[n_modes][6N] or NULL*/,
                       double *residual /*[n_modes] or NULL: |K phi + lambda K_g phi| / |K phi|, free dofs*/,
                       int32_t *n_found, int32_t *outer_iterations);
+/* Sensitivities of those load factors to the strut radii, at fixed segment geometry (the convention of pl_sens) and with u
+ * following the radii through K u = f: for every eigenpair (load_factor[i], modes[i]) - any scaling, read with the fixed
+ * dofs zeroed -, with kk = phi^T K phi, q_b = phi_e^T G_b phi_e (G_b the strut's geometric element matrix for N = 1),
+ * ka = a + e1 L^2 and dK_e = dK_e/dr_b,
+ *     w = d(phi^T K_g(u) phi)/du = sum_b q_b ka_b (-t_b at u_A, +t_b at u_B),   K nu = -w on the free dofs, nu = 0 elsewhere,
+ *     dlambda/dr_b = (lambda / kk) [phi_e^T dK_e phi_e + lambda (q_b (dka_b/dr_b) t_b.(u_B - u_A) + nu_e^T dK_e u_e)].
+ * The adjoint solves of all modes run in ONE Jacobi-PCG pass (rtol, max_iter as pl_solve_multi), so the rows are total
+ * derivatives.  For an m-fold repeated factor the single rows are NOT derivatives (the modes are an arbitrary basis of the
+ * eigenspace); their sum over the whole cluster is the derivative of the sum of those factors, and so is any combination with
+ * equal weights inside the cluster - dsum_dr with such weights is what a design loop should use.
+ * 1 <= n_modes <= 16.  A mode whose load_factor is NaN (what pl_buckling_modes writes beyond n_found) is skipped: its rows of
+ * dlam_dr and adj_load are NaN and it adds nothing to dsum_dr.  dsum_dr needs weights.  Outputs in the caller's strut
+ * numbering.  PL_ERR_ARG for bad sizes, null inputs and when all three outputs are NULL; PL_ERR_STATE in the cases of
+ * pl_buckling_modes; PL_ERR_NOCONV when an adjoint column missed rtol (outputs still written).  The handle's single-column
+ * state is left untouched. */
+int pl_buckling_modes_sens(pl_handle h, const double *u /*[6N] or NULL = last pl_solve*/, int32_t n_modes,
+                           const double *load_factor /*[n_modes]*/, const double *modes /*[n_modes][6N]*/,
+                           double rtol, int32_t max_iter,            /* adjoint solve, as pl_solve_multi */
+                           const double *weights /*[n_modes] or NULL*/,
+                           double *dlam_dr  /*[n_modes][B] or NULL*/,
+                           double *dsum_dr  /*[B] or NULL: sum_i weights[i] dlam_i/dr_b, formed on the device*/,
+                           double *adj_load /*[n_modes][6N] or NULL: w_i, unmasked - test hook*/);
 
 /* The same condensation, exact and batched, without a handle: n_inst small lattices of ONE topology (a unit cell at
  * several radius sets - the exact DDM mode, Schur datasets), each condensed by a dense Cholesky of K_II in one workgroup

@@ -23,7 +23,7 @@ EXPORTS = ["pl_default_opts", "pl_opts_size", "pl_stats_size", "pl_abi_version",
            "pl_update_radii", "pl_set_multiplicity", "pl_update_segments", "pl_assemble", "pl_assemble_bsr", "pl_get_bsr", "pl_spmv",
            "pl_spmv_free", "pl_spmv_bsr", "pl_solve", "pl_reactions", "pl_sens", "pl_energy", "pl_node_mod", "pl_schur",
            "pl_stress", "pl_stress_pnorm", "pl_buckling", "pl_buckling_pnorm",
-           "pl_spmv_multi", "pl_solve_multi", "pl_schur_block", "pl_geom_spmv_multi", "pl_buckling_modes",
+           "pl_spmv_multi", "pl_solve_multi", "pl_schur_block", "pl_geom_spmv_multi", "pl_buckling_modes", "pl_buckling_modes_sens",
            "pl_schur_cells", "pl_cells_recover", "pl_get_records", "pl_debug_partition", "pl_time_kernel", "pl_algorithmic_bytes", "pl_node_words_info", "pl_forget_history", "pl_debug_spd_solve", "pl_dist_unique_id_bytes",
            "pl_dist_unique_id", "pl_dist_loopback_id", "pl_dist_abort", "pl_dist_init", "pl_dist_set_peers", "pl_generate_lattice", "pl_lattice_fetch",
            "pl_lattice_free", "pl_penalize", "pl_boundary_index", "pl_boundary_index_rows"]
@@ -98,6 +98,7 @@ def load_library(path: str | None = None):
            "pl_solve_multi": [V, I32, V, V, D, I32, V, V], "pl_schur_block": [V, V, I32, D, I32, I32, V],
            "pl_geom_spmv_multi": [V, V, I32, I32, V, V],
            "pl_buckling_modes": [V, V, I32, I32, D, I32, D, I32, V, V, V, V, V],
+           "pl_buckling_modes_sens": [V, V, I32, V, V, D, I32, V, V, V, V],
            "pl_schur_cells": [V, I32, I32, I32, V, I32, V, V, V, V, V, V, V],
            "pl_cells_recover": [V, I32, I32, I32, V, I32, V, V, V, V, V, V, V, V, V, V, V],
            "pl_get_records": [V, V], "pl_debug_partition": [V, V, V, V, V], "pl_time_kernel": [V, I32, I32, V],
@@ -774,6 +775,36 @@ class HipLattice:
         return {"load_factor": lam, "modes": modes, "residual": res, "n_found": found.value,
                 "outer_iterations": outer.value}
 
+    def buckling_modes_sens(self, load_factor, modes, u=None, rtol=1e-12, max_iter=200000, weights=None, want_rows=True,
+                            want_load=False, raise_on_noconv=True):
+        """Sensitivities of the load factors of ``buckling_modes`` to the strut radii (pl_buckling_modes_sens), total: the
+        adjoint solves for u(r) run inside the call, all modes in one PCG pass (rtol, max_iter).  load_factor (n_modes,) and
+        modes (n_modes, N, 6) as ``buckling_modes`` returns them (any scaling; a NaN factor marks a mode to skip).  Returns a
+        dict with dlam_dr (n_modes, B) if want_rows, dsum_dr (B,) = weights @ dlam_dr formed on the device if weights is
+        given, adj_load (n_modes, N, 6) = d(phi^T K_g(u) phi)/du if want_load.  Rows of a repeated factor are not derivatives
+        one by one; a sum with equal weights over the whole cluster is.  u = None: the solution of the last solve()."""
+        lam = np.ascontiguousarray(np.asarray(load_factor, dtype=np.float64).reshape(-1))
+        k = lam.size
+        phi = np.ascontiguousarray(np.asarray(modes, dtype=np.float64)).reshape(-1)
+        if phi.size != k * 6 * self.n_nodes:
+            raise ValueError(f"modes must have shape ({k}, {self.n_nodes}, 6)")
+        u = None if u is None else _f64(np.asarray(u).reshape(-1), 6 * self.n_nodes)
+        wts = None if weights is None else _f64(np.asarray(weights).reshape(-1), k)
+        rows = np.empty((k, self.n_beams), np.float64) if want_rows else None
+        dsum = np.empty(self.n_beams, np.float64) if wts is not None else None
+        load = np.empty((k, self.n_nodes, 6), np.float64) if want_load else None
+        rc = self._lib.pl_buckling_modes_sens(self._h, _ptr(u), k, _ptr(lam), _ptr(phi), float(rtol), int(max_iter), _ptr(wts),
+                                              _ptr(rows), _ptr(dsum), _ptr(load))
+        _check(self._lib, rc, allow=() if raise_on_noconv else (PL_ERR_NOCONV,))
+        out = {}
+        if want_rows:
+            out["dlam_dr"] = rows
+        if wts is not None:
+            out["dsum_dr"] = dsum
+        if want_load:
+            out["adj_load"] = load
+        return out
+
     def geom_spmv_multi_host(self, X, u, masked=False, fixed=None):
         """The numpy restatement of ``geom_spmv_multi`` (geometric_host.geometric_apply) on this handle's records; the
         masked product needs the mask ``fixed`` (N, 6) that was given to set_bc."""
@@ -864,7 +895,7 @@ class HipLattice:
 # the reference wraps every hot-path method in @timing.category(..) @timing.timeit; here the
 # C-ABI calls are the hot path: host wall clock per call, plus the device's own HIP-event times (see solve)
 for _name in ("assemble", "assemble_bsr", "get_bsr", "solve", "set_bc", "spmv", "spmv_free", "spmv_bsr", "reactions",
-              "sens", "stress", "stress_pnorm", "buckling", "buckling_pnorm", "energy", "schur", "spmv_multi", "solve_multi", "geom_spmv_multi", "buckling_modes", "update_radii", "update_segments", "records"):
+              "sens", "stress", "stress_pnorm", "buckling", "buckling_pnorm", "energy", "schur", "spmv_multi", "solve_multi", "geom_spmv_multi", "buckling_modes", "buckling_modes_sens", "update_radii", "update_segments", "records"):
     _f = getattr(HipLattice, _name, None)
     if _f is not None:
         _f._timing_category = "hip"

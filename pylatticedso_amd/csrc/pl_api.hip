@@ -2169,6 +2169,117 @@ int pl_buckling_modes(pl_handle h, const double *u, int32_t n_modes, int32_t n_s
   return PL_OK;
 }
 
+int pl_buckling_modes_sens(pl_handle h, const double *u, int32_t n_modes, const double *load_factor, const double *modes,
+                           double rtol, int32_t max_iter, const double *weights, double *dlam_dr, double *dsum_dr,
+                           double *adj_load) {
+  const char *who = "pl_buckling_modes_sens";
+  if (!valid(h) || !load_factor || !modes) return fail(PL_ERR_ARG, "pl_buckling_modes_sens: null argument");
+  if (n_modes < 1 || n_modes > 16) return fail(PL_ERR_ARG, "pl_buckling_modes_sens: n_modes must be 1 ... 16");
+  if (!dlam_dr && !dsum_dr && !adj_load) return fail(PL_ERR_ARG, "pl_buckling_modes_sens: every output pointer is NULL");
+  if (dsum_dr && !weights) return fail(PL_ERR_ARG, "pl_buckling_modes_sens: dsum_dr needs weights");
+  if (!(rtol > 0.0) || max_iter <= 0) return fail(PL_ERR_ARG, "pl_buckling_modes_sens: rtol and max_iter must be positive");
+  if (h->n_per_groups > 0)
+    return fail(PL_ERR_STATE, "pl_buckling_modes_sens: not available with periodic constraints (pl_set_periodic)");
+  GeomWs *g = nullptr;
+  if (int rc = geom_begin(h, who, u, true, &g)) return rc;
+  const double *u_dev = u ? h->tmp.p : h->usol.p;
+  const int64_t B = h->B, n6 = h->N * 6;
+  const double nan = std::numeric_limits<double>::quiet_NaN();
+  // a mode whose load factor is NaN (beyond n_found of pl_buckling_modes) is skipped: the live ones are the columns
+  std::vector<int> live;
+  for (int j = 0; j < n_modes; ++j)
+    if (!std::isnan(load_factor[j])) live.push_back(j);
+  const int nl = (int)live.size();
+  if (dlam_dr) std::fill(dlam_dr, dlam_dr + (size_t)n_modes * B, nan);
+  if (adj_load) std::fill(adj_load, adj_load + (size_t)n_modes * n6, nan);
+  if (nl == 0) {
+    if (dsum_dr) std::fill(dsum_dr, dsum_dr + B, 0.0);
+    return PL_OK;
+  }
+  std::vector<double> packed;
+  const double *phi_host = modes;
+  if (nl < n_modes) {
+    packed.resize((size_t)nl * n6);
+    for (int j = 0; j < nl; ++j) std::memcpy(&packed[(size_t)j * n6], modes + (size_t)live[j] * n6, (size_t)n6 * sizeof(double));
+    phi_host = packed.data();
+  }
+  const MultiShape s = multi_shape(h, nl);
+  MultiWs *w = nullptr;
+  if (int rc = multi_ws(h, s, true, &w)) return rc;
+  const unsigned nchunk = std::min(grid_stream(n6), 512u);
+  if (int rc = geom_ws_modes(h, g, s, nchunk)) return rc;
+  if (int rc = geom_ws_sens(h, g, s)) return rc;
+  std::vector<double> coef((size_t)2 * s.ncol, 0.0);
+  for (int j = 0; j < nl; ++j) {
+    coef[(size_t)j] = load_factor[live[j]];
+    coef[(size_t)s.ncol + j] = weights ? weights[live[j]] : 0.0;
+  }
+  PL_HIP(hipMemcpyAsync(g->scoef.p, coef.data(), coef.size() * sizeof(double), hipMemcpyHostToDevice, h->stream));
+  PL_HIP(hipStreamSynchronize(h->stream));        // (coef is pageable host memory)
+  if (int rc = multi_upload(h, w, s, phi_host, g->X.p, -1)) return rc;      // the modes, zero on the fixed dofs
+  // PL_TIMING: HIP-event time of every stage ("[pl_buckling_modes_sens] <stage> <ms> ms")
+  const bool timing = std::getenv("PL_TIMING") != nullptr;
+  const char *stage_name[] = {"k_geom_quad", "k_geom_adjoint_load", "K phi and kk (gram)", "adjoint pcg_solve_multi", "k_geom_sens"};
+  hipEvent_t ev[6] = {};
+  int n_ev = 0;
+  auto mark = [&]() {
+    if (timing && hipEventCreate(&ev[n_ev]) == hipSuccess) (void)hipEventRecord(ev[n_ev++], h->stream);
+  };
+  int rc = PL_OK, missed = 0;
+  bool bad = false;
+  std::vector<double> status((size_t)pl::M_ST_COUNT * s.ncol);
+  do {
+    mark();
+    if ((rc = launch_geom_quad(h, g, s, g->X.p))) break;
+    mark();
+    if ((rc = launch_adjoint_load(h, g, s, w->F.p))) break;                  // loads -w_i
+    mark();
+    if (dlam_dr || dsum_dr) {
+      if ((rc = launch_spmv_multi(h, s, h->fixedbits.p, g->X.p, g->KX.p, true, nullptr))) break;
+      if ((rc = launch_gram(h, g, s, nchunk, g->X.p, g->KX.p, g->M.p))) break;       // kk_i on its diagonal
+      mark();
+      if (hipMemsetAsync(w->UB.p, 0, (size_t)s.ncb * s.stride * sizeof(double), h->stream) != hipSuccess) {
+        rc = fail(PL_ERR_HIP, "pl_buckling_modes_sens: memset failed");
+        break;
+      }
+      if ((rc = pcg_solve_multi(h, w, s, h->fixedbits.p, w->F.p, rtol, max_iter, status.data()))) break;   // nu_i in w->U
+      missed = multi_stats(s, status.data(), rtol, 0.0, nullptr, &bad);
+      mark();
+      if ((rc = launch_geom_sens(h, g, s, u_dev, g->X.p, w->U.p, dlam_dr ? g->sdlam.p : (double *)nullptr,
+                                 dsum_dr ? g->sdlam.p + (size_t)nl * B : (double *)nullptr)))
+        break;
+      mark();
+    }
+  } while (false);
+  if (timing && rc == PL_OK) {
+    (void)hipStreamSynchronize(h->stream);
+    for (int i = 0; i + 1 < n_ev; ++i) {
+      float ms = 0.f;
+      if (hipEventElapsedTime(&ms, ev[i], ev[i + 1]) == hipSuccess)
+        std::fprintf(stderr, "[pl_buckling_modes_sens] %-28s %10.4f ms\n", stage_name[i], (double)ms);
+    }
+  }
+  for (int i = 0; i < n_ev; ++i) (void)hipEventDestroy(ev[i]);
+  if (rc) return rc;
+  if (adj_load) {                                 // w_i = -(the load of the adjoint solve), unmasked
+    std::vector<double> wl((size_t)nl * n6);
+    if ((rc = multi_download(h, w, s, w->F.p, wl.data()))) return rc;
+    for (int j = 0; j < nl; ++j) {
+      double *dst = adj_load + (size_t)live[j] * n6;
+      for (int64_t e = 0; e < n6; ++e) dst[e] = -wl[(size_t)j * n6 + e];
+    }
+  }
+  if (dlam_dr)
+    for (int j = 0; j < nl; ++j)
+      if ((rc = download_struts(h, g->sdlam.p + (size_t)j * B, dlam_dr + (size_t)live[j] * B))) return rc;
+  if (dsum_dr)
+    if ((rc = download_struts(h, g->sdlam.p + (size_t)nl * B, dsum_dr))) return rc;
+  if (bad) return fail(PL_ERR_NAN, "pl_buckling_modes_sens: NaN/Inf in a residual norm of the adjoint solve");
+  if (missed)
+    return fail(PL_ERR_NOCONV, "pl_buckling_modes_sens: " + std::to_string(missed) + " adjoint column(s) did not reach rtol within max_iter");
+  return PL_OK;
+}
+
 // PL_TIMING: HIP-event time of one launch on the null stream ("[<call>] kernel_hip_event <ms> ms", four decimals)
 struct KernelEventTimer {
   const char *what;

@@ -1,5 +1,5 @@
 // Geometric stiffness K_g(u) of the lattice and the pieces of the global linear buckling analysis built on it
-// (pl_geom_spmv_multi / pl_buckling_modes).  gfx950 only.
+// (pl_geom_spmv_multi / pl_buckling_modes / pl_buckling_modes_sens).  gfx950 only.
 //
 // Linearised buckling: with u the equilibrium of the applied loads, find the smallest lambda > 0 with
 //     (K + lambda K_g(u)) phi = 0            on the free dofs of pl_set_bc,
@@ -281,6 +281,159 @@ __global__ __launch_bounds__(kBlock) void k_geom_start(int64_t n6, const int32_t
   }
 }
 
+// ---------------------------------------------------------------------------------------------------------
+// Sensitivities of the load factors to the strut radii (pl_buckling_modes_sens).  For an eigenpair
+// (lambda, phi), phi = 0 on the fixed dofs, any scaling, at fixed segment geometry (the convention of pl_sens):
+//     kk   = phi^T K phi,   q_b = phi_e^T G_b phi_e   (G_b: the strut's geometric element matrix for N = 1)
+//     w    = d(phi^T K_g(u) phi)/du = sum_b q_b ka_b (-t_b at u_A, +t_b at u_B),  ka = a + e1 L^2   (N_b = ka_b t_b.(u_B - u_A))
+//     K nu = -w on the free dofs, nu = 0 on the fixed ones                       (u depends on r through K u = f)
+//     dlambda/dr_b = (lambda / kk) [phi_e^T dK_e phi_e + lambda (q_b dka_b t_b.(u_B - u_A) + nu_e^T dK_e u_e)],  dK_e = dK_e/dr_b
+// Every kernel carries all modes in one launch, in the column-block layout of pl_multi.h.
+// ---------------------------------------------------------------------------------------------------------
+// q[cb][b * KB + k] = phi_e^T G_b phi_e of column cb KB + k: one thread per strut and column block, no scatter.  Of the
+// geometric record only the span d is read.
+template <int KB>
+__global__ __launch_bounds__(kBlock) void k_geom_quad(int64_t B, const int32_t *__restrict__ conn,
+                                                      const GeomRecord *__restrict__ rec, const double *__restrict__ phi,
+                                                      double *__restrict__ Q, int64_t stride) {
+  const int64_t b = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+  if (b >= B) return;
+  const int cb = blockIdx.y;
+  phi += (size_t)cb * stride;
+  GeomRecord fwd = load_geom(rec, b);
+  fwd.g = 1.0 / (30.0 * sqrt(fwd.dx * fwd.dx + fwd.dy * fwd.dy + fwd.dz * fwd.dz));
+  const GeomRecord rev = {fwd.g, -fwd.dx, -fwd.dy, -fwd.dz};     // the strut seen from its point1
+  double xa[6 * KB], xb[6 * KB], q[KB];
+  load_row<KB>(phi, (int64_t)conn[2 * b], xa);
+  load_row<KB>(phi, (int64_t)conn[2 * b + 1], xb);
+#pragma unroll
+  for (int k = 0; k < KB; ++k) {
+    V3 uA, tA, uB, tB, fA, mA, fB, mB;
+    column_of<KB>(xa, k, uA, tA);
+    column_of<KB>(xb, k, uB, tB);
+    geom_force(fwd, uA, tA, uB, tB, fB, mB);
+    geom_force(rev, uB, tB, uA, tA, fA, mA);
+    q[k] = dot(uA, fA) + dot(tA, mA) + dot(uB, fB) + dot(tB, mB);
+  }
+  store_cols<KB>(Q + (size_t)cb * B * KB, b, q);
+}
+
+// y_k = -w_k, the load of the adjoint solve, for the KB columns of column block blockIdx.y: the per-node gather of
+// k_geom_gather_multi (same sliced ELL and lane mapping, same lpn_sum, same order of the sum over a node's struts, no
+// atomics).  An entry adds -(+-) q_{b,k} ka_b t_b to the node's three translations, + at the strut's point2 and - at its
+// point1; the rotations get zero.  Nothing is masked here: the solve masks its loads itself.
+template <int LPN, int KB>
+__global__ __launch_bounds__(kBlock) void k_geom_adjoint_load(int64_t N, int64_t B, const int64_t *__restrict__ slice_ptr,
+                                                              const int2 *__restrict__ ent, const Record *__restrict__ rec,
+                                                              const double *__restrict__ Q, double *__restrict__ y,
+                                                              int64_t stride) {
+  const unsigned blk = xcd_block(blockIdx.x, gridDim.x);
+  const int cb = blockIdx.y;
+  Q += (size_t)cb * B * KB;
+  y += (size_t)cb * stride;
+  constexpr int kSliceNodes = kWave / LPN;
+  const int lane = threadIdx.x & 63, sub = lane / kSliceNodes;
+  const int64_t slice = (int64_t)blk * (kBlock / kWave) + (threadIdx.x >> 6);
+  const int64_t i = slice * kSliceNodes + (lane & (kSliceNodes - 1));
+  if (slice * kSliceNodes >= N) return;   // wave-uniform
+  double out[6 * KB];                    // the node's row; its rotations stay zero
+#pragma unroll
+  for (int q = 0; q < 6 * KB; ++q) out[q] = 0.0;
+  const int64_t p0 = slice_ptr[slice], p1 = slice_ptr[slice + 1];
+#pragma unroll 1
+  for (int64_t p = p0 + lane; p < p1; p += 64) {
+    const int2 e = ent[p];
+    if (e.x >= 0) {
+      const int64_t s = e.y & 0x7fffffff;
+      const Record r = load_record(rec, s);
+      double qv[KB];
+      load_cols<KB>(Q, s, qv);
+      const double L2 = r.dx * r.dx + r.dy * r.dy + r.dz * r.dz;
+      const double c = (r.a + r.e1 * L2) / sqrt(L2);              // ka / L: ka t = c d
+      const double sc = e.y < 0 ? c : -c;                         // -w: + at the strut's point1 (this node), - at point2
+#pragma unroll
+      for (int k = 0; k < KB; ++k) {
+        const double v = sc * qv[k];
+        out[0 * KB + k] += v * r.dx; out[1 * KB + k] += v * r.dy; out[2 * KB + k] += v * r.dz;
+      }
+    }
+  }
+#pragma unroll
+  for (int q = 0; q < 3 * KB; ++q) out[q] = lpn_sum<LPN>(out[q]);
+  if (i < N && sub == 0) {
+    double2 *q = reinterpret_cast<double2 *>(y + 6 * KB * i);
+#pragma unroll
+    for (int j = 0; j < 3 * KB; ++j) q[j] = {out[2 * j], out[2 * j + 1]};
+  }
+}
+
+// dlam[col][b] = dlambda_col / dr_b for the n_live columns, and dsum[b] = sum_col weight_col dlam[col][b] in the order of
+// the columns (either output may be null): one thread per strut, no scatter.  The radius derivative of the record is that
+// of k_sens and k_buckling_grad (strut_drecord); nu solves K nu = -w.  kk_col = gram[col * ncol + col] (k_multi_gram of
+// phi and K phi), coef = [lambda (ncol) | weight (ncol)].
+template <int KB>
+__global__ __launch_bounds__(kBlock) void k_geom_sens(int64_t B, const int32_t *__restrict__ conn,
+                                                      const GeomRecord *__restrict__ grec, const double *__restrict__ radius,
+                                                      const double *__restrict__ seg_len, const int32_t *__restrict__ seg_nsub,
+                                                      const double *__restrict__ mult, Material m,
+                                                      const double *__restrict__ u, const double *__restrict__ phi,
+                                                      const double *__restrict__ nu, const double *__restrict__ Q,
+                                                      const double *__restrict__ gram, const double *__restrict__ coef,
+                                                      int n_live, int ncb, int64_t stride, double *__restrict__ dlam,
+                                                      double *__restrict__ dsum) {
+  const int64_t b = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+  if (b >= B) return;
+  if (mult) m = scaled(m, mult[b]);
+  const int64_t ia = conn[2 * b], ib = conn[2 * b + 1];
+  const GeomRecord g = load_geom(grec, b);
+  const V3 d = {g.dx, g.dy, g.dz};
+  const double len[3] = {seg_len[3 * b], seg_len[3 * b + 1], seg_len[3 * b + 2]};
+  const int ns[3] = {seg_nsub[3 * b], seg_nsub[3 * b + 1], seg_nsub[3 * b + 2]};
+  const Record dr = strut_drecord(radius[b], len, ns, m, d);
+  V3 uA, tA, uB, tB, Fu, Mu;
+  load6(u + 6 * ia, uA, tA);
+  load6(u + 6 * ib, uB, tB);
+  tip_force(dr, uA, tA, uB, tB, Fu, Mu);                           // (dK_e u_e) on end B
+  const double L2 = dot(d, d);
+  const double dN = (dr.a + dr.e1 * L2) * dot(d, uB - uA) / sqrt(L2);   // dka t.(u_B - u_A)
+  const int ncol = ncb * KB;
+  double sum = 0.0;
+  for (int cb = 0; cb < ncb; ++cb) {
+    double xa[6 * KB], xb[6 * KB], t1[KB], t3[KB], qv[KB];
+    load_row<KB>(phi + (size_t)cb * stride, ia, xa);
+    load_row<KB>(phi + (size_t)cb * stride, ib, xb);
+#pragma unroll
+    for (int k = 0; k < KB; ++k) {
+      V3 pA, rA, pB, rB, F, M;
+      column_of<KB>(xa, k, pA, rA);
+      column_of<KB>(xb, k, pB, rB);
+      tip_force(dr, pA, rA, pB, rB, F, M);
+      t1[k] = strut_pairing(d, F, M, pA, rA, pB, rB);
+    }
+    load_row<KB>(nu + (size_t)cb * stride, ia, xa);
+    load_row<KB>(nu + (size_t)cb * stride, ib, xb);
+#pragma unroll
+    for (int k = 0; k < KB; ++k) {
+      V3 pA, rA, pB, rB;
+      column_of<KB>(xa, k, pA, rA);
+      column_of<KB>(xb, k, pB, rB);
+      t3[k] = strut_pairing(d, Fu, Mu, pA, rA, pB, rB);
+    }
+    load_cols<KB>(Q + (size_t)cb * B * KB, b, qv);
+#pragma unroll
+    for (int k = 0; k < KB; ++k) {
+      const int col = cb * KB + k;
+      if (col < n_live) {
+        const double lam = coef[col];
+        const double v = lam / gram[(size_t)col * ncol + col] * (t1[k] + lam * (qv[k] * dN + t3[k]));
+        if (dlam) dlam[(size_t)col * B + b] = v;
+        sum += coef[ncol + col] * v;
+      }
+    }
+  }
+  if (dsum) dsum[b] = sum;
+}
+
 }  // namespace pl
 
 namespace {
@@ -292,6 +445,7 @@ struct GeomWs {
   DevBuf<double> Y, KY, GY, X, KX, GX;
   DevBuf<double> part, M, C;       // gram partials, two gram matrices, the combination matrix
   DevBuf<int32_t> perm;            // device node -> caller node
+  DevBuf<double> sq, sdlam, scoef; // pl_buckling_modes_sens: q [ncol][B], dlam [n_modes][B] + dsum [B], lambda | weight
 };
 
 int geom_ws(pl_context *c, GeomWs **out) {
@@ -374,6 +528,73 @@ int launch_combine(pl_context *c, GeomWs *g, const MultiShape &s, const double *
   const dim3 grid(grid_stream(n6), (unsigned)s.ncb);
   PL_MULTI_KB(s.KB, hipLaunchKernelGGL((pl::k_multi_combine<KB>), grid, dim3(pl::kBlock), 0, c->stream, n6, Y,
                                        (const double *)g->C.p, Z, s.ncb, s.stride));
+  PL_HIP(hipGetLastError());
+  return PL_OK;
+}
+
+// the per-strut arrays of pl_buckling_modes_sens for the shape s and n_modes rows of output
+int geom_ws_sens(pl_context *c, GeomWs *g, const MultiShape &s) {
+  const size_t B = (size_t)c->B;
+  if (g->sq.n < (size_t)s.ncol * B) PL_HIP(g->sq.alloc((size_t)s.ncol * B));
+  if (g->sdlam.n < (size_t)(s.n_rhs + 1) * B) PL_HIP(g->sdlam.alloc((size_t)(s.n_rhs + 1) * B));
+  if (!g->scoef.p) PL_HIP(g->scoef.alloc((size_t)2 * PL_MULTI_MAX));
+  return PL_OK;
+}
+
+// Q[cb][b KB + k] = phi_e^T G_b phi_e for every strut and column, one launch
+template <int KB>
+void launch_geom_quad_t(pl_context *c, const GeomWs *g, const MultiShape &s, const double *phi) {
+  hipLaunchKernelGGL((pl::k_geom_quad<KB>), dim3(grid_for(c->B), (unsigned)s.ncb), dim3(pl::kBlock), 0, c->stream, c->B,
+                     (const int32_t *)c->conn.p, (const pl::GeomRecord *)g->rec.p, phi, g->sq.p, s.stride);
+}
+int launch_geom_quad(pl_context *c, const GeomWs *g, const MultiShape &s, const double *phi) {
+  if (s.KB == 1) launch_geom_quad_t<1>(c, g, s, phi);
+  else if (s.KB == 2) launch_geom_quad_t<2>(c, g, s, phi);
+  else launch_geom_quad_t<4>(c, g, s, phi);
+  PL_HIP(hipGetLastError());
+  return PL_OK;
+}
+
+template <int LPN, int KB>
+void launch_adjoint_load_t(pl_context *c, const GeomWs *g, const MultiShape &s, double *y) {
+  const dim3 grid(grid_for(c->n_slices, pl::kBlock / pl::kWave), (unsigned)s.ncb);   // one wave per ELL slice and column block
+  hipLaunchKernelGGL((pl::k_geom_adjoint_load<LPN, KB>), grid, dim3(pl::kBlock), 0, c->stream, c->N, c->B, c->slice_ptr.p,
+                     c->ent.p, c->rec.p, (const double *)g->sq.p, y, s.stride);
+}
+template <int LPN>
+void launch_adjoint_load_lpn(pl_context *c, const GeomWs *g, const MultiShape &s, double *y) {
+  if (s.KB == 1) launch_adjoint_load_t<LPN, 1>(c, g, s, y);
+  else if (s.KB == 2) launch_adjoint_load_t<LPN, 2>(c, g, s, y);
+  else launch_adjoint_load_t<LPN, 4>(c, g, s, y);
+}
+// y_j = -w_j from g->sq for every column of the shape, one launch
+int launch_adjoint_load(pl_context *c, const GeomWs *g, const MultiShape &s, double *y) {
+  switch (c->lpn) {
+    case 1: launch_adjoint_load_lpn<1>(c, g, s, y); break;
+    case 2: launch_adjoint_load_lpn<2>(c, g, s, y); break;
+    case 4: launch_adjoint_load_lpn<4>(c, g, s, y); break;
+    case 8: launch_adjoint_load_lpn<8>(c, g, s, y); break;
+    case 16: launch_adjoint_load_lpn<16>(c, g, s, y); break;
+    default: return fail(PL_ERR_ARG, "lanes per node must be 1, 2, 4, 8 or 16");
+  }
+  PL_HIP(hipGetLastError());
+  return PL_OK;
+}
+
+// rows of dlambda/dr (dlam may be null) and their weighted sum (dsum may be null) from phi, nu, g->sq, g->M and g->scoef
+template <int KB>
+void launch_geom_sens_t(pl_context *c, const GeomWs *g, const MultiShape &s, const double *u, const double *phi, const double *nu,
+                        double *dlam, double *dsum) {
+  hipLaunchKernelGGL((pl::k_geom_sens<KB>), dim3(grid_for(c->B)), dim3(pl::kBlock), 0, c->stream, c->B, (const int32_t *)c->conn.p,
+                     (const pl::GeomRecord *)g->rec.p, (const double *)c->radius.p, (const double *)c->seg_len.p,
+                     (const int32_t *)c->seg_nsub.p, (const double *)c->mult.p, c->mat, u, phi, nu, (const double *)g->sq.p,
+                     (const double *)g->M.p, (const double *)g->scoef.p, s.n_rhs, s.ncb, s.stride, dlam, dsum);
+}
+int launch_geom_sens(pl_context *c, const GeomWs *g, const MultiShape &s, const double *u, const double *phi, const double *nu,
+                     double *dlam, double *dsum) {
+  if (s.KB == 1) launch_geom_sens_t<1>(c, g, s, u, phi, nu, dlam, dsum);
+  else if (s.KB == 2) launch_geom_sens_t<2>(c, g, s, u, phi, nu, dlam, dsum);
+  else launch_geom_sens_t<4>(c, g, s, u, phi, nu, dlam, dsum);
   PL_HIP(hipGetLastError());
   return PL_OK;
 }

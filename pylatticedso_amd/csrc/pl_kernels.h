@@ -629,16 +629,24 @@ __global__ __launch_bounds__(kBlock) void k_compose_solution(int64_t n6, const u
 // Per-strut sensitivity s_b = lam_e^T (dK_e/dr) u_e and strain energy (one thread per strut, no scatter).
 // ---------------------------------------------------------------------------------------------------------
 // One strut: r its radius, d = x_B - x_A, (u, t) / (l, m) the translations and rotations of u / lam at its ends.
-__device__ __forceinline__ double strut_sens(double r, const double *len, const int *ns, const Material &m, V3 d,
-                                             V3 uA, V3 tA, V3 uB, V3 tB, V3 lA, V3 mA, V3 lB, V3 mB) {
+// dK_e/dr at fixed segment geometry, as a record: the radius derivative of the condensed scalars on the span d.
+__device__ __forceinline__ Record strut_drecord(double r, const double *len, const int *ns, const Material &m, V3 d) {
   const Flex f = strut_flexibility(r, len, ns, m);
-  const Record dr = make_record(dscalars_dr(f, r), d);
-  V3 F, M;
-  tip_force(dr, uA, tA, uB, tB, F, M);
-  // energy-conjugate pairing: lam_e . (dK u)_e = F.(dlu) + M.(dlth) with the SAME relative deformations of lam
+  return make_record(dscalars_dr(f, r), d);
+}
+// lam_e . (K_e u)_e for the element of record q (F, M = tip_force(q; u)): the energy-conjugate pairing
+// F.(dlu) + M.(dlth) with the SAME relative deformations of lam
+__device__ __forceinline__ double strut_pairing(V3 d, V3 F, V3 M, V3 lA, V3 mA, V3 lB, V3 mB) {
   const V3 dlu = lB - lA + cross(d, mA);
   const V3 dlt = mB - mA;
   return dot(F, dlu) + dot(M, dlt);
+}
+__device__ __forceinline__ double strut_sens(double r, const double *len, const int *ns, const Material &m, V3 d,
+                                             V3 uA, V3 tA, V3 uB, V3 tB, V3 lA, V3 mA, V3 lB, V3 mB) {
+  const Record dr = strut_drecord(r, len, ns, m, d);
+  V3 F, M;
+  tip_force(dr, uA, tA, uB, tB, F, M);
+  return strut_pairing(d, F, M, lA, mA, lB, mB);
 }
 
 __global__ __launch_bounds__(kBlock) void k_sens(int64_t B, const double *__restrict__ xyz,

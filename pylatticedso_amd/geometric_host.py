@@ -1,6 +1,6 @@
 """Numpy / scipy restatement of the geometric stiffness and the global linear buckling analysis
-(include/pylattice_hip.h: pl_geom_spmv_multi / pl_buckling_modes; csrc/pl_geom.h), in the manner of
-buckling_host.py.  No device call.
+(include/pylattice_hip.h: pl_geom_spmv_multi / pl_buckling_modes / pl_buckling_modes_sens; csrc/pl_geom.h; DESIGN.md section
+10d), in the manner of buckling_host.py.  No device call.
 
 With u the equilibrium of the applied loads, the load factors are the smallest lambda > 0 with (K + lambda K_g(u)) phi = 0
 on the free dofs.  Per strut, d = x_B - x_A, L = |d|, t = d / L and N = F.t the record's TOTAL axial force (tension > 0; a
@@ -289,3 +289,81 @@ def buckling_modes_subspace(K, Kg, fixed=None, n_modes=4, n_sub=0, tol=1e-9, max
     out = _finish(K, Kg, free, np.where(np.abs(mu) <= ZERO_RITZ * (np.abs(mu).max() if len(mu) else 0.0), 0.0, mu), X, n_modes)
     out.update(outer_iterations=outer, converged=converged, sigma=sigma_max)
     return out
+
+
+def _pairing(rec, conn, x, y):
+    """(B,) y_e^T K_e x_e for the elements of the records ``rec`` (pl_kernels.h strut_pairing): the tip force of x against
+    the relative deformations of y."""
+    conn = np.asarray(conn).reshape(-1, 2)
+    y = np.asarray(y, dtype=float).reshape(-1, 6)
+    F, M = SH.tip_force(rec, conn, x)
+    A, B = conn[:, 0], conn[:, 1]
+    return SH._dot(F, y[B, :3] - y[A, :3] + np.cross(rec[:, 5:8], y[A, 3:])) + SH._dot(M, y[B, 3:] - y[A, 3:])
+
+
+def buckling_sensitivity(rec, drec_dr, beam_conn, u, fixed, load_factor, modes, solve=None):
+    """What pl_buckling_modes_sens computes: (dlam_dr (n_modes, B), adj_load (n_modes, N, 6)), the derivatives of the load
+    factors to the strut radii at fixed segment geometry, u following the radii through K u = f, and the loads w of the
+    adjoint solves.  rec: the condensed records, drec_dr: their radius derivative (stress_host.drecords_dr), u (N, 6) the
+    full equilibrium field, fixed (N, 6) the Dirichlet mask, (load_factor, modes) the eigenpairs (any scaling; the modes are
+    read with the fixed dofs zeroed; a NaN factor gives NaN rows).  Per strut, with G_b = element_matrix(d_b, 1),
+    ka = a + e1 L^2 (axial_force = ka t.(u_B - u_A)) and dK_e = dK_e/dr_b:
+
+        kk = phi^T K phi,  q_b = phi_e^T G_b phi_e,  w = sum_b q_b ka_b (-t_b at u_A, +t_b at u_B),  K nu = -w (free dofs)
+        dlambda/dr_b = (lambda / kk) [phi_e^T dK_e phi_e + lambda (q_b dka_b t_b.(u_B - u_A) + nu_e^T dK_e u_e)]
+
+    The rows of an m-fold repeated factor are not derivatives one by one (the modes are an arbitrary basis of the eigenspace);
+    their sum over the cluster is the derivative of the sum of those factors.  solve(b) -> K_ff^-1 b replaces the sparse LU."""
+    rec = np.asarray(rec, dtype=float).reshape(-1, 8)
+    drec = np.asarray(drec_dr, dtype=float).reshape(-1, 8)
+    conn = np.asarray(beam_conn).reshape(-1, 2)
+    u = np.asarray(u, dtype=float).reshape(-1, 6)
+    n = len(u)
+    lam = np.asarray(load_factor, dtype=float).reshape(-1)
+    fixed = np.asarray(fixed).reshape(n, 6) != 0
+    modes = np.where(fixed[None], 0.0, np.asarray(modes, dtype=float).reshape(len(lam), n, 6))
+    free = _free(fixed, 6 * n)
+    K = elastic_matrix(rec, conn, n)
+    if solve is None:
+        solve = spla.splu(K[free][:, free].tocsc()).solve
+    d = rec[:, 5:8]
+    L2 = SH._dot(d, d)
+    t = d / np.sqrt(L2)[:, None]
+    A, B = conn[:, 0], conn[:, 1]
+    G = element_matrix(d, np.ones(len(d)))
+    ka, dka = rec[:, 0] + rec[:, 2] * L2, drec[:, 0] + drec[:, 2] * L2
+    stretch = SH._dot(t, u[B, :3] - u[A, :3])
+    dlam = np.full((len(lam), len(rec)), np.nan)
+    load = np.full((len(lam), n, 6), np.nan)
+    for i in range(len(lam)):
+        if np.isnan(lam[i]):
+            continue
+        phi = modes[i]
+        kk = float(phi.reshape(-1) @ (K @ phi.reshape(-1)))
+        pe = np.concatenate([phi[A], phi[B]], axis=1)
+        q = np.einsum("bi,bij,bj->b", pe, G, pe)
+        w = np.zeros((n, 6))
+        np.add.at(w[:, :3], B, (q * ka)[:, None] * t)
+        np.add.at(w[:, :3], A, -(q * ka)[:, None] * t)
+        nu = np.zeros(6 * n)
+        nu[free] = solve(-w.reshape(-1)[free])
+        dlam[i] = lam[i] / kk * (_pairing(drec, conn, phi, phi) + lam[i] * (q * dka * stretch + _pairing(drec, conn, u, nu)))
+        load[i] = w
+    return dlam, load
+
+
+def load_factor_aggregate(load_factor, p):
+    """(J, dJ_dlambda): the p-norm J = (sum_i mu_i^p)^(1/p) of mu = 1 / lambda over the finite entries of load_factor,
+    evaluated as mu_max (sum (mu / mu_max)^p)^(1/p), and its derivative (zero on the other entries).  J >= 1 / lambda_1, and J
+    is a symmetric function of the factors: equal factors get equal weights, which the rows of a repeated factor need
+    (buckling_sensitivity).  No finite entry: (0, zeros)."""
+    lam = np.asarray(load_factor, dtype=float).reshape(-1)
+    ok = np.isfinite(lam)
+    dJ = np.zeros_like(lam)
+    if not ok.any():
+        return 0.0, dJ
+    mu = 1.0 / lam[ok]
+    mmax = mu.max()
+    s = ((mu / mmax) ** p).sum()
+    dJ[ok] = -(mu / mmax) ** (p - 1.0) * s ** (1.0 / p - 1.0) * mu * mu          # dJ/dmu dmu/dlambda
+    return float(mmax * s ** (1.0 / p)), dJ

@@ -23,6 +23,7 @@ import time
 
 import numpy as np
 
+from . import geometric_host as GH
 from .lattice_sim import LatticeSim, open_lattice_parameters
 from .utils_simulation import solve_FEM_FenicsX
 
@@ -62,6 +63,9 @@ class LatticeOpti(LatticeSim):
         if self._ddm_mode and "buckling" in (info.get("constraints") or {}):
             raise NotImplementedError('the "buckling" constraint needs simulation_type "FEM": strut forces on the '
                                       "recovered interiors of DDM cells are not implemented")
+        if self._ddm_mode and "global_buckling" in (info.get("constraints") or {}):
+            raise NotImplementedError('the "global_buckling" constraint needs simulation_type "FEM": the geometric stiffness of '
+                                      "the recovered interiors of DDM cells is not implemented")
         comp = ((params.get("simulation_parameters", {}).get("DDM") or {}).get("schur_complement_computation") or {})
         if ddm_gradient is None:
             ddm_gradient = comp.get("gradient", "finite_difference") if self._ddm_mode else "finite_difference"
@@ -102,6 +106,9 @@ class LatticeOpti(LatticeSim):
         self._last_buckling = None
         if "buckling" in self.constraints_dict:
             self._history["max_buckling"] = []
+        self._last_global_buckling = None
+        if "global_buckling" in self.constraints_dict:
+            self._history["min_load_factor"] = []
         self._set_number_parameters_optimization()
         # strut -> (cell, type) of the LAST cell that holds it: Cell.change_beam_radius (cell.py:896-917) is called
         # cell after cell, so a strut shared by several cells ends with the last one's radius
@@ -636,7 +643,11 @@ class LatticeOpti(LatticeSim):
         lam^T (dK/dr_b) u with K lam = dq/du on the free dofs, through _strut_to_cell, the parameterisation's chain and the
         normalisation of the variables."""
         lam = self._adjoint(dq_du)
-        s = dq_dr - self.device_model().sens(self._model.u, lam)
+        return self._strut_gradient_to_parameters(dq_dr - self.device_model().sens(self._model.u, lam))
+
+    def _strut_gradient_to_parameters(self, s):
+        """dq/d(theta) from the total per-strut derivatives dq/dr_b: _strut_to_cell, the parameterisation's chain and the
+        normalisation of the variables."""
         g = self._chain_cell_sensitivities(self._strut_to_cell(s))
         scale = np.ones(self.number_parameters)          # d(physical variable)/d(theta)
         if self.enable_normalization:
@@ -678,6 +689,41 @@ class LatticeOpti(LatticeSim):
         _, _, dbp_du, dbp_dr = self.strut_buckling_aggregate(want_grad=True)
         return self._aggregate_gradient(dbp_du, dbp_dr) / b_allow
 
+    # -- global buckling constraint (FEM mode): p-norm of 1 / lambda_i, pl_buckling_modes + pl_buckling_modes_sens ------------
+    def _global_buckling_settings(self):
+        c = self.constraints_dict["global_buckling"]
+        kw = {k: c[k] for k in ("n_sub", "rtol", "max_iter", "tol", "max_outer") if k in c}
+        return float(c.get("value", 1.0)), int(c.get("n_modes", 4)), float(c.get("p", 8)), kw
+
+    def global_buckling_aggregate(self, want_grad=False):
+        """(J_p, lambda_1, dJ/dr_b or None) of the current equilibrium: J_p = (sum_i lambda_i^-p)^(1/p) over the constraint's
+        n_modes smallest positive load factors (J_p >= 1 / lambda_1; 0 and lambda_1 = inf when none exists).  dJ/dr_b is the
+        device's weighted sum of the rows of pl_buckling_modes_sens and is total: the adjoint for u(r) is inside that call."""
+        _, n_modes, p, kw = self._global_buckling_settings()
+        self.global_buckling(n_modes, **kw)
+        out = self.global_buckling_sensitivity(p, want_rows=False) if want_grad else None
+        lam = self.buckling_load_factors
+        lam1 = float(lam[0]) if np.isfinite(lam[0]) else float("inf")
+        J = out["aggregate"] if want_grad else GH.load_factor_aggregate(lam, p)[0]
+        self._last_global_buckling = (J, lam1)
+        return J, lam1, (out["dJ_dr"] if want_grad else None)
+
+    def global_buckling_constraint(self, r):
+        """lambda_min J_p - 1 (<= 0 when feasible: J_p >= 1 / lambda_1, so lambda_1 >= lambda_min then; -1 when no positive load
+        factor exists)."""
+        self.set_optimization_parameters(r)
+        if not self._sim_is_current:
+            self._simulate_lattice_equilibrium()
+        return self._global_buckling_settings()[0] * self.global_buckling_aggregate()[0] - 1.0
+
+    def global_buckling_constraint_gradient(self, r):
+        """d(global_buckling_constraint)/d(theta): lambda_min dJ/dr_b through the tail of _aggregate_gradient."""
+        self.set_optimization_parameters(r)
+        if not self._sim_is_current:
+            self._simulate_lattice_equilibrium()
+        _, _, dJ_dr = self.global_buckling_aggregate(want_grad=True)
+        return self._global_buckling_settings()[0] * self._strut_gradient_to_parameters(dJ_dr)
+
     # -- driver (SciPy SLSQP, as the reference) ---------------------------------------------------------------------
     def _initialize_optimization_solver(self):
         from scipy.optimize import Bounds
@@ -706,6 +752,9 @@ class LatticeOpti(LatticeSim):
             self._history["max_stress"].append(None if self._last_stress is None else self._last_stress[1])
         if "max_buckling" in self._history:
             self._history["max_buckling"].append(None if self._last_buckling is None else self._last_buckling[1])
+        if "min_load_factor" in self._history:
+            self._history["min_load_factor"].append(None if self._last_global_buckling is None
+                                                    else self._last_global_buckling[1])
         self._history["parameters"].append(list(map(float, r)))
         self._history["timestamp"].append(time.time())
 
@@ -728,6 +777,9 @@ class LatticeOpti(LatticeSim):
         if "buckling" in self.constraints_dict:
             jac = {"jac": self.buckling_constraint_gradient} if self.enable_gradient_computing else {}
             self.constraints.append(NonlinearConstraint(self.buckling_constraint, -np.inf, 0.0, **jac))
+        if "global_buckling" in self.constraints_dict:
+            jac = {"jac": self.global_buckling_constraint_gradient} if self.enable_gradient_computing else {}
+            self.constraints.append(NonlinearConstraint(self.global_buckling_constraint, -np.inf, 0.0, **jac))
         kw = dict(fun=self.objective, x0=self.initial_parameters, method="SLSQP", bounds=self.bounds,
                   constraints=self.constraints, callback=self.callback_function,
                   options={"maxiter": self.optim_max_iteration, "ftol": self.optim_ftol, "disp": self.optim_disp,

@@ -671,6 +671,30 @@ class LatticeSim(LatticeViews):
         self.buckling_modes = out["modes"]
         return out
 
+    def global_buckling_sensitivity(self, p=8, want_rows=True, **kw):
+        """Derivatives of the load factors of the last ``global_buckling`` to the strut radii, on the device
+        (pl_buckling_modes_sens), and of their aggregate J = (sum_i lambda_i^-p)^(1/p) >= 1 / lambda_1
+        (geometric_host.load_factor_aggregate): dict with aggregate, dJ_dr (n_beams,) - the device's weighted sum with the
+        weights dJ/dlambda_i - and dlam_dr (n_modes, n_beams) (want_rows=False leaves it out).  All are total derivatives at
+        fixed segment geometry: the displacements follow the radii.  The rows of a repeated factor are not derivatives one by
+        one; J weighs equal factors equally, so dJ_dr is - as long as the aggregate holds whole clusters.  Keyword arguments
+        (rtol, max_iter) go to ``HipLattice.buckling_modes_sens``."""
+        if self._device is None or getattr(self, "_compat_rows", False):
+            raise RuntimeError("global_buckling needs a solve_FEM_FenicsX on this lattice first (default strut model; the "
+                               "reference_compat model has no device buckling pass)")
+        if getattr(self, "buckling_load_factors", None) is None:
+            raise RuntimeError("global_buckling_sensitivity needs a global_buckling on this lattice first")
+        from .geometric_host import load_factor_aggregate
+        lam = self.buckling_load_factors
+        J, wts = load_factor_aggregate(lam, p)
+        model = getattr(self, "_model", None)       # (as global_buckling)
+        out = self._device.buckling_modes_sens(lam, self.buckling_modes, None if model is None else model._u_solver,
+                                               weights=wts, want_rows=want_rows, **kw)
+        res = {"aggregate": J, "dJ_dr": out["dsum_dr"]}
+        if want_rows:
+            res["dlam_dr"] = out["dlam_dr"]
+        return res
+
     # ------------------------------------------------------------------------------------------------
     # Domain decomposition (lattice_sim.py:846-919, 1111-1252)
     # ------------------------------------------------------------------------------------------------

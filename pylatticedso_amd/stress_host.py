@@ -79,6 +79,17 @@ def records(node_xyz, beam_conn, radius, seg_len, seg_nsub, young, poisson, kapp
     return _record(_scalars(flexibility(radius, seg_len, seg_nsub, young, poisson, kappa, pen_coef, mult)), d)
 
 
+def drecords_dr(node_xyz, beam_conn, radius, seg_len, seg_nsub, young, poisson, kappa=0.9, pen_coef=1.5, mult=None):
+    """(B, 8) radius derivative of ``records`` at fixed segment geometry (pl_device.h dscalars_dr / make_record): the
+    derivatives of (a, c, e1, e2, e3) in columns 0 ... 4 and the span d itself, not a derivative, in columns 5 ... 7, so the
+    result is a record that ``tip_force`` reads: tip_force(drecords_dr(...), conn, u) = (dK_e/dr u_e) on end B."""
+    xyz = np.asarray(node_xyz, dtype=float).reshape(-1, 3)
+    conn = np.asarray(beam_conn).reshape(-1, 2)
+    d = xyz[conn[:, 1]] - xyz[conn[:, 0]]
+    r = np.asarray(radius, dtype=float)
+    return _record(_dscalars_dr(flexibility(r, seg_len, seg_nsub, young, poisson, kappa, pen_coef, mult), r), d)
+
+
 def tip_force(rec, conn, u):
     """(F, M_B) (B, 3) each: what the strut applies to its end beam_conn[:, 1] (pl_device.h tip_force)."""
     u = np.asarray(u, dtype=float).reshape(-1, 6)
