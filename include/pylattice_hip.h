@@ -325,6 +325,19 @@ int pl_reactions(pl_handle h, const double *u, double *R);
  * Material.compute_gradient (material_definition.py:163-231). */
 int pl_sens(pl_handle h, const double *u, const double *lam, double *dCdr);
 
+/* The same contraction for every pair of several fields in one pass (csrc/pl_sensgram.h): the strut's
+ * dK_e/dr record - the expensive part of pl_sens - is built once per strut instead of once per pair.  A building block
+ * beside pl_sens and pl_spmv_multi: the diagonal holds the compliance sensitivities of n_rhs load cases, an off-diagonal
+ * entry a state x adjoint pair, and with the six total fields of a periodic homogenisation the whole Gram is the radius
+ * derivative of the homogenised stiffness (u_k^T K u_l = scale_k H[k][l], no adjoint solve). */
+#define PL_SENS_GRAM_MAX 8
+/* gram[p][b] = x_k,e^T (dK_e/dr_b) x_l,e at fixed segment geometry for every pair k <= l < n_rhs,
+ * p = k*n_rhs - k*(k-1)/2 + (l - k)  (rows of the upper triangle, row-major); x: [n_rhs][6N] host, gram: [n_rhs(n_rhs+1)/2][B]
+ * host, caller's strut numbering.  Same dK_e/dr as pl_sens (radius, segments, multiplicity, material of the handle).
+ * Single-GPU FEM handles (PL_ERR_STATE on pl_create_ddm / pl_dist_init handles); n_rhs < 1 or > PL_SENS_GRAM_MAX, NULL: PL_ERR_ARG.
+ * Purely per strut: Dirichlet data and periodic constraints of the handle do not enter.  Leaves the handle's solver state untouched. */
+int pl_sens_gram(pl_handle h, int32_t n_rhs, const double *x, double *gram);
+
 /* Displacements of the penalisation points ("node_mod" points: the junctions between the penalised end segments and the
  * middle segment of every strut, LatticeSim.set_penalized_beams lattice_sim.py:245-308, which the reference meshes as
  * FE vertices and reads back in set_result_diplacement_on_lattice_object, full_scale_lattice_simulation.py:77-107).
@@ -533,7 +546,9 @@ int pl_debug_partition(pl_handle h, int32_t *tile_of_node, int32_t *agg_of_node,
  * 9 = one iteration of the mixed PCG (precision 2) - 8 and 9 call the solver's own iteration, so they apply the operator
  * as the handle's plan does (both passes where it eliminates nodes); 10 = the operator exactly as the next pl_solve applies it (BOTH passes
  * under node elimination, fp32-stored operands in the fp32 solver modes) - what a roofline of "K*p" must be priced with;
- * 11 = one whole PCG iteration exactly as the next pl_solve runs it (storage width and node elimination of its plan). */
+ * 11 = one whole PCG iteration exactly as the next pl_solve runs it (storage width and node elimination of its plan);
+ * 12 = the kernel of pl_sens_gram alone, on the columns (and with the column count) of the last pl_sens_gram call of this
+ * handle, which stay on the device (PL_ERR_STATE without such a call). */
 int pl_time_kernel(pl_handle h, int which, int reps, double *avg_ms);
 /* Algorithmic byte counts of SURVEY.md section 8(d) for this handle: out[0]=spmv, out[1]=pcg_iter, out[2]=bsr - with the
  * storage widths the next pl_solve uses: strut records and the explicit K are fp64 in every mode, the PCG vectors are 4 bytes

@@ -21,7 +21,7 @@ PL_OK, PL_ERR_ARG, PL_ERR_HIP, PL_ERR_STATE, PL_ERR_NOCONV, PL_ERR_NAN, PL_ERR_N
 EXPORTS = ["pl_default_opts", "pl_opts_size", "pl_stats_size", "pl_abi_version", "pl_last_error", "pl_version", "pl_lzone", "pl_create", "pl_create_ddm",
            "pl_ddm_set_preconditioner", "pl_ddm_set_geometry", "pl_ddm_update_matrices", "pl_destroy", "pl_set_bc", "pl_set_periodic",
            "pl_update_radii", "pl_set_multiplicity", "pl_update_segments", "pl_assemble", "pl_assemble_bsr", "pl_get_bsr", "pl_spmv",
-           "pl_spmv_free", "pl_spmv_bsr", "pl_solve", "pl_reactions", "pl_sens", "pl_energy", "pl_node_mod", "pl_schur",
+           "pl_spmv_free", "pl_spmv_bsr", "pl_solve", "pl_reactions", "pl_sens", "pl_sens_gram", "pl_energy", "pl_node_mod", "pl_schur",
            "pl_stress", "pl_stress_pnorm", "pl_buckling", "pl_buckling_pnorm",
            "pl_spmv_multi", "pl_solve_multi", "pl_schur_block", "pl_geom_spmv_multi", "pl_buckling_modes", "pl_buckling_modes_sens",
            "pl_schur_cells", "pl_cells_recover", "pl_get_records", "pl_debug_partition", "pl_time_kernel", "pl_algorithmic_bytes", "pl_node_words_info", "pl_forget_history", "pl_debug_spd_solve", "pl_dist_unique_id_bytes",
@@ -91,7 +91,7 @@ def load_library(path: str | None = None):
            "pl_update_radii": [V, V], "pl_set_multiplicity": [V, V], "pl_update_segments": [V, V, V], "pl_assemble": [V],
            "pl_assemble_bsr": [V, I32, V, V], "pl_get_bsr": [V, V, V, V], "pl_spmv": [V, V, V],
            "pl_spmv_free": [V, V, V], "pl_spmv_bsr": [V, V, V], "pl_solve": [V, D, I32, V, V],
-           "pl_reactions": [V, V, V], "pl_sens": [V, V, V, V], "pl_energy": [V, V, V], "pl_node_mod": [V, V, V],
+           "pl_reactions": [V, V, V], "pl_sens": [V, V, V, V], "pl_sens_gram": [V, I32, V, V], "pl_energy": [V, V, V], "pl_node_mod": [V, V, V],
            "pl_stress": [V, V, I32, V, V], "pl_stress_pnorm": [V, V, I32, D, V, V, V, V],
            "pl_buckling": [V, V, I32, D, I32, V, V, V], "pl_buckling_pnorm": [V, V, I32, D, I32, D, V, V, V, V],
            "pl_schur": [V, V, I32, D, I32, V], "pl_spmv_multi": [V, I32, I32, V, V],
@@ -169,6 +169,8 @@ def debug_spd_solve(A, b, device=0, fp32_factor=False):
 
 # columns one pl_spmv_multi / pl_solve_multi call takes (PL_MULTI_MAX of include/pylattice_hip.h)
 MULTI_MAX = 64
+# columns of one pl_sens_gram call (PL_SENS_GRAM_MAX)
+SENS_GRAM_MAX = 8
 
 # what one workgroup of pl_schur_cells holds (include/pylattice_hip.h): larger cells go through pl_schur
 SCHUR_CELLS_MAX_BOUNDARY, SCHUR_CELLS_MAX_INTERIOR, SCHUR_CELLS_MAX_BEAMS = 32, 16, 512
@@ -601,6 +603,27 @@ class HipLattice:
         lam_a = None if lam is None else _f64(np.asarray(lam).reshape(-1), 6 * self.n_nodes)
         out = np.empty(self.n_beams, np.float64)
         _check(self._lib, self._lib.pl_sens(self._h, _ptr(u), _ptr(lam_a), _ptr(out)))
+        return out
+
+    def sens_gram(self, X):
+        """G[k, l, b] = X[k]_e^T (dK_e/dr_b) X[l]_e for every pair of the k columns of X in one pass over the struts
+        (pl_sens_gram): X (k, N, 6) or (k, 6 N), k = 1 ... SENS_GRAM_MAX (the library checks it); returns the full symmetric
+        (k, k, B) array - the library computes the upper triangle, the lower one is its mirror.  The same dK_e/dr as
+        ``sens``: fixed segment geometry."""
+        x = np.asarray(X, dtype=np.float64)
+        n6 = 6 * self.n_nodes
+        if x.ndim == 3 and x.shape[1:] == (self.n_nodes, 6):
+            x = x.reshape(x.shape[0], n6)
+        elif not (x.ndim == 2 and x.shape[1] == n6):
+            raise ValueError(f"X must have shape (k, {self.n_nodes}, 6) or (k, {n6}), got {x.shape}")
+        x = np.ascontiguousarray(x)
+        k = x.shape[0]
+        tri = np.empty((max(k * (k + 1) // 2, 1), self.n_beams), np.float64)
+        _check(self._lib, self._lib.pl_sens_gram(self._h, k, _ptr(x), _ptr(tri)))
+        iu = np.triu_indices(k)
+        out = np.empty((k, k, self.n_beams), np.float64)
+        out[iu] = tri
+        out[iu[1], iu[0]] = tri
         return out
 
     def node_mod(self, u):

@@ -6,6 +6,7 @@
 #include "pl_stress.h"
 #include "pl_buckling.h"
 #include "pl_geom.h"
+#include "pl_sensgram.h"
 
 
 // ==========================================================================================================
@@ -1536,6 +1537,44 @@ int pl_sens(pl_handle h, const double *u, const double *lam, double *dCdr) {
   return PL_OK;
 }
 
+int pl_sens_gram(pl_handle h, int32_t n_rhs, const double *x, double *gram) {
+  if (!valid(h) || !x || !gram) return fail(PL_ERR_ARG, "pl_sens_gram: null argument");
+  if (n_rhs < 1 || n_rhs > PL_SENS_GRAM_MAX) return fail(PL_ERR_ARG, "pl_sens_gram: n_rhs must be 1 ... PL_SENS_GRAM_MAX");
+  if (h->opkind != 0) return fail(PL_ERR_STATE, "pl_sens_gram: not available on a DDM handle");
+  if (h->dist.active) return fail(PL_ERR_STATE, "pl_sens_gram: not available on a multi-GPU handle");
+  PL_HIP(hipSetDevice(h->opt.device));
+  const size_t n6 = (size_t)h->N * 6, B = (size_t)h->B, pairs = (size_t)n_rhs * (n_rhs + 1) / 2;
+  if (h->gram_x.n < n_rhs * n6) PL_HIP(h->gram_x.alloc(n_rhs * n6));
+  if (h->gram_out.n < pairs * B) PL_HIP(h->gram_out.alloc(pairs * B));
+  if (h->pinG_n < pairs * B) {
+    if (h->pinG) (void)hipHostFree(h->pinG);
+    h->pinG = nullptr;
+    h->pinG_n = 0;
+    void *p = nullptr;
+    PL_HIP(hipHostMalloc(&p, pairs * B * sizeof(double), hipHostMallocDefault));
+    h->pinG = static_cast<double *>(p);
+    h->pinG_n = pairs * B;
+  }
+  h->gram_cols = 0;
+  std::vector<double> stage;
+  int rc = PL_OK;
+  for (int32_t k = 0; k < n_rhs; ++k) {
+    rc = upload6(h, x + k * n6, h->gram_x.p + k * n6, stage);
+    if (rc) return rc;
+  }
+  rc = launch_sens_gram(h, n_rhs, h->gram_x.p, h->gram_out.p);
+  if (rc) return rc;
+  h->gram_cols = n_rhs;
+  PL_HIP(hipMemcpyAsync(h->pinG, h->gram_out.p, pairs * B * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+  PL_HIP(hipStreamSynchronize(h->stream));
+  const double *stg = h->pinG;
+  pl::parallel_for(h->B, [&](int64_t b0, int64_t b1, unsigned) {
+    for (size_t p = 0; p < pairs; ++p)
+      for (int64_t b = b0; b < b1; ++b) gram[p * B + (size_t)h->bperm[b]] = stg[p * B + (size_t)b];
+  }, 1 << 14);
+  return PL_OK;
+}
+
 int pl_node_mod(pl_handle h, const double *u, double *out) {
   if (!valid(h) || !u || !out) return fail(PL_ERR_ARG, "pl_node_mod: null argument");
   if (h->opkind != 0) return fail(PL_ERR_STATE, "pl_node_mod: not available on a DDM handle");
@@ -2648,6 +2687,9 @@ int pl_time_kernel(pl_handle h, int which, int reps, double *avg_ms) {
                              : apply_operator<double>(h, h->p.p, h->Ap.p, h->scal.p + pl::S_PAP * pl::kSlots);
       case 11:   // one whole iteration exactly as the next pl_solve runs it (storage width and node elimination of its plan)
         return mp_applies(h) && h->opt.precision == 1 ? mp_iteration<float>(h, k, k, p32, Ap32, x32, r32) : pcg_iteration(h, k);
+      case 12:   // the kernel of pl_sens_gram on the columns its last call left on the device
+        if (h->gram_cols < 1) return fail(PL_ERR_STATE, "pl_time_kernel: 12 needs a pl_sens_gram call on this handle first");
+        return launch_sens_gram(h, h->gram_cols, h->gram_x.p, h->gram_out.p);
       default: return fail(PL_ERR_ARG, "pl_time_kernel: unknown kernel id");
     }
   };

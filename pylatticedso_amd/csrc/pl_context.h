@@ -269,6 +269,12 @@ struct pl_context {
   DevBuf<double> sens_out;     // [B] per-strut sensitivities of pl_sens (kept: a design loop calls it every iteration)
   DevBuf<double> usol;         // composed solution of the last pl_solve (pl_sens with u = NULL reads it)
   bool usol_valid = false;
+  // pl_sens_gram (pl_sensgram.h): uploaded columns [n][6N], Gram rows [n (n + 1) / 2][B] and their pinned staging buffer,
+  // kept and grown on demand like sens_out; gram_cols = column count of the last call (pl_time_kernel 12)
+  DevBuf<double> gram_x, gram_out;
+  double *pinG = nullptr;
+  size_t pinG_n = 0;
+  int gram_cols = 0;
   std::shared_ptr<void> multi_ws;   // workspace of the multi-column calls (pl_multi.h), created by the first of them
   std::shared_ptr<void> geom_ws;    // workspace of the geometric-stiffness calls (pl_geom.h), likewise
   // pl_stress / pl_stress_pnorm (pl_stress.h), allocated by the first call: per-station sigma_vm [B][4], block partials of the
@@ -289,6 +295,7 @@ struct pl_context {
     if (ev_t1) (void)hipEventDestroy(ev_t1);
     if (pin6) (void)hipHostFree(pin6);
     if (pinB) (void)hipHostFree(pinB);
+    if (pinG) (void)hipHostFree(pinG);
     if (ev_ov_a) (void)hipEventDestroy(ev_ov_a);
     if (ev_ov_x) (void)hipEventDestroy(ev_ov_x);
     if (comm_stream) (void)hipStreamDestroy(comm_stream);

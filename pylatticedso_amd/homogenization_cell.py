@@ -96,6 +96,8 @@ class HomogenizedCell:
         self.pcg_iterations = []
         self.device = device if device is not None else lattice.device_model(precond=1)
         self.homogenizeMatrix = None
+        self.homogenizeMatrix_raw = None            # un-symmetrised, and its radius derivative (homogenized_sensitivity)
+        self.dHomogenizeMatrix_raw = None
         self.orthotropicMatrix = None
         self.saveDataToExport = None
         self.generalizedStress = None
@@ -245,10 +247,63 @@ class HomogenizedCell:
             columns.append(np.array([s[a][b] for a, b in _VOIGT]))
             self.saveDataToExport.append(u_tot)
         self.homogenizeMatrix = np.column_stack(columns)
+        self.homogenizeMatrix_raw = self.homogenizeMatrix.copy()      # (the matrix the engineering constants are read from)
+        self.dHomogenizeMatrix_raw = None
         self.convert_to_orthotropic_form()
         self.compute_errors()
         self.homogenizeMatrix = 0.5 * (self.homogenizeMatrix + self.homogenizeMatrix.T)
         return self.homogenizeMatrix
+
+    # ---- radius sensitivities (no counterpart in the reference) ---------------------------
+    def _per(self, d, per):
+        if per == "strut":
+            return d
+        if per == "radius":
+            from . import homogenization_host as HH
+            return HH.per_radius(d, self.lattice.lattice.beam_type, len(self.lattice.radii))
+        raise ValueError("per must be 'strut' or 'radius'")
+
+    def _raw_sensitivity(self):
+        """dH_raw (6, 6, B) of the un-symmetrised matrix, computed once per solve and kept in ``dHomogenizeMatrix_raw``."""
+        if self.saveDataToExport is None or self.homogenizeMatrix_raw is None:
+            raise RuntimeError("homogenized_sensitivity: call solve_full_homogenization first")
+        if self.dHomogenizeMatrix_raw is None:
+            from . import homogenization_host as HH
+            dev = self.device
+            U = np.stack(self.saveDataToExport)
+            if self.solver == "device":
+                self.dHomogenizeMatrix_raw = dev.sens_gram(U) / HH.SCALE[:, None, None]
+            else:
+                from . import stress_host as SH
+                drec = SH.drecords_dr(dev.node_xyz, dev.beam_conn, dev._radius, dev._seg_len, dev._seg_nsub, *dev._material,
+                                      mult=dev._mult)
+                self.dHomogenizeMatrix_raw = HH.homogenized_sensitivity(drec, dev.beam_conn, U)
+        return self.dHomogenizeMatrix_raw
+
+    def homogenized_sensitivity(self, per="strut"):
+        """Derivative of ``homogenizeMatrix`` (symmetrised, like the matrix it differentiates) to the strut radii: (6, 6, B)
+        with per="strut", (6, 6, n_geometries) with per="radius" - summed over ``lattice.lattice.beam_type``, the derivative
+        to the cell's ``radii`` entries.  After ``solve_full_homogenization`` (RuntimeError before it).
+
+        The six total fields are in equilibrium against every periodic variation, so with E_kl = u_k^T K u_l =
+        scale_k H_raw[k, l], scale = (1, 1, 1, 2, 2, 2), the derivative is dE_kl/dr_b = u_k,e^T (dK_e/dr_b) u_l,e: no adjoint
+        solve, ONE device.sens_gram(saveDataToExport) call (pl_sens_gram); solver="host" evaluates the same formula with
+        homogenization_host on the handle's radii and segments.  The un-symmetrised derivative stays in
+        ``dHomogenizeMatrix_raw``.
+
+        Convention: FIXED SEGMENT GEOMETRY, as pl_sens.  Exact when joint penalisation is off; with penalisation on, the
+        change of the penalised lengths with the radius is not included, exactly as in LatticeOpti's gradients."""
+        raw = self._raw_sensitivity()
+        return self._per(0.5 * (raw + raw.transpose(1, 0, 2)), per)
+
+    def orthotropic_sensitivity(self, per="strut"):
+        """dict Ex, Ey, Ez, Gxy, Gxz, Gyz, nuxy, nuxz, nuyz -> derivative array (B,) or (n_geometries,) of the engineering
+        constants of ``orthotropicMatrix`` (read from the UN-symmetrised matrix, as ``_engineering_constants`` does);
+        same call order and the same fixed-segment-geometry convention as ``homogenized_sensitivity``."""
+        from . import homogenization_host as HH
+        raw = self._raw_sensitivity()
+        d = HH.engineering_constants_sensitivity(self.homogenizeMatrix_raw, raw)
+        return dict(zip(HH.CONSTANTS, self._per(d, per)))
 
     # ---- post-processing (:444-541) --------------------------------------------------------------------------
     def _engineering_constants(self):
@@ -306,3 +361,57 @@ def directional_modulus(matS: np.ndarray, theta: float, phi: float):
     S4 = matS[idx[:, :, None, None], idx[None, None, :, :]] / (coef[:, :, None, None] * coef[None, None, :, :])
     inv_e = np.einsum("ijkl,i,j,k,l->", S4, u, u, u, u)
     return u / inv_e
+
+
+def fit_cell_radii(lattice, target, rows=None, bounds=None, x0=None, xtol=1e-10, max_nfev=50, solver="device"):
+    """Inverse design of one cell: the ``radii`` of the one-cell ``lattice`` whose ``homogenizeMatrix`` matches
+    ``target`` (6, 6) in the least-squares sense over the entries ``rows`` (pairs (i, j); default: the 21 entries of the upper
+    triangle).  scipy.optimize.least_squares (trust-region reflective) with the analytic Jacobian of
+    ``HomogenizedCell.homogenized_sensitivity(per="radius")``; residuals and Jacobian are divided by the norm of the
+    selected target entries.  Every evaluation rebuilds the lattice with the trial radii (``reset_cell_with_new_radii``, a
+    fresh device model), homogenises it and takes ONE pl_sens_gram call for the Jacobian.
+
+    bounds: (lower, upper) as least_squares takes them; default (1e-3 min(x0), inf).  x0: default the lattice's current
+    radii.  Only xtol stops the iteration early (a zero-residual fit converges quadratically, and the relative decrease of
+    its cost never becomes small).  With joint penalisation on, the Jacobian leaves the change of the penalised lengths
+    out (fixed segment geometry): the fit still converges, linearly.
+
+    Returns (result, analysis): the scipy result (``x`` the radii, ``nfev``, ``cost`` ...) and the HomogenizedCell of
+    ``result.x``; the lattice is left at those radii.  ValueError when the lattice has more than one cell."""
+    from scipy.optimize import least_squares
+    if lattice.get_number_cells() > 1:
+        raise ValueError("The lattice must contain only one cell for homogenization.")
+    target = np.asarray(target, dtype=float)
+    if target.shape != (6, 6):
+        raise ValueError("target must be a (6, 6) matrix")
+    rows = [(i, j) for i in range(6) for j in range(i, 6)] if rows is None else [(int(i), int(j)) for i, j in rows]
+    ii, jj = np.array([r[0] for r in rows]), np.array([r[1] for r in rows])
+    norm = float(np.linalg.norm(target[ii, jj])) or 1.0
+    x0 = np.asarray(lattice.radii if x0 is None else x0, dtype=float)
+    if x0.shape != (len(lattice.radii),):
+        raise ValueError(f"x0 must hold {len(lattice.radii)} radii")
+    if bounds is None:
+        bounds = (1e-3 * x0.min(), np.inf)
+    last = {}
+
+    def evaluate(x):
+        key = tuple(float(v) for v in x)
+        if last.get("key") != key:
+            lattice.reset_cell_with_new_radii(list(key))
+            analysis = HomogenizedCell(lattice, solver=solver)
+            analysis.prepare_simulation()
+            analysis.apply_dirichlet_for_homogenization()
+            analysis.periodic_boundary_condition()
+            analysis.solve_full_homogenization()
+            last.update(key=key, analysis=analysis, dH=analysis.homogenized_sensitivity(per="radius"))
+        return last
+
+    def residual(x):
+        return (evaluate(x)["analysis"].homogenizeMatrix[ii, jj] - target[ii, jj]) / norm
+
+    def jacobian(x):
+        return evaluate(x)["dH"][ii, jj] / norm
+
+    result = least_squares(residual, x0, jac=jacobian, bounds=bounds, method="trf", xtol=xtol, ftol=None, gtol=None,
+                           max_nfev=max_nfev)
+    return result, evaluate(result.x)["analysis"]

@@ -176,3 +176,19 @@ def get_homogenized_properties(lattice):
     analysis.print_homogenized_matrix()
     analysis.print_errors()
     return analysis.get_S_orthotropic(), analysis
+
+
+def get_homogenized_sensitivities(lattice, per="radius"):
+    """Homogenised stiffness of a one-cell lattice and its radius derivative: (H (6, 6), dH, analysis) with dH (6, 6,
+    n_geometries) to the cell's ``radii`` entries (per="radius") or (6, 6, B) per strut (per="strut"), at fixed segment
+    geometry (HomogenizedCell.homogenized_sensitivity).  The six solves of
+    ``get_homogenized_properties`` and one pl_sens_gram call; nothing is printed."""
+    from .homogenization_cell import HomogenizedCell
+    if lattice.get_number_cells() > 1:
+        raise ValueError("The lattice must contain only one cell for homogenization.")
+    analysis = HomogenizedCell(lattice)
+    analysis.prepare_simulation()
+    analysis.apply_dirichlet_for_homogenization()
+    analysis.periodic_boundary_condition()
+    H = analysis.solve_full_homogenization()
+    return H, analysis.homogenized_sensitivity(per=per), analysis
