@@ -489,6 +489,43 @@ int pl_buckling_modes_sens(pl_handle h, const double *u /*[6N] or NULL = last pl
                            double *dsum_dr  /*[B] or NULL: sum_i weights[i] dlam_i/dr_b, formed on the device*/,
                            double *adj_load /*[n_modes][6N] or NULL: w_i, unmasked - test hook*/);
 
+/* ---- natural frequencies (csrc/pl_mass.h) -----------------------------------------------------------
+ * Free vibration K phi = omega^2 M phi on the free dofs of pl_set_bc, M the CONSISTENT mass of the struts: each strut is ONE
+ * element between its two lattice nodes (the discretisation of K_g), a uniform circular section of its plain radius r over
+ * the node-to-node length L - the textbook rho A L / 420 [[156, 22 L, 54, -13 L], ...] in both bending planes, the axial and
+ * torsional blocks [[2, 1], [1, 2]] and, with rotary != 0, the Rayleigh rotary inertia of bending rho I / (30 L) [[36, 3 L, ...
+ * Penalised end zones stiffen K only, strut overlap at the nodes is ignored, a multiplicity k counts k times.  Limits: those
+ * of the buckling calls - a strut vibrating between its own joints is over-stiff, single-GPU FEM handles, the Jacobi inner
+ * solve, clustered spectra need n_sub past the cluster.
+ * All four calls: PL_ERR_STATE on DDM and multi-rank handles; the last three also before pl_set_mass, before pl_assemble and
+ * with pl_set_periodic constraints.  The handle's single-column state is left untouched. */
+/* Density (> 0), rotary inertia of bending on / off (1 / 0) and optional translational point masses node_mass[N] >= 0 (NULL:
+ * none) in the caller's node numbering.  The strut masses follow the handle's current radii and multiplicities in every later
+ * call without further notice.  PL_ERR_ARG for a density that is not positive and a negative node_mass. */
+int pl_set_mass(pl_handle h, double density, int32_t rotary, const double *node_mass /*[N] >= 0 or NULL*/);
+/* y_j = M x_j (masked != 0: P M P x_j, needs pl_set_bc), j < n_rhs <= PL_MULTI_MAX; x, y: [n_rhs][6N] host arrays. */
+int pl_mass_spmv_multi(pl_handle h, int32_t n_rhs, int masked, const double *x, double *y);
+/* The n_modes smallest omega^2, ascending, and their modes (0 on fixed dofs, phi_i^T M phi_j = delta_ij, largest component
+ * positive): the block subspace iteration of pl_buckling_modes on M phi = mu K phi, omega^2 = 1 / mu, without a shift (M is
+ * positive definite).  n_sub, rtol, max_iter, tol, max_outer, n_found and PL_ERR_NOCONV as there; PL_ERR_STATE also before
+ * pl_set_bc. */
+int pl_vibration_modes(pl_handle h, int32_t n_modes, int32_t n_sub, double rtol, int32_t max_iter, double tol,
+                       int32_t max_outer, double *omega2 /*[n_modes]*/, double *modes /*[n_modes][6N] or NULL*/,
+                       double *residual /*[n_modes] or NULL: |K phi - omega^2 M phi| / |K phi|, free dofs*/,
+                       int32_t *n_found, int32_t *outer_iterations);
+/* Sensitivities of omega^2 to the strut radii at fixed segment geometry (the convention of pl_sens): for every eigenpair
+ * (omega2[i], modes[i]) - any scaling, read with the fixed dofs zeroed -
+ *     domega2_i/dr_b = (phi_e^T (dK_e/dr_b) phi_e - omega_i^2 phi_e^T (dM_e/dr_b) phi_e) / (phi_i^T M phi_i),
+ * dM_e/dr = (2 / r) M_e[axial and transverse terms] + (4 / r) M_e[torsional and rotary terms]; the point masses have no
+ * derivative.  No solve: one pass over the struts.  Rows of a repeated frequency are not derivatives one by one; a sum with
+ * equal weights over the whole cluster is (pl_buckling_modes_sens).  1 <= n_modes <= 16; a NaN omega2[i] marks a mode to
+ * skip: its row is NaN and it adds nothing to dsum_dr.  dsum_dr needs weights.  Outputs in the caller's strut numbering.
+ * PL_ERR_ARG for bad sizes, null inputs and when both outputs are NULL. */
+int pl_vibration_modes_sens(pl_handle h, int32_t n_modes, const double *omega2 /*[n_modes]*/,
+                            const double *modes /*[n_modes][6N]*/, const double *weights /*[n_modes] or NULL*/,
+                            double *domega2_dr /*[n_modes][B] or NULL*/,
+                            double *dsum_dr /*[B] or NULL: sum_i weights[i] domega2_i/dr_b, formed on the device*/);
+
 /* The same condensation, exact and batched, without a handle: n_inst small lattices of ONE topology (a unit cell at
  * several radius sets - the exact DDM mode, Schur datasets), each condensed by a dense Cholesky of K_II in one workgroup
  * of a single launch.  Material, pen_coef and device come from o (stamped by pl_default_opts; the solver fields are

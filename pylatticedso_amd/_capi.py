@@ -24,6 +24,7 @@ EXPORTS = ["pl_default_opts", "pl_opts_size", "pl_stats_size", "pl_abi_version",
            "pl_spmv_free", "pl_spmv_bsr", "pl_solve", "pl_reactions", "pl_sens", "pl_sens_gram", "pl_energy", "pl_node_mod", "pl_schur",
            "pl_stress", "pl_stress_pnorm", "pl_buckling", "pl_buckling_pnorm",
            "pl_spmv_multi", "pl_solve_multi", "pl_schur_block", "pl_geom_spmv_multi", "pl_buckling_modes", "pl_buckling_modes_sens",
+           "pl_set_mass", "pl_mass_spmv_multi", "pl_vibration_modes", "pl_vibration_modes_sens",
            "pl_schur_cells", "pl_cells_recover", "pl_get_records", "pl_debug_partition", "pl_time_kernel", "pl_algorithmic_bytes", "pl_node_words_info", "pl_forget_history", "pl_debug_spd_solve", "pl_dist_unique_id_bytes",
            "pl_dist_unique_id", "pl_dist_loopback_id", "pl_dist_abort", "pl_dist_init", "pl_dist_set_peers", "pl_generate_lattice", "pl_lattice_fetch",
            "pl_lattice_free", "pl_penalize", "pl_boundary_index", "pl_boundary_index_rows"]
@@ -99,6 +100,9 @@ def load_library(path: str | None = None):
            "pl_geom_spmv_multi": [V, V, I32, I32, V, V],
            "pl_buckling_modes": [V, V, I32, I32, D, I32, D, I32, V, V, V, V, V],
            "pl_buckling_modes_sens": [V, V, I32, V, V, D, I32, V, V, V, V],
+           "pl_set_mass": [V, D, I32, V], "pl_mass_spmv_multi": [V, I32, I32, V, V],
+           "pl_vibration_modes": [V, I32, I32, D, I32, D, I32, V, V, V, V, V],
+           "pl_vibration_modes_sens": [V, I32, V, V, V, V, V],
            "pl_schur_cells": [V, I32, I32, I32, V, I32, V, V, V, V, V, V, V],
            "pl_cells_recover": [V, I32, I32, I32, V, I32, V, V, V, V, V, V, V, V, V, V, V],
            "pl_get_records": [V, V], "pl_debug_partition": [V, V, V, V, V], "pl_time_kernel": [V, I32, I32, V],
@@ -848,6 +852,106 @@ class HipLattice:
             return GH.buckling_modes_dense(K, Kg, fixed, n_modes)
         return GH.buckling_modes_subspace(K, Kg, fixed, n_modes, n_sub, tol, max_outer)
 
+    # -- natural frequencies ------------------------------------------------------------------------------
+    def set_mass(self, density, rotary=True, node_mass=None):
+        """Mass model of the handle (pl_set_mass): the consistent mass of the struts at ``density``, with the rotary inertia
+        of bending if ``rotary``, plus optional translational point masses node_mass (N,) >= 0.  The strut masses follow
+        later update_radii / set_multiplicity calls by themselves."""
+        nm = None if node_mass is None else _f64(np.asarray(node_mass).reshape(-1), self.n_nodes)
+        _check(self._lib, self._lib.pl_set_mass(self._h, float(density), int(bool(rotary)), _ptr(nm)))
+        self._mass = (float(density), bool(rotary), nm)
+
+    def mass_spmv_multi(self, X, masked=False):
+        """Y[j] = M X[j] for k columns in one launch (pl_mass_spmv_multi), M the consistent mass of ``set_mass``; masked:
+        P M P X[j] under the mask of set_bc.  X (k, N, 6) or (k, 6 N); returns (k, N, 6)."""
+        x = self._columns("X", X)
+        y = np.empty_like(x)
+        _check(self._lib, self._lib.pl_mass_spmv_multi(self._h, x.shape[0], int(bool(masked)), _ptr(x), _ptr(y)))
+        return y.reshape(x.shape[0], self.n_nodes, 6)
+
+    def vibration_modes(self, n_modes=4, n_sub=0, rtol=1e-10, max_iter=200000, tol=1e-9, max_outer=200,
+                        raise_on_noconv=True):
+        """The n_modes smallest omega^2 of K phi = omega^2 M phi on the free dofs of set_bc and their modes
+        (pl_vibration_modes): dict with omega2 (n_modes,) ascending, modes (n_modes, N, 6) (phi^T M phi = 1, largest
+        component positive), residual (n_modes,), n_found and outer_iterations; entries beyond n_found are NaN.  n_sub:
+        columns of the subspace iteration (0 = the library's choice); rtol, max_iter: its inner PCG; tol, max_outer: its
+        stopping rule."""
+        n_modes = int(n_modes)
+        om2 = np.empty(max(n_modes, 0), np.float64)
+        modes = np.empty((max(n_modes, 0), self.n_nodes, 6), np.float64)
+        res = np.empty(max(n_modes, 0), np.float64)
+        found, outer = C.c_int32(), C.c_int32()
+        rc = self._lib.pl_vibration_modes(self._h, n_modes, int(n_sub), float(rtol), int(max_iter), float(tol), int(max_outer),
+                                          _ptr(om2), _ptr(modes), _ptr(res), C.byref(found), C.byref(outer))
+        _check(self._lib, rc, allow=() if raise_on_noconv else (PL_ERR_NOCONV,))
+        return {"omega2": om2, "modes": modes, "residual": res, "n_found": found.value, "outer_iterations": outer.value}
+
+    def vibration_modes_sens(self, omega2, modes, weights=None, want_rows=True):
+        """Sensitivities of the omega^2 of ``vibration_modes`` to the strut radii (pl_vibration_modes_sens), one pass over
+        the struts and no solve.  omega2 (n_modes,) and modes (n_modes, N, 6) as ``vibration_modes`` returns them (any
+        scaling; a NaN omega2 marks a mode to skip).  Returns a dict with domega2_dr (n_modes, B) if want_rows and dsum_dr
+        (B,) = weights @ domega2_dr formed on the device if weights is given.  Rows of a repeated frequency are not
+        derivatives one by one; a sum with equal weights over the whole cluster is."""
+        om2 = np.ascontiguousarray(np.asarray(omega2, dtype=np.float64).reshape(-1))
+        k = om2.size
+        phi = np.ascontiguousarray(np.asarray(modes, dtype=np.float64)).reshape(-1)
+        if phi.size != k * 6 * self.n_nodes:
+            raise ValueError(f"modes must have shape ({k}, {self.n_nodes}, 6)")
+        wts = None if weights is None else _f64(np.asarray(weights).reshape(-1), k)
+        rows = np.empty((k, self.n_beams), np.float64) if want_rows else None
+        dsum = np.empty(self.n_beams, np.float64) if wts is not None else None
+        _check(self._lib, self._lib.pl_vibration_modes_sens(self._h, k, _ptr(om2), _ptr(phi), _ptr(wts), _ptr(rows), _ptr(dsum)))
+        out = {}
+        if want_rows:
+            out["domega2_dr"] = rows
+        if wts is not None:
+            out["dsum_dr"] = dsum
+        return out
+
+    def _mass_model(self):
+        if getattr(self, "_mass", None) is None:
+            raise ValueError("call set_mass first")
+        return self._mass
+
+    def mass_spmv_multi_host(self, X, masked=False, fixed=None):
+        """The numpy restatement of ``mass_spmv_multi`` (mass_host.mass_apply) on this handle's geometry, radii and
+        multiplicities; the masked product needs the mask ``fixed`` (N, 6) that was given to set_bc."""
+        from . import mass_host as MH
+        if masked and fixed is None:
+            raise ValueError("the masked product needs the mask given to set_bc")
+        rho, rotary, nm = self._mass_model()
+        x = self._columns("X", X).reshape(-1, self.n_nodes, 6)
+        return MH.mass_apply(self.node_xyz, self.beam_conn, self._radius, rho, x, self._mult, rotary, nm,
+                             fixed if masked else None)
+
+    def mass_matrix_host(self):
+        """The sparse restated M (mass_host.mass_matrix) of this handle's geometry, radii, multiplicities and mass model."""
+        from . import mass_host as MH
+        rho, rotary, nm = self._mass_model()
+        return MH.mass_matrix(self.node_xyz, self.beam_conn, self._radius, rho, self._mult, rotary, nm)
+
+    def vibration_modes_host(self, fixed, n_modes=4, n_sub=0, tol=1e-9, max_outer=200, dense=False):
+        """The scipy restatement of ``vibration_modes`` on this handle's records: mass_host.vibration_modes_subspace (exact
+        solves), or vibration_modes_dense with dense=True.  fixed (N, 6): the mask that was given to set_bc."""
+        from . import geometric_host as GH
+        from . import mass_host as MH
+        K = GH.elastic_matrix(self.records(), self.beam_conn, self.n_nodes)
+        M = self.mass_matrix_host()
+        if dense:
+            return MH.vibration_modes_dense(K, M, fixed, n_modes)
+        return MH.vibration_modes_subspace(K, M, fixed, n_modes, n_sub, tol, max_outer)
+
+    def vibration_modes_sens_host(self, omega2, modes, fixed):
+        """The numpy restatement of ``vibration_modes_sens`` (mass_host.vibration_sensitivity)."""
+        from . import mass_host as MH
+        from . import stress_host as SH
+        rho, rotary, nm = self._mass_model()
+        E, nu, kappa, pen = self._material
+        drec = SH.drecords_dr(self.node_xyz, self.beam_conn, self._radius, self._seg_len, self._seg_nsub, E, nu, kappa, pen,
+                              self._mult)
+        return MH.vibration_sensitivity(self.node_xyz, self.beam_conn, self._radius, rho, drec, fixed, omega2, modes,
+                                        self._mult, rotary, nm)
+
     # -- measurement ------------------------------------------------------------------------------------
     def time_kernel(self, which, reps=20):
         ms = C.c_double()
@@ -918,7 +1022,7 @@ class HipLattice:
 # the reference wraps every hot-path method in @timing.category(..) @timing.timeit; here the
 # C-ABI calls are the hot path: host wall clock per call, plus the device's own HIP-event times (see solve)
 for _name in ("assemble", "assemble_bsr", "get_bsr", "solve", "set_bc", "spmv", "spmv_free", "spmv_bsr", "reactions",
-              "sens", "stress", "stress_pnorm", "buckling", "buckling_pnorm", "energy", "schur", "spmv_multi", "solve_multi", "geom_spmv_multi", "buckling_modes", "buckling_modes_sens", "update_radii", "update_segments", "records"):
+              "sens", "stress", "stress_pnorm", "buckling", "buckling_pnorm", "energy", "schur", "spmv_multi", "solve_multi", "geom_spmv_multi", "buckling_modes", "buckling_modes_sens", "mass_spmv_multi", "vibration_modes", "vibration_modes_sens", "update_radii", "update_segments", "records"):
     _f = getattr(HipLattice, _name, None)
     if _f is not None:
         _f._timing_category = "hip"

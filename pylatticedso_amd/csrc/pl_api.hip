@@ -1,11 +1,14 @@
 // libpylattice_hip.so - the C ABI declared in include/pylattice_hip.h (gfx950 / MI355X).  One translation unit:
 // pl_context.h (handle state) <- pl_ops.h (operator launches) <- pl_assembly.h <- pl_solver.h (+ pl_warm.h, pl_schedule.h) <- this file.
+#include <functional>
+
 #include "pl_solver.h"
 #include "pl_condense.h"
 #include "pl_multi.h"
 #include "pl_stress.h"
 #include "pl_buckling.h"
 #include "pl_geom.h"
+#include "pl_mass.h"
 #include "pl_sensgram.h"
 
 
@@ -2063,19 +2066,40 @@ int pl_geom_spmv_multi(pl_handle h, const double *u, int32_t n_rhs, int masked, 
   return multi_download(h, w, s, w->U.p, y);
 }
 
-int pl_buckling_modes(pl_handle h, const double *u, int32_t n_modes, int32_t n_sub, double rtol, int32_t max_iter, double tol,
-                      int32_t max_outer, double *load_factor, double *modes, double *residual, int32_t *n_found,
-                      int32_t *outer_iterations) {
-  if (!valid(h) || !load_factor || !n_found || !outer_iterations) return fail(PL_ERR_ARG, "pl_buckling_modes: null argument");
+namespace {
+// The pencil G phi = mu K phi of the block subspace iteration: G = sign * A, A the second operator beside K.
+//   pl_buckling_modes:   A = K_g(u), sign = -1, value lambda = 1 / mu, shifted by the most negative Ritz value seen,
+//                        modes K-orthonormal, residual |K phi + lambda K_g phi| / |K phi|
+//   pl_vibration_modes:  A = M,      sign = +1, value omega^2 = 1 / mu, no shift (M is positive definite),
+//                        modes scaled by omega to phi^T M phi = 1, residual |K phi - omega^2 M phi| / |K phi|
+struct Pencil {
+  const char *who;
+  double sign;
+  bool shifted, second_normalised;
+  std::function<int(const MultiShape &, const double *, double *)> apply;     // y = P A x for every column of the shape
+};
+
+// argument checks the two eigen-calls share; n_sub = 0 becomes the library's choice
+int pencil_check(pl_handle h, const char *who, int32_t n_modes, int32_t &n_sub, double rtol, int32_t max_iter, double tol,
+                 int32_t max_outer, const double *value, const int32_t *n_found, const int32_t *outer_iterations) {
+  const std::string w(who);
+  if (!valid(h) || !value || !n_found || !outer_iterations) return fail(PL_ERR_ARG, w + ": null argument");
   if (n_sub == 0) n_sub = std::max(8, (2 * std::max(n_modes, 1) + 3) / 4 * 4);
-  if (n_sub < 4 || n_sub > 32 || n_sub % 4 != 0) return fail(PL_ERR_ARG, "pl_buckling_modes: n_sub must be a multiple of 4 in 4 ... 32 (or 0)");
-  if (n_modes < 1 || n_modes > n_sub / 2) return fail(PL_ERR_ARG, "pl_buckling_modes: n_modes must be 1 ... n_sub / 2");
-  if (!(rtol > 0.0) || max_iter <= 0) return fail(PL_ERR_ARG, "pl_buckling_modes: rtol and max_iter must be positive");
-  if (!(tol > 0.0) || max_outer <= 0) return fail(PL_ERR_ARG, "pl_buckling_modes: tol and max_outer must be positive");
+  if (n_sub < 4 || n_sub > 32 || n_sub % 4 != 0) return fail(PL_ERR_ARG, w + ": n_sub must be a multiple of 4 in 4 ... 32 (or 0)");
+  if (n_modes < 1 || n_modes > n_sub / 2) return fail(PL_ERR_ARG, w + ": n_modes must be 1 ... n_sub / 2");
+  if (!(rtol > 0.0) || max_iter <= 0) return fail(PL_ERR_ARG, w + ": rtol and max_iter must be positive");
+  if (!(tol > 0.0) || max_outer <= 0) return fail(PL_ERR_ARG, w + ": tol and max_outer must be positive");
   if (valid(h) && h->n_per_groups > 0)
-    return fail(PL_ERR_STATE, "pl_buckling_modes: not available with periodic constraints (pl_set_periodic)");
-  GeomWs *g = nullptr;
-  if (int rc = geom_begin(h, "pl_buckling_modes", u, true, &g)) return rc;
+    return fail(PL_ERR_STATE, w + ": not available with periodic constraints (pl_set_periodic)");
+  return PL_OK;
+}
+
+// The n_modes largest mu > 0 of the pencil by block subspace iteration around pcg_solve_multi, value[j] = 1 / mu_j
+// ascending: second operator, solve, Rayleigh-Ritz, combine.  The handle checks are the caller's.
+int pencil_modes(pl_handle h, GeomWs *g, const Pencil &pc, int32_t n_modes, int32_t n_sub, double rtol, int32_t max_iter,
+                 double tol, int32_t max_outer, double *value, double *modes, double *residual, int32_t *n_found,
+                 int32_t *outer_iterations) {
+  const std::string who(pc.who);
   const int64_t N = h->N, n6 = N * 6;
   const MultiShape s = multi_shape(h, n_sub);     // KB = 4, ncol = n_sub
   const int n = s.ncol;
@@ -2100,18 +2124,18 @@ int pl_buckling_modes(pl_handle h, const double *u, int32_t n_modes, int32_t n_s
   double mu_low = 0.0, ztol = 0.0, ms_solve = 0.0;
   int rank = 0, outer = 0;
   bool converged = false;
-  // Rayleigh-Ritz on span(Y) with products that are applied: X <- Y C, K X <- (K Y) C, K_g X <- (K_g Y) C
+  // Rayleigh-Ritz on span(Y) with products that are applied: X <- Y C, K X <- (K Y) C, A X <- (A Y) C
   auto ritz = [&]() -> int {
     if (int rc = launch_spmv_multi(h, s, h->fixedbits.p, g->Y.p, g->KY.p, true, nullptr)) return rc;
-    if (int rc = launch_geom_multi(h, g, s, g->Y.p, g->GY.p, true)) return rc;
+    if (int rc = pc.apply(s, g->Y.p, g->GY.p)) return rc;
     if (int rc = launch_gram(h, g, s, nchunk, g->Y.p, g->KY.p, g->M.p)) return rc;
     if (int rc = launch_gram(h, g, s, nchunk, g->Y.p, g->GY.p, g->M.p + (size_t)n * n)) return rc;
     PL_HIP(hipMemcpyAsync(Mh.data(), g->M.p, Mh.size() * sizeof(double), hipMemcpyDeviceToHost, h->stream));
     PL_HIP(hipStreamSynchronize(h->stream));
     for (double v : Mh)
-      if (!std::isfinite(v)) return fail(PL_ERR_NAN, "pl_buckling_modes: NaN/Inf in a projected matrix");
+      if (!std::isfinite(v)) return fail(PL_ERR_NAN, who + ": NaN/Inf in a projected matrix");
     std::vector<double> Km(Mh.begin(), Mh.begin() + (size_t)n * n), Gm((size_t)n * n);
-    for (size_t q = 0; q < Gm.size(); ++q) Gm[q] = -Mh[(size_t)n * n + q];      // G = -K_g
+    for (size_t q = 0; q < Gm.size(); ++q) Gm[q] = pc.sign * Mh[(size_t)n * n + q];      // G = sign A
     rank = ritz_host(n, Km, Gm, mu, Cm);
     PL_HIP(hipMemcpyAsync(g->C.p, Cm.data(), Cm.size() * sizeof(double), hipMemcpyHostToDevice, h->stream));
     PL_HIP(hipStreamSynchronize(h->stream));     // (Cm is pageable host memory)
@@ -2129,13 +2153,13 @@ int pl_buckling_modes(pl_handle h, const double *u, int32_t n_modes, int32_t n_s
   if (int rc = ritz()) return rc;                 // K-orthonormalises the start vectors
   while (rank > 0) {
     if (outer == max_outer) break;
-    const double sigma = std::max(0.0, -mu_low);
-    // Y = K^-1 (G X) + sigma X: one multi-column solve with K_g X as loads, W = K^-1 K_g X = -K^-1 G X
+    const double sigma = pc.shifted ? std::max(0.0, -mu_low) : 0.0;
+    // Y = K^-1 (G X) + sigma X: one multi-column solve with A X as loads, W = K^-1 A X = sign K^-1 G X
     const auto t0 = std::chrono::steady_clock::now();
     if (int rc = pcg_solve_multi(h, w, s, h->fixedbits.p, g->GX.p, rtol, max_iter, status.data())) return rc;
     ms_solve += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
     hipLaunchKernelGGL(pl::k_multi_axpby, dim3(grid_stream((int64_t)s.ncb * s.stride / 2)), dim3(pl::kBlock), 0, h->stream,
-                       (int64_t)s.ncb * s.stride / 2, -1.0, (const double *)w->U.p, sigma, (const double *)g->X.p, g->Y.p);
+                       (int64_t)s.ncb * s.stride / 2, pc.sign, (const double *)w->U.p, sigma, (const double *)g->X.p, g->Y.p);
     PL_HIP(hipGetLastError());
     if (int rc = ritz()) return rc;
     ++outer;
@@ -2148,13 +2172,13 @@ int pl_buckling_modes(pl_handle h, const double *u, int32_t n_modes, int32_t n_s
     }
     if (change < tol) { converged = true; break; }
   }
-  if (rank == 0) converged = true;                // G vanishes on the free dofs: no factor exists
+  if (rank == 0) converged = true;                // G vanishes on the free dofs: no value exists
   int found = 0;
   while (found < n_modes && cur[found] > 0.0) ++found;
   *n_found = found;
   *outer_iterations = outer;
   const double nan = std::numeric_limits<double>::quiet_NaN();
-  for (int j = 0; j < n_modes; ++j) load_factor[j] = j < found ? 1.0 / cur[j] : nan;
+  for (int j = 0; j < n_modes; ++j) value[j] = j < found ? 1.0 / cur[j] : nan;
   if (residual)
     for (int j = 0; j < n_modes; ++j) residual[j] = nan;
   if (modes) std::fill(modes, modes + (size_t)n_modes * n6, nan);
@@ -2175,7 +2199,7 @@ int pl_buckling_modes(pl_handle h, const double *u, int32_t n_modes, int32_t n_s
       if (int rc = multi_download(h, w, sd, g->GX.p, Gp.data())) return rc;
       for (int j = 0; j < found; ++j) {
         double rr = 0.0, kk = 0.0;
-        const double lam = load_factor[j];
+        const double lam = -pc.sign * value[j];      // K phi - value G phi
         for (int64_t e = 0; e < n6; ++e) {
           const double k = Kp[(size_t)j * n6 + e], r = k + lam * Gp[(size_t)j * n6 + e];
           rr += r * r;
@@ -2192,20 +2216,40 @@ int pl_buckling_modes(pl_handle h, const double *u, int32_t n_modes, int32_t n_s
           if (std::fabs(p[e]) > std::fabs(p[big])) big = e;
         if (p[big] < 0.0)
           for (int64_t e = 0; e < n6; ++e) p[e] = -p[e];
+        if (pc.second_normalised) {               // phi^T K phi = 1 and phi^T G phi = mu: scale by 1 / sqrt(mu)
+          const double sc = std::sqrt(value[j]);
+          for (int64_t e = 0; e < n6; ++e) p[e] *= sc;
+        }
       }
   }
   if (timing) {
     PL_HIP(hipStreamSynchronize(h->stream));
     const double ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_begin).count();
-    std::fprintf(stderr, "[pl_buckling_modes] %-28s %10.4f ms\n", "whole_call_host_clock", ms);
-    std::fprintf(stderr, "[pl_buckling_modes] %-28s %10d\n", "outer_steps", outer);
+    std::fprintf(stderr, "[%s] %-28s %10.4f ms\n", pc.who, "whole_call_host_clock", ms);
+    std::fprintf(stderr, "[%s] %-28s %10d\n", pc.who, "outer_steps", outer);
     if (outer > 0) {
-      std::fprintf(stderr, "[pl_buckling_modes] %-28s %10.4f ms\n", "outer_step_mean_host_clock", ms / outer);
-      std::fprintf(stderr, "[pl_buckling_modes] %-28s %10.4f ms\n", "inner_solve_mean_host_clock", ms_solve / outer);
+      std::fprintf(stderr, "[%s] %-28s %10.4f ms\n", pc.who, "outer_step_mean_host_clock", ms / outer);
+      std::fprintf(stderr, "[%s] %-28s %10.4f ms\n", pc.who, "inner_solve_mean_host_clock", ms_solve / outer);
     }
   }
-  if (!converged) return fail(PL_ERR_NOCONV, "pl_buckling_modes: max_outer reached before the Ritz values settled");
+  if (!converged) return fail(PL_ERR_NOCONV, who + ": max_outer reached before the Ritz values settled");
   return PL_OK;
+}
+}  // namespace
+
+int pl_buckling_modes(pl_handle h, const double *u, int32_t n_modes, int32_t n_sub, double rtol, int32_t max_iter, double tol,
+                      int32_t max_outer, double *load_factor, double *modes, double *residual, int32_t *n_found,
+                      int32_t *outer_iterations) {
+  if (int rc = pencil_check(h, "pl_buckling_modes", n_modes, n_sub, rtol, max_iter, tol, max_outer, load_factor, n_found,
+                            outer_iterations))
+    return rc;
+  GeomWs *g = nullptr;
+  if (int rc = geom_begin(h, "pl_buckling_modes", u, true, &g)) return rc;
+  const Pencil pc = {"pl_buckling_modes", -1.0, true, false, [h, g](const MultiShape &s, const double *x, double *y) {
+                       return launch_geom_multi(h, g, s, x, y, true);
+                     }};
+  return pencil_modes(h, g, pc, n_modes, n_sub, rtol, max_iter, tol, max_outer, load_factor, modes, residual, n_found,
+                      outer_iterations);
 }
 
 int pl_buckling_modes_sens(pl_handle h, const double *u, int32_t n_modes, const double *load_factor, const double *modes,
@@ -2316,6 +2360,167 @@ int pl_buckling_modes_sens(pl_handle h, const double *u, int32_t n_modes, const 
   if (bad) return fail(PL_ERR_NAN, "pl_buckling_modes_sens: NaN/Inf in a residual norm of the adjoint solve");
   if (missed)
     return fail(PL_ERR_NOCONV, "pl_buckling_modes_sens: " + std::to_string(missed) + " adjoint column(s) did not reach rtol within max_iter");
+  return PL_OK;
+}
+
+// ---- natural frequencies (pl_mass.h) -----------------------------------------------------------------------------------
+namespace {
+// what the three mass calls share after their argument checks: the handle checks and the mass records of the current radii
+int mass_begin(pl_handle h, const char *who, bool need_bc, MassWs **m) {
+  if (int rc = multi_check_handle(h, who, need_bc)) return rc;
+  if (h->n_per_groups > 0)
+    return fail(PL_ERR_STATE, std::string(who) + ": not available with periodic constraints (pl_set_periodic)");
+  if (!h->mass_ws) return fail(PL_ERR_STATE, std::string(who) + ": call pl_set_mass first");
+  PL_HIP(hipSetDevice(h->opt.device));
+  *m = static_cast<MassWs *>(h->mass_ws.get());
+  return launch_mass_records(h, *m);
+}
+}  // namespace
+
+int pl_set_mass(pl_handle h, double density, int32_t rotary, const double *node_mass) {
+  if (!valid(h)) return fail(PL_ERR_ARG, "pl_set_mass: null handle");
+  if (!(density > 0.0) || !std::isfinite(density)) return fail(PL_ERR_ARG, "pl_set_mass: density must be positive and finite");
+  if (rotary != 0 && rotary != 1) return fail(PL_ERR_ARG, "pl_set_mass: rotary must be 0 or 1");
+  if (h->opkind != 0) return fail(PL_ERR_STATE, "pl_set_mass: not available on a DDM handle");
+  if (h->dist.active || h->opt.grid_nodes > 0)
+    return fail(PL_ERR_STATE, "pl_set_mass: single-GPU handles only (this one belongs to a multi-rank run)");
+  if (node_mass)
+    for (int64_t i = 0; i < h->N; ++i)
+      if (!(node_mass[i] >= 0.0) || !std::isfinite(node_mass[i]))
+        return fail(PL_ERR_ARG, "pl_set_mass: node_mass must be finite and not negative");
+  PL_HIP(hipSetDevice(h->opt.device));
+  if (!h->mass_ws) h->mass_ws = std::make_shared<MassWs>();
+  MassWs *m = static_cast<MassWs *>(h->mass_ws.get());
+  m->density = density;
+  m->rotary = rotary;
+  m->have_nm = node_mass != nullptr;
+  if (node_mass) {
+    std::vector<double> nm((size_t)h->N);
+    for (int64_t i = 0; i < h->N; ++i) nm[(size_t)i] = node_mass[h->perm[i]];
+    if (m->node_mass.n < (size_t)h->N) PL_HIP(m->node_mass.alloc((size_t)h->N));
+    PL_HIP(hipMemcpy(m->node_mass.p, nm.data(), (size_t)h->N * sizeof(double), hipMemcpyHostToDevice));
+  }
+  return PL_OK;
+}
+
+int pl_mass_spmv_multi(pl_handle h, int32_t n_rhs, int masked, const double *x, double *y) {
+  if (!valid(h) || !x || !y) return fail(PL_ERR_ARG, "pl_mass_spmv_multi: null argument");
+  if (n_rhs < 1 || n_rhs > PL_MULTI_MAX) return fail(PL_ERR_ARG, "pl_mass_spmv_multi: n_rhs must be 1 ... PL_MULTI_MAX");
+  MassWs *m = nullptr;
+  if (int rc = mass_begin(h, "pl_mass_spmv_multi", masked != 0, &m)) return rc;
+  const MultiShape s = multi_shape(h, n_rhs);
+  MultiWs *w = nullptr;
+  if (int rc = multi_ws(h, s, false, &w)) return rc;
+  if (int rc = multi_upload(h, w, s, x, w->F.p, masked ? -1 : 0)) return rc;
+  const bool timing = std::getenv("PL_TIMING") != nullptr;
+  if (timing) PL_HIP(hipEventRecord(h->ev0, h->stream));
+  if (int rc = launch_mass_multi(h, m, s, w->F.p, w->U.p, masked != 0)) return rc;
+  if (timing) {
+    PL_HIP(hipEventRecord(h->ev1, h->stream));
+    PL_HIP(hipEventSynchronize(h->ev1));
+    float ms = 0.f;
+    PL_HIP(hipEventElapsedTime(&ms, h->ev0, h->ev1));
+    std::fprintf(stderr, "[pl_mass_spmv_multi] %-28s %10.4f ms\n", "kernel_hip_event", (double)ms);
+  }
+  return multi_download(h, w, s, w->U.p, y);
+}
+
+int pl_vibration_modes(pl_handle h, int32_t n_modes, int32_t n_sub, double rtol, int32_t max_iter, double tol,
+                       int32_t max_outer, double *omega2, double *modes, double *residual, int32_t *n_found,
+                       int32_t *outer_iterations) {
+  if (int rc = pencil_check(h, "pl_vibration_modes", n_modes, n_sub, rtol, max_iter, tol, max_outer, omega2, n_found,
+                            outer_iterations))
+    return rc;
+  MassWs *m = nullptr;
+  if (int rc = mass_begin(h, "pl_vibration_modes", true, &m)) return rc;
+  GeomWs *g = nullptr;
+  if (int rc = geom_ws(h, &g)) return rc;
+  const Pencil pc = {"pl_vibration_modes", 1.0, false, true, [h, m](const MultiShape &s, const double *x, double *y) {
+                       return launch_mass_multi(h, m, s, x, y, true);
+                     }};
+  return pencil_modes(h, g, pc, n_modes, n_sub, rtol, max_iter, tol, max_outer, omega2, modes, residual, n_found,
+                      outer_iterations);
+}
+
+int pl_vibration_modes_sens(pl_handle h, int32_t n_modes, const double *omega2, const double *modes, const double *weights,
+                            double *domega2_dr, double *dsum_dr) {
+  const char *who = "pl_vibration_modes_sens";
+  if (!valid(h) || !omega2 || !modes) return fail(PL_ERR_ARG, "pl_vibration_modes_sens: null argument");
+  if (n_modes < 1 || n_modes > 16) return fail(PL_ERR_ARG, "pl_vibration_modes_sens: n_modes must be 1 ... 16");
+  if (!domega2_dr && !dsum_dr) return fail(PL_ERR_ARG, "pl_vibration_modes_sens: every output pointer is NULL");
+  if (dsum_dr && !weights) return fail(PL_ERR_ARG, "pl_vibration_modes_sens: dsum_dr needs weights");
+  MassWs *m = nullptr;
+  if (int rc = mass_begin(h, who, true, &m)) return rc;
+  GeomWs *g = nullptr;
+  if (int rc = geom_ws(h, &g)) return rc;
+  const int64_t B = h->B, n6 = h->N * 6;
+  const double nan = std::numeric_limits<double>::quiet_NaN();
+  // a mode whose omega^2 is NaN (beyond n_found of pl_vibration_modes) is skipped: the live ones are the columns
+  std::vector<int> live;
+  for (int j = 0; j < n_modes; ++j)
+    if (!std::isnan(omega2[j])) live.push_back(j);
+  const int nl = (int)live.size();
+  if (domega2_dr) std::fill(domega2_dr, domega2_dr + (size_t)n_modes * B, nan);
+  if (nl == 0) {
+    if (dsum_dr) std::fill(dsum_dr, dsum_dr + B, 0.0);
+    return PL_OK;
+  }
+  std::vector<double> packed;
+  const double *phi_host = modes;
+  if (nl < n_modes) {
+    packed.resize((size_t)nl * n6);
+    for (int j = 0; j < nl; ++j) std::memcpy(&packed[(size_t)j * n6], modes + (size_t)live[j] * n6, (size_t)n6 * sizeof(double));
+    phi_host = packed.data();
+  }
+  const MultiShape s = multi_shape(h, nl);
+  MultiWs *w = nullptr;
+  if (int rc = multi_ws(h, s, false, &w)) return rc;
+  const unsigned nchunk = std::min(grid_stream(n6), 512u);
+  if (int rc = geom_ws_modes(h, g, s, nchunk)) return rc;
+  if (g->sdlam.n < (size_t)(nl + 1) * B) PL_HIP(g->sdlam.alloc((size_t)(nl + 1) * B));
+  if (!g->scoef.p) PL_HIP(g->scoef.alloc((size_t)2 * PL_MULTI_MAX));
+  std::vector<double> coef((size_t)2 * s.ncol, 0.0);
+  for (int j = 0; j < nl; ++j) {
+    coef[(size_t)j] = omega2[live[j]];
+    coef[(size_t)s.ncol + j] = weights ? weights[live[j]] : 0.0;
+  }
+  PL_HIP(hipMemcpyAsync(g->scoef.p, coef.data(), coef.size() * sizeof(double), hipMemcpyHostToDevice, h->stream));
+  PL_HIP(hipStreamSynchronize(h->stream));        // (coef is pageable host memory)
+  if (int rc = multi_upload(h, w, s, phi_host, g->X.p, -1)) return rc;      // the modes, zero on the fixed dofs
+  // PL_TIMING: HIP-event time of every stage ("[pl_vibration_modes_sens] <stage> <ms> ms")
+  const bool timing = std::getenv("PL_TIMING") != nullptr;
+  const char *stage_name[] = {"M phi and mm (gram)", "k_mass_sens"};
+  hipEvent_t ev[3] = {};
+  int n_ev = 0;
+  auto mark = [&]() {
+    if (timing && hipEventCreate(&ev[n_ev]) == hipSuccess) (void)hipEventRecord(ev[n_ev++], h->stream);
+  };
+  int rc = PL_OK;
+  do {
+    mark();
+    if ((rc = launch_mass_multi(h, m, s, g->X.p, g->GX.p, true))) break;
+    if ((rc = launch_gram(h, g, s, nchunk, g->X.p, g->GX.p, g->M.p))) break;         // mm_i = phi_i^T M phi_i on its diagonal
+    mark();
+    if ((rc = launch_mass_sens(h, g, m, s, g->X.p, domega2_dr ? g->sdlam.p : (double *)nullptr,
+                               dsum_dr ? g->sdlam.p + (size_t)nl * B : (double *)nullptr)))
+      break;
+    mark();
+  } while (false);
+  if (timing && rc == PL_OK) {
+    (void)hipStreamSynchronize(h->stream);
+    for (int i = 0; i + 1 < n_ev; ++i) {
+      float ms = 0.f;
+      if (hipEventElapsedTime(&ms, ev[i], ev[i + 1]) == hipSuccess)
+        std::fprintf(stderr, "[pl_vibration_modes_sens] %-28s %10.4f ms\n", stage_name[i], (double)ms);
+    }
+  }
+  for (int i = 0; i < n_ev; ++i) (void)hipEventDestroy(ev[i]);
+  if (rc) return rc;
+  if (domega2_dr)
+    for (int j = 0; j < nl; ++j)
+      if ((rc = download_struts(h, g->sdlam.p + (size_t)j * B, domega2_dr + (size_t)live[j] * B))) return rc;
+  if (dsum_dr)
+    if ((rc = download_struts(h, g->sdlam.p + (size_t)nl * B, dsum_dr))) return rc;
   return PL_OK;
 }
 

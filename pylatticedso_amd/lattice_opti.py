@@ -66,6 +66,9 @@ class LatticeOpti(LatticeSim):
         if self._ddm_mode and "global_buckling" in (info.get("constraints") or {}):
             raise NotImplementedError('the "global_buckling" constraint needs simulation_type "FEM": the geometric stiffness of '
                                       "the recovered interiors of DDM cells is not implemented")
+        if self._ddm_mode and "frequency" in (info.get("constraints") or {}):
+            raise NotImplementedError('the "frequency" constraint needs simulation_type "FEM": the mass of the recovered '
+                                      "interiors of DDM cells is not implemented")
         comp = ((params.get("simulation_parameters", {}).get("DDM") or {}).get("schur_complement_computation") or {})
         if ddm_gradient is None:
             ddm_gradient = comp.get("gradient", "finite_difference") if self._ddm_mode else "finite_difference"
@@ -109,6 +112,9 @@ class LatticeOpti(LatticeSim):
         self._last_global_buckling = None
         if "global_buckling" in self.constraints_dict:
             self._history["min_load_factor"] = []
+        self._last_frequency = None
+        if "frequency" in self.constraints_dict:
+            self._history["min_frequency"] = []
         self._set_number_parameters_optimization()
         # strut -> (cell, type) of the LAST cell that holds it: Cell.change_beam_radius (cell.py:896-917) is called
         # cell after cell, so a strut shared by several cells ends with the last one's radius
@@ -724,6 +730,39 @@ class LatticeOpti(LatticeSim):
         _, _, dJ_dr = self.global_buckling_aggregate(want_grad=True)
         return self._global_buckling_settings()[0] * self._strut_gradient_to_parameters(dJ_dr)
 
+    # -- frequency constraint (FEM mode): p-norm of 1 / omega_i^2, pl_vibration_modes + pl_vibration_modes_sens -------------------
+    def _frequency_settings(self):
+        c = self.constraints_dict["frequency"]
+        kw = {k: c[k] for k in ("n_sub", "rtol", "max_iter", "tol", "max_outer") if k in c}
+        mass = dict(density=float(c.get("density", 1.0)), rotary=bool(c.get("rotary", True)), node_mass=c.get("node_mass", None))
+        return float(c["value"]), int(c.get("n_modes", 4)), float(c.get("p", 8)), mass, kw
+
+    def frequency_aggregate(self, want_grad=False):
+        """(J_p, f_1 in Hz, dJ/dr_b or None) of the current design: J_p = (sum_i (omega_i^2)^-p)^(1/p) over the constraint's
+        n_modes lowest natural frequencies (J_p >= 1 / omega_1^2).  dJ/dr_b is the device's weighted sum of the rows of
+        pl_vibration_modes_sens; it needs no adjoint solve."""
+        _, n_modes, p, mass, kw = self._frequency_settings()
+        self.natural_frequencies(n_modes, **mass, **kw)
+        out = self.natural_frequency_sensitivity(p, want_rows=False) if want_grad else None
+        J = out["aggregate"] if want_grad else GH.load_factor_aggregate(self.vibration_omega2, p)[0]
+        self._last_frequency = (J, float(self.natural_frequencies_hz[0]))
+        return J, self._last_frequency[1], (out["dJ_dr"] if want_grad else None)
+
+    def frequency_constraint(self, r):
+        """(2 pi f_min)^2 J_p - 1 (<= 0 when feasible: J_p >= 1 / omega_1^2, so f_1 >= f_min then)."""
+        self.set_optimization_parameters(r)
+        if not self._sim_is_current:
+            self._simulate_lattice_equilibrium()
+        return (2.0 * np.pi * self._frequency_settings()[0]) ** 2 * self.frequency_aggregate()[0] - 1.0
+
+    def frequency_constraint_gradient(self, r):
+        """d(frequency_constraint)/d(theta): (2 pi f_min)^2 dJ/dr_b through _strut_gradient_to_parameters."""
+        self.set_optimization_parameters(r)
+        if not self._sim_is_current:
+            self._simulate_lattice_equilibrium()
+        _, _, dJ_dr = self.frequency_aggregate(want_grad=True)
+        return (2.0 * np.pi * self._frequency_settings()[0]) ** 2 * self._strut_gradient_to_parameters(dJ_dr)
+
     # -- driver (SciPy SLSQP, as the reference) ---------------------------------------------------------------------
     def _initialize_optimization_solver(self):
         from scipy.optimize import Bounds
@@ -755,6 +794,8 @@ class LatticeOpti(LatticeSim):
         if "min_load_factor" in self._history:
             self._history["min_load_factor"].append(None if self._last_global_buckling is None
                                                     else self._last_global_buckling[1])
+        if "min_frequency" in self._history:
+            self._history["min_frequency"].append(None if self._last_frequency is None else self._last_frequency[1])
         self._history["parameters"].append(list(map(float, r)))
         self._history["timestamp"].append(time.time())
 
@@ -780,6 +821,9 @@ class LatticeOpti(LatticeSim):
         if "global_buckling" in self.constraints_dict:
             jac = {"jac": self.global_buckling_constraint_gradient} if self.enable_gradient_computing else {}
             self.constraints.append(NonlinearConstraint(self.global_buckling_constraint, -np.inf, 0.0, **jac))
+        if "frequency" in self.constraints_dict:
+            jac = {"jac": self.frequency_constraint_gradient} if self.enable_gradient_computing else {}
+            self.constraints.append(NonlinearConstraint(self.frequency_constraint, -np.inf, 0.0, **jac))
         kw = dict(fun=self.objective, x0=self.initial_parameters, method="SLSQP", bounds=self.bounds,
                   constraints=self.constraints, callback=self.callback_function,
                   options={"maxiter": self.optim_max_iteration, "ftol": self.optim_ftol, "disp": self.optim_disp,

@@ -695,6 +695,43 @@ class LatticeSim(LatticeViews):
             res["dlam_dr"] = out["dlam_dr"]
         return res
 
+    def natural_frequencies(self, n_modes=4, density=1.0, rotary=True, node_mass=None, **kw):
+        """Natural frequencies of the lattice under the supports of the last solve_FEM_FenicsX, on the device
+        (pl_set_mass, pl_vibration_modes): the n_modes smallest omega^2 of K phi = omega^2 M phi and their modes, M the
+        consistent mass of the struts at ``density`` (every strut one element between its two joints, its plain radius over
+        the whole length; ``rotary``: with the rotary inertia of bending), plus translational point masses node_mass
+        (n_nodes,).  The loads play no part.  Keyword arguments (n_sub, rtol, max_iter, tol, max_outer) go to
+        ``HipLattice.vibration_modes``.  Sets ``natural_frequencies_hz`` = sqrt(omega^2) / 2 pi and ``vibration_omega2``
+        (n_modes,), ``vibration_modes`` (n_modes, n_nodes, 6) with phi^T M phi = 1 - NaN beyond the modes that exist - and
+        returns the device call's dict with ``frequency`` (Hz) added."""
+        if self._device is None or getattr(self, "_compat_rows", False):
+            raise RuntimeError("natural_frequencies needs a solve_FEM_FenicsX on this lattice first (default strut model; "
+                               "the reference_compat model has no device mass)")
+        self._device.set_mass(density, rotary, node_mass)
+        out = self._device.vibration_modes(n_modes, **kw)
+        out["frequency"] = np.sqrt(out["omega2"]) / (2.0 * np.pi)
+        self.natural_frequencies_hz = out["frequency"]
+        self.vibration_omega2 = out["omega2"]
+        self.vibration_modes = out["modes"]
+        return out
+
+    def natural_frequency_sensitivity(self, p=8, want_rows=True):
+        """Derivatives of the omega^2 of the last ``natural_frequencies`` to the strut radii, on the device
+        (pl_vibration_modes_sens: one pass over the struts, no solve), and of their aggregate
+        J = (sum_i (omega_i^2)^-p)^(1/p) >= 1 / omega_1^2 (geometric_host.load_factor_aggregate): dict with aggregate, dJ_dr
+        (n_beams,) - the device's weighted sum with the weights dJ/d(omega_i^2) - and domega2_dr (n_modes, n_beams)
+        (want_rows=False leaves it out), at fixed segment geometry.  The rows of a repeated frequency are not derivatives one
+        by one; J weighs equal frequencies equally, so dJ_dr is - as long as the aggregate holds whole clusters."""
+        if getattr(self, "vibration_omega2", None) is None or self._device is None:
+            raise RuntimeError("natural_frequency_sensitivity needs a natural_frequencies on this lattice first")
+        from .geometric_host import load_factor_aggregate
+        J, wts = load_factor_aggregate(self.vibration_omega2, p)
+        out = self._device.vibration_modes_sens(self.vibration_omega2, self.vibration_modes, weights=wts, want_rows=want_rows)
+        res = {"aggregate": J, "dJ_dr": out["dsum_dr"]}
+        if want_rows:
+            res["domega2_dr"] = out["domega2_dr"]
+        return res
+
     # ------------------------------------------------------------------------------------------------
     # Domain decomposition (lattice_sim.py:846-919, 1111-1252)
     # ------------------------------------------------------------------------------------------------
