@@ -526,6 +526,32 @@ int pl_vibration_modes_sens(pl_handle h, int32_t n_modes, const double *omega2 /
                             double *domega2_dr /*[n_modes][B] or NULL*/,
                             double *dsum_dr /*[B] or NULL: sum_i weights[i] domega2_i/dr_b, formed on the device*/);
 
+/* ---- transient response (csrc/pl_dyn.h) -------------------------------------------------------------
+ * M a + C v + K u = f(t) on the free dofs of pl_set_bc, the supports held at zero: K the strut operator, M the consistent
+ * mass of pl_set_mass, C = ray_m M + ray_k K (Rayleigh damping), integrated by the implicit Newmark scheme (beta, gamma) in
+ * acceleration form.  Both calls: PL_ERR_STATE on DDM and multi-rank handles, before pl_set_mass, before pl_assemble and with
+ * pl_set_periodic constraints.  The handle's single-column state is left untouched. */
+/* y_j = c_K K x_j + c_M M x_j in ONE gather (masked != 0: P (...) P x_j, needs pl_set_bc), j < n_rhs <= PL_MULTI_MAX; x, y:
+ * [n_rhs][6N] host arrays.  This is the operator of the time step's solve. */
+int pl_dyn_spmv_multi(pl_handle h, double c_K, double c_M, int32_t n_rhs, int masked, const double *x, double *y);
+/* n_steps steps of size dt from (u0, v0) under the load f_n = sum_p amp[n][p] pattern[p], n = 0 ... n_steps.  a_0 solves
+ * M a_0 = f_0 - K u_0 - C v_0; every step solves (M (1 + gamma dt ray_m) + K (beta dt^2 + gamma dt ray_k)) a_{n+1} =
+ * f_{n+1} - K ut - C vt for the predictors ut, vt, one column, zero start, Jacobi PCG to rtol within max_iter.  u0, v0 and the
+ * patterns are read with the fixed dofs zeroed.  Row n of the outputs is time n dt: probe holds u, v, a of the probe_nodes
+ * (caller numbering), energy the kinetic energy 1/2 v.M v, the strain energy 1/2 u.K u and the external work by the trapezoid
+ * W_{n+1} = W_n + 1/2 (f_n + f_{n+1}).(u_{n+1} - u_n), snaps[k] is u of row (k + 1) snap_every, state the last u, v, a (a
+ * later call started from state's u and v continues the history), iters[n] the PCG iterations of row n's solve.
+ * PL_ERR_ARG: dt <= 0, n_steps < 1, gamma < 1/2, beta < (1/2 + gamma)^2 / 4 (unconditionally stable schemes only), a negative
+ * Rayleigh coefficient, n_pat > 4, a probe index out of range.  PL_ERR_STATE also before pl_set_bc and when the handle holds
+ * non-zero prescribed displacements.  PL_ERR_NOCONV names the step whose solve missed rtol; the outputs are then not written. */
+int pl_transient(pl_handle h, int32_t n_steps, double dt, double beta, double gamma, double ray_m, double ray_k,
+                 int32_t n_pat, const double *pattern /*[n_pat][6N] or NULL*/, const double *amp /*[n_steps+1][n_pat]*/,
+                 const double *u0, const double *v0 /*[6N] or NULL = 0*/, double rtol, int32_t max_iter,
+                 int32_t n_probe, const int32_t *probe_nodes, double *probe /*[n_steps+1][3][n_probe][6]: u, v, a*/,
+                 double *energy /*[n_steps+1][3]: kinetic, strain, external work*/,
+                 int32_t snap_every, double *snaps /*[n_steps/snap_every][6N] u, or NULL*/,
+                 double *state /*[3][6N]: final u, v, a, or NULL*/, int32_t *iters /*[n_steps+1] or NULL*/);
+
 /* The same condensation, exact and batched, without a handle: n_inst small lattices of ONE topology (a unit cell at
  * several radius sets - the exact DDM mode, Schur datasets), each condensed by a dense Cholesky of K_II in one workgroup
  * of a single launch.  Material, pen_coef and device come from o (stamped by pl_default_opts; the solver fields are

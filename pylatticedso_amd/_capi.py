@@ -25,6 +25,7 @@ EXPORTS = ["pl_default_opts", "pl_opts_size", "pl_stats_size", "pl_abi_version",
            "pl_stress", "pl_stress_pnorm", "pl_buckling", "pl_buckling_pnorm",
            "pl_spmv_multi", "pl_solve_multi", "pl_schur_block", "pl_geom_spmv_multi", "pl_buckling_modes", "pl_buckling_modes_sens",
            "pl_set_mass", "pl_mass_spmv_multi", "pl_vibration_modes", "pl_vibration_modes_sens",
+           "pl_dyn_spmv_multi", "pl_transient",
            "pl_schur_cells", "pl_cells_recover", "pl_get_records", "pl_debug_partition", "pl_time_kernel", "pl_algorithmic_bytes", "pl_node_words_info", "pl_forget_history", "pl_debug_spd_solve", "pl_dist_unique_id_bytes",
            "pl_dist_unique_id", "pl_dist_loopback_id", "pl_dist_abort", "pl_dist_init", "pl_dist_set_peers", "pl_generate_lattice", "pl_lattice_fetch",
            "pl_lattice_free", "pl_penalize", "pl_boundary_index", "pl_boundary_index_rows"]
@@ -103,6 +104,8 @@ def load_library(path: str | None = None):
            "pl_set_mass": [V, D, I32, V], "pl_mass_spmv_multi": [V, I32, I32, V, V],
            "pl_vibration_modes": [V, I32, I32, D, I32, D, I32, V, V, V, V, V],
            "pl_vibration_modes_sens": [V, I32, V, V, V, V, V],
+           "pl_dyn_spmv_multi": [V, D, D, I32, I32, V, V],
+           "pl_transient": [V, I32, D, D, D, D, D, I32, V, V, V, V, D, I32, I32, V, V, V, I32, V, V, V],
            "pl_schur_cells": [V, I32, I32, I32, V, I32, V, V, V, V, V, V, V],
            "pl_cells_recover": [V, I32, I32, I32, V, I32, V, V, V, V, V, V, V, V, V, V, V],
            "pl_get_records": [V, V], "pl_debug_partition": [V, V, V, V, V], "pl_time_kernel": [V, I32, I32, V],
@@ -952,6 +955,67 @@ class HipLattice:
         return MH.vibration_sensitivity(self.node_xyz, self.beam_conn, self._radius, rho, drec, fixed, omega2, modes,
                                         self._mult, rotary, nm)
 
+    # -- transient response -------------------------------------------------------------------------------
+    def dyn_spmv_multi(self, c_K, c_M, X, masked=False):
+        """Y[j] = c_K K X[j] + c_M M X[j] for k columns in one fused gather (pl_dyn_spmv_multi), M the consistent mass of
+        ``set_mass``; masked: P (...) P X[j] under the mask of set_bc.  X (k, N, 6) or (k, 6 N); returns (k, N, 6)."""
+        x = self._columns("X", X)
+        y = np.empty_like(x)
+        _check(self._lib, self._lib.pl_dyn_spmv_multi(self._h, float(c_K), float(c_M), x.shape[0], int(bool(masked)), _ptr(x),
+                                                      _ptr(y)))
+        return y.reshape(x.shape[0], self.n_nodes, 6)
+
+    def transient(self, dt, n_steps, patterns=None, amp=None, u0=None, v0=None, beta=0.25, gamma=0.5, ray_m=0.0, ray_k=0.0,
+                  rtol=1e-10, max_iter=100000, probes=None, snap_every=0, want_state=True):
+        """n_steps implicit Newmark steps of M a + (ray_m M + ray_k K) v + K u = amp[n] @ patterns on the free dofs of
+        set_bc (pl_transient).  patterns (n_pat, N, 6), n_pat <= 4, amp (n_steps + 1, n_pat); u0, v0 (N, 6) or None = 0;
+        probes: node indices.  Returns a dict: time (n_steps + 1,), probe (n_steps + 1, 3, n_probe, 6) = u, v, a of the
+        probed nodes, energy (n_steps + 1, 3) = kinetic, strain, external work, iters (n_steps + 1,), state (3, N, 6) = the
+        last u, v, a, and snaps (n_steps // snap_every, N, 6) if snap_every > 0."""
+        n_steps, n6 = int(n_steps), 6 * self.n_nodes
+        rows = max(n_steps, 0) + 1
+        pat = am = None
+        n_pat = 0
+        if patterns is not None:
+            pat = np.ascontiguousarray(np.asarray(patterns, dtype=np.float64)).reshape(-1, n6)
+            n_pat = pat.shape[0]
+            am = np.ascontiguousarray(np.asarray(amp, dtype=np.float64).reshape(-1))
+            if am.size != rows * n_pat:
+                raise ValueError(f"amp must have shape ({rows}, {n_pat})")
+        uu = None if u0 is None else _f64(np.asarray(u0).reshape(-1), n6)
+        vv = None if v0 is None else _f64(np.asarray(v0).reshape(-1), n6)
+        pr = np.zeros(0, np.int32) if probes is None else np.ascontiguousarray(np.asarray(probes).reshape(-1), dtype=np.int32)
+        probe = np.zeros((rows, 3, pr.size, 6), np.float64)
+        energy = np.zeros((rows, 3), np.float64)
+        iters = np.zeros(rows, np.int32)
+        snap_every = int(snap_every)
+        snaps = np.zeros((n_steps // snap_every, self.n_nodes, 6), np.float64) if snap_every > 0 and n_steps > 0 else None
+        state = np.zeros((3, self.n_nodes, 6), np.float64) if want_state else None
+        _check(self._lib, self._lib.pl_transient(self._h, n_steps, float(dt), float(beta), float(gamma), float(ray_m),
+                                                 float(ray_k), n_pat, _ptr(pat), _ptr(am), _ptr(uu), _ptr(vv), float(rtol),
+                                                 int(max_iter), pr.size, _ptr(pr) if pr.size else None,
+                                                 _ptr(probe) if pr.size else None, _ptr(energy), snap_every, _ptr(snaps),
+                                                 _ptr(state), _ptr(iters)))
+        out = {"time": float(dt) * np.arange(rows), "probe": probe, "energy": energy, "iters": iters}
+        if want_state:
+            out["state"] = state
+        if snaps is not None:
+            out["snaps"] = snaps
+        return out
+
+    def transient_host(self, fixed, dt, n_steps, patterns=None, amp=None, u0=None, v0=None, beta=0.25, gamma=0.5, ray_m=0.0,
+                       ray_k=0.0, solve=None, probes=None, snap_every=0):
+        """The numpy / scipy restatement of ``transient`` (dynamics_host.newmark) on this handle's own BSR K and the restated
+        M of its mass model.  fixed (N, 6): the mask that was given to set_bc."""
+        import scipy.sparse as sp
+        from . import dynamics_host as DH
+        self.assemble_bsr(False)
+        rowptr, col, vals = self.get_bsr()
+        K = sp.bsr_matrix((vals, col, rowptr), shape=(6 * self.n_nodes, 6 * self.n_nodes)).tocsr()
+        K.sum_duplicates()
+        return DH.newmark(K, self.mass_matrix_host(), fixed, dt, n_steps, patterns, amp, u0, v0, beta, gamma, ray_m, ray_k,
+                          solve, probes, snap_every)
+
     # -- measurement ------------------------------------------------------------------------------------
     def time_kernel(self, which, reps=20):
         ms = C.c_double()
@@ -1022,7 +1086,7 @@ class HipLattice:
 # the reference wraps every hot-path method in @timing.category(..) @timing.timeit; here the
 # C-ABI calls are the hot path: host wall clock per call, plus the device's own HIP-event times (see solve)
 for _name in ("assemble", "assemble_bsr", "get_bsr", "solve", "set_bc", "spmv", "spmv_free", "spmv_bsr", "reactions",
-              "sens", "stress", "stress_pnorm", "buckling", "buckling_pnorm", "energy", "schur", "spmv_multi", "solve_multi", "geom_spmv_multi", "buckling_modes", "buckling_modes_sens", "mass_spmv_multi", "vibration_modes", "vibration_modes_sens", "update_radii", "update_segments", "records"):
+              "sens", "stress", "stress_pnorm", "buckling", "buckling_pnorm", "energy", "schur", "spmv_multi", "solve_multi", "geom_spmv_multi", "buckling_modes", "buckling_modes_sens", "mass_spmv_multi", "vibration_modes", "vibration_modes_sens", "dyn_spmv_multi", "transient", "update_radii", "update_segments", "records"):
     _f = getattr(HipLattice, _name, None)
     if _f is not None:
         _f._timing_category = "hip"

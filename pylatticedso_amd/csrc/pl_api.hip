@@ -9,6 +9,7 @@
 #include "pl_buckling.h"
 #include "pl_geom.h"
 #include "pl_mass.h"
+#include "pl_dyn.h"
 #include "pl_sensgram.h"
 
 
@@ -2521,6 +2522,200 @@ int pl_vibration_modes_sens(pl_handle h, int32_t n_modes, const double *omega2, 
       if ((rc = download_struts(h, g->sdlam.p + (size_t)j * B, domega2_dr + (size_t)live[j] * B))) return rc;
   if (dsum_dr)
     if ((rc = download_struts(h, g->sdlam.p + (size_t)nl * B, dsum_dr))) return rc;
+  return PL_OK;
+}
+
+// ---- transient response (pl_dyn.h) -------------------------------------------------------------------------------------
+int pl_dyn_spmv_multi(pl_handle h, double c_K, double c_M, int32_t n_rhs, int masked, const double *x, double *y) {
+  if (!valid(h) || !x || !y) return fail(PL_ERR_ARG, "pl_dyn_spmv_multi: null argument");
+  if (n_rhs < 1 || n_rhs > PL_MULTI_MAX) return fail(PL_ERR_ARG, "pl_dyn_spmv_multi: n_rhs must be 1 ... PL_MULTI_MAX");
+  if (!std::isfinite(c_K) || !std::isfinite(c_M)) return fail(PL_ERR_ARG, "pl_dyn_spmv_multi: c_K and c_M must be finite");
+  MassWs *m = nullptr;
+  if (int rc = mass_begin(h, "pl_dyn_spmv_multi", masked != 0, &m)) return rc;
+  const MultiShape s = dyn_shape(h, n_rhs);
+  MultiWs *w = nullptr;
+  if (int rc = multi_ws(h, s, false, &w)) return rc;
+  if (int rc = multi_upload(h, w, s, x, w->F.p, masked ? -1 : 0)) return rc;
+  MultiOp op;
+  op.c_K = c_K;
+  op.c_M = c_M;
+  op.mass = m;
+  const bool timing = std::getenv("PL_TIMING") != nullptr;
+  if (timing) PL_HIP(hipEventRecord(h->ev0, h->stream));
+  if (int rc = launch_dyn_multi(h, op, s, h->fixedbits.p, w->F.p, w->U.p, masked != 0, nullptr)) return rc;
+  if (timing) {
+    PL_HIP(hipEventRecord(h->ev1, h->stream));
+    PL_HIP(hipEventSynchronize(h->ev1));
+    float ms = 0.f;
+    PL_HIP(hipEventElapsedTime(&ms, h->ev0, h->ev1));
+    std::fprintf(stderr, "[pl_dyn_spmv_multi] %-28s %10.4f ms\n", "kernel_hip_event", (double)ms);
+  }
+  return multi_download(h, w, s, w->U.p, y);
+}
+
+int pl_transient(pl_handle h, int32_t n_steps, double dt, double beta, double gamma, double ray_m, double ray_k, int32_t n_pat,
+                 const double *pattern, const double *amp, const double *u0, const double *v0, double rtol, int32_t max_iter,
+                 int32_t n_probe, const int32_t *probe_nodes, double *probe, double *energy, int32_t snap_every, double *snaps,
+                 double *state, int32_t *iters) {
+  const char *who = "pl_transient";
+  if (!valid(h)) return fail(PL_ERR_ARG, "pl_transient: null handle");
+  if (n_steps < 1) return fail(PL_ERR_ARG, "pl_transient: n_steps must be at least 1");
+  if (!(dt > 0.0) || !std::isfinite(dt)) return fail(PL_ERR_ARG, "pl_transient: dt must be positive and finite");
+  if (!(gamma >= 0.5) || !std::isfinite(gamma)) return fail(PL_ERR_ARG, "pl_transient: gamma must be at least 1/2");
+  if (!(beta >= 0.25 * (0.5 + gamma) * (0.5 + gamma)) || !std::isfinite(beta))
+    return fail(PL_ERR_ARG, "pl_transient: beta must be at least (1/2 + gamma)^2 / 4 (unconditionally stable schemes only)");
+  if (!(ray_m >= 0.0) || !(ray_k >= 0.0) || !std::isfinite(ray_m) || !std::isfinite(ray_k))
+    return fail(PL_ERR_ARG, "pl_transient: the Rayleigh coefficients must be finite and not negative");
+  if (n_pat < 0 || n_pat > 4) return fail(PL_ERR_ARG, "pl_transient: n_pat must be 0 ... 4");
+  if (n_pat > 0 && (!pattern || !amp)) return fail(PL_ERR_ARG, "pl_transient: n_pat > 0 needs pattern and amp");
+  if (!(rtol > 0.0) || max_iter <= 0) return fail(PL_ERR_ARG, "pl_transient: rtol and max_iter must be positive");
+  if (n_probe < 0 || (n_probe > 0 && (!probe_nodes || !probe))) return fail(PL_ERR_ARG, "pl_transient: n_probe > 0 needs probe_nodes and probe");
+  if (snap_every < 0 || (snaps && snap_every < 1)) return fail(PL_ERR_ARG, "pl_transient: snaps needs snap_every >= 1");
+  const int64_t N = h->N, n6 = N * 6;
+  for (int i = 0; i < n_probe; ++i)
+    if (probe_nodes[i] < 0 || probe_nodes[i] >= N) return fail(PL_ERR_ARG, "pl_transient: probe node index out of range");
+  MassWs *m = nullptr;
+  if (int rc = mass_begin(h, who, true, &m)) return rc;
+  {   // supports are held at zero: prescribed values on the handle are refused
+    std::vector<double> ub((size_t)n6);
+    PL_HIP(hipMemcpyAsync(ub.data(), h->ubar.p, (size_t)n6 * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+    PL_HIP(hipStreamSynchronize(h->stream));
+    for (double v : ub)
+      if (v != 0.0) return fail(PL_ERR_STATE, "pl_transient: the handle carries non-zero prescribed displacements (pl_set_bc)");
+  }
+  const int rows = n_steps + 1;
+  const int n_snap = snaps ? n_steps / snap_every : 0;
+  // the probed nodes, each once: slot of the node in the device's probe block
+  std::vector<int32_t> slot_of((size_t)N, -1), probe_to_slot((size_t)n_probe);
+  int n_slot = 0;
+  for (int i = 0; i < n_probe; ++i) {
+    const int64_t di = h->iperm[probe_nodes[i]];
+    if (slot_of[(size_t)di] < 0) slot_of[(size_t)di] = n_slot++;
+    probe_to_slot[(size_t)i] = slot_of[(size_t)di];
+  }
+  // workspaces: the column block of four first (it sets the capacity), then the single column of the solves
+  MultiShape s4;
+  s4.n_rhs = 3; s4.KB = 4; s4.ncb = 1; s4.ncol = 4; s4.stride = n6 * 4;
+  MultiShape sp;                                   // the patterns: n_pat single columns
+  sp.n_rhs = n_pat; sp.KB = 1; sp.ncb = n_pat; sp.ncol = n_pat; sp.stride = n6;
+  const MultiShape s1 = multi_shape(h, 1);
+  MultiWs *w = nullptr;
+  if (int rc = multi_ws(h, s4, true, &w)) return rc;
+  if (int rc = multi_ws(h, s1, true, &w)) return rc;
+  if (!h->dyn_ws) h->dyn_ws = std::make_shared<DynWs>();
+  DynWs *d = static_cast<DynWs *>(h->dyn_ws.get());
+  PL_HIP(dyn_grow(d->st, (size_t)n6 * 4));
+  PL_HIP(dyn_grow(d->Ks, (size_t)n6 * 4));
+  PL_HIP(dyn_grow(d->Ms, (size_t)n6 * 4));
+  PL_HIP(dyn_grow(d->ut, (size_t)n6));
+  PL_HIP(dyn_grow(d->vt, (size_t)n6));
+  PL_HIP(dyn_grow(d->f2, (size_t)n6 * 2));
+  PL_HIP(dyn_grow(d->pattern, (size_t)n6 * std::max(n_pat, 1)));
+  PL_HIP(dyn_grow(d->amp, (size_t)rows * std::max(n_pat, 1)));
+  PL_HIP(dyn_grow(d->probe_slot, (size_t)N));
+  PL_HIP(dyn_grow(d->probe, (size_t)rows * 18 * std::max(n_slot, 1)));
+  PL_HIP(dyn_grow(d->energy, (size_t)rows * pl::DYN_E_COUNT * pl::kSlots));
+  if (n_snap > 0) PL_HIP(dyn_grow(d->snaps, (size_t)n_snap * n6));
+  // uploads: the start state (free dofs only), the patterns (free dofs only), the amplitudes, the probe map
+  {
+    std::vector<double> s0((size_t)3 * n6, 0.0);
+    if (u0) std::memcpy(s0.data(), u0, (size_t)n6 * sizeof(double));
+    if (v0) std::memcpy(s0.data() + n6, v0, (size_t)n6 * sizeof(double));
+    if (int rc = multi_upload(h, w, s4, s0.data(), d->st.p, -1)) return rc;
+  }
+  if (n_pat > 0) {
+    if (int rc = multi_upload(h, w, sp, pattern, d->pattern.p, -1)) return rc;
+    PL_HIP(hipMemcpyAsync(d->amp.p, amp, (size_t)rows * n_pat * sizeof(double), hipMemcpyHostToDevice, h->stream));
+  }
+  PL_HIP(hipMemcpyAsync(d->probe_slot.p, slot_of.data(), (size_t)N * sizeof(int32_t), hipMemcpyHostToDevice, h->stream));
+  PL_HIP(hipStreamSynchronize(h->stream));         // (amp and slot_of are pageable host memory)
+  PL_HIP(hipMemsetAsync(d->f2.p, 0, (size_t)n6 * 2 * sizeof(double), h->stream));
+  PL_HIP(hipMemsetAsync(d->energy.p, 0, (size_t)rows * pl::DYN_E_COUNT * pl::kSlots * sizeof(double), h->stream));
+  PL_HIP(hipMemsetAsync(w->UB.p, 0, (size_t)n6 * sizeof(double), h->stream));      // zero prescribed values in every solve
+
+  const bool timing = std::getenv("PL_TIMING") != nullptr;
+  const auto t_begin = std::chrono::steady_clock::now();
+  double ms_solve = 0.0;
+  long total_iters = 0;
+  const dim3 gs(grid_stream(n6));
+  std::vector<double> status((size_t)pl::M_ST_COUNT * s1.ncol);
+  MultiOp op;
+  op.mass = m;
+  // K and M on the state, then the energies of row erow; form: the predictors, the load of row erow + 1 and the right-hand side
+  auto products_and_predict = [&](const pl::NewmarkCoef &q, bool form, int erow) -> int {
+    if (int rc = launch_spmv_multi(h, s4, h->fixedbits.p, d->st.p, d->Ks.p, true, nullptr)) return rc;
+    if (int rc = launch_mass_multi(h, m, s4, d->st.p, d->Ms.p, true)) return rc;
+    const int row = erow + 1;
+    hipLaunchKernelGGL(pl::k_newmark_predict, gs, dim3(pl::kBlock), 0, h->stream, n6, (const double *)d->st.p,
+                       (const double *)d->Ks.p, (const double *)d->Ms.p, (const uint8_t *)h->fixedbits.p, q, form ? 1 : 0,
+                       (int)n_pat, (const double *)d->pattern.p, (const double *)d->amp.p + (size_t)(form ? row : 0) * n_pat,
+                       d->ut.p, d->vt.p, d->f2.p + (size_t)(row & 1) * n6, w->F.p, d->energy.p, erow);
+    PL_HIP(hipGetLastError());
+    return PL_OK;
+  };
+  for (int row = 0; row <= n_steps; ++row) {       // row 0: the initial acceleration, the same three stages with dt = 0
+    const pl::NewmarkCoef q = {row == 0 ? 0.0 : dt, beta, gamma, ray_m, ray_k};
+    op.c_M = 1.0 + gamma * q.dt * ray_m;
+    op.c_K = beta * q.dt * q.dt + gamma * q.dt * ray_k;
+    if (int rc = products_and_predict(q, true, row - 1)) return rc;
+    const auto t0 = std::chrono::steady_clock::now();
+    if (int rc = pcg_solve_multi(h, w, s1, h->fixedbits.p, w->F.p, rtol, max_iter, status.data(), op)) return rc;
+    ms_solve += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    const double rr = status[pl::M_ST_RR * s1.ncol], bb = status[pl::M_ST_BB * s1.ncol];
+    const int its = (int)status[pl::M_ST_ITER * s1.ncol];
+    total_iters += its;
+    if (iters) iters[row] = its;
+    if (!std::isfinite(rr) || !std::isfinite(bb))
+      return fail(PL_ERR_NAN, "pl_transient: NaN/Inf in a residual norm of step " + std::to_string(row));
+    if (!(rr <= rtol * rtol * bb))
+      return fail(PL_ERR_NOCONV, "pl_transient: the solve of step " + std::to_string(row) + " did not reach rtol within max_iter");
+    double *snap = nullptr;
+    if (n_snap > 0 && row > 0 && row % snap_every == 0) snap = d->snaps.p + (size_t)(row / snap_every - 1) * n6;
+    hipLaunchKernelGGL(pl::k_newmark_correct, gs, dim3(pl::kBlock), 0, h->stream, n6, (const double *)d->ut.p,
+                       (const double *)d->vt.p, (const double *)w->U.p, (const double *)d->f2.p + (size_t)((row & 1) ^ 1) * n6,
+                       (const double *)d->f2.p + (size_t)(row & 1) * n6, q, d->st.p, (const int32_t *)d->probe_slot.p, n_slot,
+                       d->probe.p, snap, d->energy.p, row);
+    PL_HIP(hipGetLastError());
+  }
+  {   // the energies of the last row
+    const pl::NewmarkCoef q = {dt, beta, gamma, ray_m, ray_k};
+    if (int rc = products_and_predict(q, false, n_steps)) return rc;
+  }
+  // histories come down once
+  if (energy) {
+    std::vector<double> eh((size_t)rows * pl::DYN_E_COUNT * pl::kSlots);
+    PL_HIP(hipMemcpyAsync(eh.data(), d->energy.p, eh.size() * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+    PL_HIP(hipStreamSynchronize(h->stream));
+    double work = 0.0;
+    for (int r = 0; r < rows; ++r)
+      for (int k = 0; k < pl::DYN_E_COUNT; ++k) {
+        double t = 0.0;
+        for (int q = 0; q < pl::kSlots; ++q) t += eh[((size_t)r * pl::DYN_E_COUNT + k) * pl::kSlots + q];
+        if (k == pl::DYN_E_WORK) t = (work += t);
+        energy[(size_t)r * 3 + k] = t;
+      }
+  }
+  if (n_probe > 0) {
+    std::vector<double> ph((size_t)rows * 18 * n_slot);
+    PL_HIP(hipMemcpyAsync(ph.data(), d->probe.p, ph.size() * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+    PL_HIP(hipStreamSynchronize(h->stream));
+    for (size_t rq = 0; rq < (size_t)rows * 3; ++rq)
+      for (int i = 0; i < n_probe; ++i)
+        std::memcpy(probe + (rq * n_probe + i) * 6, ph.data() + (rq * n_slot + probe_to_slot[(size_t)i]) * 6, 6 * sizeof(double));
+  }
+  for (int k = 0; k < n_snap; ++k)
+    if (int rc = download6(h, d->snaps.p + (size_t)k * n6, snaps + (size_t)k * n6)) return rc;
+  if (state)
+    if (int rc = multi_download(h, w, s4, d->st.p, state)) return rc;
+  if (timing) {
+    PL_HIP(hipStreamSynchronize(h->stream));
+    const double ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_begin).count();
+    std::fprintf(stderr, "[%s] %-28s %10.4f ms\n", who, "whole_call_host_clock", ms);
+    std::fprintf(stderr, "[%s] %-28s %10d\n", who, "steps", (int)n_steps);
+    std::fprintf(stderr, "[%s] %-28s %10.4f ms\n", who, "step_mean_host_clock", ms / rows);
+    std::fprintf(stderr, "[%s] %-28s %10.4f ms\n", who, "inner_solve_mean_host_clock", ms_solve / rows);
+    std::fprintf(stderr, "[%s] %-28s %10.2f\n", who, "iterations_per_step", (double)total_iters / rows);
+  }
   return PL_OK;
 }
 

@@ -596,6 +596,25 @@ inline MultiScal multi_scal(MultiWs *w, int ncol) {
   return m;
 }
 
+// The SPD operator the k-column PCG works on: c_K K + c_M M (pl_dyn.h).  The default is K alone, applied and preconditioned by
+// the launches of this file; any other operator needs the mass data of pl_set_mass and goes through the fused kernels.
+struct MassWs;
+struct MultiOp {
+  double c_K = 1.0, c_M = 0.0;
+  const MassWs *mass = nullptr;
+  bool plain() const { return mass == nullptr; }
+};
+// (pl_dyn.h)
+int launch_dyn_multi(pl_context *c, const MultiOp &op, const MultiShape &s, const uint8_t *fixedbits, const double *x, double *y,
+                     bool masked, double *dot_dev);
+int launch_dyn_diag(pl_context *c, const MultiOp &op, const uint8_t *fixedbits, double *diag, double *dinv);
+// y_j = A x_j for the operator of the running solve
+inline int multi_apply(pl_context *c, const MultiOp &op, const MultiShape &s, const uint8_t *fixedbits, const double *x, double *y,
+                       bool masked, double *dot_dev) {
+  return op.plain() ? launch_spmv_multi(c, s, fixedbits, x, y, masked, dot_dev)
+                    : launch_dyn_multi(c, op, s, fixedbits, x, y, masked, dot_dev);
+}
+
 #define PL_MULTI_KB(KBV, CALL)                         \
   do {                                                 \
     if ((KBV) == 1) { constexpr int KB = 1; CALL; }    \
@@ -604,10 +623,11 @@ inline MultiScal multi_scal(MultiWs *w, int ncol) {
   } while (0)
 
 // One iteration of the k-column Jacobi PCG (it selects the scalar / flag set by parity): four launches, whatever ncol.
-int multi_iteration(pl_context *c, MultiWs *w, const MultiShape &s, const MultiScal &m, const uint8_t *fixedbits, int it) {
+int multi_iteration(pl_context *c, MultiWs *w, const MultiShape &s, const MultiScal &m, const uint8_t *fixedbits, int it,
+                    const MultiOp &op = MultiOp()) {
   const int64_t n6 = c->N * 6;
   const int a = it & 1, b = a ^ 1;
-  int rc = launch_spmv_multi(c, s, fixedbits, w->P.p, w->AP.p, true, m.set[a] + (size_t)pl::M_PAP * s.ncol * pl::kSlots);
+  int rc = multi_apply(c, op, s, fixedbits, w->P.p, w->AP.p, true, m.set[a] + (size_t)pl::M_PAP * s.ncol * pl::kSlots);
   if (rc) return rc;
   multi_periodic_average(c, s, w->AP.p);   // the operator is Q K Q; p.Kp above is already p.QKQp (p = Q p)
   const dim3 g(grid_stream(n6), (unsigned)s.ncb);
@@ -623,7 +643,8 @@ int multi_iteration(pl_context *c, MultiWs *w, const MultiShape &s, const MultiS
 }
 
 // Jacobi diagonal and inverse for `fixedbits` into the workspace (the handle's own dinv belongs to its own preconditioner)
-int multi_diag(pl_context *c, MultiWs *w, const uint8_t *fixedbits) {
+int multi_diag(pl_context *c, MultiWs *w, const uint8_t *fixedbits, const MultiOp &op = MultiOp()) {
+  if (!op.plain()) return launch_dyn_diag(c, op, fixedbits, w->diag.p, w->dinv.p);
   const unsigned g = grid_for(c->n_slices, pl::kBlock / pl::kWave);
 #define PL_D(L)                                                                                                        \
   hipLaunchKernelGGL((pl::k_diag_gather<L>), dim3(g), dim3(pl::kBlock), 0, c->stream, c->N, c->slice_ptr.p, c->ent.p, \
@@ -635,20 +656,20 @@ int multi_diag(pl_context *c, MultiWs *w, const uint8_t *fixedbits) {
   return PL_OK;
 }
 
-// K u_j = f_j on the free dofs of `fixedbits`, u_j = ubar_j on the others: w->UB (zero on free dofs) and w->F (f_dev == null:
-// zero loads) hold the data in column blocks, w->U receives the full fields.  status_host[M_ST_COUNT][ncol] gets ||r||^2,
+// K u_j = f_j (with `op`: (c_K K + c_M M) u_j = f_j) on the free dofs of `fixedbits`, u_j = ubar_j on the others: w->UB (zero on
+// free dofs) and w->F (f_dev == null: zero loads) hold the data in column blocks, w->U receives the full fields.  status_host[M_ST_COUNT][ncol] gets ||r||^2,
 // ||b||^2, iterations and the frozen flag of every column.  The host looks at the status block every check_every
 // iterations in one small download; nothing else drains the stream.
 int pcg_solve_multi(pl_context *c, MultiWs *w, const MultiShape &s, const uint8_t *fixedbits, const double *f_dev, double rtol,
-                    int max_iter, double *status_host) {
+                    int max_iter, double *status_host, const MultiOp &op = MultiOp()) {
   const int64_t n6 = c->N * 6;
   const MultiScal m = multi_scal(w, s.ncol);
   const size_t scal_bytes = ((size_t)(2 * pl::M_COUNT + 1) * pl::kSlots + 1 + pl::M_ST_COUNT) * s.ncol * sizeof(double);
   PL_HIP(hipMemsetAsync(w->scal.p, 0, scal_bytes, c->stream));
   PL_HIP(hipMemsetAsync(w->flags.p, 0, (size_t)2 * s.ncol * sizeof(int), c->stream));
-  int rc = multi_diag(c, w, fixedbits);
+  int rc = multi_diag(c, w, fixedbits, op);
   if (rc) return rc;
-  rc = launch_spmv_multi(c, s, fixedbits, w->UB.p, w->KU.p, false, nullptr);   // lifting: K ubar
+  rc = multi_apply(c, op, s, fixedbits, w->UB.p, w->KU.p, false, nullptr);   // lifting: K ubar
   if (rc) return rc;
   const dim3 g(grid_stream(n6), (unsigned)s.ncb);
   PL_MULTI_KB(s.KB, hipLaunchKernelGGL((pl::k_multi_init<KB>), g, dim3(pl::kBlock), 0, c->stream, n6, f_dev, (const double *)w->KU.p,
@@ -675,7 +696,7 @@ int pcg_solve_multi(pl_context *c, MultiWs *w, const MultiShape &s, const uint8_
   while (all == 0 && it < max_iter) {
     const int stop = std::min(max_iter, it + every);
     for (; it < stop; ++it) {
-      rc = multi_iteration(c, w, s, m, fixedbits, it);
+      rc = multi_iteration(c, w, s, m, fixedbits, it, op);
       if (rc) return rc;
     }
     all = look();

@@ -1,0 +1,130 @@
+"""numpy / scipy restatement of the transient response (csrc/pl_dyn.h, pl_transient): implicit Newmark
+time stepping of M a + C v + K u = f(t) on the free dofs, C = ray_m M + ray_k K, in acceleration form.  No device.
+
+Step n -> n + 1 with dt:
+    ut = u_n + dt v_n + dt^2 (1/2 - beta) a_n,   vt = v_n + dt (1 - gamma) a_n
+    (M (1 + gamma dt ray_m) + K (beta dt^2 + gamma dt ray_k)) a_{n+1} = f_{n+1} - K ut - C vt
+    u_{n+1} = ut + beta dt^2 a_{n+1},   v_{n+1} = vt + gamma dt a_{n+1}
+and M a_0 = f_0 - K u_0 - C v_0.  With beta = 1/4, gamma = 1/2 (the average acceleration) an undamped mode of frequency omega
+is carried with its amplitude kept and the phase ``newmark_phase(omega, dt)`` per step."""
+import numpy as np
+import scipy.linalg
+import scipy.sparse as sp
+
+
+def check_scheme(dt, n_steps, beta, gamma, ray_m=0.0, ray_k=0.0):
+    """The argument checks of pl_transient: unconditionally stable implicit schemes only."""
+    if not (dt > 0.0 and np.isfinite(dt)):
+        raise ValueError("dt must be positive and finite")
+    if int(n_steps) < 1:
+        raise ValueError("n_steps must be at least 1")
+    if not gamma >= 0.5:
+        raise ValueError("gamma must be at least 1/2")
+    if not beta >= 0.25 * (0.5 + gamma) ** 2:
+        raise ValueError("beta must be at least (1/2 + gamma)^2 / 4 (unconditionally stable schemes only)")
+    if not (ray_m >= 0.0 and ray_k >= 0.0):
+        raise ValueError("the Rayleigh coefficients must not be negative")
+
+
+def newmark_phase(omega, dt):
+    """Phase advance per step of an undamped mode under the average-acceleration scheme: 2 atan(omega dt / 2)."""
+    return 2.0 * np.arctan(0.5 * np.asarray(omega, float) * dt)
+
+
+def jacobi_pcg(rtol, max_iter=100000, counts=None):
+    """A ``solve`` for ``newmark``: Jacobi-preconditioned CG from a zero start to ||r|| <= rtol ||b||, the solver of the
+    device.  counts: a list that receives the iterations of every solve."""
+    def solve(S, b):
+        dinv = 1.0 / S.diagonal()
+        x = np.zeros_like(b)
+        r = b.copy()
+        bb = float(r @ r)
+        it = 0
+        if bb > 0.0:
+            z = dinv * r
+            p = z.copy()
+            rz = float(r @ z)
+            while it < max_iter:
+                Ap = S @ p
+                alpha = rz / float(p @ Ap)
+                x += alpha * p
+                r -= alpha * Ap
+                it += 1
+                if float(r @ r) <= rtol * rtol * bb:
+                    break
+                z = dinv * r
+                rz_new = float(r @ z)
+                p = z + (rz_new / rz) * p
+                rz = rz_new
+        if counts is not None:
+            counts.append(it)
+        return x
+    return solve
+
+
+def _dense_solver():
+    cache = {}
+
+    def solve(S, b):
+        key = id(S)
+        if key not in cache:
+            cache.clear()
+            cache[key] = (S, scipy.linalg.cho_factor(S.toarray() if sp.issparse(S) else np.asarray(S)))
+        return scipy.linalg.cho_solve(cache[key][1], b)
+    return solve
+
+
+def newmark(K, M, fixed, dt, n_steps, patterns=None, amp=None, u0=None, v0=None, beta=0.25, gamma=0.5, ray_m=0.0, ray_k=0.0,
+            solve=None, probes=None, snap_every=0):
+    """The arrays of pl_transient from the matrices K, M (6N x 6N, dense or sparse) and the mask fixed (N, 6) / (6N,).
+
+    patterns (n_pat, 6N) or (n_pat, N, 6) with amp (n_steps + 1, n_pat) give the load f_n = amp[n] @ patterns; u0, v0 (6N,)
+    or None = 0; all are read with the fixed dofs zeroed.  solve(S, b): the solver of the reduced systems (free dofs only);
+    None = dense Cholesky, factorised once per matrix.  Returns a dict: u, v, a (n_steps + 1, N, 6) - the whole history -,
+    probe (n_steps + 1, 3, n_probe, 6) for the node indices ``probes``, energy (n_steps + 1, 3) = kinetic, strain, external
+    work (trapezoid), snaps (n_steps // snap_every, N, 6) if snap_every > 0, state (3, N, 6) and time (n_steps + 1,)."""
+    check_scheme(dt, n_steps, beta, gamma, ray_m, ray_k)
+    n_steps = int(n_steps)
+    fx = np.asarray(fixed).reshape(-1) != 0
+    n6 = fx.size
+    free = np.flatnonzero(~fx)
+    K, M = sp.csr_matrix(K), sp.csr_matrix(M)
+    Kf, Mf = K[free][:, free].tocsr(), M[free][:, free].tocsr()
+    Cf = ray_m * Mf + ray_k * Kf
+    if patterns is None:
+        P = np.zeros((0, free.size))
+        A = np.zeros((n_steps + 1, 0))
+    else:
+        P = np.asarray(patterns, float).reshape(-1, n6)[:, free]
+        A = np.asarray(amp, float).reshape(n_steps + 1, P.shape[0])
+    u = np.zeros(free.size) if u0 is None else np.asarray(u0, float).reshape(-1)[free].copy()
+    v = np.zeros(free.size) if v0 is None else np.asarray(v0, float).reshape(-1)[free].copy()
+    solve = solve or _dense_solver()
+    S = ((1.0 + gamma * dt * ray_m) * Mf + (beta * dt * dt + gamma * dt * ray_k) * Kf).tocsr()
+
+    U, V, Acc = (np.zeros((n_steps + 1, n6)) for _ in range(3))
+    energy = np.zeros((n_steps + 1, 3))
+    f = A[0] @ P
+    a = solve(Mf, f - Kf @ u - Cf @ v)
+    work = 0.0
+    for n in range(n_steps + 1):
+        if n > 0:
+            ut = u + dt * v + dt * dt * (0.5 - beta) * a
+            vt = v + dt * (1.0 - gamma) * a
+            f_new = A[n] @ P
+            a = solve(S, f_new - Kf @ ut - Cf @ vt)
+            u_new = ut + beta * dt * dt * a
+            v = vt + gamma * dt * a
+            work += 0.5 * float((f + f_new) @ (u_new - u))
+            u, f = u_new, f_new
+        U[n, free], V[n, free], Acc[n, free] = u, v, a
+        energy[n] = 0.5 * float(v @ (Mf @ v)), 0.5 * float(u @ (Kf @ u)), work
+    N = n6 // 6
+    out = {"u": U.reshape(-1, N, 6), "v": V.reshape(-1, N, 6), "a": Acc.reshape(-1, N, 6), "energy": energy,
+           "time": dt * np.arange(n_steps + 1),
+           "state": np.stack([U[-1], V[-1], Acc[-1]]).reshape(3, N, 6)}
+    pr = np.zeros(0, int) if probes is None else np.asarray(probes, int).reshape(-1)
+    out["probe"] = np.stack([out["u"][:, pr], out["v"][:, pr], out["a"][:, pr]], axis=1)
+    if snap_every and snap_every > 0:
+        out["snaps"] = out["u"][snap_every::snap_every][: n_steps // snap_every].copy()
+    return out

@@ -715,6 +715,66 @@ class LatticeSim(LatticeViews):
         self.vibration_modes = out["modes"]
         return out
 
+    def transient_response(self, dt, n_steps, density, amplitude=None, base_acceleration=None, damping=(0.0, 0.0),
+                           probes=None, rotary=True, node_mass=None, **kw):
+        """Response in time under the supports and the force set of the last solve_FEM_FenicsX, on the device (pl_set_mass,
+        pl_transient): implicit Newmark steps of M a + C v + K u = f(t) from rest, M the consistent mass of the struts at
+        ``density`` (as ``natural_frequencies``), C = damping[0] M + damping[1] K.  The force set is load pattern 0 with the
+        factor ``amplitude``: a callable of the time, an array (n_steps + 1,), or None = 1 throughout (a suddenly applied
+        load).  ``base_acceleration`` = (direction (3,), a_g (n_steps + 1,)) adds the inertia load -M e_direction a_g[n] of a
+        moving base, the response then being relative to it.  probes: node indices (default: the loaded nodes).  Keyword
+        arguments (beta, gamma, rtol, max_iter, u0, v0, snap_every) go to ``HipLattice.transient``.  Sets ``transient_time``
+        (n_steps + 1,), ``transient_probe`` (n_steps + 1, 3, n_probe, 6) = u, v, a of the probes, ``transient_energy``
+        (n_steps + 1, 3) = kinetic, strain, external work, ``transient_state`` (3, n_nodes, 6) and returns the device call's
+        dict."""
+        if getattr(self, "_compat_rows", False) or self.domain_decomposition_solver:
+            raise NotImplementedError("transient_response: the default strut model on a FEM lattice only (no reference_compat "
+                                      "rows, no domain decomposition)")
+        if self._device is None:
+            raise RuntimeError("transient_response needs a solve_FEM_FenicsX on this lattice first")
+        dev, n, rows = self._device, self.lattice.n_nodes, int(n_steps) + 1
+        dev.set_mass(density, rotary, node_mass)
+        time = float(dt) * np.arange(rows)
+        force = np.zeros((n, 6))
+        force[:, :3] = np.asarray(self.applied_force)[:n, :3]      # (only the translational components are loads)
+        if amplitude is None:
+            amp0 = np.ones(rows)
+        elif callable(amplitude):
+            amp0 = np.array([float(amplitude(t)) for t in time])
+        else:
+            amp0 = np.asarray(amplitude, float).reshape(-1)
+            if amp0.size != rows:
+                raise ValueError(f"amplitude must have {rows} entries")
+        patterns, amps = [force], [amp0]
+        if base_acceleration is not None:
+            direction, a_g = base_acceleration
+            a_g = np.asarray(a_g, float).reshape(-1)
+            if a_g.size != rows:
+                raise ValueError(f"base_acceleration needs {rows} accelerations")
+            e = np.zeros((1, n, 6))
+            e[0, :, :3] = np.asarray(direction, float).reshape(3)
+            patterns.append(-dev.mass_spmv_multi(e)[0])
+            amps.append(a_g)
+        if probes is None:
+            probes = np.flatnonzero(np.abs(force).sum(axis=1) > 0)
+        probes = np.asarray(probes, int).reshape(-1)
+        out = dev.transient(dt, n_steps, np.stack(patterns), np.stack(amps, axis=1), ray_m=damping[0], ray_k=damping[1],
+                            probes=probes, **kw)
+        self.transient_time, self.transient_probe = out["time"], out["probe"]
+        self.transient_energy, self.transient_state = out["energy"], out["state"]
+        self._transient_probes = probes
+        return out
+
+    def dynamic_amplification(self):
+        """max_t |u| / |u_static| of every probe of the last ``transient_response``, |.| the norm of the three translations and
+        u_static the displacements of the last solve_FEM_FenicsX (n_probe,); 2 is the undamped one-degree-of-freedom value
+        for a suddenly applied load."""
+        if getattr(self, "transient_probe", None) is None:
+            raise RuntimeError("dynamic_amplification needs a transient_response on this lattice first")
+        u_dyn = np.linalg.norm(self.transient_probe[:, 0, :, :3], axis=2).max(axis=0)
+        u_static = np.linalg.norm(np.asarray(self.displacement_vector)[self._transient_probes, :3], axis=1)
+        return u_dyn / u_static
+
     def natural_frequency_sensitivity(self, p=8, want_rows=True):
         """Derivatives of the omega^2 of the last ``natural_frequencies`` to the strut radii, on the device
         (pl_vibration_modes_sens: one pass over the struts, no solve), and of their aggregate
