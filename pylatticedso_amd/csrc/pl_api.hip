@@ -1618,20 +1618,41 @@ int stress_begin(pl_handle h, const char *who, const double *u, int32_t where, c
   }
   return PL_OK;
 }
-// kernel time of a stress call on stderr when PL_TIMING is set (tools/time_stress.py), as pl_spmv_multi does
-struct StressTimer {
-  pl_handle h;
+// PL_TIMING in the environment: HIP-event times of a call's device stages on stderr, "[<who>] <stage> <ms> ms" with four
+// decimals (tools/time_*.py read this format).  mark(stage) records an event on the stream; a stage runs from its mark to the
+// next one, so the last mark only closes the stage before it.  report() waits for the last mark and prints every stage.
+struct EventTimer {
+  static constexpr int kMaxMarks = 8;
   const char *who;
+  hipStream_t stream;
   bool on;
-  StressTimer(pl_handle h_, const char *w) : h(h_), who(w), on(std::getenv("PL_TIMING") != nullptr) {
-    if (on) (void)hipEventRecord(h->ev0, h->stream);
+  hipEvent_t ev[kMaxMarks] = {};
+  const char *stage[kMaxMarks] = {};
+  int n = 0;
+  // first != null: the timer starts with mark(first)
+  EventTimer(const char *w, hipStream_t s, const char *first = nullptr) : who(w), stream(s), on(std::getenv("PL_TIMING") != nullptr) {
+    if (first) mark(first);
   }
-  void stop() {
-    if (!on) return;
-    float ms = 0.f;
-    if (hipEventRecord(h->ev1, h->stream) == hipSuccess && hipEventSynchronize(h->ev1) == hipSuccess &&
-        hipEventElapsedTime(&ms, h->ev0, h->ev1) == hipSuccess)
-      std::fprintf(stderr, "[%s] %-28s %10.4f ms\n", who, "kernel_hip_event", (double)ms);
+  EventTimer(const EventTimer &) = delete;
+  void mark(const char *name = nullptr) {
+    if (!on || n == kMaxMarks || hipEventCreate(&ev[n]) != hipSuccess) return;
+    stage[n] = name;
+    (void)hipEventRecord(ev[n++], stream);
+  }
+  void report() {
+    if (n < 2 || hipEventSynchronize(ev[n - 1]) != hipSuccess) return;
+    for (int i = 0; i + 1 < n; ++i) {
+      float ms = 0.f;
+      if (hipEventElapsedTime(&ms, ev[i], ev[i + 1]) == hipSuccess)
+        std::fprintf(stderr, "[%s] %-28s %10.4f ms\n", who, stage[i], (double)ms);
+    }
+  }
+  void stop() {   // closes the running stage and prints
+    mark();
+    report();
+  }
+  ~EventTimer() {
+    for (int i = 0; i < n; ++i) (void)hipEventDestroy(ev[i]);
   }
 };
 }  // namespace
@@ -1644,7 +1665,7 @@ int pl_stress(pl_handle h, const double *u, int32_t where, double *station, doub
   DevBuf<double> d_station;
   if (station) PL_HIP(d_station.alloc((size_t)B * 20));
   if (peak && !h->st_dr.p) PL_HIP(h->st_dr.alloc((size_t)B));
-  StressTimer timer(h, "pl_stress");
+  EventTimer timer("pl_stress", h->stream, "kernel_hip_event");
   hipLaunchKernelGGL(pl::k_stress_stations, dim3(grid_for(B)), dim3(pl::kBlock), 0, h->stream, B, h->conn.p, h->rec.p,
                      h->radius.p, h->seg_len.p, h->mult.p, h->mat.pen, (int)where, u_dev, d_station.p,
                      peak ? h->st_dr.p : (double *)nullptr, (double *)nullptr, (double *)nullptr);
@@ -1684,7 +1705,7 @@ int pl_stress_pnorm(pl_handle h, const double *u, int32_t where, double p, doubl
   const bool grad = dphi_du || dphi_dr;
   if (grad && !h->st_G.p) PL_HIP(h->st_G.alloc((size_t)B * 6));
   if (dphi_dr && !h->st_dr.p) PL_HIP(h->st_dr.alloc((size_t)B));
-  StressTimer timer(h, "pl_stress_pnorm");
+  EventTimer timer("pl_stress_pnorm", h->stream, "kernel_hip_event");
   hipLaunchKernelGGL(pl::k_stress_stations, dim3(grid), dim3(pl::kBlock), 0, h->stream, B, h->conn.p, h->rec.p, h->radius.p,
                      h->seg_len.p, h->mult.p, h->mat.pen, (int)where, u_dev, (double *)nullptr, (double *)nullptr,
                      h->st_vm4.p, h->st_part.p);
@@ -1760,7 +1781,7 @@ int pl_buckling(pl_handle h, const double *u, int32_t length, double k_eff, int3
   const int64_t B = h->B;
   if (!h->st_vm4.p) PL_HIP(h->st_vm4.alloc((size_t)B * 4));   // rows 0..2 of [4][B]: beta, N, N_cr
   double *d_util = h->st_vm4.p, *d_n = h->st_vm4.p + B, *d_cr = h->st_vm4.p + 2 * B;
-  StressTimer timer(h, "pl_buckling");
+  EventTimer timer("pl_buckling", h->stream, "kernel_hip_event");
   hipLaunchKernelGGL(pl::k_buckling_util, dim3(grid_for(B)), dim3(pl::kBlock), 0, h->stream, B, h->conn.p, h->rec.p,
                      h->radius.p, h->seg_len.p, h->mult.p, h->mat, (int)length, k_eff, (int)shear, u_dev,
                      util ? d_util : (double *)nullptr, n_axial ? d_n : (double *)nullptr,
@@ -1791,7 +1812,7 @@ int pl_buckling_pnorm(pl_handle h, const double *u, int32_t length, double k_eff
   const bool grad = dbp_du || dbp_dr;
   if (grad && !h->st_G.p) PL_HIP(h->st_G.alloc((size_t)B * 6));
   if (dbp_dr && !h->st_dr.p) PL_HIP(h->st_dr.alloc((size_t)B));
-  StressTimer timer(h, "pl_buckling_pnorm");
+  EventTimer timer("pl_buckling_pnorm", h->stream, "kernel_hip_event");
   hipLaunchKernelGGL(pl::k_buckling_util, dim3(grid), dim3(pl::kBlock), 0, h->stream, B, h->conn.p, h->rec.p, h->radius.p,
                      h->seg_len.p, h->mult.p, h->mat, (int)length, k_eff, (int)shear, u_dev, h->st_vm4.p, (double *)nullptr,
                      (double *)nullptr, h->st_part.p);
@@ -1882,26 +1903,35 @@ int pl_schur(pl_handle h, const int32_t *boundary_nodes, int32_t nb, double rtol
 }
 
 // ---- several right-hand sides in one pass (pl_multi.h) ---------------------------------------------------------------
-int pl_spmv_multi(pl_handle h, int32_t n_rhs, int masked, const double *x, double *y) {
-  if (!valid(h) || !x || !y) return fail(PL_ERR_ARG, "pl_spmv_multi: null argument");
-  if (n_rhs < 1 || n_rhs > PL_MULTI_MAX) return fail(PL_ERR_ARG, "pl_spmv_multi: n_rhs must be 1 ... PL_MULTI_MAX");
-  if (int rc = multi_check_handle(h, "pl_spmv_multi", masked != 0)) return rc;
-  PL_HIP(hipSetDevice(h->opt.device));
-  const MultiShape s = multi_shape(h, n_rhs);
+extern "C++" {   // (a template)
+namespace {
+// What the four pl_*_spmv_multi calls share: the checks of x, y and n_rhs, the workspace, the upload (masked: the free dofs
+// only), one launch of k_gather_multi between the marks of the PL_TIMING line, and the download.  begin() makes the call's own
+// checks and preparations (0 = go on); term() then gives the operator, shape(h, n_rhs) its column blocks.
+template <class Begin, class TermOf>
+int spmv_multi_call(pl_handle h, const char *who, MultiShape (*shape)(const pl_context *, int), int32_t n_rhs, int masked,
+                    const double *x, double *y, Begin begin, TermOf term) {
+  if (!valid(h) || !x || !y) return fail(PL_ERR_ARG, std::string(who) + ": null argument");
+  if (n_rhs < 1 || n_rhs > PL_MULTI_MAX) return fail(PL_ERR_ARG, std::string(who) + ": n_rhs must be 1 ... PL_MULTI_MAX");
+  if (int rc = begin()) return rc;
+  const MultiShape s = shape(h, n_rhs);
   MultiWs *w = nullptr;
   if (int rc = multi_ws(h, s, false, &w)) return rc;
   if (int rc = multi_upload(h, w, s, x, w->F.p, masked ? -1 : 0)) return rc;
-  const bool timing = std::getenv("PL_TIMING") != nullptr;
-  if (timing) PL_HIP(hipEventRecord(h->ev0, h->stream));
-  if (int rc = launch_spmv_multi(h, s, h->fixedbits.p, w->F.p, w->U.p, masked != 0, nullptr)) return rc;
-  if (timing) {
-    PL_HIP(hipEventRecord(h->ev1, h->stream));
-    PL_HIP(hipEventSynchronize(h->ev1));
-    float ms = 0.f;
-    PL_HIP(hipEventElapsedTime(&ms, h->ev0, h->ev1));
-    std::fprintf(stderr, "[pl_spmv_multi] %-28s %10.4f ms\n", "kernel_hip_event", (double)ms);
-  }
+  EventTimer timer(who, h->stream, "kernel_hip_event");
+  if (int rc = launch_gather_multi(h, s, term(), h->fixedbits.p, w->F.p, w->U.p, masked != 0, nullptr)) return rc;
+  timer.stop();
   return multi_download(h, w, s, w->U.p, y);
+}
+}  // namespace
+}  // extern "C++"
+
+int pl_spmv_multi(pl_handle h, int32_t n_rhs, int masked, const double *x, double *y) {
+  return spmv_multi_call(h, "pl_spmv_multi", multi_shape, n_rhs, masked, x, y, [&]() -> int {
+    if (int rc = multi_check_handle(h, "pl_spmv_multi", masked != 0)) return rc;
+    PL_HIP(hipSetDevice(h->opt.device));
+    return PL_OK;
+  }, [&] { return pl::StiffTerm{h->rec.p}; });
 }
 
 namespace {
@@ -2046,25 +2076,10 @@ int geom_begin(pl_handle h, const char *who, const double *u, bool need_bc, Geom
 }  // namespace
 
 int pl_geom_spmv_multi(pl_handle h, const double *u, int32_t n_rhs, int masked, const double *x, double *y) {
-  if (!valid(h) || !x || !y) return fail(PL_ERR_ARG, "pl_geom_spmv_multi: null argument");
-  if (n_rhs < 1 || n_rhs > PL_MULTI_MAX) return fail(PL_ERR_ARG, "pl_geom_spmv_multi: n_rhs must be 1 ... PL_MULTI_MAX");
   GeomWs *g = nullptr;
-  if (int rc = geom_begin(h, "pl_geom_spmv_multi", u, masked != 0, &g)) return rc;
-  const MultiShape s = multi_shape(h, n_rhs);
-  MultiWs *w = nullptr;
-  if (int rc = multi_ws(h, s, false, &w)) return rc;
-  if (int rc = multi_upload(h, w, s, x, w->F.p, masked ? -1 : 0)) return rc;
-  const bool timing = std::getenv("PL_TIMING") != nullptr;
-  if (timing) PL_HIP(hipEventRecord(h->ev0, h->stream));
-  if (int rc = launch_geom_multi(h, g, s, w->F.p, w->U.p, masked != 0)) return rc;
-  if (timing) {
-    PL_HIP(hipEventRecord(h->ev1, h->stream));
-    PL_HIP(hipEventSynchronize(h->ev1));
-    float ms = 0.f;
-    PL_HIP(hipEventElapsedTime(&ms, h->ev0, h->ev1));
-    std::fprintf(stderr, "[pl_geom_spmv_multi] %-28s %10.4f ms\n", "kernel_hip_event", (double)ms);
-  }
-  return multi_download(h, w, s, w->U.p, y);
+  return spmv_multi_call(h, "pl_geom_spmv_multi", multi_shape, n_rhs, masked, x, y,
+                         [&] { return geom_begin(h, "pl_geom_spmv_multi", u, masked != 0, &g); },
+                         [&] { return pl::GeomTerm{g->rec.p}; });
 }
 
 namespace {
@@ -2253,6 +2268,63 @@ int pl_buckling_modes(pl_handle h, const double *u, int32_t n_modes, int32_t n_s
                       outer_iterations);
 }
 
+namespace {
+// What the two mode-sensitivity calls share around their kernels.  A mode whose value is NaN (beyond n_found of the modes call)
+// is skipped: the live ones are the columns.
+struct ModeSens {
+  std::vector<int> live;           // column -> mode
+  MultiShape s;
+  MultiWs *w = nullptr;
+  unsigned nchunk = 0;
+};
+// Fills the rows of the skipped modes with NaN, packs the live modes into g->X (zero on the fixed dofs), uploads [value | weight]
+// to g->scoef and sizes the workspaces (solver: those of pcg_solve_multi too; quad: g->sq).  No live mode: dsum = 0 and
+// ms->live stays empty - the caller returns PL_OK.
+int mode_sens_begin(pl_handle h, GeomWs *g, int32_t n_modes, const double *value, const double *modes, const double *weights,
+                    bool solver, bool quad, double *rows, double *dsum, ModeSens *ms) {
+  const int64_t B = h->B, n6 = h->N * 6;
+  for (int j = 0; j < n_modes; ++j)
+    if (!std::isnan(value[j])) ms->live.push_back(j);
+  const int nl = (int)ms->live.size();
+  if (rows) std::fill(rows, rows + (size_t)n_modes * B, std::numeric_limits<double>::quiet_NaN());
+  if (nl == 0) {
+    if (dsum) std::fill(dsum, dsum + B, 0.0);
+    return PL_OK;
+  }
+  std::vector<double> packed;
+  const double *phi_host = modes;
+  if (nl < n_modes) {
+    packed.resize((size_t)nl * n6);
+    for (int j = 0; j < nl; ++j)
+      std::memcpy(&packed[(size_t)j * n6], modes + (size_t)ms->live[j] * n6, (size_t)n6 * sizeof(double));
+    phi_host = packed.data();
+  }
+  const MultiShape s = ms->s = multi_shape(h, nl);
+  if (int rc = multi_ws(h, s, solver, &ms->w)) return rc;
+  ms->nchunk = std::min(grid_stream(n6), 512u);
+  if (int rc = geom_ws_modes(h, g, s, ms->nchunk)) return rc;
+  if (int rc = geom_ws_sens(h, g, s, quad)) return rc;
+  std::vector<double> coef((size_t)2 * s.ncol, 0.0);
+  for (int j = 0; j < nl; ++j) {
+    coef[(size_t)j] = value[ms->live[j]];
+    coef[(size_t)s.ncol + j] = weights ? weights[ms->live[j]] : 0.0;
+  }
+  PL_HIP(hipMemcpyAsync(g->scoef.p, coef.data(), coef.size() * sizeof(double), hipMemcpyHostToDevice, h->stream));
+  PL_HIP(hipStreamSynchronize(h->stream));        // (coef is pageable host memory)
+  return multi_upload(h, ms->w, s, phi_host, g->X.p, -1);
+}
+// the per-strut rows g->sdlam[column] back to the rows of their modes, and the weighted sum behind them
+int mode_sens_end(pl_handle h, GeomWs *g, const ModeSens &ms, double *rows, double *dsum) {
+  const size_t B = (size_t)h->B, nl = ms.live.size();
+  if (rows)
+    for (size_t j = 0; j < nl; ++j)
+      if (int rc = download_struts(h, g->sdlam.p + j * B, rows + (size_t)ms.live[j] * B)) return rc;
+  if (dsum)
+    if (int rc = download_struts(h, g->sdlam.p + nl * B, dsum)) return rc;
+  return PL_OK;
+}
+}  // namespace
+
 int pl_buckling_modes_sens(pl_handle h, const double *u, int32_t n_modes, const double *load_factor, const double *modes,
                            double rtol, int32_t max_iter, const double *weights, double *dlam_dr, double *dsum_dr,
                            double *adj_load) {
@@ -2268,83 +2340,43 @@ int pl_buckling_modes_sens(pl_handle h, const double *u, int32_t n_modes, const 
   if (int rc = geom_begin(h, who, u, true, &g)) return rc;
   const double *u_dev = u ? h->tmp.p : h->usol.p;
   const int64_t B = h->B, n6 = h->N * 6;
-  const double nan = std::numeric_limits<double>::quiet_NaN();
-  // a mode whose load factor is NaN (beyond n_found of pl_buckling_modes) is skipped: the live ones are the columns
-  std::vector<int> live;
-  for (int j = 0; j < n_modes; ++j)
-    if (!std::isnan(load_factor[j])) live.push_back(j);
+  if (adj_load) std::fill(adj_load, adj_load + (size_t)n_modes * n6, std::numeric_limits<double>::quiet_NaN());
+  ModeSens ms;
+  if (int rc = mode_sens_begin(h, g, n_modes, load_factor, modes, weights, true, true, dlam_dr, dsum_dr, &ms)) return rc;
+  if (ms.live.empty()) return PL_OK;
+  const std::vector<int> &live = ms.live;
   const int nl = (int)live.size();
-  if (dlam_dr) std::fill(dlam_dr, dlam_dr + (size_t)n_modes * B, nan);
-  if (adj_load) std::fill(adj_load, adj_load + (size_t)n_modes * n6, nan);
-  if (nl == 0) {
-    if (dsum_dr) std::fill(dsum_dr, dsum_dr + B, 0.0);
-    return PL_OK;
-  }
-  std::vector<double> packed;
-  const double *phi_host = modes;
-  if (nl < n_modes) {
-    packed.resize((size_t)nl * n6);
-    for (int j = 0; j < nl; ++j) std::memcpy(&packed[(size_t)j * n6], modes + (size_t)live[j] * n6, (size_t)n6 * sizeof(double));
-    phi_host = packed.data();
-  }
-  const MultiShape s = multi_shape(h, nl);
-  MultiWs *w = nullptr;
-  if (int rc = multi_ws(h, s, true, &w)) return rc;
-  const unsigned nchunk = std::min(grid_stream(n6), 512u);
-  if (int rc = geom_ws_modes(h, g, s, nchunk)) return rc;
-  if (int rc = geom_ws_sens(h, g, s)) return rc;
-  std::vector<double> coef((size_t)2 * s.ncol, 0.0);
-  for (int j = 0; j < nl; ++j) {
-    coef[(size_t)j] = load_factor[live[j]];
-    coef[(size_t)s.ncol + j] = weights ? weights[live[j]] : 0.0;
-  }
-  PL_HIP(hipMemcpyAsync(g->scoef.p, coef.data(), coef.size() * sizeof(double), hipMemcpyHostToDevice, h->stream));
-  PL_HIP(hipStreamSynchronize(h->stream));        // (coef is pageable host memory)
-  if (int rc = multi_upload(h, w, s, phi_host, g->X.p, -1)) return rc;      // the modes, zero on the fixed dofs
-  // PL_TIMING: HIP-event time of every stage ("[pl_buckling_modes_sens] <stage> <ms> ms")
-  const bool timing = std::getenv("PL_TIMING") != nullptr;
-  const char *stage_name[] = {"k_geom_quad", "k_geom_adjoint_load", "K phi and kk (gram)", "adjoint pcg_solve_multi", "k_geom_sens"};
-  hipEvent_t ev[6] = {};
-  int n_ev = 0;
-  auto mark = [&]() {
-    if (timing && hipEventCreate(&ev[n_ev]) == hipSuccess) (void)hipEventRecord(ev[n_ev++], h->stream);
-  };
+  const MultiShape s = ms.s;
+  MultiWs *w = ms.w;
+  EventTimer timer(who, h->stream);
   int rc = PL_OK, missed = 0;
   bool bad = false;
   std::vector<double> status((size_t)pl::M_ST_COUNT * s.ncol);
   do {
-    mark();
+    timer.mark("k_geom_quad");
     if ((rc = launch_geom_quad(h, g, s, g->X.p))) break;
-    mark();
+    timer.mark("k_geom_adjoint_load");
     if ((rc = launch_adjoint_load(h, g, s, w->F.p))) break;                  // loads -w_i
-    mark();
+    timer.mark("K phi and kk (gram)");
     if (dlam_dr || dsum_dr) {
       if ((rc = launch_spmv_multi(h, s, h->fixedbits.p, g->X.p, g->KX.p, true, nullptr))) break;
-      if ((rc = launch_gram(h, g, s, nchunk, g->X.p, g->KX.p, g->M.p))) break;       // kk_i on its diagonal
-      mark();
+      if ((rc = launch_gram(h, g, s, ms.nchunk, g->X.p, g->KX.p, g->M.p))) break;    // kk_i on its diagonal
+      timer.mark("adjoint pcg_solve_multi");
       if (hipMemsetAsync(w->UB.p, 0, (size_t)s.ncb * s.stride * sizeof(double), h->stream) != hipSuccess) {
         rc = fail(PL_ERR_HIP, "pl_buckling_modes_sens: memset failed");
         break;
       }
       if ((rc = pcg_solve_multi(h, w, s, h->fixedbits.p, w->F.p, rtol, max_iter, status.data()))) break;   // nu_i in w->U
       missed = multi_stats(s, status.data(), rtol, 0.0, nullptr, &bad);
-      mark();
+      timer.mark("k_geom_sens");
       if ((rc = launch_geom_sens(h, g, s, u_dev, g->X.p, w->U.p, dlam_dr ? g->sdlam.p : (double *)nullptr,
                                  dsum_dr ? g->sdlam.p + (size_t)nl * B : (double *)nullptr)))
         break;
-      mark();
+      timer.mark();
     }
   } while (false);
-  if (timing && rc == PL_OK) {
-    (void)hipStreamSynchronize(h->stream);
-    for (int i = 0; i + 1 < n_ev; ++i) {
-      float ms = 0.f;
-      if (hipEventElapsedTime(&ms, ev[i], ev[i + 1]) == hipSuccess)
-        std::fprintf(stderr, "[pl_buckling_modes_sens] %-28s %10.4f ms\n", stage_name[i], (double)ms);
-    }
-  }
-  for (int i = 0; i < n_ev; ++i) (void)hipEventDestroy(ev[i]);
   if (rc) return rc;
+  timer.report();
   if (adj_load) {                                 // w_i = -(the load of the adjoint solve), unmasked
     std::vector<double> wl((size_t)nl * n6);
     if ((rc = multi_download(h, w, s, w->F.p, wl.data()))) return rc;
@@ -2353,11 +2385,7 @@ int pl_buckling_modes_sens(pl_handle h, const double *u, int32_t n_modes, const 
       for (int64_t e = 0; e < n6; ++e) dst[e] = -wl[(size_t)j * n6 + e];
     }
   }
-  if (dlam_dr)
-    for (int j = 0; j < nl; ++j)
-      if ((rc = download_struts(h, g->sdlam.p + (size_t)j * B, dlam_dr + (size_t)live[j] * B))) return rc;
-  if (dsum_dr)
-    if ((rc = download_struts(h, g->sdlam.p + (size_t)nl * B, dsum_dr))) return rc;
+  if ((rc = mode_sens_end(h, g, ms, dlam_dr, dsum_dr))) return rc;
   if (bad) return fail(PL_ERR_NAN, "pl_buckling_modes_sens: NaN/Inf in a residual norm of the adjoint solve");
   if (missed)
     return fail(PL_ERR_NOCONV, "pl_buckling_modes_sens: " + std::to_string(missed) + " adjoint column(s) did not reach rtol within max_iter");
@@ -2405,25 +2433,9 @@ int pl_set_mass(pl_handle h, double density, int32_t rotary, const double *node_
 }
 
 int pl_mass_spmv_multi(pl_handle h, int32_t n_rhs, int masked, const double *x, double *y) {
-  if (!valid(h) || !x || !y) return fail(PL_ERR_ARG, "pl_mass_spmv_multi: null argument");
-  if (n_rhs < 1 || n_rhs > PL_MULTI_MAX) return fail(PL_ERR_ARG, "pl_mass_spmv_multi: n_rhs must be 1 ... PL_MULTI_MAX");
   MassWs *m = nullptr;
-  if (int rc = mass_begin(h, "pl_mass_spmv_multi", masked != 0, &m)) return rc;
-  const MultiShape s = multi_shape(h, n_rhs);
-  MultiWs *w = nullptr;
-  if (int rc = multi_ws(h, s, false, &w)) return rc;
-  if (int rc = multi_upload(h, w, s, x, w->F.p, masked ? -1 : 0)) return rc;
-  const bool timing = std::getenv("PL_TIMING") != nullptr;
-  if (timing) PL_HIP(hipEventRecord(h->ev0, h->stream));
-  if (int rc = launch_mass_multi(h, m, s, w->F.p, w->U.p, masked != 0)) return rc;
-  if (timing) {
-    PL_HIP(hipEventRecord(h->ev1, h->stream));
-    PL_HIP(hipEventSynchronize(h->ev1));
-    float ms = 0.f;
-    PL_HIP(hipEventElapsedTime(&ms, h->ev0, h->ev1));
-    std::fprintf(stderr, "[pl_mass_spmv_multi] %-28s %10.4f ms\n", "kernel_hip_event", (double)ms);
-  }
-  return multi_download(h, w, s, w->U.p, y);
+  return spmv_multi_call(h, "pl_mass_spmv_multi", multi_shape, n_rhs, masked, x, y,
+                         [&] { return mass_begin(h, "pl_mass_spmv_multi", masked != 0, &m); }, [&] { return mass_term(m); });
 }
 
 int pl_vibration_modes(pl_handle h, int32_t n_modes, int32_t n_sub, double rtol, int32_t max_iter, double tol,
@@ -2454,103 +2466,29 @@ int pl_vibration_modes_sens(pl_handle h, int32_t n_modes, const double *omega2, 
   if (int rc = mass_begin(h, who, true, &m)) return rc;
   GeomWs *g = nullptr;
   if (int rc = geom_ws(h, &g)) return rc;
-  const int64_t B = h->B, n6 = h->N * 6;
-  const double nan = std::numeric_limits<double>::quiet_NaN();
-  // a mode whose omega^2 is NaN (beyond n_found of pl_vibration_modes) is skipped: the live ones are the columns
-  std::vector<int> live;
-  for (int j = 0; j < n_modes; ++j)
-    if (!std::isnan(omega2[j])) live.push_back(j);
-  const int nl = (int)live.size();
-  if (domega2_dr) std::fill(domega2_dr, domega2_dr + (size_t)n_modes * B, nan);
-  if (nl == 0) {
-    if (dsum_dr) std::fill(dsum_dr, dsum_dr + B, 0.0);
-    return PL_OK;
-  }
-  std::vector<double> packed;
-  const double *phi_host = modes;
-  if (nl < n_modes) {
-    packed.resize((size_t)nl * n6);
-    for (int j = 0; j < nl; ++j) std::memcpy(&packed[(size_t)j * n6], modes + (size_t)live[j] * n6, (size_t)n6 * sizeof(double));
-    phi_host = packed.data();
-  }
-  const MultiShape s = multi_shape(h, nl);
-  MultiWs *w = nullptr;
-  if (int rc = multi_ws(h, s, false, &w)) return rc;
-  const unsigned nchunk = std::min(grid_stream(n6), 512u);
-  if (int rc = geom_ws_modes(h, g, s, nchunk)) return rc;
-  if (g->sdlam.n < (size_t)(nl + 1) * B) PL_HIP(g->sdlam.alloc((size_t)(nl + 1) * B));
-  if (!g->scoef.p) PL_HIP(g->scoef.alloc((size_t)2 * PL_MULTI_MAX));
-  std::vector<double> coef((size_t)2 * s.ncol, 0.0);
-  for (int j = 0; j < nl; ++j) {
-    coef[(size_t)j] = omega2[live[j]];
-    coef[(size_t)s.ncol + j] = weights ? weights[live[j]] : 0.0;
-  }
-  PL_HIP(hipMemcpyAsync(g->scoef.p, coef.data(), coef.size() * sizeof(double), hipMemcpyHostToDevice, h->stream));
-  PL_HIP(hipStreamSynchronize(h->stream));        // (coef is pageable host memory)
-  if (int rc = multi_upload(h, w, s, phi_host, g->X.p, -1)) return rc;      // the modes, zero on the fixed dofs
-  // PL_TIMING: HIP-event time of every stage ("[pl_vibration_modes_sens] <stage> <ms> ms")
-  const bool timing = std::getenv("PL_TIMING") != nullptr;
-  const char *stage_name[] = {"M phi and mm (gram)", "k_mass_sens"};
-  hipEvent_t ev[3] = {};
-  int n_ev = 0;
-  auto mark = [&]() {
-    if (timing && hipEventCreate(&ev[n_ev]) == hipSuccess) (void)hipEventRecord(ev[n_ev++], h->stream);
-  };
-  int rc = PL_OK;
-  do {
-    mark();
-    if ((rc = launch_mass_multi(h, m, s, g->X.p, g->GX.p, true))) break;
-    if ((rc = launch_gram(h, g, s, nchunk, g->X.p, g->GX.p, g->M.p))) break;         // mm_i = phi_i^T M phi_i on its diagonal
-    mark();
-    if ((rc = launch_mass_sens(h, g, m, s, g->X.p, domega2_dr ? g->sdlam.p : (double *)nullptr,
-                               dsum_dr ? g->sdlam.p + (size_t)nl * B : (double *)nullptr)))
-      break;
-    mark();
-  } while (false);
-  if (timing && rc == PL_OK) {
-    (void)hipStreamSynchronize(h->stream);
-    for (int i = 0; i + 1 < n_ev; ++i) {
-      float ms = 0.f;
-      if (hipEventElapsedTime(&ms, ev[i], ev[i + 1]) == hipSuccess)
-        std::fprintf(stderr, "[pl_vibration_modes_sens] %-28s %10.4f ms\n", stage_name[i], (double)ms);
-    }
-  }
-  for (int i = 0; i < n_ev; ++i) (void)hipEventDestroy(ev[i]);
-  if (rc) return rc;
-  if (domega2_dr)
-    for (int j = 0; j < nl; ++j)
-      if ((rc = download_struts(h, g->sdlam.p + (size_t)j * B, domega2_dr + (size_t)live[j] * B))) return rc;
-  if (dsum_dr)
-    if ((rc = download_struts(h, g->sdlam.p + (size_t)nl * B, dsum_dr))) return rc;
-  return PL_OK;
+  const int64_t B = h->B;
+  ModeSens ms;
+  if (int rc = mode_sens_begin(h, g, n_modes, omega2, modes, weights, false, false, domega2_dr, dsum_dr, &ms)) return rc;
+  if (ms.live.empty()) return PL_OK;
+  const size_t nl = ms.live.size();
+  EventTimer timer(who, h->stream, "M phi and mm (gram)");
+  if (int rc = launch_mass_multi(h, m, ms.s, g->X.p, g->GX.p, true)) return rc;
+  if (int rc = launch_gram(h, g, ms.s, ms.nchunk, g->X.p, g->GX.p, g->M.p)) return rc;     // mm_i = phi_i^T M phi_i on its diagonal
+  timer.mark("k_mass_sens");
+  if (int rc = launch_mass_sens(h, g, m, ms.s, g->X.p, domega2_dr ? g->sdlam.p : (double *)nullptr,
+                                dsum_dr ? g->sdlam.p + nl * B : (double *)nullptr))
+    return rc;
+  timer.stop();
+  return mode_sens_end(h, g, ms, domega2_dr, dsum_dr);
 }
 
 // ---- transient response (pl_dyn.h) -------------------------------------------------------------------------------------
 int pl_dyn_spmv_multi(pl_handle h, double c_K, double c_M, int32_t n_rhs, int masked, const double *x, double *y) {
-  if (!valid(h) || !x || !y) return fail(PL_ERR_ARG, "pl_dyn_spmv_multi: null argument");
-  if (n_rhs < 1 || n_rhs > PL_MULTI_MAX) return fail(PL_ERR_ARG, "pl_dyn_spmv_multi: n_rhs must be 1 ... PL_MULTI_MAX");
-  if (!std::isfinite(c_K) || !std::isfinite(c_M)) return fail(PL_ERR_ARG, "pl_dyn_spmv_multi: c_K and c_M must be finite");
   MassWs *m = nullptr;
-  if (int rc = mass_begin(h, "pl_dyn_spmv_multi", masked != 0, &m)) return rc;
-  const MultiShape s = dyn_shape(h, n_rhs);
-  MultiWs *w = nullptr;
-  if (int rc = multi_ws(h, s, false, &w)) return rc;
-  if (int rc = multi_upload(h, w, s, x, w->F.p, masked ? -1 : 0)) return rc;
-  MultiOp op;
-  op.c_K = c_K;
-  op.c_M = c_M;
-  op.mass = m;
-  const bool timing = std::getenv("PL_TIMING") != nullptr;
-  if (timing) PL_HIP(hipEventRecord(h->ev0, h->stream));
-  if (int rc = launch_dyn_multi(h, op, s, h->fixedbits.p, w->F.p, w->U.p, masked != 0, nullptr)) return rc;
-  if (timing) {
-    PL_HIP(hipEventRecord(h->ev1, h->stream));
-    PL_HIP(hipEventSynchronize(h->ev1));
-    float ms = 0.f;
-    PL_HIP(hipEventElapsedTime(&ms, h->ev0, h->ev1));
-    std::fprintf(stderr, "[pl_dyn_spmv_multi] %-28s %10.4f ms\n", "kernel_hip_event", (double)ms);
-  }
-  return multi_download(h, w, s, w->U.p, y);
+  return spmv_multi_call(h, "pl_dyn_spmv_multi", dyn_shape, n_rhs, masked, x, y, [&]() -> int {
+    if (!std::isfinite(c_K) || !std::isfinite(c_M)) return fail(PL_ERR_ARG, "pl_dyn_spmv_multi: c_K and c_M must be finite");
+    return mass_begin(h, "pl_dyn_spmv_multi", masked != 0, &m);
+  }, [&] { return pl::DynTerm{h->rec.p, mass_term(m), c_K, c_M}; });
 }
 
 int pl_transient(pl_handle h, int32_t n_steps, double dt, double beta, double gamma, double ray_m, double ray_k, int32_t n_pat,
@@ -2719,29 +2657,6 @@ int pl_transient(pl_handle h, int32_t n_steps, double dt, double beta, double ga
   return PL_OK;
 }
 
-// PL_TIMING: HIP-event time of one launch on the null stream ("[<call>] kernel_hip_event <ms> ms", four decimals)
-struct KernelEventTimer {
-  const char *what;
-  bool on;
-  hipEvent_t e0 = nullptr, e1 = nullptr;
-  KernelEventTimer(const char *w, bool enabled) : what(w), on(enabled) {
-    if (on && (hipEventCreate(&e0) != hipSuccess || hipEventCreate(&e1) != hipSuccess)) on = false;
-    if (on) (void)hipEventRecord(e0, nullptr);
-  }
-  void stop() {
-    if (on) (void)hipEventRecord(e1, nullptr);
-  }
-  void report() {                                  // after the stream was synchronised
-    float ms = 0.0f;
-    if (on && hipEventElapsedTime(&ms, e0, e1) == hipSuccess)
-      std::fprintf(stderr, "[%s] %-28s %10.4f ms\n", what, "kernel_hip_event", (double)ms);
-  }
-  ~KernelEventTimer() {
-    if (e0) (void)hipEventDestroy(e0);
-    if (e1) (void)hipEventDestroy(e1);
-  }
-};
-
 int pl_schur_cells(const pl_opts_t *o, int32_t n_inst, int32_t n_nodes, int32_t n_beams, const int32_t *beam_conn,
                    int32_t nb, const int32_t *boundary_nodes, const double *node_xyz, const double *beam_radius,
                    const double *seg_len, const int32_t *seg_nsub, double *S, int32_t *info) {
@@ -2833,9 +2748,9 @@ int pl_schur_cells(const pl_opts_t *o, int32_t n_inst, int32_t n_nodes, int32_t 
   if (lds > 64 * 1024)
     PL_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&pl::k_schur_cells),
                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-  KernelEventTimer kernel_time("pl_schur_cells", stage.on);
+  EventTimer kernel_time("pl_schur_cells", nullptr, "kernel_hip_event");
   hipLaunchKernelGGL(pl::k_schur_cells, dim3((unsigned)n_inst), dim3(pl::kCondBlock), lds, nullptr, a);
-  kernel_time.stop();
+  kernel_time.mark();
   PL_HIP(hipGetLastError());
   PL_HIP(hipDeviceSynchronize());
   kernel_time.report();
@@ -2938,9 +2853,9 @@ int pl_cells_recover(const pl_opts_t *o, int32_t n_inst, int32_t n_nodes, int32_
   if (lds > 64 * 1024)
     PL_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&pl::k_cells_recover),
                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-  KernelEventTimer kernel_time("pl_cells_recover", stage.on);
+  EventTimer kernel_time("pl_cells_recover", nullptr, "kernel_hip_event");
   hipLaunchKernelGGL(pl::k_cells_recover, dim3((unsigned)n_inst), dim3((unsigned)block), lds, nullptr, a);
-  kernel_time.stop();
+  kernel_time.mark();
   PL_HIP(hipGetLastError());
   PL_HIP(hipDeviceSynchronize());
   kernel_time.report();

@@ -9,7 +9,7 @@
 // a_0 is the same three stages with dt = 0: M a_0 = f_0 - K u_0 - C v_0.  The matrix of the solve is S = c_K K + c_M M, SPD for
 // c_K >= 0, c_M > 0; the solver is the multi-column Jacobi PCG of pl_multi.h on one column with S in the place of K.
 //
-// S x is ONE gather (k_dyn_gather_multi): the node -> strut walk of k_spmv_gather_multi / k_mass_gather_multi, the ELL entry
+// S x is ONE gather (k_gather_multi with DynTerm): the node -> strut walk of the K and M products, the ELL entry
 // and the neighbour's row read once, the stiffness record and the mass record read at the same strut index, both closed
 // forms summed into the same registers.  The linear scalars of the stiffness record (a, c, e1, e2, e3) carry c_K and the four
 // mass scalars (m / 6, c, j, g) carry c_M, so the sum costs no multiplication per dof.
@@ -40,126 +40,41 @@ __device__ __forceinline__ void mass_diag(const MassCoef &q, V3 d, double *dg) {
   }
 }
 
-// ---------------------------------------------------------------------------------------------------------
-// y_k = c_K K x_k + c_M M x_k (MASK: P (...), x_k assumed 0 on fixed dofs) for the KB columns of column block blockIdx.y.
-// Lane mapping, sliced ELL, xcd_block, lpn_sum, masked store, thirds-of-a-row store and the dot_out slots are those of
-// k_spmv_gather_multi.  Per entry: one ent[p], one load_row of the neighbour; the stiffness record is loaded, reversed, scaled
-// and used up before the mass record is loaded, so only one of the two is live at a time.
-// ---------------------------------------------------------------------------------------------------------
-template <int LPN, int KB, bool MASK>
-__global__ __launch_bounds__(kBlock) void k_dyn_gather_multi(int64_t N, const int64_t *__restrict__ slice_ptr,
-                                                             const int2 *__restrict__ ent, const Record *__restrict__ rec,
-                                                             const MassRecord *__restrict__ mrec, int rotary,
-                                                             const double *__restrict__ node_mass, double c_K, double c_M,
-                                                             const uint8_t *__restrict__ fixedbits,
-                                                             const double *__restrict__ x, double *__restrict__ y,
-                                                             double *__restrict__ dot_out, int64_t stride) {
-  __shared__ double red[KB][kBlock / kWave];
-  const unsigned blk = xcd_block(blockIdx.x, gridDim.x);
-  const int cb = blockIdx.y;
-  x += (size_t)cb * stride;
-  y += (size_t)cb * stride;
-  constexpr int kSliceNodes = kWave / LPN;
-  const int lane = threadIdx.x & 63, sub = lane / kSliceNodes;
-  const int64_t slice = (int64_t)blk * (kBlock / kWave) + (threadIdx.x >> 6);
-  const int64_t i = slice * kSliceNodes + (lane & (kSliceNodes - 1));
-  double acc[KB];
-#pragma unroll
-  for (int k = 0; k < KB; ++k) acc[k] = 0.0;
-  if (slice * kSliceNodes < N) {          // wave-uniform
-    const bool live = i < N;
-    double xs[6 * KB], out[6 * KB];
-#pragma unroll
-    for (int q = 0; q < 6 * KB; ++q) { xs[q] = 0.0; out[q] = 0.0; }
-    if (live) load_row<KB>(x, i, xs);
-    const int64_t p0 = slice_ptr[slice], p1 = slice_ptr[slice + 1];
-#pragma unroll 1
-    for (int64_t p = p0 + lane; p < p1; p += 64) {
-      const int2 e = ent[p];
-      if (e.x >= 0) {
-        const int64_t b = e.y & 0x7fffffff;
-        double xo[6 * KB];
-        load_row<KB>(x, (int64_t)e.x, xo);
-        {
-          Record r = load_record(rec, b);
-          if (e.y < 0) r = reversed(r);   // this node is the strut's point1
-          r = scaled_record(r, c_K);
-#pragma unroll
-          for (int k = 0; k < KB; ++k) {
-            V3 uo, to, us, ts, f, m;
-            column_of<KB>(xo, k, uo, to);
-            column_of<KB>(xs, k, us, ts);
-            tip_force(r, uo, to, us, ts, f, m);
-            out[0 * KB + k] += f.x; out[1 * KB + k] += f.y; out[2 * KB + k] += f.z;
-            out[3 * KB + k] += m.x; out[4 * KB + k] += m.y; out[5 * KB + k] += m.z;
-          }
-        }
-        {
-          const MassRecord r = load_mass(mrec, b);
-          MassCoef c = mass_coef(r, rotary);
-          c = {c_M * c.m6, c_M * c.c, c_M * c.j, c_M * c.g};
-          const double sg = e.y < 0 ? -1.0 : 1.0;                     // point1: d -> -d
-          const V3 d = {sg * r.dx, sg * r.dy, sg * r.dz};
-#pragma unroll
-          for (int k = 0; k < KB; ++k) {
-            V3 uo, to, us, ts, f, m;
-            column_of<KB>(xo, k, uo, to);
-            column_of<KB>(xs, k, us, ts);
-            mass_force(c, d, uo, to, us, ts, f, m);
-            out[0 * KB + k] += f.x; out[1 * KB + k] += f.y; out[2 * KB + k] += f.z;
-            out[3 * KB + k] += m.x; out[4 * KB + k] += m.y; out[5 * KB + k] += m.z;
-          }
-        }
-      }
+// c_K K + c_M M in k_gather_multi (pl_multi.h): per entry the stiffness record is loaded, reversed, scaled and used up before
+// the mass record is loaded, so only one of the two is live at a time - that is why the fused product fits in the registers of
+// the mass product.  Built for column blocks of 1 and 2: at 4 it would need scratch.
+struct DynTerm {
+  static constexpr int kMaxKB = 2;
+  const Record *__restrict__ rec;
+  MassTerm mass;
+  double c_K, c_M;
+  template <int KB>
+  __device__ __forceinline__ void entry(int64_t strut, bool point1, const double (&xo)[6 * KB], const double (&xs)[6 * KB],
+                                        double (&out)[6 * KB]) const {
+    {
+      Record r = load_record(rec, strut);
+      if (point1) r = reversed(r);
+      r = scaled_record(r, c_K);
+      add_tip_forces<KB>(r, xo, xs, out);
     }
-#pragma unroll
-    for (int q = 0; q < 6 * KB; ++q) out[q] = lpn_sum<LPN>(out[q]);
-    if (live) {
-      if (node_mass) {                    // kernel-uniform; every lane of the node holds the whole row by now
-        const double nm = c_M * node_mass[i];
-#pragma unroll
-        for (int q = 0; q < 3 * KB; ++q) out[q] += nm * xs[q];
-      }
-      if (MASK) {
-        const unsigned fb = fixedbits[i];
-#pragma unroll
-        for (int d = 0; d < 6; ++d)
-          if (fb & (1u << d)) {
-#pragma unroll
-            for (int k = 0; k < KB; ++k) out[d * KB + k] = 0.0;
-          }
-      }
-      double2 *q = reinterpret_cast<double2 *>(y + 6 * KB * i);
-      if (LPN >= 4) {   // lanes sub = 0, 1, 2 of a node store one third of its row each (2 dofs x KB columns, contiguous)
-        if (sub == 0) {
-#pragma unroll
-          for (int j = 0; j < KB; ++j) q[j] = {out[2 * j], out[2 * j + 1]};
-        } else if (sub == 1) {
-#pragma unroll
-          for (int j = KB; j < 2 * KB; ++j) q[j] = {out[2 * j], out[2 * j + 1]};
-        } else if (sub == 2) {
-#pragma unroll
-          for (int j = 2 * KB; j < 3 * KB; ++j) q[j] = {out[2 * j], out[2 * j + 1]};
-        }
-      } else if (sub == 0) {
-#pragma unroll
-        for (int j = 0; j < 3 * KB; ++j) q[j] = {out[2 * j], out[2 * j + 1]};
-      }
-      if (dot_out && sub == 0) {
-#pragma unroll
-        for (int k = 0; k < KB; ++k)
-          acc[k] = xs[0 * KB + k] * out[0 * KB + k] + xs[1 * KB + k] * out[1 * KB + k] + xs[2 * KB + k] * out[2 * KB + k] +
-                   xs[3 * KB + k] * out[3 * KB + k] + xs[4 * KB + k] * out[4 * KB + k] + xs[5 * KB + k] * out[5 * KB + k];
-      }
+    {
+      const MassRecord r = load_mass(mass.rec, strut);
+      MassCoef c = mass_coef(r, mass.rotary);
+      c = {c_M * c.m6, c_M * c.c, c_M * c.j, c_M * c.g};
+      const double sg = point1 ? -1.0 : 1.0;                     // point1: d -> -d
+      const V3 d = {sg * r.dx, sg * r.dy, sg * r.dz};
+      add_mass_forces<KB>(c, d, xo, xs, out);
     }
   }
-  if (dot_out) {   // kernel-uniform
-    double *dst[KB];
+  template <int KB>
+  __device__ __forceinline__ void node(int64_t i, const double (&xs)[6 * KB], double (&out)[6 * KB]) const {
+    if (mass.node_mass) {               // kernel-uniform
+      const double nm = c_M * mass.node_mass[i];
 #pragma unroll
-    for (int k = 0; k < KB; ++k) dst[k] = dot_out + (size_t)(cb * KB + k) * kSlots;
-    block_add_slots<KB>(acc, red, dst);
+      for (int q = 0; q < 3 * KB; ++q) out[q] += nm * xs[q];
+    }
   }
-}
+};
 
 // diag(c_K K + c_M M) and its inverse on the free dofs (0 on fixed dofs and where the diagonal vanishes), as k_diag_gather
 template <int LPN>
@@ -290,7 +205,7 @@ __global__ __launch_bounds__(kBlock) void k_newmark_correct(int64_t n6, const do
 namespace {
 
 // widest column block the fused gather is built for (make resource-usage: no scratch at 1 and 2)
-constexpr int kDynKB = 2;
+constexpr int kDynKB = pl::DynTerm::kMaxKB;
 
 // column blocks of the fused product: KB = min(n_rhs, kDynKB)
 inline MultiShape dyn_shape(const pl_context *c, int n_rhs) {
@@ -303,43 +218,11 @@ inline MultiShape dyn_shape(const pl_context *c, int n_rhs) {
   return s;
 }
 
-template <int LPN, int KB>
-void launch_dyn_multi_t(pl_context *c, const MultiOp &op, const MultiShape &s, const uint8_t *fixedbits, const double *x,
-                        double *y, bool masked, double *dot_dev) {
-  const dim3 grid(grid_for(c->n_slices, pl::kBlock / pl::kWave), (unsigned)s.ncb);   // one wave per ELL slice and column block
-  const MassWs *m = op.mass;
-  if (masked)
-    hipLaunchKernelGGL((pl::k_dyn_gather_multi<LPN, KB, true>), grid, dim3(pl::kBlock), 0, c->stream, c->N, c->slice_ptr.p,
-                       c->ent.p, (const pl::Record *)c->rec.p, (const pl::MassRecord *)m->rec.p, m->rotary, m->nm(), op.c_K,
-                       op.c_M, fixedbits, x, y, dot_dev, s.stride);
-  else
-    hipLaunchKernelGGL((pl::k_dyn_gather_multi<LPN, KB, false>), grid, dim3(pl::kBlock), 0, c->stream, c->N, c->slice_ptr.p,
-                       c->ent.p, (const pl::Record *)c->rec.p, (const pl::MassRecord *)m->rec.p, m->rotary, m->nm(), op.c_K,
-                       op.c_M, fixedbits, x, y, dot_dev, s.stride);
-}
-template <int LPN>
-int launch_dyn_multi_lpn(pl_context *c, const MultiOp &op, const MultiShape &s, const uint8_t *fixedbits, const double *x,
-                         double *y, bool masked, double *dot_dev) {
-  if (s.KB == 1) launch_dyn_multi_t<LPN, 1>(c, op, s, fixedbits, x, y, masked, dot_dev);
-  else if (s.KB == 2) launch_dyn_multi_t<LPN, 2>(c, op, s, fixedbits, x, y, masked, dot_dev);
-  else return fail(PL_ERR_ARG, "the fused K, M product is built for column blocks of 1 and 2");   // a missing kernel is an error
-  return PL_OK;
-}
 // y_j = (c_K K + c_M M) x_j (masked: P (...)) for every column of the shape, one launch; the mass records must be current
 int launch_dyn_multi(pl_context *c, const MultiOp &op, const MultiShape &s, const uint8_t *fixedbits, const double *x, double *y,
                      bool masked, double *dot_dev) {
-  int rc = PL_OK;
-  switch (c->lpn) {
-    case 1: rc = launch_dyn_multi_lpn<1>(c, op, s, fixedbits, x, y, masked, dot_dev); break;
-    case 2: rc = launch_dyn_multi_lpn<2>(c, op, s, fixedbits, x, y, masked, dot_dev); break;
-    case 4: rc = launch_dyn_multi_lpn<4>(c, op, s, fixedbits, x, y, masked, dot_dev); break;
-    case 8: rc = launch_dyn_multi_lpn<8>(c, op, s, fixedbits, x, y, masked, dot_dev); break;
-    case 16: rc = launch_dyn_multi_lpn<16>(c, op, s, fixedbits, x, y, masked, dot_dev); break;
-    default: return fail(PL_ERR_ARG, "lanes per node must be 1, 2, 4, 8 or 16");
-  }
-  if (rc) return rc;
-  PL_HIP(hipGetLastError());
-  return PL_OK;
+  if (s.KB > kDynKB) return fail(PL_ERR_ARG, "the fused K, M product is built for column blocks of 1 and 2");   // a missing kernel is an error
+  return launch_gather_multi(c, s, pl::DynTerm{c->rec.p, mass_term(op.mass), op.c_K, op.c_M}, fixedbits, x, y, masked, dot_dev);
 }
 
 int launch_dyn_diag(pl_context *c, const MultiOp &op, const uint8_t *fixedbits, double *diag, double *dinv) {

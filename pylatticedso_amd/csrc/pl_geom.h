@@ -70,100 +70,27 @@ __global__ __launch_bounds__(kBlock) void k_geom_records(int64_t B, const int32_
   o[1] = {r.dy, r.dz};
 }
 
-// ---------------------------------------------------------------------------------------------------------
-// y_k = K_g x_k (MASK: P K_g x_k, x_k assumed 0 on fixed dofs) for the KB columns of column block blockIdx.y: the per-node
-// gather of k_spmv_gather_multi (same sliced ELL and lane mapping, same lpn_sum, same order of the sum over a node's
-// struts, no atomics), the geometric record loaded once per entry and negated in d for a strut's point1.
-// dot_out != null: x_k . y_k is added to dot_out[(cb KB + k) * kSlots + slot].
-// ---------------------------------------------------------------------------------------------------------
-template <int LPN, int KB, bool MASK>
-__global__ __launch_bounds__(kBlock) void k_geom_gather_multi(int64_t N, const int64_t *__restrict__ slice_ptr,
-                                                              const int2 *__restrict__ ent,
-                                                              const GeomRecord *__restrict__ rec,
-                                                              const uint8_t *__restrict__ fixedbits,
-                                                              const double *__restrict__ x, double *__restrict__ y,
-                                                              double *__restrict__ dot_out, int64_t stride) {
-  __shared__ double red[KB][kBlock / kWave];
-  const unsigned blk = xcd_block(blockIdx.x, gridDim.x);
-  const int cb = blockIdx.y;
-  x += (size_t)cb * stride;
-  y += (size_t)cb * stride;
-  constexpr int kSliceNodes = kWave / LPN;
-  const int lane = threadIdx.x & 63, sub = lane / kSliceNodes;
-  const int64_t slice = (int64_t)blk * (kBlock / kWave) + (threadIdx.x >> 6);
-  const int64_t i = slice * kSliceNodes + (lane & (kSliceNodes - 1));
-  double acc[KB];
+// K_g in k_gather_multi (pl_multi.h): the geometric record loaded once per entry and negated in d for a strut's point1
+struct GeomTerm {
+  static constexpr int kMaxKB = 4;
+  const GeomRecord *__restrict__ rec;
+  template <int KB>
+  __device__ __forceinline__ void entry(int64_t strut, bool point1, const double (&xo)[6 * KB], const double (&xs)[6 * KB],
+                                        double (&out)[6 * KB]) const {
+    GeomRecord r = load_geom(rec, strut);
+    if (point1) { r.dx = -r.dx; r.dy = -r.dy; r.dz = -r.dz; }
 #pragma unroll
-  for (int k = 0; k < KB; ++k) acc[k] = 0.0;
-  if (slice * kSliceNodes < N) {          // wave-uniform
-    const bool live = i < N;
-    double xs[6 * KB], out[6 * KB];
-#pragma unroll
-    for (int q = 0; q < 6 * KB; ++q) { xs[q] = 0.0; out[q] = 0.0; }
-    if (live) load_row<KB>(x, i, xs);
-    const int64_t p0 = slice_ptr[slice], p1 = slice_ptr[slice + 1];
-#pragma unroll 1
-    for (int64_t p = p0 + lane; p < p1; p += 64) {
-      const int2 e = ent[p];
-      if (e.x >= 0) {
-        GeomRecord r = load_geom(rec, e.y & 0x7fffffff);
-        double xo[6 * KB];
-        load_row<KB>(x, (int64_t)e.x, xo);
-        if (e.y < 0) { r.dx = -r.dx; r.dy = -r.dy; r.dz = -r.dz; }   // this node is the strut's point1
-#pragma unroll
-        for (int k = 0; k < KB; ++k) {
-          V3 uo, to, us, ts, f, m;
-          column_of<KB>(xo, k, uo, to);
-          column_of<KB>(xs, k, us, ts);
-          geom_force(r, uo, to, us, ts, f, m);
-          out[0 * KB + k] += f.x; out[1 * KB + k] += f.y; out[2 * KB + k] += f.z;
-          out[3 * KB + k] += m.x; out[4 * KB + k] += m.y; out[5 * KB + k] += m.z;
-        }
-      }
-    }
-#pragma unroll
-    for (int q = 0; q < 6 * KB; ++q) out[q] = lpn_sum<LPN>(out[q]);
-    if (live) {
-      if (MASK) {
-        const unsigned fb = fixedbits[i];
-#pragma unroll
-        for (int d = 0; d < 6; ++d)
-          if (fb & (1u << d)) {
-#pragma unroll
-            for (int k = 0; k < KB; ++k) out[d * KB + k] = 0.0;
-          }
-      }
-      double2 *q = reinterpret_cast<double2 *>(y + 6 * KB * i);
-      if (LPN >= 4) {   // lanes sub = 0, 1, 2 of a node store one third of its row each (2 dofs x KB columns, contiguous)
-        if (sub == 0) {
-#pragma unroll
-          for (int j = 0; j < KB; ++j) q[j] = {out[2 * j], out[2 * j + 1]};
-        } else if (sub == 1) {
-#pragma unroll
-          for (int j = KB; j < 2 * KB; ++j) q[j] = {out[2 * j], out[2 * j + 1]};
-        } else if (sub == 2) {
-#pragma unroll
-          for (int j = 2 * KB; j < 3 * KB; ++j) q[j] = {out[2 * j], out[2 * j + 1]};
-        }
-      } else if (sub == 0) {
-#pragma unroll
-        for (int j = 0; j < 3 * KB; ++j) q[j] = {out[2 * j], out[2 * j + 1]};
-      }
-      if (dot_out && sub == 0) {
-#pragma unroll
-        for (int k = 0; k < KB; ++k)
-          acc[k] = xs[0 * KB + k] * out[0 * KB + k] + xs[1 * KB + k] * out[1 * KB + k] + xs[2 * KB + k] * out[2 * KB + k] +
-                   xs[3 * KB + k] * out[3 * KB + k] + xs[4 * KB + k] * out[4 * KB + k] + xs[5 * KB + k] * out[5 * KB + k];
-      }
+    for (int k = 0; k < KB; ++k) {
+      V3 uo, to, us, ts, f, m;
+      column_of<KB>(xo, k, uo, to);
+      column_of<KB>(xs, k, us, ts);
+      geom_force(r, uo, to, us, ts, f, m);
+      add_column<KB>(out, k, f, m);
     }
   }
-  if (dot_out) {   // kernel-uniform
-    double *dst[KB];
-#pragma unroll
-    for (int k = 0; k < KB; ++k) dst[k] = dot_out + (size_t)(cb * KB + k) * kSlots;
-    block_add_slots<KB>(acc, red, dst);
-  }
-}
+  template <int KB>
+  __device__ __forceinline__ void node(int64_t, const double (&)[6 * KB], double (&)[6 * KB]) const {}
+};
 
 // ---------------------------------------------------------------------------------------------------------
 // All ncol x ncol dot products M[i][j] = A_i . B_j of two arrays in the column-block layout, in two stages of a fixed
@@ -319,7 +246,7 @@ __global__ __launch_bounds__(kBlock) void k_geom_quad(int64_t B, const int32_t *
 }
 
 // y_k = -w_k, the load of the adjoint solve, for the KB columns of column block blockIdx.y: the per-node gather of
-// k_geom_gather_multi (same sliced ELL and lane mapping, same lpn_sum, same order of the sum over a node's struts, no
+// k_gather_multi (same sliced ELL and lane mapping, same lpn_sum, same order of the sum over a node's struts, no
 // atomics).  An entry adds -(+-) q_{b,k} ka_b t_b to the node's three translations, + at the strut's point2 and - at its
 // point1; the rotations get zero.  Nothing is masked here: the solve masks its loads itself.
 template <int LPN, int KB>
@@ -480,34 +407,9 @@ int launch_geom_records(pl_context *c, GeomWs *g, const double *u_dev) {
   return PL_OK;
 }
 
-template <int LPN, int KB>
-void launch_geom_multi_t(pl_context *c, const GeomWs *g, const MultiShape &s, const double *x, double *y, bool masked) {
-  const dim3 grid(grid_for(c->n_slices, pl::kBlock / pl::kWave), (unsigned)s.ncb);   // one wave per ELL slice and column block
-  if (masked)
-    hipLaunchKernelGGL((pl::k_geom_gather_multi<LPN, KB, true>), grid, dim3(pl::kBlock), 0, c->stream, c->N, c->slice_ptr.p,
-                       c->ent.p, g->rec.p, c->fixedbits.p, x, y, (double *)nullptr, s.stride);
-  else
-    hipLaunchKernelGGL((pl::k_geom_gather_multi<LPN, KB, false>), grid, dim3(pl::kBlock), 0, c->stream, c->N, c->slice_ptr.p,
-                       c->ent.p, g->rec.p, c->fixedbits.p, x, y, (double *)nullptr, s.stride);
-}
-template <int LPN>
-void launch_geom_multi_lpn(pl_context *c, const GeomWs *g, const MultiShape &s, const double *x, double *y, bool masked) {
-  if (s.KB == 1) launch_geom_multi_t<LPN, 1>(c, g, s, x, y, masked);
-  else if (s.KB == 2) launch_geom_multi_t<LPN, 2>(c, g, s, x, y, masked);
-  else launch_geom_multi_t<LPN, 4>(c, g, s, x, y, masked);
-}
 // y_j = K_g x_j (masked: P K_g x_j) for every column of the shape, one launch
-int launch_geom_multi(pl_context *c, const GeomWs *g, const MultiShape &s, const double *x, double *y, bool masked) {
-  switch (c->lpn) {
-    case 1: launch_geom_multi_lpn<1>(c, g, s, x, y, masked); break;
-    case 2: launch_geom_multi_lpn<2>(c, g, s, x, y, masked); break;
-    case 4: launch_geom_multi_lpn<4>(c, g, s, x, y, masked); break;
-    case 8: launch_geom_multi_lpn<8>(c, g, s, x, y, masked); break;
-    case 16: launch_geom_multi_lpn<16>(c, g, s, x, y, masked); break;
-    default: return fail(PL_ERR_ARG, "lanes per node must be 1, 2, 4, 8 or 16");
-  }
-  PL_HIP(hipGetLastError());
-  return PL_OK;
+inline int launch_geom_multi(pl_context *c, const GeomWs *g, const MultiShape &s, const double *x, double *y, bool masked) {
+  return launch_gather_multi(c, s, pl::GeomTerm{g->rec.p}, c->fixedbits.p, x, y, masked, nullptr);
 }
 
 // M[i][j] = A_i . B_j (ncol x ncol, row-major, on the device)
@@ -532,10 +434,10 @@ int launch_combine(pl_context *c, GeomWs *g, const MultiShape &s, const double *
   return PL_OK;
 }
 
-// the per-strut arrays of pl_buckling_modes_sens for the shape s and n_modes rows of output
-int geom_ws_sens(pl_context *c, GeomWs *g, const MultiShape &s) {
+// the per-strut arrays of the mode-sensitivity calls for the shape s and n_modes rows of output (quad: q of k_geom_quad too)
+int geom_ws_sens(pl_context *c, GeomWs *g, const MultiShape &s, bool quad) {
   const size_t B = (size_t)c->B;
-  if (g->sq.n < (size_t)s.ncol * B) PL_HIP(g->sq.alloc((size_t)s.ncol * B));
+  if (quad && g->sq.n < (size_t)s.ncol * B) PL_HIP(g->sq.alloc((size_t)s.ncol * B));
   if (g->sdlam.n < (size_t)(s.n_rhs + 1) * B) PL_HIP(g->sdlam.alloc((size_t)(s.n_rhs + 1) * B));
   if (!g->scoef.p) PL_HIP(g->scoef.alloc((size_t)2 * PL_MULTI_MAX));
   return PL_OK;

@@ -77,109 +77,45 @@ __global__ __launch_bounds__(kBlock) void k_mass_records(int64_t B, const Record
   o[2] = {r.dz, 0.0};
 }
 
-// ---------------------------------------------------------------------------------------------------------
-// y_k = M x_k (MASK: P M x_k, x_k assumed 0 on fixed dofs) for the KB columns of column block blockIdx.y: the per-node
-// gather of k_geom_gather_multi (same sliced ELL and lane mapping, same lpn_sum, same order of the sum over a node's
-// struts, no atomics), the mass record loaded once per entry and negated in d for a strut's point1.  node_mass != null:
-// the node's point mass times its own translations is added once per node, after the sum over the lanes.
-// dot_out != null: x_k . y_k is added to dot_out[(cb KB + k) * kSlots + slot].
-// ---------------------------------------------------------------------------------------------------------
-template <int LPN, int KB, bool MASK>
-__global__ __launch_bounds__(kBlock) void k_mass_gather_multi(int64_t N, const int64_t *__restrict__ slice_ptr,
-                                                              const int2 *__restrict__ ent,
-                                                              const MassRecord *__restrict__ rec, int rotary,
-                                                              const double *__restrict__ node_mass,
-                                                              const uint8_t *__restrict__ fixedbits,
-                                                              const double *__restrict__ x, double *__restrict__ y,
-                                                              double *__restrict__ dot_out, int64_t stride) {
-  __shared__ double red[KB][kBlock / kWave];
-  const unsigned blk = xcd_block(blockIdx.x, gridDim.x);
-  const int cb = blockIdx.y;
-  x += (size_t)cb * stride;
-  y += (size_t)cb * stride;
-  constexpr int kSliceNodes = kWave / LPN;
-  const int lane = threadIdx.x & 63, sub = lane / kSliceNodes;
-  const int64_t slice = (int64_t)blk * (kBlock / kWave) + (threadIdx.x >> 6);
-  const int64_t i = slice * kSliceNodes + (lane & (kSliceNodes - 1));
-  double acc[KB];
+// the mass forces of the element (coefficients c, span d as seen from this node) for the KB columns
+template <int KB>
+__device__ __forceinline__ void add_mass_forces(const MassCoef &c, V3 d, const double (&xo)[6 * KB], const double (&xs)[6 * KB],
+                                                double (&out)[6 * KB]) {
 #pragma unroll
-  for (int k = 0; k < KB; ++k) acc[k] = 0.0;
-  if (slice * kSliceNodes < N) {          // wave-uniform
-    const bool live = i < N;
-    double xs[6 * KB], out[6 * KB];
-#pragma unroll
-    for (int q = 0; q < 6 * KB; ++q) { xs[q] = 0.0; out[q] = 0.0; }
-    if (live) load_row<KB>(x, i, xs);
-    const int64_t p0 = slice_ptr[slice], p1 = slice_ptr[slice + 1];
-#pragma unroll 1
-    for (int64_t p = p0 + lane; p < p1; p += 64) {
-      const int2 e = ent[p];
-      if (e.x >= 0) {
-        const MassRecord r = load_mass(rec, e.y & 0x7fffffff);
-        const MassCoef c = mass_coef(r, rotary);
-        const double sg = e.y < 0 ? -1.0 : 1.0;                     // this node is the strut's point1: d -> -d
-        const V3 d = {sg * r.dx, sg * r.dy, sg * r.dz};
-        double xo[6 * KB];
-        load_row<KB>(x, (int64_t)e.x, xo);
-#pragma unroll
-        for (int k = 0; k < KB; ++k) {
-          V3 uo, to, us, ts, f, m;
-          column_of<KB>(xo, k, uo, to);
-          column_of<KB>(xs, k, us, ts);
-          mass_force(c, d, uo, to, us, ts, f, m);
-          out[0 * KB + k] += f.x; out[1 * KB + k] += f.y; out[2 * KB + k] += f.z;
-          out[3 * KB + k] += m.x; out[4 * KB + k] += m.y; out[5 * KB + k] += m.z;
-        }
-      }
-    }
-#pragma unroll
-    for (int q = 0; q < 6 * KB; ++q) out[q] = lpn_sum<LPN>(out[q]);
-    if (live) {
-      if (node_mass) {                    // kernel-uniform; every lane of the node holds the whole row by now
-        const double nm = node_mass[i];
-#pragma unroll
-        for (int q = 0; q < 3 * KB; ++q) out[q] += nm * xs[q];
-      }
-      if (MASK) {
-        const unsigned fb = fixedbits[i];
-#pragma unroll
-        for (int d = 0; d < 6; ++d)
-          if (fb & (1u << d)) {
-#pragma unroll
-            for (int k = 0; k < KB; ++k) out[d * KB + k] = 0.0;
-          }
-      }
-      double2 *q = reinterpret_cast<double2 *>(y + 6 * KB * i);
-      if (LPN >= 4) {   // lanes sub = 0, 1, 2 of a node store one third of its row each (2 dofs x KB columns, contiguous)
-        if (sub == 0) {
-#pragma unroll
-          for (int j = 0; j < KB; ++j) q[j] = {out[2 * j], out[2 * j + 1]};
-        } else if (sub == 1) {
-#pragma unroll
-          for (int j = KB; j < 2 * KB; ++j) q[j] = {out[2 * j], out[2 * j + 1]};
-        } else if (sub == 2) {
-#pragma unroll
-          for (int j = 2 * KB; j < 3 * KB; ++j) q[j] = {out[2 * j], out[2 * j + 1]};
-        }
-      } else if (sub == 0) {
-#pragma unroll
-        for (int j = 0; j < 3 * KB; ++j) q[j] = {out[2 * j], out[2 * j + 1]};
-      }
-      if (dot_out && sub == 0) {
-#pragma unroll
-        for (int k = 0; k < KB; ++k)
-          acc[k] = xs[0 * KB + k] * out[0 * KB + k] + xs[1 * KB + k] * out[1 * KB + k] + xs[2 * KB + k] * out[2 * KB + k] +
-                   xs[3 * KB + k] * out[3 * KB + k] + xs[4 * KB + k] * out[4 * KB + k] + xs[5 * KB + k] * out[5 * KB + k];
-      }
-    }
-  }
-  if (dot_out) {   // kernel-uniform
-    double *dst[KB];
-#pragma unroll
-    for (int k = 0; k < KB; ++k) dst[k] = dot_out + (size_t)(cb * KB + k) * kSlots;
-    block_add_slots<KB>(acc, red, dst);
+  for (int k = 0; k < KB; ++k) {
+    V3 uo, to, us, ts, f, m;
+    column_of<KB>(xo, k, uo, to);
+    column_of<KB>(xs, k, us, ts);
+    mass_force(c, d, uo, to, us, ts, f, m);
+    add_column<KB>(out, k, f, m);
   }
 }
+
+// M in k_gather_multi (pl_multi.h): the mass record loaded once per entry and negated in d for a strut's point1.
+// node_mass != null: the node's point mass times its own translations is added once per node, after the sum over the lanes.
+struct MassTerm {
+  static constexpr int kMaxKB = 4;
+  const MassRecord *__restrict__ rec;
+  int rotary;
+  const double *__restrict__ node_mass;
+  template <int KB>
+  __device__ __forceinline__ void entry(int64_t strut, bool point1, const double (&xo)[6 * KB], const double (&xs)[6 * KB],
+                                        double (&out)[6 * KB]) const {
+    const MassRecord r = load_mass(rec, strut);
+    const MassCoef c = mass_coef(r, rotary);
+    const double sg = point1 ? -1.0 : 1.0;                       // this node is the strut's point1: d -> -d
+    const V3 d = {sg * r.dx, sg * r.dy, sg * r.dz};
+    add_mass_forces<KB>(c, d, xo, xs, out);
+  }
+  template <int KB>
+  __device__ __forceinline__ void node(int64_t i, const double (&xs)[6 * KB], double (&out)[6 * KB]) const {
+    if (node_mass) {                    // kernel-uniform
+      const double nm = node_mass[i];
+#pragma unroll
+      for (int q = 0; q < 3 * KB; ++q) out[q] += nm * xs[q];
+    }
+  }
+};
 
 // ---------------------------------------------------------------------------------------------------------
 // Sensitivities of omega^2 to the strut radii (pl_vibration_modes_sens).  For an eigenpair
@@ -261,36 +197,10 @@ int launch_mass_records(pl_context *c, MassWs *m) {
   return PL_OK;
 }
 
-template <int LPN, int KB>
-void launch_mass_multi_t(pl_context *c, const MassWs *m, const MultiShape &s, const double *x, double *y, bool masked) {
-  const dim3 grid(grid_for(c->n_slices, pl::kBlock / pl::kWave), (unsigned)s.ncb);   // one wave per ELL slice and column block
-  if (masked)
-    hipLaunchKernelGGL((pl::k_mass_gather_multi<LPN, KB, true>), grid, dim3(pl::kBlock), 0, c->stream, c->N, c->slice_ptr.p,
-                       c->ent.p, (const pl::MassRecord *)m->rec.p, m->rotary, m->nm(), c->fixedbits.p, x, y, (double *)nullptr,
-                       s.stride);
-  else
-    hipLaunchKernelGGL((pl::k_mass_gather_multi<LPN, KB, false>), grid, dim3(pl::kBlock), 0, c->stream, c->N, c->slice_ptr.p,
-                       c->ent.p, (const pl::MassRecord *)m->rec.p, m->rotary, m->nm(), c->fixedbits.p, x, y, (double *)nullptr,
-                       s.stride);
-}
-template <int LPN>
-void launch_mass_multi_lpn(pl_context *c, const MassWs *m, const MultiShape &s, const double *x, double *y, bool masked) {
-  if (s.KB == 1) launch_mass_multi_t<LPN, 1>(c, m, s, x, y, masked);
-  else if (s.KB == 2) launch_mass_multi_t<LPN, 2>(c, m, s, x, y, masked);
-  else launch_mass_multi_t<LPN, 4>(c, m, s, x, y, masked);
-}
+inline pl::MassTerm mass_term(const MassWs *m) { return {m->rec.p, m->rotary, m->nm()}; }
 // y_j = M x_j (masked: P M x_j) for every column of the shape, one launch
-int launch_mass_multi(pl_context *c, const MassWs *m, const MultiShape &s, const double *x, double *y, bool masked) {
-  switch (c->lpn) {
-    case 1: launch_mass_multi_lpn<1>(c, m, s, x, y, masked); break;
-    case 2: launch_mass_multi_lpn<2>(c, m, s, x, y, masked); break;
-    case 4: launch_mass_multi_lpn<4>(c, m, s, x, y, masked); break;
-    case 8: launch_mass_multi_lpn<8>(c, m, s, x, y, masked); break;
-    case 16: launch_mass_multi_lpn<16>(c, m, s, x, y, masked); break;
-    default: return fail(PL_ERR_ARG, "lanes per node must be 1, 2, 4, 8 or 16");
-  }
-  PL_HIP(hipGetLastError());
-  return PL_OK;
+inline int launch_mass_multi(pl_context *c, const MassWs *m, const MultiShape &s, const double *x, double *y, bool masked) {
+  return launch_gather_multi(c, s, mass_term(m), c->fixedbits.p, x, y, masked, nullptr);
 }
 
 // rows of domega^2/dr (dom may be null) and their weighted sum (dsum may be null) from phi, g->M and g->scoef

@@ -109,17 +109,26 @@ __device__ __forceinline__ double slots_read_v(const double *set, int which, int
 }
 
 // ---------------------------------------------------------------------------------------------------------
-// y_k = K x_k (MASK: P K x_k, x_k assumed 0 on fixed dofs) for the KB columns of column block blockIdx.y: the per-node
-// gather of k_spmv_gather (same lane mapping, same sliced ELL, same order of the sum over a node's struts and the same
-// lpn_sum, so every column is what the single-column kernel gives), each record loaded and reversed ONCE.  No atomics in
-// the product.  dot_out != null: x_k . y_k is added to dot_out[(cb KB + k) * kSlots + slot].
+// y_k = A x_k (MASK: P A x_k, x_k assumed 0 on fixed dofs) for the KB columns of column block blockIdx.y, A a sum of strut
+// elements chosen by `term`: the per-node gather of k_spmv_gather (same lane mapping, same sliced ELL, same order of the sum
+// over a node's struts and the same lpn_sum, so with the stiffness term every column is what the single-column kernel
+// gives).  No atomics in the product, and every sum has a fixed order: equal inputs give equal bits.
+// dot_out != null: x_k . y_k is added to dot_out[(cb KB + k) * kSlots + slot].
+//
+// A term is a small struct passed by value (its record pointers and scalars) with
+//     entry<KB>(strut, point1, xo, xs, out)   one ELL entry: load the strut's record ONCE, orient it for point1 (this node is
+//                                             the strut's point1), add the forces of the KB columns on this node to out;
+//                                             xo is the row of the node at the other end, xs this node's own
+//     node<KB>(i, xs, out)                    once per live node, after the sum over its lanes and before the mask
+//     kMaxKB                                  the widest column block the term is built for
+// K: StiffTerm below, K_g: GeomTerm (pl_geom.h), M: MassTerm (pl_mass.h), c_K K + c_M M: DynTerm (pl_dyn.h).
 // ---------------------------------------------------------------------------------------------------------
-template <int LPN, int KB, bool MASK>
-__global__ __launch_bounds__(kBlock) void k_spmv_gather_multi(int64_t N, const int64_t *__restrict__ slice_ptr,
-                                                              const int2 *__restrict__ ent, const Record *__restrict__ rec,
-                                                              const uint8_t *__restrict__ fixedbits,
-                                                              const double *__restrict__ x, double *__restrict__ y,
-                                                              double *__restrict__ dot_out, int64_t stride) {
+template <int LPN, int KB, bool MASK, class Term>
+__global__ __launch_bounds__(kBlock) void k_gather_multi(int64_t N, const int64_t *__restrict__ slice_ptr,
+                                                         const int2 *__restrict__ ent, const Term term,
+                                                         const uint8_t *__restrict__ fixedbits,
+                                                         const double *__restrict__ x, double *__restrict__ y,
+                                                         double *__restrict__ dot_out, int64_t stride) {
   __shared__ double red[KB][kBlock / kWave];
   const unsigned blk = xcd_block(blockIdx.x, gridDim.x);
   const int cb = blockIdx.y;
@@ -143,24 +152,15 @@ __global__ __launch_bounds__(kBlock) void k_spmv_gather_multi(int64_t N, const i
     for (int64_t p = p0 + lane; p < p1; p += 64) {
       const int2 e = ent[p];
       if (e.x >= 0) {
-        Record r = load_record(rec, e.y & 0x7fffffff);
         double xo[6 * KB];
         load_row<KB>(x, (int64_t)e.x, xo);
-        if (e.y < 0) r = reversed(r);   // this node is the strut's point1
-#pragma unroll
-        for (int k = 0; k < KB; ++k) {
-          V3 uo, to, us, ts, f, m;
-          column_of<KB>(xo, k, uo, to);
-          column_of<KB>(xs, k, us, ts);
-          tip_force(r, uo, to, us, ts, f, m);
-          out[0 * KB + k] += f.x; out[1 * KB + k] += f.y; out[2 * KB + k] += f.z;
-          out[3 * KB + k] += m.x; out[4 * KB + k] += m.y; out[5 * KB + k] += m.z;
-        }
+        term.template entry<KB>((int64_t)(e.y & 0x7fffffff), e.y < 0, xo, xs, out);
       }
     }
 #pragma unroll
     for (int q = 0; q < 6 * KB; ++q) out[q] = lpn_sum<LPN>(out[q]);
     if (live) {
+      term.template node<KB>(i, xs, out);   // every lane of the node holds the whole row by now
       if (MASK) {
         const unsigned fb = fixedbits[i];
 #pragma unroll
@@ -201,6 +201,42 @@ __global__ __launch_bounds__(kBlock) void k_spmv_gather_multi(int64_t N, const i
     block_add_slots<KB>(acc, red, dst);
   }
 }
+
+// the force f and moment m of one entry on this node, column k, into the node's row
+template <int KB>
+__device__ __forceinline__ void add_column(double (&out)[6 * KB], int k, V3 f, V3 m) {
+  out[0 * KB + k] += f.x; out[1 * KB + k] += f.y; out[2 * KB + k] += f.z;
+  out[3 * KB + k] += m.x; out[4 * KB + k] += m.y; out[5 * KB + k] += m.z;
+}
+
+// the stiffness forces of the oriented record r for the KB columns (tip_force, pl_device.h)
+template <int KB>
+__device__ __forceinline__ void add_tip_forces(const Record &r, const double (&xo)[6 * KB], const double (&xs)[6 * KB],
+                                               double (&out)[6 * KB]) {
+#pragma unroll
+  for (int k = 0; k < KB; ++k) {
+    V3 uo, to, us, ts, f, m;
+    column_of<KB>(xo, k, uo, to);
+    column_of<KB>(xs, k, us, ts);
+    tip_force(r, uo, to, us, ts, f, m);
+    add_column<KB>(out, k, f, m);
+  }
+}
+
+// K: the condensed strut record, reversed for a strut's point1
+struct StiffTerm {
+  static constexpr int kMaxKB = 4;
+  const Record *__restrict__ rec;
+  template <int KB>
+  __device__ __forceinline__ void entry(int64_t strut, bool point1, const double (&xo)[6 * KB], const double (&xs)[6 * KB],
+                                        double (&out)[6 * KB]) const {
+    Record r = load_record(rec, strut);
+    if (point1) r = reversed(r);
+    add_tip_forces<KB>(r, xo, xs, out);
+  }
+  template <int KB>
+  __device__ __forceinline__ void node(int64_t, const double (&)[6 * KB], double (&)[6 * KB]) const {}
+};
 
 // ---------------------------------------------------------------------------------------------------------
 // Vector kernels: grid.x strides over the 6N dofs, grid.y = column block; a thread handles the KB columns of a dof.
@@ -540,37 +576,42 @@ int multi_download(pl_context *c, MultiWs *w, const MultiShape &s, const double 
   return PL_OK;
 }
 
-template <int LPN, int KB>
-void launch_gather_multi_t(pl_context *c, const MultiShape &s, const uint8_t *fixedbits, const double *x, double *y,
-                           bool masked, double *dot_dev) {
+// y_j = A x_j (masked: P A x_j), A the operator of `term`, for every column of the shape: one launch of k_gather_multi at the
+// handle's lanes per node, the shape's column block and the mask.  A column block wider than the term is built for is an
+// error: there is no other path.
+template <class Term>
+int launch_gather_multi(pl_context *c, const MultiShape &s, Term term, const uint8_t *fixedbits, const double *x, double *y,
+                        bool masked, double *dot_dev) {
+  if (s.KB > Term::kMaxKB) return fail(PL_ERR_ARG, "the product is not built for column blocks of " + std::to_string(s.KB));
   const dim3 g(grid_for(c->n_slices, pl::kBlock / pl::kWave), (unsigned)s.ncb);   // one wave per ELL slice and column block
-  if (masked)
-    hipLaunchKernelGGL((pl::k_spmv_gather_multi<LPN, KB, true>), g, dim3(pl::kBlock), 0, c->stream, c->N, c->slice_ptr.p,
-                       c->ent.p, c->rec.p, fixedbits, x, y, dot_dev, s.stride);
-  else
-    hipLaunchKernelGGL((pl::k_spmv_gather_multi<LPN, KB, false>), g, dim3(pl::kBlock), 0, c->stream, c->N, c->slice_ptr.p,
-                       c->ent.p, c->rec.p, fixedbits, x, y, dot_dev, s.stride);
-}
-template <int LPN>
-void launch_gather_multi_lpn(pl_context *c, const MultiShape &s, const uint8_t *fixedbits, const double *x, double *y,
-                             bool masked, double *dot_dev) {
-  if (s.KB == 1) launch_gather_multi_t<LPN, 1>(c, s, fixedbits, x, y, masked, dot_dev);
-  else if (s.KB == 2) launch_gather_multi_t<LPN, 2>(c, s, fixedbits, x, y, masked, dot_dev);
-  else launch_gather_multi_t<LPN, 4>(c, s, fixedbits, x, y, masked, dot_dev);
-}
-// y_j = K x_j (masked: P K x_j) for every column of the shape, one launch
-int launch_spmv_multi(pl_context *c, const MultiShape &s, const uint8_t *fixedbits, const double *x, double *y, bool masked,
-                      double *dot_dev) {
+  auto go = [&](auto lpn, auto kb) {
+    constexpr int LPN = decltype(lpn)::value, KB = decltype(kb)::value;
+    if constexpr (KB <= Term::kMaxKB) {
+      const auto kernel = masked ? pl::k_gather_multi<LPN, KB, true, Term> : pl::k_gather_multi<LPN, KB, false, Term>;
+      hipLaunchKernelGGL(kernel, g, dim3(pl::kBlock), 0, c->stream, c->N, (const int64_t *)c->slice_ptr.p, (const int2 *)c->ent.p,
+                         term, fixedbits, x, y, dot_dev, s.stride);
+    }
+  };
+  auto at = [&](auto lpn) {
+    if (s.KB == 1) go(lpn, std::integral_constant<int, 1>());
+    else if (s.KB == 2) go(lpn, std::integral_constant<int, 2>());
+    else go(lpn, std::integral_constant<int, 4>());
+  };
   switch (c->lpn) {
-    case 1: launch_gather_multi_lpn<1>(c, s, fixedbits, x, y, masked, dot_dev); break;
-    case 2: launch_gather_multi_lpn<2>(c, s, fixedbits, x, y, masked, dot_dev); break;
-    case 4: launch_gather_multi_lpn<4>(c, s, fixedbits, x, y, masked, dot_dev); break;
-    case 8: launch_gather_multi_lpn<8>(c, s, fixedbits, x, y, masked, dot_dev); break;
-    case 16: launch_gather_multi_lpn<16>(c, s, fixedbits, x, y, masked, dot_dev); break;
+    case 1: at(std::integral_constant<int, 1>()); break;
+    case 2: at(std::integral_constant<int, 2>()); break;
+    case 4: at(std::integral_constant<int, 4>()); break;
+    case 8: at(std::integral_constant<int, 8>()); break;
+    case 16: at(std::integral_constant<int, 16>()); break;
     default: return fail(PL_ERR_ARG, "lanes per node must be 1, 2, 4, 8 or 16");
   }
   PL_HIP(hipGetLastError());
   return PL_OK;
+}
+// y_j = K x_j (masked: P K x_j)
+inline int launch_spmv_multi(pl_context *c, const MultiShape &s, const uint8_t *fixedbits, const double *x, double *y, bool masked,
+                             double *dot_dev) {
+  return launch_gather_multi(c, s, pl::StiffTerm{c->rec.p}, fixedbits, x, y, masked, dot_dev);
 }
 
 inline void multi_periodic_average(pl_context *c, const MultiShape &s, double *v) {
