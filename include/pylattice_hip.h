@@ -552,6 +552,28 @@ int pl_transient(pl_handle h, int32_t n_steps, double dt, double beta, double ga
                  int32_t snap_every, double *snaps /*[n_steps/snap_every][6N] u, or NULL*/,
                  double *state /*[3][6N]: final u, v, a, or NULL*/, int32_t *iters /*[n_steps+1] or NULL*/);
 
+/* ---- transient sensitivities (csrc/pl_dyn_sens.h) ----------------------------------------------------
+ * The run of pl_transient (same scheme, same solver, same preconditions and error codes), one scalar output per row
+ * y_n = l . u_n (out_vec = l, read with the fixed dofs zeroed), an objective of the outputs with weights w_n >= 0 (NULL = 1)
+ *     kind 0: J = sum w_n y_n,   kind 1: J = 1/2 sum w_n y_n^2,   kind 2: J = (sum w_n |y_n|^p)^(1/p), p >= 2
+ * and dJ/dr_b for every strut radius at fixed segment geometry (the convention of pl_sens) by the discrete adjoint of the
+ * scheme: one backward sweep of n_steps + 1 solves with the matrices of the forward steps.  A base acceleration is an argument
+ * here: base_dir with base_acc adds the load -base_acc[n] P M e_dir (e_dir: the rigid translation base_dir of ALL nodes), the
+ * only load that follows the design; the patterns are dead loads.  n_pat = 0 is legal with a base acceleration.  The histories
+ * u + ray_k v and a + ray_m v + a_g e_dir stay on the device for the call: 2 * 48 N (n_steps + 1) bytes; the adjoint is kept for
+ * PL_TRANSIENT_SENS_CHUNK rows at a time.  No floating-point atomics in the contraction: two calls return the same bits.
+ * PL_ERR_ARG also: kind outside 0 ... 2, p < 2 with kind 2, a negative weight, a NULL out_vec, J or dJ_dr, base_dir without
+ * base_acc.  PL_ERR_NOCONV names the row and the pass (forward / adjoint) whose solve missed rtol; no output is then written.
+ * The handle's single-column state and its earlier results are left untouched. */
+#define PL_TRANSIENT_SENS_CHUNK 32
+int pl_transient_sens(pl_handle h, int32_t n_steps, double dt, double beta, double gamma, double ray_m, double ray_k,
+                      int32_t n_pat, const double *pattern /*[n_pat][6N] or NULL*/, const double *amp /*[n_steps+1][n_pat]*/,
+                      const double *base_dir /*[3] or NULL*/, const double *base_acc /*[n_steps+1], with base_dir*/,
+                      const double *u0, const double *v0 /*[6N] or NULL = 0*/, double rtol, int32_t max_iter,
+                      const double *out_vec /*[6N]: l*/, int32_t kind, double p, const double *weight /*[n_steps+1] or NULL = 1*/,
+                      double *J, double *y /*[n_steps+1] or NULL*/, double *dJ_dr /*[B], caller's strut numbering*/,
+                      int32_t *iters /*[2][n_steps+1] or NULL: forward, adjoint*/);
+
 /* The same condensation, exact and batched, without a handle: n_inst small lattices of ONE topology (a unit cell at
  * several radius sets - the exact DDM mode, Schur datasets), each condensed by a dense Cholesky of K_II in one workgroup
  * of a single launch.  Material, pen_coef and device come from o (stamped by pl_default_opts; the solver fields are

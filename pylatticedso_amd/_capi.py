@@ -25,7 +25,7 @@ EXPORTS = ["pl_default_opts", "pl_opts_size", "pl_stats_size", "pl_abi_version",
            "pl_stress", "pl_stress_pnorm", "pl_buckling", "pl_buckling_pnorm",
            "pl_spmv_multi", "pl_solve_multi", "pl_schur_block", "pl_geom_spmv_multi", "pl_buckling_modes", "pl_buckling_modes_sens",
            "pl_set_mass", "pl_mass_spmv_multi", "pl_vibration_modes", "pl_vibration_modes_sens",
-           "pl_dyn_spmv_multi", "pl_transient",
+           "pl_dyn_spmv_multi", "pl_transient", "pl_transient_sens",
            "pl_schur_cells", "pl_cells_recover", "pl_get_records", "pl_debug_partition", "pl_time_kernel", "pl_algorithmic_bytes", "pl_node_words_info", "pl_forget_history", "pl_debug_spd_solve", "pl_dist_unique_id_bytes",
            "pl_dist_unique_id", "pl_dist_loopback_id", "pl_dist_abort", "pl_dist_init", "pl_dist_set_peers", "pl_generate_lattice", "pl_lattice_fetch",
            "pl_lattice_free", "pl_penalize", "pl_boundary_index", "pl_boundary_index_rows"]
@@ -106,6 +106,7 @@ def load_library(path: str | None = None):
            "pl_vibration_modes_sens": [V, I32, V, V, V, V, V],
            "pl_dyn_spmv_multi": [V, D, D, I32, I32, V, V],
            "pl_transient": [V, I32, D, D, D, D, D, I32, V, V, V, V, D, I32, I32, V, V, V, I32, V, V, V],
+           "pl_transient_sens": [V, I32, D, D, D, D, D, I32, V, V, V, V, V, V, D, I32, V, I32, D, V, V, V, V, V],
            "pl_schur_cells": [V, I32, I32, I32, V, I32, V, V, V, V, V, V, V],
            "pl_cells_recover": [V, I32, I32, I32, V, I32, V, V, V, V, V, V, V, V, V, V, V],
            "pl_get_records": [V, V], "pl_debug_partition": [V, V, V, V, V], "pl_time_kernel": [V, I32, I32, V],
@@ -178,6 +179,8 @@ def debug_spd_solve(A, b, device=0, fp32_factor=False):
 MULTI_MAX = 64
 # columns of one pl_sens_gram call (PL_SENS_GRAM_MAX)
 SENS_GRAM_MAX = 8
+# rows of the adjoint one pl_transient_sens contraction launch takes (PL_TRANSIENT_SENS_CHUNK)
+TRANSIENT_SENS_CHUNK = 32
 
 # what one workgroup of pl_schur_cells holds (include/pylattice_hip.h): larger cells go through pl_schur
 SCHUR_CELLS_MAX_BOUNDARY, SCHUR_CELLS_MAX_INTERIOR, SCHUR_CELLS_MAX_BEAMS = 32, 16, 512
@@ -1015,6 +1018,65 @@ class HipLattice:
         K.sum_duplicates()
         return DH.newmark(K, self.mass_matrix_host(), fixed, dt, n_steps, patterns, amp, u0, v0, beta, gamma, ray_m, ray_k,
                           solve, probes, snap_every)
+
+    def transient_sens(self, dt, n_steps, out_vec, kind=2, p=8.0, weight=None, patterns=None, amp=None, base_dir=None,
+                       base_acc=None, u0=None, v0=None, beta=0.25, gamma=0.5, ray_m=0.0, ray_k=0.0, rtol=1e-10,
+                       max_iter=100000):
+        """The run of ``transient`` with one output per row y_n = out_vec . u_n, the objective J of the outputs (kind 0:
+        sum w y, 1: 1/2 sum w y^2, 2: (sum w |y|^p)^(1/p); weight (n_steps + 1,) >= 0 or None = 1) and dJ/dr for every
+        strut radius by the discrete adjoint of the scheme (pl_transient_sens).  out_vec (N, 6), read with the fixed dofs
+        zeroed; base_dir (3,) with base_acc (n_steps + 1,) adds the load -base_acc[n] M e_dir, which follows the design.
+        Returns a dict: J, y (n_steps + 1,), dJ_dr (B,), iters (2, n_steps + 1) = forward, adjoint."""
+        n_steps, n6 = int(n_steps), 6 * self.n_nodes
+        rows = max(n_steps, 0) + 1
+        pat = am = None
+        n_pat = 0
+        if patterns is not None:
+            pat = np.ascontiguousarray(np.asarray(patterns, dtype=np.float64)).reshape(-1, n6)
+            n_pat = pat.shape[0]
+            am = np.ascontiguousarray(np.asarray(amp, dtype=np.float64).reshape(-1))
+            if am.size != rows * n_pat:
+                raise ValueError(f"amp must have shape ({rows}, {n_pat})")
+        bd = None if base_dir is None else _f64(np.asarray(base_dir).reshape(-1), 3)
+        ba = None if base_acc is None else _f64(np.asarray(base_acc).reshape(-1), rows)
+        uu = None if u0 is None else _f64(np.asarray(u0).reshape(-1), n6)
+        vv = None if v0 is None else _f64(np.asarray(v0).reshape(-1), n6)
+        lv = _f64(np.asarray(out_vec).reshape(-1), n6)
+        wt = None if weight is None else _f64(np.asarray(weight).reshape(-1), rows)
+        J = C.c_double()
+        y = np.zeros(rows, np.float64)
+        grad = np.zeros(self.n_beams, np.float64)
+        iters = np.zeros((2, rows), np.int32)
+        _check(self._lib, self._lib.pl_transient_sens(self._h, n_steps, float(dt), float(beta), float(gamma), float(ray_m),
+                                                      float(ray_k), n_pat, _ptr(pat), _ptr(am), _ptr(bd), _ptr(ba), _ptr(uu),
+                                                      _ptr(vv), float(rtol), int(max_iter), _ptr(lv), int(kind), float(p),
+                                                      _ptr(wt), C.byref(J), _ptr(y), _ptr(grad), _ptr(iters)))
+        return {"J": J.value, "y": y, "dJ_dr": grad, "iters": iters}
+
+    def transient_sens_host(self, fixed, dt, n_steps, out_vec, kind=2, p=8.0, weight=None, patterns=None, amp=None,
+                            base_dir=None, base_acc=None, u0=None, v0=None, beta=0.25, gamma=0.5, ray_m=0.0, ray_k=0.0,
+                            solve=None):
+        """The numpy / scipy restatement of ``transient_sens`` (dynamics_host.newmark_sensitivity) on this handle's own BSR
+        K, the restated M of its mass model and the restated record and mass derivatives.  fixed (N, 6): the mask that was
+        given to set_bc."""
+        import scipy.sparse as sp
+        from . import dynamics_host as DH
+        from . import mass_host as MH
+        from . import stress_host as SH
+        self.assemble_bsr(False)
+        rowptr, col, vals = self.get_bsr()
+        K = sp.bsr_matrix((vals, col, rowptr), shape=(6 * self.n_nodes, 6 * self.n_nodes)).tocsr()
+        K.sum_duplicates()
+        rho, rotary, nm = self._mass_model()
+        E, nu, kappa, pen = self._material
+        drec = SH.drecords_dr(self.node_xyz, self.beam_conn, self._radius, self._seg_len, self._seg_nsub, E, nu, kappa, pen,
+                              self._mult)
+        conn = np.asarray(self.beam_conn).reshape(-1, 2)
+        xyz = np.asarray(self.node_xyz, dtype=np.float64).reshape(-1, 3)
+        dM = MH.delement_matrix_dr(xyz[conn[:, 1]] - xyz[conn[:, 0]], np.asarray(self._radius, dtype=np.float64).reshape(-1),
+                                   rho, self._mult, rotary)
+        return DH.newmark_sensitivity(K, self.mass_matrix_host(), fixed, conn, drec, dM, dt, n_steps, out_vec, kind, p, weight,
+                                      patterns, amp, base_dir, base_acc, u0, v0, beta, gamma, ray_m, ray_k, solve)
 
     # -- measurement ------------------------------------------------------------------------------------
     def time_kernel(self, which, reps=20):

@@ -10,6 +10,7 @@
 #include "pl_geom.h"
 #include "pl_mass.h"
 #include "pl_dyn.h"
+#include "pl_dyn_sens.h"
 #include "pl_sensgram.h"
 
 
@@ -2491,46 +2492,63 @@ int pl_dyn_spmv_multi(pl_handle h, double c_K, double c_M, int32_t n_rhs, int ma
   }, [&] { return pl::DynTerm{h->rec.p, mass_term(m), c_K, c_M}; });
 }
 
-int pl_transient(pl_handle h, int32_t n_steps, double dt, double beta, double gamma, double ray_m, double ray_k, int32_t n_pat,
-                 const double *pattern, const double *amp, const double *u0, const double *v0, double rtol, int32_t max_iter,
-                 int32_t n_probe, const int32_t *probe_nodes, double *probe, double *energy, int32_t snap_every, double *snaps,
-                 double *state, int32_t *iters) {
-  const char *who = "pl_transient";
-  if (!valid(h)) return fail(PL_ERR_ARG, "pl_transient: null handle");
-  if (n_steps < 1) return fail(PL_ERR_ARG, "pl_transient: n_steps must be at least 1");
-  if (!(dt > 0.0) || !std::isfinite(dt)) return fail(PL_ERR_ARG, "pl_transient: dt must be positive and finite");
-  if (!(gamma >= 0.5) || !std::isfinite(gamma)) return fail(PL_ERR_ARG, "pl_transient: gamma must be at least 1/2");
-  if (!(beta >= 0.25 * (0.5 + gamma) * (0.5 + gamma)) || !std::isfinite(beta))
-    return fail(PL_ERR_ARG, "pl_transient: beta must be at least (1/2 + gamma)^2 / 4 (unconditionally stable schemes only)");
-  if (!(ray_m >= 0.0) || !(ray_k >= 0.0) || !std::isfinite(ray_m) || !std::isfinite(ray_k))
-    return fail(PL_ERR_ARG, "pl_transient: the Rayleigh coefficients must be finite and not negative");
-  if (n_pat < 0 || n_pat > 4) return fail(PL_ERR_ARG, "pl_transient: n_pat must be 0 ... 4");
-  if (n_pat > 0 && (!pattern || !amp)) return fail(PL_ERR_ARG, "pl_transient: n_pat > 0 needs pattern and amp");
-  if (!(rtol > 0.0) || max_iter <= 0) return fail(PL_ERR_ARG, "pl_transient: rtol and max_iter must be positive");
-  if (n_probe < 0 || (n_probe > 0 && (!probe_nodes || !probe))) return fail(PL_ERR_ARG, "pl_transient: n_probe > 0 needs probe_nodes and probe");
-  if (snap_every < 0 || (snaps && snap_every < 1)) return fail(PL_ERR_ARG, "pl_transient: snaps needs snap_every >= 1");
+namespace {
+// The run that pl_transient and pl_transient_sens share: its arguments, their checks and the forward pass.
+struct TransientRun {
+  int32_t n_steps;
+  double dt, beta, gamma, ray_m, ray_k;
+  int32_t n_pat;                     // the caller's patterns [n_pat][6N] (host)
+  const double *pattern, *amp;       // amp: [n_steps + 1][n_pat_dev] for the device's patterns (the caller's, then the base load)
+  const double *u0, *v0;
+  double rtol;
+  int32_t max_iter;
+};
+
+int transient_check(pl_handle h, const std::string &who, const TransientRun &a) {
+  if (!valid(h)) return fail(PL_ERR_ARG, who + ": null handle");
+  if (a.n_steps < 1) return fail(PL_ERR_ARG, who + ": n_steps must be at least 1");
+  if (!(a.dt > 0.0) || !std::isfinite(a.dt)) return fail(PL_ERR_ARG, who + ": dt must be positive and finite");
+  if (!(a.gamma >= 0.5) || !std::isfinite(a.gamma)) return fail(PL_ERR_ARG, who + ": gamma must be at least 1/2");
+  if (!(a.beta >= 0.25 * (0.5 + a.gamma) * (0.5 + a.gamma)) || !std::isfinite(a.beta))
+    return fail(PL_ERR_ARG, who + ": beta must be at least (1/2 + gamma)^2 / 4 (unconditionally stable schemes only)");
+  if (!(a.ray_m >= 0.0) || !(a.ray_k >= 0.0) || !std::isfinite(a.ray_m) || !std::isfinite(a.ray_k))
+    return fail(PL_ERR_ARG, who + ": the Rayleigh coefficients must be finite and not negative");
+  if (a.n_pat < 0 || a.n_pat > 4) return fail(PL_ERR_ARG, who + ": n_pat must be 0 ... 4");
+  if (a.n_pat > 0 && (!a.pattern || !a.amp)) return fail(PL_ERR_ARG, who + ": n_pat > 0 needs pattern and amp");
+  if (!(a.rtol > 0.0) || a.max_iter <= 0) return fail(PL_ERR_ARG, who + ": rtol and max_iter must be positive");
+  return PL_OK;
+}
+
+// the handle checks, the mass records of the current radii, and supports held at zero: prescribed values are refused
+int transient_begin(pl_handle h, const char *who, MassWs **m) {
+  if (int rc = mass_begin(h, who, true, m)) return rc;
+  const int64_t n6 = h->N * 6;
+  std::vector<double> ub((size_t)n6);
+  PL_HIP(hipMemcpyAsync(ub.data(), h->ubar.p, (size_t)n6 * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+  PL_HIP(hipStreamSynchronize(h->stream));
+  for (double v : ub)
+    if (v != 0.0) return fail(PL_ERR_STATE, std::string(who) + ": the handle carries non-zero prescribed displacements (pl_set_bc)");
+  return PL_OK;
+}
+
+// The row loop: the initial acceleration and n_steps steps, with the probe block, the energies and the snapshots left on the
+// device (DynWs) and the last state in d->st.  hist != null (pl_transient_sens): the base-acceleration pattern P M e_dir is
+// formed behind the caller's patterns, and every row leaves wK, wM and the slots of l . u (pl_dyn_sens.h).
+struct TransientClock {              // what the PL_TIMING lines of the callers need
+  std::chrono::steady_clock::time_point t_begin;
+  double ms_solve = 0.0;
+  long total_iters = 0;
+};
+int transient_forward(pl_handle h, const char *who, MassWs *m, const TransientRun &a, const std::vector<int32_t> &slot_of,
+                      int n_slot, int snap_every, int n_snap, int32_t *iters, const DynHistory *hist, MultiWs **w_out,
+                      DynWs **d_out, TransientClock *clk) {
+  const int32_t n_steps = a.n_steps, n_pat = a.n_pat, max_iter = a.max_iter;
+  const double dt = a.dt, beta = a.beta, gamma = a.gamma, ray_m = a.ray_m, ray_k = a.ray_k, rtol = a.rtol;
+  const double *pattern = a.pattern, *amp = a.amp, *u0 = a.u0, *v0 = a.v0;
   const int64_t N = h->N, n6 = N * 6;
-  for (int i = 0; i < n_probe; ++i)
-    if (probe_nodes[i] < 0 || probe_nodes[i] >= N) return fail(PL_ERR_ARG, "pl_transient: probe node index out of range");
-  MassWs *m = nullptr;
-  if (int rc = mass_begin(h, who, true, &m)) return rc;
-  {   // supports are held at zero: prescribed values on the handle are refused
-    std::vector<double> ub((size_t)n6);
-    PL_HIP(hipMemcpyAsync(ub.data(), h->ubar.p, (size_t)n6 * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-    PL_HIP(hipStreamSynchronize(h->stream));
-    for (double v : ub)
-      if (v != 0.0) return fail(PL_ERR_STATE, "pl_transient: the handle carries non-zero prescribed displacements (pl_set_bc)");
-  }
   const int rows = n_steps + 1;
-  const int n_snap = snaps ? n_steps / snap_every : 0;
-  // the probed nodes, each once: slot of the node in the device's probe block
-  std::vector<int32_t> slot_of((size_t)N, -1), probe_to_slot((size_t)n_probe);
-  int n_slot = 0;
-  for (int i = 0; i < n_probe; ++i) {
-    const int64_t di = h->iperm[probe_nodes[i]];
-    if (slot_of[(size_t)di] < 0) slot_of[(size_t)di] = n_slot++;
-    probe_to_slot[(size_t)i] = slot_of[(size_t)di];
-  }
+  const bool base = hist && hist->base_dir;
+  const int n_pat_dev = n_pat + (base ? 1 : 0);
   // workspaces: the column block of four first (it sets the capacity), then the single column of the solves
   MultiShape s4;
   s4.n_rhs = 3; s4.KB = 4; s4.ncb = 1; s4.ncol = 4; s4.stride = n6 * 4;
@@ -2548,8 +2566,8 @@ int pl_transient(pl_handle h, int32_t n_steps, double dt, double beta, double ga
   PL_HIP(dyn_grow(d->ut, (size_t)n6));
   PL_HIP(dyn_grow(d->vt, (size_t)n6));
   PL_HIP(dyn_grow(d->f2, (size_t)n6 * 2));
-  PL_HIP(dyn_grow(d->pattern, (size_t)n6 * std::max(n_pat, 1)));
-  PL_HIP(dyn_grow(d->amp, (size_t)rows * std::max(n_pat, 1)));
+  PL_HIP(dyn_grow(d->pattern, (size_t)n6 * std::max(n_pat_dev, 1)));
+  PL_HIP(dyn_grow(d->amp, (size_t)rows * std::max(n_pat_dev, 1)));
   PL_HIP(dyn_grow(d->probe_slot, (size_t)N));
   PL_HIP(dyn_grow(d->probe, (size_t)rows * 18 * std::max(n_slot, 1)));
   PL_HIP(dyn_grow(d->energy, (size_t)rows * pl::DYN_E_COUNT * pl::kSlots));
@@ -2561,9 +2579,20 @@ int pl_transient(pl_handle h, int32_t n_steps, double dt, double beta, double ga
     if (v0) std::memcpy(s0.data() + n6, v0, (size_t)n6 * sizeof(double));
     if (int rc = multi_upload(h, w, s4, s0.data(), d->st.p, -1)) return rc;
   }
-  if (n_pat > 0) {
+  if (n_pat > 0)
     if (int rc = multi_upload(h, w, sp, pattern, d->pattern.p, -1)) return rc;
-    PL_HIP(hipMemcpyAsync(d->amp.p, amp, (size_t)rows * n_pat * sizeof(double), hipMemcpyHostToDevice, h->stream));
+  if (base) {   // P M e_dir on the single-column gather; its amplitude column carries -a_g
+    std::vector<double> e((size_t)n6, 0.0);
+    for (int64_t i = 0; i < N; ++i)
+      for (int k = 0; k < 3; ++k) e[(size_t)(6 * i + k)] = hist->base_dir[k];
+    if (int rc = multi_upload(h, w, s1, e.data(), hist->s->edir.p, 0)) return rc;
+    if (int rc = launch_mass_multi(h, m, s1, hist->s->edir.p, d->pattern.p + (size_t)n_pat * n6, true)) return rc;
+  }
+  if (n_pat_dev > 0)
+    PL_HIP(hipMemcpyAsync(d->amp.p, amp, (size_t)rows * n_pat_dev * sizeof(double), hipMemcpyHostToDevice, h->stream));
+  if (hist) {
+    if (int rc = multi_upload(h, w, s1, hist->l_host, hist->s->l.p, -1)) return rc;
+    PL_HIP(hipMemsetAsync(hist->s->yslots.p, 0, (size_t)rows * pl::kSlots * sizeof(double), h->stream));
   }
   PL_HIP(hipMemcpyAsync(d->probe_slot.p, slot_of.data(), (size_t)N * sizeof(int32_t), hipMemcpyHostToDevice, h->stream));
   PL_HIP(hipStreamSynchronize(h->stream));         // (amp and slot_of are pageable host memory)
@@ -2571,7 +2600,6 @@ int pl_transient(pl_handle h, int32_t n_steps, double dt, double beta, double ga
   PL_HIP(hipMemsetAsync(d->energy.p, 0, (size_t)rows * pl::DYN_E_COUNT * pl::kSlots * sizeof(double), h->stream));
   PL_HIP(hipMemsetAsync(w->UB.p, 0, (size_t)n6 * sizeof(double), h->stream));      // zero prescribed values in every solve
 
-  const bool timing = std::getenv("PL_TIMING") != nullptr;
   const auto t_begin = std::chrono::steady_clock::now();
   double ms_solve = 0.0;
   long total_iters = 0;
@@ -2586,7 +2614,7 @@ int pl_transient(pl_handle h, int32_t n_steps, double dt, double beta, double ga
     const int row = erow + 1;
     hipLaunchKernelGGL(pl::k_newmark_predict, gs, dim3(pl::kBlock), 0, h->stream, n6, (const double *)d->st.p,
                        (const double *)d->Ks.p, (const double *)d->Ms.p, (const uint8_t *)h->fixedbits.p, q, form ? 1 : 0,
-                       (int)n_pat, (const double *)d->pattern.p, (const double *)d->amp.p + (size_t)(form ? row : 0) * n_pat,
+                       n_pat_dev, (const double *)d->pattern.p, (const double *)d->amp.p + (size_t)(form ? row : 0) * n_pat_dev,
                        d->ut.p, d->vt.p, d->f2.p + (size_t)(row & 1) * n6, w->F.p, d->energy.p, erow);
     PL_HIP(hipGetLastError());
     return PL_OK;
@@ -2604,21 +2632,67 @@ int pl_transient(pl_handle h, int32_t n_steps, double dt, double beta, double ga
     total_iters += its;
     if (iters) iters[row] = its;
     if (!std::isfinite(rr) || !std::isfinite(bb))
-      return fail(PL_ERR_NAN, "pl_transient: NaN/Inf in a residual norm of step " + std::to_string(row));
+      return fail(PL_ERR_NAN, std::string(who) + ": NaN/Inf in a residual norm of step " + std::to_string(row));
     if (!(rr <= rtol * rtol * bb))
-      return fail(PL_ERR_NOCONV, "pl_transient: the solve of step " + std::to_string(row) + " did not reach rtol within max_iter");
+      return fail(PL_ERR_NOCONV, std::string(who) + (hist ? ": the forward solve of step " : ": the solve of step ") +
+                                     std::to_string(row) + " did not reach rtol within max_iter");
     double *snap = nullptr;
     if (n_snap > 0 && row > 0 && row % snap_every == 0) snap = d->snaps.p + (size_t)(row / snap_every - 1) * n6;
     hipLaunchKernelGGL(pl::k_newmark_correct, gs, dim3(pl::kBlock), 0, h->stream, n6, (const double *)d->ut.p,
                        (const double *)d->vt.p, (const double *)w->U.p, (const double *)d->f2.p + (size_t)((row & 1) ^ 1) * n6,
                        (const double *)d->f2.p + (size_t)(row & 1) * n6, q, d->st.p, (const int32_t *)d->probe_slot.p, n_slot,
                        d->probe.p, snap, d->energy.p, row);
+    if (hist) {
+      DynSensWs *s = hist->s;
+      hipLaunchKernelGGL(pl::k_newmark_history, gs, dim3(pl::kBlock), 0, h->stream, n6, (const double *)d->st.p,
+                         (const double *)s->l.p, base ? (const double *)s->edir.p : (const double *)nullptr,
+                         base ? hist->base_acc[row] : 0.0, ray_m, ray_k, s->wK.p + (size_t)row * n6, s->wM.p + (size_t)row * n6,
+                         s->yslots.p + (size_t)row * pl::kSlots);
+    }
     PL_HIP(hipGetLastError());
   }
-  {   // the energies of the last row
+  if (!hist) {   // the energies of the last row
     const pl::NewmarkCoef q = {dt, beta, gamma, ray_m, ray_k};
     if (int rc = products_and_predict(q, false, n_steps)) return rc;
   }
+  clk->t_begin = t_begin;
+  clk->ms_solve = ms_solve;
+  clk->total_iters = total_iters;
+  *w_out = w;
+  *d_out = d;
+  return PL_OK;
+}
+}  // namespace
+
+int pl_transient(pl_handle h, int32_t n_steps, double dt, double beta, double gamma, double ray_m, double ray_k, int32_t n_pat,
+                 const double *pattern, const double *amp, const double *u0, const double *v0, double rtol, int32_t max_iter,
+                 int32_t n_probe, const int32_t *probe_nodes, double *probe, double *energy, int32_t snap_every, double *snaps,
+                 double *state, int32_t *iters) {
+  const char *who = "pl_transient";
+  const TransientRun a = {n_steps, dt, beta, gamma, ray_m, ray_k, n_pat, pattern, amp, u0, v0, rtol, max_iter};
+  if (int rc = transient_check(h, who, a)) return rc;
+  if (n_probe < 0 || (n_probe > 0 && (!probe_nodes || !probe))) return fail(PL_ERR_ARG, "pl_transient: n_probe > 0 needs probe_nodes and probe");
+  if (snap_every < 0 || (snaps && snap_every < 1)) return fail(PL_ERR_ARG, "pl_transient: snaps needs snap_every >= 1");
+  const int64_t N = h->N, n6 = N * 6;
+  for (int i = 0; i < n_probe; ++i)
+    if (probe_nodes[i] < 0 || probe_nodes[i] >= N) return fail(PL_ERR_ARG, "pl_transient: probe node index out of range");
+  MassWs *m = nullptr;
+  if (int rc = transient_begin(h, who, &m)) return rc;
+  const int rows = n_steps + 1;
+  const int n_snap = snaps ? n_steps / snap_every : 0;
+  // the probed nodes, each once: slot of the node in the device's probe block
+  std::vector<int32_t> slot_of((size_t)N, -1), probe_to_slot((size_t)n_probe);
+  int n_slot = 0;
+  for (int i = 0; i < n_probe; ++i) {
+    const int64_t di = h->iperm[probe_nodes[i]];
+    if (slot_of[(size_t)di] < 0) slot_of[(size_t)di] = n_slot++;
+    probe_to_slot[(size_t)i] = slot_of[(size_t)di];
+  }
+  MultiWs *w = nullptr;
+  DynWs *d = nullptr;
+  TransientClock clk;
+  if (int rc = transient_forward(h, who, m, a, slot_of, n_slot, snap_every, n_snap, iters, nullptr, &w, &d, &clk)) return rc;
+  const MultiShape s4 = {3, 4, 1, 4, n6 * 4};
   // histories come down once
   if (energy) {
     std::vector<double> eh((size_t)rows * pl::DYN_E_COUNT * pl::kSlots);
@@ -2645,14 +2719,177 @@ int pl_transient(pl_handle h, int32_t n_steps, double dt, double beta, double ga
     if (int rc = download6(h, d->snaps.p + (size_t)k * n6, snaps + (size_t)k * n6)) return rc;
   if (state)
     if (int rc = multi_download(h, w, s4, d->st.p, state)) return rc;
-  if (timing) {
+  if (std::getenv("PL_TIMING") != nullptr) {
     PL_HIP(hipStreamSynchronize(h->stream));
-    const double ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_begin).count();
+    const double ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - clk.t_begin).count();
     std::fprintf(stderr, "[%s] %-28s %10.4f ms\n", who, "whole_call_host_clock", ms);
     std::fprintf(stderr, "[%s] %-28s %10d\n", who, "steps", (int)n_steps);
     std::fprintf(stderr, "[%s] %-28s %10.4f ms\n", who, "step_mean_host_clock", ms / rows);
-    std::fprintf(stderr, "[%s] %-28s %10.4f ms\n", who, "inner_solve_mean_host_clock", ms_solve / rows);
-    std::fprintf(stderr, "[%s] %-28s %10.2f\n", who, "iterations_per_step", (double)total_iters / rows);
+    std::fprintf(stderr, "[%s] %-28s %10.4f ms\n", who, "inner_solve_mean_host_clock", clk.ms_solve / rows);
+    std::fprintf(stderr, "[%s] %-28s %10.2f\n", who, "iterations_per_step", (double)clk.total_iters / rows);
+  }
+  return PL_OK;
+}
+
+int pl_transient_sens(pl_handle h, int32_t n_steps, double dt, double beta, double gamma, double ray_m, double ray_k,
+                      int32_t n_pat, const double *pattern, const double *amp, const double *base_dir, const double *base_acc,
+                      const double *u0, const double *v0, double rtol, int32_t max_iter, const double *out_vec, int32_t kind,
+                      double p, const double *weight, double *J, double *y, double *dJ_dr, int32_t *iters) {
+  const char *who = "pl_transient_sens";
+  TransientRun a = {n_steps, dt, beta, gamma, ray_m, ray_k, n_pat, pattern, amp, u0, v0, rtol, max_iter};
+  if (int rc = transient_check(h, who, a)) return rc;
+  if (!out_vec || !J || !dJ_dr) return fail(PL_ERR_ARG, "pl_transient_sens: out_vec, J and dJ_dr must not be NULL");
+  if (kind < 0 || kind > 2) return fail(PL_ERR_ARG, "pl_transient_sens: kind must be 0, 1 or 2");
+  if (kind == 2 && !(p >= 2.0 && std::isfinite(p))) return fail(PL_ERR_ARG, "pl_transient_sens: p must be at least 2 (and finite)");
+  if (base_dir && !base_acc) return fail(PL_ERR_ARG, "pl_transient_sens: base_dir needs base_acc");
+  const int rows = n_steps + 1;
+  if (weight)
+    for (int n = 0; n < rows; ++n)
+      if (!(weight[n] >= 0.0) || !std::isfinite(weight[n]))
+        return fail(PL_ERR_ARG, "pl_transient_sens: the weights must be finite and not negative");
+  MassWs *m = nullptr;
+  if (int rc = transient_begin(h, who, &m)) return rc;
+  const int64_t N = h->N, n6 = N * 6, B = h->B;
+  if (!h->dyn_sens_ws) h->dyn_sens_ws = std::make_shared<DynSensWs>();
+  DynSensWs *s = static_cast<DynSensWs *>(h->dyn_sens_ws.get());
+  PL_HIP(dyn_grow(s->wK, (size_t)rows * n6));
+  PL_HIP(dyn_grow(s->wM, (size_t)rows * n6));
+  PL_HIP(dyn_grow(s->lam, (size_t)pl::kSensChunk * n6));
+  for (DevBuf<double> *b : {&s->mu, &s->nu, &s->Kl, &s->Ml, &s->l, &s->edir}) PL_HIP(dyn_grow(*b, (size_t)n6));
+  PL_HIP(dyn_grow(s->yslots, (size_t)rows * pl::kSlots));
+  PL_HIP(dyn_grow(s->acc, (size_t)pl::kSensGroups * B));
+  PL_HIP(dyn_grow(s->grad, (size_t)B));
+  // the amplitudes of the device's patterns: the caller's columns, then -a_g for P M e_dir
+  const int n_pat_dev = n_pat + (base_dir ? 1 : 0);
+  std::vector<double> amp_dev((size_t)rows * std::max(n_pat_dev, 1), 0.0);
+  for (int n = 0; n < rows; ++n) {
+    for (int q = 0; q < n_pat; ++q) amp_dev[(size_t)n * n_pat_dev + q] = amp[(size_t)n * n_pat + q];
+    if (base_dir) amp_dev[(size_t)n * n_pat_dev + n_pat] = -base_acc[n];
+  }
+  a.amp = amp_dev.data();
+  DynHistory hist;
+  hist.s = s;
+  hist.l_host = out_vec;
+  hist.base_dir = base_dir;
+  hist.base_acc = base_acc;
+  const std::vector<int32_t> no_probe((size_t)N, -1);
+  std::vector<int32_t> its((size_t)2 * rows, 0);
+  MultiWs *w = nullptr;
+  DynWs *d = nullptr;
+  TransientClock clk;
+  if (int rc = transient_forward(h, who, m, a, no_probe, 0, 0, 0, its.data(), &hist, &w, &d, &clk)) return rc;
+  // the one host look between the passes: y_n from its slots, J and c_n = dJ/dy_n
+  std::vector<double> yh((size_t)rows), c((size_t)rows, 0.0);
+  {
+    std::vector<double> ys((size_t)rows * pl::kSlots);
+    PL_HIP(hipMemcpyAsync(ys.data(), s->yslots.p, ys.size() * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+    PL_HIP(hipStreamSynchronize(h->stream));
+    for (int n = 0; n < rows; ++n) {
+      double t = 0.0;
+      for (int q = 0; q < pl::kSlots; ++q) t += ys[(size_t)n * pl::kSlots + q];
+      yh[(size_t)n] = t;
+    }
+  }
+  const bool timing = std::getenv("PL_TIMING") != nullptr;
+  const double ms_forward = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - clk.t_begin).count();
+  double Jv = 0.0;
+  auto wt = [&](int n) { return weight ? weight[n] : 1.0; };
+  if (kind == 0) {
+    for (int n = 0; n < rows; ++n) { Jv += wt(n) * yh[n]; c[n] = wt(n); }
+  } else if (kind == 1) {
+    for (int n = 0; n < rows; ++n) { Jv += wt(n) * yh[n] * yh[n]; c[n] = wt(n) * yh[n]; }
+    Jv *= 0.5;
+  } else {   // scaled by the largest |y|: |y|^p cannot overflow
+    double top = 0.0, sum = 0.0;
+    for (int n = 0; n < rows; ++n) top = std::max(top, std::fabs(yh[n]));
+    if (top > 0.0)
+      for (int n = 0; n < rows; ++n) sum += wt(n) * std::pow(std::fabs(yh[n]) / top, p);
+    const double Js = sum > 0.0 ? std::pow(sum, 1.0 / p) : 0.0;
+    Jv = top * Js;
+    if (Js > 0.0)
+      for (int n = 0; n < rows; ++n) {
+        const double sgn = yh[n] > 0.0 ? 1.0 : (yh[n] < 0.0 ? -1.0 : 0.0);
+        c[n] = std::pow(Js, 1.0 - p) * wt(n) * std::pow(std::fabs(yh[n]) / top, p - 1.0) * sgn;
+      }
+  }
+  if (!std::isfinite(Jv)) return fail(PL_ERR_NAN, "pl_transient_sens: the objective is not finite");
+  // the backward sweep
+  const double c2 = dt * dt * (0.5 - beta), c3 = dt * (1.0 - gamma), cu = beta * dt * dt, cv = gamma * dt;
+  const double ca = cu + cv * dt + c2, cb = cv + c3;
+  const dim3 gs(grid_stream(n6));
+  const MultiShape s1 = multi_shape(h, 1);
+  std::vector<double> status((size_t)pl::M_ST_COUNT * s1.ncol);
+  MultiOp op;
+  op.mass = m;
+  double ms_solve = 0.0, ms_sens = 0.0;
+  long adj_iters = 0;
+  PL_HIP(hipMemsetAsync(s->acc.p, 0, (size_t)pl::kSensGroups * B * sizeof(double), h->stream));
+  auto adjoint = [&](const double *lam, double c_cur, double a_, double b_, double cl_next, int row) {
+    hipLaunchKernelGGL(pl::k_newmark_adjoint, gs, dim3(pl::kBlock), 0, h->stream, n6, lam, (const double *)s->Kl.p,
+                       (const double *)s->Ml.p, (const double *)s->l.p, dt, ray_m, ray_k, c_cur, a_, b_, cl_next, s->mu.p,
+                       s->nu.p, w->F.p, s->lam.p + (size_t)(row % pl::kSensChunk) * n6);
+  };
+  auto contract = [&](int row0) -> int {   // the chunk whose first row is row0
+    const int nrows = std::min(pl::kSensChunk, rows - row0);
+    if (timing) PL_HIP(hipEventRecord(h->ev0, h->stream));
+    if (int rc = launch_transient_sens(h, m, s, row0, nrows)) return rc;
+    if (timing) {
+      float t = 0.0f;
+      PL_HIP(hipEventRecord(h->ev1, h->stream));
+      PL_HIP(hipEventSynchronize(h->ev1));
+      PL_HIP(hipEventElapsedTime(&t, h->ev0, h->ev1));
+      ms_sens += t;
+    }
+    return PL_OK;
+  };
+  adjoint(nullptr, 0.0, ca, cb, cu * c[(size_t)n_steps], 0);     // mu = nu = 0 and the right-hand side of row n_steps
+  PL_HIP(hipGetLastError());
+  for (int row = n_steps; row >= 0; --row) {
+    const double qdt = row == 0 ? 0.0 : dt;
+    op.c_M = 1.0 + gamma * qdt * ray_m;
+    op.c_K = beta * qdt * qdt + gamma * qdt * ray_k;
+    const auto t0 = std::chrono::steady_clock::now();
+    if (int rc = pcg_solve_multi(h, w, s1, h->fixedbits.p, w->F.p, rtol, max_iter, status.data(), op)) return rc;
+    ms_solve += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    const double rr = status[pl::M_ST_RR * s1.ncol], bb = status[pl::M_ST_BB * s1.ncol];
+    its[(size_t)rows + row] = (int)status[pl::M_ST_ITER * s1.ncol];
+    adj_iters += its[(size_t)rows + row];
+    if (!std::isfinite(rr) || !std::isfinite(bb))
+      return fail(PL_ERR_NAN, "pl_transient_sens: NaN/Inf in a residual norm of the adjoint solve of step " + std::to_string(row));
+    if (!(rr <= rtol * rtol * bb))
+      return fail(PL_ERR_NOCONV, "pl_transient_sens: the adjoint solve of step " + std::to_string(row) +
+                                     " did not reach rtol within max_iter");
+    if (row > 0) {
+      if (int rc = launch_spmv_multi(h, s1, h->fixedbits.p, w->U.p, s->Kl.p, true, nullptr)) return rc;
+      if (int rc = launch_mass_multi(h, m, s1, w->U.p, s->Ml.p, true)) return rc;
+      if (row > 1) adjoint(w->U.p, c[(size_t)row], ca, cb, cu * c[(size_t)row - 1], row);
+      else adjoint(w->U.p, c[(size_t)row], c2, c3, 0.0, row);     // the right-hand side of M lam_0
+      PL_HIP(hipGetLastError());
+    } else {
+      PL_HIP(hipMemcpyAsync(s->lam.p, w->U.p, (size_t)n6 * sizeof(double), hipMemcpyDeviceToDevice, h->stream));
+    }
+    if (row % pl::kSensChunk == 0)
+      if (int rc = contract(row)) return rc;
+  }
+  hipLaunchKernelGGL(pl::k_transient_sens_sum, dim3(grid_for(B)), dim3(pl::kBlock), 0, h->stream, B, (const double *)s->acc.p,
+                     s->grad.p);
+  PL_HIP(hipGetLastError());
+  if (int rc = download_struts(h, s->grad.p, dJ_dr)) return rc;
+  *J = Jv;
+  if (y) std::memcpy(y, yh.data(), (size_t)rows * sizeof(double));
+  if (iters) std::memcpy(iters, its.data(), its.size() * sizeof(int32_t));
+  if (timing) {
+    PL_HIP(hipStreamSynchronize(h->stream));
+    const double ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - clk.t_begin).count();
+    std::fprintf(stderr, "[%s] %-28s %10.4f ms\n", who, "whole_call_host_clock", ms);
+    std::fprintf(stderr, "[%s] %-28s %10d\n", who, "steps", (int)n_steps);
+    std::fprintf(stderr, "[%s] %-28s %10.4f ms\n", who, "forward_pass_host_clock", ms_forward);
+    std::fprintf(stderr, "[%s] %-28s %10.4f ms\n", who, "adjoint_pass_host_clock", ms - ms_forward);
+    std::fprintf(stderr, "[%s] %-28s %10.4f ms\n", who, "inner_solve_mean_host_clock", (clk.ms_solve + ms_solve) / (2 * rows));
+    std::fprintf(stderr, "[%s] %-28s %10.2f\n", who, "forward_iterations_per_step", (double)clk.total_iters / rows);
+    std::fprintf(stderr, "[%s] %-28s %10.2f\n", who, "adjoint_iterations_per_step", (double)adj_iters / rows);
+    std::fprintf(stderr, "[%s] %-28s %10.4f ms\n", who, "k_transient_sens", ms_sens);
+    std::fprintf(stderr, "[%s] %-28s %10.2f %%\n", who, "k_transient_sens_share", 100.0 * ms_sens / ms);
   }
   return PL_OK;
 }

@@ -128,3 +128,105 @@ def newmark(K, M, fixed, dt, n_steps, patterns=None, amp=None, u0=None, v0=None,
     if snap_every and snap_every > 0:
         out["snaps"] = out["u"][snap_every::snap_every][: n_steps // snap_every].copy()
     return out
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# Discrete adjoint of the scheme: radius sensitivities of one scalar output per row (csrc/pl_dyn_sens.h, pl_transient_sens;
+# DESIGN.md section 10h)
+# ---------------------------------------------------------------------------------------------------------------------
+def objective(y, kind, p=8.0, weight=None):
+    """(J, c) with c_n = dJ/dy_n for the outputs y (n_steps + 1,) and weights w >= 0 (None = 1):
+    kind 0: J = sum w y, 1: J = 1/2 sum w y^2, 2: J = (sum w |y|^p)^(1/p), p >= 2 (c = 0 where J = 0)."""
+    y = np.asarray(y, float).reshape(-1)
+    w = np.ones_like(y) if weight is None else np.asarray(weight, float).reshape(-1)
+    if w.shape != y.shape or (w < 0.0).any():
+        raise ValueError("weight must have one entry per row and must not be negative")
+    if kind == 0:
+        return float(w @ y), w.copy()
+    if kind == 1:
+        return 0.5 * float(w @ (y * y)), w * y
+    if kind == 2:
+        if not p >= 2.0:
+            raise ValueError("p must be at least 2")
+        # scaled by the largest |y|: no overflow of |y|^p
+        top = float(np.abs(y).max())
+        if top == 0.0:
+            return 0.0, np.zeros_like(y)
+        s = np.abs(y) / top
+        Js = float(w @ s ** p) ** (1.0 / p)
+        if Js == 0.0:
+            return 0.0, np.zeros_like(y)
+        return top * Js, Js ** (1.0 - p) * w * s ** (p - 1.0) * np.sign(y)
+    raise ValueError("kind must be 0, 1 or 2")
+
+
+def newmark_sensitivity(K, M, fixed, conn, drec_dr, dM_dr, dt, n_steps, out_vec, kind=2, p=8.0, weight=None, patterns=None,
+                        amp=None, base_dir=None, base_acc=None, u0=None, v0=None, beta=0.25, gamma=0.5, ray_m=0.0, ray_k=0.0,
+                        solve=None):
+    """What pl_transient_sens computes: J of the outputs y_n = l . u_n of ``newmark`` and dJ/dr_b at fixed segment geometry
+    by the discrete adjoint of the scheme (discretise, then differentiate).
+
+    conn (B, 2), drec_dr (B, 8) the radius derivative of the condensed records (stress_host.drecords_dr) and dM_dr
+    (B, 12, 12) that of the mass elements (mass_host.delement_matrix_dr) give dK_e/dr_b and dM_e/dr_b; out_vec = l (6N,) or
+    (N, 6), read with the fixed dofs zeroed.  base_dir (3,) with base_acc (n_steps + 1,) adds the load -a_g[n] M e_dir, e_dir
+    the rigid translation of ALL nodes: the only load that follows the design.  Point masses have no derivative.
+
+    With c2 = dt^2 (1/2 - beta), c3 = dt (1 - gamma), cu = beta dt^2, cv = gamma dt and c_n = dJ/dy_n, mu = nu = 0, for
+    n = N ... 1:
+        S lam_n = (cu + cv dt + c2) mu + (cv + c3) nu - cu c_n l
+        mu, nu <- mu - c_n l - K lam_n,  nu + dt mu - C lam_n            (the OLD mu on the right)
+    and M lam_0 = c2 mu + c3 nu;
+        dJ/dr_b = sum_n lam_n,e^T dK_e (u_n + ray_k v_n)_e + lam_n,e^T dM_e (a_n + ray_m v_n + a_g[n] e_dir)_e.
+    Returns a dict: J, y (n_steps + 1,), dJ_dr (B,), lam (n_steps + 1, N, 6), c (n_steps + 1,)."""
+    from . import geometric_host as GH
+    n_steps = int(n_steps)
+    fx = np.asarray(fixed).reshape(-1) != 0
+    n6 = fx.size
+    N = n6 // 6
+    free = np.flatnonzero(~fx)
+    K, M = sp.csr_matrix(K), sp.csr_matrix(M)
+    P = np.zeros((0, n6)) if patterns is None else np.asarray(patterns, float).reshape(-1, n6)
+    A = np.zeros((n_steps + 1, 0)) if patterns is None else np.asarray(amp, float).reshape(n_steps + 1, P.shape[0])
+    e_dir = np.zeros((N, 6))
+    a_g = np.zeros(n_steps + 1)
+    if base_dir is not None:
+        if base_acc is None:
+            raise ValueError("base_dir needs base_acc")
+        e_dir[:, :3] = np.asarray(base_dir, float).reshape(3)
+        a_g = np.asarray(base_acc, float).reshape(n_steps + 1)
+        P = np.vstack([P, -(M @ e_dir.reshape(-1))[None]])
+        A = np.column_stack([A, a_g])
+    fwd = newmark(K, M, fixed, dt, n_steps, P if P.shape[0] else None, A if P.shape[0] else None, u0, v0, beta, gamma,
+                  ray_m, ray_k, solve)
+    U, V, Acc = (fwd[q].reshape(n_steps + 1, n6) for q in "uva")
+    l = np.where(fx, 0.0, np.asarray(out_vec, float).reshape(-1))
+    y = U @ l
+    J, c = objective(y, kind, p, weight)
+
+    Kf, Mf = K[free][:, free].tocsr(), M[free][:, free].tocsr()
+    Cf = ray_m * Mf + ray_k * Kf
+    S = ((1.0 + gamma * dt * ray_m) * Mf + (beta * dt * dt + gamma * dt * ray_k) * Kf).tocsr()
+    solve = solve or _dense_solver()
+    c2, c3, cu, cv = dt * dt * (0.5 - beta), dt * (1.0 - gamma), beta * dt * dt, gamma * dt
+    lf = l[free]
+    mu, nu = np.zeros(free.size), np.zeros(free.size)
+    lam = np.zeros((n_steps + 1, n6))
+    for n in range(n_steps, 0, -1):
+        x = solve(S, (cu + cv * dt + c2) * mu + (cv + c3) * nu - cu * c[n] * lf)
+        lam[n, free] = x
+        mu, nu = mu - c[n] * lf - Kf @ x, nu + dt * mu - Cf @ x
+    lam[0, free] = solve(Mf, c2 * mu + c3 * nu)
+
+    conn = np.asarray(conn).reshape(-1, 2)
+    drec = np.asarray(drec_dr, float).reshape(-1, 8)
+    dM = np.asarray(dM_dr, float).reshape(-1, 12, 12)
+    ia, ib = conn[:, 0], conn[:, 1]
+    wK = (U + ray_k * V).reshape(-1, N, 6)
+    wM = (Acc + ray_m * V).reshape(-1, N, 6) + a_g[:, None, None] * e_dir[None]
+    lam3 = lam.reshape(-1, N, 6)
+    grad = np.zeros(len(conn))
+    for n in range(n_steps + 1):
+        le = np.concatenate([lam3[n][ia], lam3[n][ib]], axis=1)
+        we = np.concatenate([wM[n][ia], wM[n][ib]], axis=1)
+        grad += GH._pairing(drec, conn, wK[n], lam3[n]) + np.einsum("bi,bij,bj->b", le, dM, we)
+    return {"J": J, "y": y, "dJ_dr": grad, "lam": lam3, "c": c}

@@ -69,6 +69,9 @@ class LatticeOpti(LatticeSim):
         if self._ddm_mode and "frequency" in (info.get("constraints") or {}):
             raise NotImplementedError('the "frequency" constraint needs simulation_type "FEM": the mass of the recovered '
                                       "interiors of DDM cells is not implemented")
+        if self._ddm_mode and "peak_displacement" in (info.get("constraints") or {}):
+            raise NotImplementedError('the "peak_displacement" constraint needs simulation_type "FEM": the transient response '
+                                      "of the recovered interiors of DDM cells is not implemented")
         comp = ((params.get("simulation_parameters", {}).get("DDM") or {}).get("schur_complement_computation") or {})
         if ddm_gradient is None:
             ddm_gradient = comp.get("gradient", "finite_difference") if self._ddm_mode else "finite_difference"
@@ -115,6 +118,10 @@ class LatticeOpti(LatticeSim):
         self._last_frequency = None
         if "frequency" in self.constraints_dict:
             self._history["min_frequency"] = []
+        self._last_peak_displacement = None
+        self._peak_cache = None             # (parameters, aggregate): the value and the gradient of one design share one call
+        if "peak_displacement" in self.constraints_dict:
+            self._history["peak_displacement"] = []
         self._set_number_parameters_optimization()
         # strut -> (cell, type) of the LAST cell that holds it: Cell.change_beam_radius (cell.py:896-917) is called
         # cell after cell, so a strut shared by several cells ends with the last one's radius
@@ -763,6 +770,44 @@ class LatticeOpti(LatticeSim):
         _, _, dJ_dr = self.frequency_aggregate(want_grad=True)
         return (2.0 * np.pi * self._frequency_settings()[0]) ** 2 * self._strut_gradient_to_parameters(dJ_dr)
 
+    # -- peak displacement constraint (FEM mode): p-norm over time of one output of the transient response, pl_transient_sens ------
+    def _peak_displacement_settings(self):
+        c = self.constraints_dict["peak_displacement"]
+        run = dict(dt=float(c["dt"]), n_steps=int(c["n_steps"]), density=float(c["density"]), amplitude=c.get("amplitude", None),
+                   base_acceleration=c.get("base_acceleration", None), damping=tuple(c.get("damping", (0.0, 0.0))),
+                   rotary=bool(c.get("rotary", True)), node_mass=c.get("node_mass", None))
+        kw = {k: c[k] for k in ("beta", "gamma", "rtol", "max_iter") if k in c}
+        return float(c["max_displacement"]), run, kw, c.get("output", None), float(c.get("p", 8))
+
+    def peak_displacement_aggregate(self):
+        """(J_p, max_n |y_n|, dJ/dr_b) of the current design under the constraint's transient run: y_n = l . u_n the output of
+        row n, J_p = (sum_n |y_n|^p)^(1/p) >= max_n |y_n|.  One pl_transient_sens call gives all three (the forward pass and
+        the adjoint sweep); the value and the gradient of one design share it."""
+        key = tuple(map(float, self.actual_optimization_parameters)) if len(self.actual_optimization_parameters) else None
+        if self._peak_cache is not None and key is not None and self._peak_cache[0] == key:
+            return self._peak_cache[1]
+        _, run, kw, output, p = self._peak_displacement_settings()
+        self._transient_settings = self._transient_setup("peak_displacement", kw=kw, **run)
+        out = self.transient_sensitivity(output, kind=2, p=p)
+        res = (out["J"], float(np.abs(out["y"]).max()), out["dJ_dr"])
+        self._last_peak_displacement = res[:2]
+        self._peak_cache = (key, res)
+        return res
+
+    def peak_displacement_constraint(self, r):
+        """J_p / max_displacement - 1 (<= 0 when feasible: J_p >= max_n |y_n|, so the peak stays below max_displacement then)."""
+        self.set_optimization_parameters(r)
+        if not self._sim_is_current:
+            self._simulate_lattice_equilibrium()
+        return self.peak_displacement_aggregate()[0] / self._peak_displacement_settings()[0] - 1.0
+
+    def peak_displacement_constraint_gradient(self, r):
+        """d(peak_displacement_constraint)/d(theta): dJ/dr_b / max_displacement through _strut_gradient_to_parameters."""
+        self.set_optimization_parameters(r)
+        if not self._sim_is_current:
+            self._simulate_lattice_equilibrium()
+        return self._strut_gradient_to_parameters(self.peak_displacement_aggregate()[2]) / self._peak_displacement_settings()[0]
+
     # -- driver (SciPy SLSQP, as the reference) ---------------------------------------------------------------------
     def _initialize_optimization_solver(self):
         from scipy.optimize import Bounds
@@ -796,6 +841,9 @@ class LatticeOpti(LatticeSim):
                                                     else self._last_global_buckling[1])
         if "min_frequency" in self._history:
             self._history["min_frequency"].append(None if self._last_frequency is None else self._last_frequency[1])
+        if "peak_displacement" in self._history:
+            self._history["peak_displacement"].append(None if self._last_peak_displacement is None
+                                                      else self._last_peak_displacement[1])
         self._history["parameters"].append(list(map(float, r)))
         self._history["timestamp"].append(time.time())
 
@@ -824,6 +872,9 @@ class LatticeOpti(LatticeSim):
         if "frequency" in self.constraints_dict:
             jac = {"jac": self.frequency_constraint_gradient} if self.enable_gradient_computing else {}
             self.constraints.append(NonlinearConstraint(self.frequency_constraint, -np.inf, 0.0, **jac))
+        if "peak_displacement" in self.constraints_dict:
+            jac = {"jac": self.peak_displacement_constraint_gradient} if self.enable_gradient_computing else {}
+            self.constraints.append(NonlinearConstraint(self.peak_displacement_constraint, -np.inf, 0.0, **jac))
         kw = dict(fun=self.objective, x0=self.initial_parameters, method="SLSQP", bounds=self.bounds,
                   constraints=self.constraints, callback=self.callback_function,
                   options={"maxiter": self.optim_max_iteration, "ftol": self.optim_ftol, "disp": self.optim_disp,

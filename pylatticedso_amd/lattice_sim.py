@@ -727,30 +727,13 @@ class LatticeSim(LatticeViews):
         (n_steps + 1,), ``transient_probe`` (n_steps + 1, 3, n_probe, 6) = u, v, a of the probes, ``transient_energy``
         (n_steps + 1, 3) = kinetic, strain, external work, ``transient_state`` (3, n_nodes, 6) and returns the device call's
         dict."""
-        if getattr(self, "_compat_rows", False) or self.domain_decomposition_solver:
-            raise NotImplementedError("transient_response: the default strut model on a FEM lattice only (no reference_compat "
-                                      "rows, no domain decomposition)")
-        if self._device is None:
-            raise RuntimeError("transient_response needs a solve_FEM_FenicsX on this lattice first")
-        dev, n, rows = self._device, self.lattice.n_nodes, int(n_steps) + 1
-        dev.set_mass(density, rotary, node_mass)
-        time = float(dt) * np.arange(rows)
-        force = np.zeros((n, 6))
-        force[:, :3] = np.asarray(self.applied_force)[:n, :3]      # (only the translational components are loads)
-        if amplitude is None:
-            amp0 = np.ones(rows)
-        elif callable(amplitude):
-            amp0 = np.array([float(amplitude(t)) for t in time])
-        else:
-            amp0 = np.asarray(amplitude, float).reshape(-1)
-            if amp0.size != rows:
-                raise ValueError(f"amplitude must have {rows} entries")
+        s = self._transient_setup("transient_response", dt, n_steps, density, amplitude, base_acceleration, damping, rotary,
+                                  node_mass, kw)
+        dev, n = self._device, self.lattice.n_nodes
+        force, amp0 = s["force"], s["amp0"]
         patterns, amps = [force], [amp0]
         if base_acceleration is not None:
-            direction, a_g = base_acceleration
-            a_g = np.asarray(a_g, float).reshape(-1)
-            if a_g.size != rows:
-                raise ValueError(f"base_acceleration needs {rows} accelerations")
+            direction, a_g = s["base_acceleration"]
             e = np.zeros((1, n, 6))
             e[0, :, :3] = np.asarray(direction, float).reshape(3)
             patterns.append(-dev.mass_spmv_multi(e)[0])
@@ -763,7 +746,69 @@ class LatticeSim(LatticeViews):
         self.transient_time, self.transient_probe = out["time"], out["probe"]
         self.transient_energy, self.transient_state = out["energy"], out["state"]
         self._transient_probes = probes
+        self._transient_settings = s
         return out
+
+    def _transient_setup(self, who, dt, n_steps, density, amplitude, base_acceleration, damping, rotary, node_mass, kw):
+        """The checks of ``transient_response``, the mass model on the device, and the settings of the run as a dict: what
+        ``transient_sensitivity`` runs again."""
+        if getattr(self, "_compat_rows", False) or self.domain_decomposition_solver:
+            raise NotImplementedError(f"{who}: the default strut model on a FEM lattice only (no reference_compat "
+                                      "rows, no domain decomposition)")
+        if self._device is None:
+            raise RuntimeError(f"{who} needs a solve_FEM_FenicsX on this lattice first")
+        n, rows = self.lattice.n_nodes, int(n_steps) + 1
+        self._device.set_mass(density, rotary, node_mass)
+        time = float(dt) * np.arange(rows)
+        force = np.zeros((n, 6))
+        force[:, :3] = np.asarray(self.applied_force)[:n, :3]      # (only the translational components are loads)
+        if amplitude is None:
+            amp0 = np.ones(rows)
+        elif callable(amplitude):
+            amp0 = np.array([float(amplitude(t)) for t in time])
+        else:
+            amp0 = np.asarray(amplitude, float).reshape(-1)
+            if amp0.size != rows:
+                raise ValueError(f"amplitude must have {rows} entries")
+        if base_acceleration is not None:
+            direction, a_g = base_acceleration
+            a_g = np.asarray(a_g, float).reshape(-1)
+            if a_g.size != rows:
+                raise ValueError(f"base_acceleration needs {rows} accelerations")
+            base_acceleration = (np.asarray(direction, float).reshape(3), a_g)
+        run = {q: kw[q] for q in ("beta", "gamma", "rtol", "max_iter", "u0", "v0") if q in kw}
+        return dict(dt=float(dt), n_steps=int(n_steps), density=density, rotary=rotary, node_mass=node_mass, force=force,
+                    amp0=amp0, base_acceleration=base_acceleration, damping=(float(damping[0]), float(damping[1])), run=run)
+
+    def transient_sensitivity(self, output=None, kind=2, p=8, weight=None):
+        """Radius derivatives of an objective of the last ``transient_response``, on the device (pl_transient_sens: the run
+        again with the same time step, density, amplitude, base acceleration, damping and scheme, then the discrete adjoint
+        of the scheme backwards in time).  One output per row y_n = l . u_n: ``output`` is l as an (n_nodes, 6) array, a
+        (node, dof) pair, or None = the force pattern scaled to unit norm.  J of the outputs with the weights ``weight``
+        (n_steps + 1,) or None = 1: kind 0 sum w y, 1 1/2 sum w y^2, 2 (sum w |y|^p)^(1/p) >= max |y| for w = 1.  Returns a
+        dict with J, y (n_steps + 1,) and dJ_dr (n_beams,) at fixed segment geometry, plus the iterations of both passes."""
+        if getattr(self, "_compat_rows", False) or self.domain_decomposition_solver:
+            raise NotImplementedError("transient_sensitivity: the default strut model on a FEM lattice only (no "
+                                      "reference_compat rows, no domain decomposition)")
+        s = getattr(self, "_transient_settings", None)
+        if s is None or self._device is None:
+            raise RuntimeError("transient_sensitivity needs a transient_response on this lattice first")
+        n = self.lattice.n_nodes
+        if output is None:
+            norm = float(np.linalg.norm(s["force"]))
+            if norm == 0.0:
+                raise ValueError("transient_sensitivity: no force pattern to take the output from; give output")
+            l = s["force"] / norm
+        elif np.ndim(output) == 1 and np.size(output) == 2:
+            l = np.zeros((n, 6))
+            l[int(output[0]), int(output[1])] = 1.0
+        else:
+            l = np.asarray(output, float).reshape(n, 6)
+        base = s["base_acceleration"]
+        self._device.set_mass(s["density"], s["rotary"], s["node_mass"])
+        return self._device.transient_sens(s["dt"], s["n_steps"], l, kind, p, weight, s["force"][None], s["amp0"][:, None],
+                                           None if base is None else base[0], None if base is None else base[1],
+                                           ray_m=s["damping"][0], ray_k=s["damping"][1], **s["run"])
 
     def dynamic_amplification(self):
         """max_t |u| / |u_static| of every probe of the last ``transient_response``, |.| the norm of the three translations and
