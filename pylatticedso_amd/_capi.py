@@ -513,13 +513,26 @@ class HipLattice:
         self.close()
 
     # -- data -------------------------------------------------------------------------------------------
+    def _opt_vec6(self, a):
+        """An optional nodal vector ((N, 6) or (6 N,)) as contiguous float64; None stays None (the library's NULL)."""
+        return None if a is None else _f64(np.asarray(a).reshape(-1), 6 * self.n_nodes)
+
+    def _pnorm(self, call, u, want_grad, *args):
+        """(value, max, d/du (N, 6) or None, d/dr (B,) or None) of a pl_*_pnorm entry point, which takes (handle, u, *args,
+        &value, &max, du, dr)."""
+        val, vmax = C.c_double(), C.c_double()
+        du = np.empty((self.n_nodes, 6), np.float64) if want_grad else None
+        dr = np.empty(self.n_beams, np.float64) if want_grad else None
+        _check(self._lib, call(self._h, _ptr(self._opt_vec6(u)), *args, C.byref(val), C.byref(vmax), _ptr(du), _ptr(dr)))
+        return val.value, vmax.value, du, dr
+
     def set_bc(self, fixed, ubar=None, f=None):
         n6 = 6 * self.n_nodes
         fx = np.ascontiguousarray(np.asarray(fixed).reshape(-1) != 0, dtype=np.uint8)
         if fx.size != n6:
             raise ValueError("fixed must have 6*n_nodes entries")
-        ub = None if ubar is None else _f64(np.asarray(ubar).reshape(-1), n6)
-        ff = None if f is None else _f64(np.asarray(f).reshape(-1), n6)
+        ub = self._opt_vec6(ubar)
+        ff = self._opt_vec6(f)
         _check(self._lib, self._lib.pl_set_bc(self._h, _ptr(fx), _ptr(ub), _ptr(ff)))
 
     def update_radii(self, radius):
@@ -609,8 +622,8 @@ class HipLattice:
     def sens(self, u, lam=None):
         """Per-strut sensitivities lam^T (dK_e/dr) u (pl_sens).  u = None: the solution of the last solve() of this handle,
         still on the device (no upload)."""
-        u = None if u is None else _f64(np.asarray(u).reshape(-1), 6 * self.n_nodes)
-        lam_a = None if lam is None else _f64(np.asarray(lam).reshape(-1), 6 * self.n_nodes)
+        u = self._opt_vec6(u)
+        lam_a = self._opt_vec6(lam)
         out = np.empty(self.n_beams, np.float64)
         _check(self._lib, self._lib.pl_sens(self._h, _ptr(u), _ptr(lam_a), _ptr(out)))
         return out
@@ -647,7 +660,7 @@ class HipLattice:
         """Section forces and von Mises stress at the stations [A, q1, q2, B] of every strut (pl_stress): dict with N, V, T,
         Mb, sigma_vm of shape (B, 4) (NaN at absent stations) and peak (B,).  u = None: the solution of the last solve().
         where = 0: all stations, 1: the two ends of the middle segment only."""
-        u = None if u is None else _f64(np.asarray(u).reshape(-1), 6 * self.n_nodes)
+        u = self._opt_vec6(u)
         st = np.empty((self.n_beams, 4, 5), np.float64)
         peak = np.empty(self.n_beams, np.float64)
         _check(self._lib, self._lib.pl_stress(self._h, _ptr(u), int(where), _ptr(st), _ptr(peak)))
@@ -658,13 +671,7 @@ class HipLattice:
     def stress_pnorm(self, p, u=None, where=0, want_grad=True):
         """(phi, sigma_max, dphi_du (N, 6), dphi_dr (B,)) of the p-norm aggregate of sigma_vm over the stations
         (pl_stress_pnorm); the two derivatives are None with want_grad=False.  dphi_dr: at fixed u and segment geometry."""
-        u = None if u is None else _f64(np.asarray(u).reshape(-1), 6 * self.n_nodes)
-        phi, smax = C.c_double(), C.c_double()
-        du = np.empty((self.n_nodes, 6), np.float64) if want_grad else None
-        dr = np.empty(self.n_beams, np.float64) if want_grad else None
-        _check(self._lib, self._lib.pl_stress_pnorm(self._h, _ptr(u), int(where), float(p), C.byref(phi), C.byref(smax),
-                                                    _ptr(du), _ptr(dr)))
-        return phi.value, smax.value, du, dr
+        return self._pnorm(self._lib.pl_stress_pnorm, u, want_grad, int(where), float(p))
 
     def stress_host(self, u, where=0):
         """The numpy restatement of ``stress`` (stress_host.strut_stress) on this handle's records and segment data."""
@@ -683,7 +690,7 @@ class HipLattice:
         """Euler buckling utilisation of every strut (pl_buckling): dict with util = max(0, -N) / N_cr, n_axial (signed N of
         one copy) and n_crit, each (B,).  u = None: the solution of the last solve().  length = 0: node-to-node buckling
         length, 1: the middle segment (NaN on a strut without one); k_eff: effective-length factor; shear = 1: Engesser."""
-        u = None if u is None else _f64(np.asarray(u).reshape(-1), 6 * self.n_nodes)
+        u = self._opt_vec6(u)
         out = {name: np.empty(self.n_beams, np.float64) for name in ("util", "n_axial", "n_crit")}
         _check(self._lib, self._lib.pl_buckling(self._h, _ptr(u), int(length), float(k_eff), int(shear), _ptr(out["util"]),
                                                 _ptr(out["n_axial"]), _ptr(out["n_crit"])))
@@ -692,13 +699,7 @@ class HipLattice:
     def buckling_pnorm(self, p, u=None, length=1, k_eff=1.0, shear=0, want_grad=True):
         """(bp, util_max, dbp_du (N, 6), dbp_dr (B,)) of the p-norm aggregate of the utilisations (pl_buckling_pnorm); the
         two derivatives are None with want_grad=False.  dbp_dr: at fixed u and segment geometry."""
-        u = None if u is None else _f64(np.asarray(u).reshape(-1), 6 * self.n_nodes)
-        bp, bmax = C.c_double(), C.c_double()
-        du = np.empty((self.n_nodes, 6), np.float64) if want_grad else None
-        dr = np.empty(self.n_beams, np.float64) if want_grad else None
-        _check(self._lib, self._lib.pl_buckling_pnorm(self._h, _ptr(u), int(length), float(k_eff), int(shear), float(p),
-                                                      C.byref(bp), C.byref(bmax), _ptr(du), _ptr(dr)))
-        return bp.value, bmax.value, du, dr
+        return self._pnorm(self._lib.pl_buckling_pnorm, u, want_grad, int(length), float(k_eff), int(shear), float(p))
 
     def buckling_host(self, u, length=1, k_eff=1.0, shear=0):
         """The numpy restatement of ``buckling`` (buckling_host.strut_buckling) on this handle's records and segment data."""
@@ -784,7 +785,7 @@ class HipLattice:
         axial forces in u (None: the solution of the last solve()); masked: P K_g P X[j] under the mask of set_bc.
         X (k, N, 6) or (k, 6 N); returns (k, N, 6)."""
         x = self._columns("X", X)
-        u = None if u is None else _f64(np.asarray(u).reshape(-1), 6 * self.n_nodes)
+        u = self._opt_vec6(u)
         y = np.empty_like(x)
         _check(self._lib, self._lib.pl_geom_spmv_multi(self._h, _ptr(u), x.shape[0], int(bool(masked)), _ptr(x), _ptr(y)))
         return y.reshape(x.shape[0], self.n_nodes, 6)
@@ -796,7 +797,7 @@ class HipLattice:
         largest component positive), residual (n_modes,), n_found and outer_iterations; entries beyond n_found are NaN.
         u = None: the solution of the last solve().  n_sub: columns of the subspace iteration (0 = the library's choice);
         rtol, max_iter: its inner PCG; tol, max_outer: its stopping rule."""
-        u = None if u is None else _f64(np.asarray(u).reshape(-1), 6 * self.n_nodes)
+        u = self._opt_vec6(u)
         n_modes = int(n_modes)
         lam = np.empty(max(n_modes, 0), np.float64)
         modes = np.empty((max(n_modes, 0), self.n_nodes, 6), np.float64)
@@ -821,7 +822,7 @@ class HipLattice:
         phi = np.ascontiguousarray(np.asarray(modes, dtype=np.float64)).reshape(-1)
         if phi.size != k * 6 * self.n_nodes:
             raise ValueError(f"modes must have shape ({k}, {self.n_nodes}, 6)")
-        u = None if u is None else _f64(np.asarray(u).reshape(-1), 6 * self.n_nodes)
+        u = self._opt_vec6(u)
         wts = None if weights is None else _f64(np.asarray(weights).reshape(-1), k)
         rows = np.empty((k, self.n_beams), np.float64) if want_rows else None
         dsum = np.empty(self.n_beams, np.float64) if wts is not None else None
@@ -985,8 +986,8 @@ class HipLattice:
             am = np.ascontiguousarray(np.asarray(amp, dtype=np.float64).reshape(-1))
             if am.size != rows * n_pat:
                 raise ValueError(f"amp must have shape ({rows}, {n_pat})")
-        uu = None if u0 is None else _f64(np.asarray(u0).reshape(-1), n6)
-        vv = None if v0 is None else _f64(np.asarray(v0).reshape(-1), n6)
+        uu = self._opt_vec6(u0)
+        vv = self._opt_vec6(v0)
         pr = np.zeros(0, np.int32) if probes is None else np.ascontiguousarray(np.asarray(probes).reshape(-1), dtype=np.int32)
         probe = np.zeros((rows, 3, pr.size, 6), np.float64)
         energy = np.zeros((rows, 3), np.float64)
@@ -1039,8 +1040,8 @@ class HipLattice:
                 raise ValueError(f"amp must have shape ({rows}, {n_pat})")
         bd = None if base_dir is None else _f64(np.asarray(base_dir).reshape(-1), 3)
         ba = None if base_acc is None else _f64(np.asarray(base_acc).reshape(-1), rows)
-        uu = None if u0 is None else _f64(np.asarray(u0).reshape(-1), n6)
-        vv = None if v0 is None else _f64(np.asarray(v0).reshape(-1), n6)
+        uu = self._opt_vec6(u0)
+        vv = self._opt_vec6(v0)
         lv = _f64(np.asarray(out_vec).reshape(-1), n6)
         wt = None if weight is None else _f64(np.asarray(weight).reshape(-1), rows)
         J = C.c_double()

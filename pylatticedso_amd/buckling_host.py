@@ -83,13 +83,8 @@ def buckling_pnorm(rec, node_count, beam_conn, radius, seg_len, seg_nsub, u, p, 
     total = float((x ** p).sum())
     w = np.where(live, x ** (p - 1.0) * total ** (1.0 / p - 1.0), 0.0)            # dB / d beta_b
     gF = (-w / (ev["k"] * ev["n_cr"]))[:, None] * ev["t"]                          # dB / dF; dB / dM_B = 0
-    rec, conn, d = ev["rec"], ev["conn"], ev["d"]
-    a, e1, e2 = rec[:, 0:1], rec[:, 2:3], rec[:, 3:4]
-    Gu = a * gF + e1 * SH._dot(gF, d)[:, None] * d                                 # the symmetric tip block applied to (g_F, 0)
-    Gth = -e2 * np.cross(d, gF)
-    du = np.zeros((node_count, 6))
-    np.add.at(du, conn[:, 1], np.column_stack([Gu, Gth]))
-    np.add.at(du, conn[:, 0], np.column_stack([-Gu, -Gth - np.cross(d, Gu)]))
+    conn, d = ev["conn"], ev["d"]
+    du = SH.scatter_tip_gradient(ev["rec"], conn, node_count, gF, np.zeros_like(gF))
     f = SH.flexibility(ev["r"], seg_len, seg_nsub, young, poisson, kappa, pen_coef, mult)
     dF, _ = SH.tip_force(SH._record(SH._dscalars_dr(f, ev["r"]), d), conn, u)
     q = ev["q"]

@@ -1509,37 +1509,19 @@ int pl_reactions(pl_handle h, const double *u, double *R) { return spmv_common(h
 int pl_sens(pl_handle h, const double *u, const double *lam, double *dCdr) {
   if (!valid(h) || !dCdr) return fail(PL_ERR_ARG, "pl_sens: null argument");
   if (h->opkind != 0) return fail(PL_ERR_STATE, "pl_sens: not available on a DDM handle");
-  // u == NULL: the solution of the last pl_solve, still on the device (a design loop evaluates the sensitivities of the
-  // displacement field it has just computed: no 6N-vector upload)
-  if (!u && !(h->usol.p && h->usol_valid)) return fail(PL_ERR_STATE, "pl_sens: u = NULL needs a pl_solve on this handle first");
-  PL_HIP(hipSetDevice(h->opt.device));
-  std::vector<double> stage;
-  int rc = PL_OK;
-  const double *u_dev = h->usol.p;
-  if (u) {
-    rc = upload6(h, u, h->tmp.p, stage);
-    if (rc) return rc;
-    u_dev = h->tmp.p;
-  }
+  const double *u_dev = nullptr;
+  if (int rc = state_on_device(h, "pl_sens", u, &u_dev)) return rc;
   const double *lam_dev = u_dev;
   if (lam) {
-    rc = upload6(h, lam, h->tmp2.p, stage);
-    if (rc) return rc;
+    std::vector<double> stage;
+    if (int rc = upload6(h, lam, h->tmp2.p, stage)) return rc;
     lam_dev = h->tmp2.p;
   }
   if (!h->sens_out.p) PL_HIP(h->sens_out.alloc(h->B));
   hipLaunchKernelGGL(pl::k_sens, dim3(grid_for(h->B)), dim3(pl::kBlock), 0, h->stream, h->B, h->xyz.p, h->conn.p,
                      h->radius.p, h->seg_len.p, h->seg_nsub.p, h->mult.p, h->mat, u_dev, lam_dev, h->sens_out.p);
   PL_HIP(hipGetLastError());
-  double *stg = nullptr;
-  rc = stagingB(h, &stg);
-  if (rc) return rc;
-  PL_HIP(hipMemcpyAsync(stg, h->sens_out.p, h->B * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-  PL_HIP(hipStreamSynchronize(h->stream));
-  pl::parallel_for(h->B, [&](int64_t b0, int64_t b1, unsigned) {
-    for (int64_t b = b0; b < b1; ++b) dCdr[h->bperm[b]] = stg[b];
-  }, 1 << 16);
-  return PL_OK;
+  return download_struts(h, h->sens_out.p, dCdr);
 }
 
 int pl_sens_gram(pl_handle h, int32_t n_rhs, const double *x, double *gram) {
@@ -1572,11 +1554,7 @@ int pl_sens_gram(pl_handle h, int32_t n_rhs, const double *x, double *gram) {
   h->gram_cols = n_rhs;
   PL_HIP(hipMemcpyAsync(h->pinG, h->gram_out.p, pairs * B * sizeof(double), hipMemcpyDeviceToHost, h->stream));
   PL_HIP(hipStreamSynchronize(h->stream));
-  const double *stg = h->pinG;
-  pl::parallel_for(h->B, [&](int64_t b0, int64_t b1, unsigned) {
-    for (size_t p = 0; p < pairs; ++p)
-      for (int64_t b = b0; b < b1; ++b) gram[p * B + (size_t)h->bperm[b]] = stg[p * B + (size_t)b];
-  }, 1 << 14);
+  for (size_t p = 0; p < pairs; ++p) struts_to_caller(h, h->pinG + p * B, gram + p * B);   // rows [pairs][B], one transfer
   return PL_OK;
 }
 
@@ -1593,11 +1571,7 @@ int pl_node_mod(pl_handle h, const double *u, double *out) {
   hipLaunchKernelGGL(pl::k_node_mod, dim3(grid_for(h->B)), dim3(pl::kBlock), 0, h->stream, h->B, h->xyz.p, h->conn.p,
                      h->radius.p, h->seg_len.p, h->seg_nsub.p, h->mult.p, h->mat, h->rec.p, h->tmp.p, dev.p);
   PL_HIP(hipGetLastError());
-  std::vector<double> tmp((size_t)h->B * 12);
-  PL_HIP(hipMemcpyAsync(tmp.data(), dev.p, tmp.size() * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-  PL_HIP(hipStreamSynchronize(h->stream));
-  for (int64_t b = 0; b < h->B; ++b) std::memcpy(out + 12 * (size_t)h->bperm[b], &tmp[12 * (size_t)b], 12 * sizeof(double));
-  return PL_OK;
+  return download_struts(h, dev.p, out, 12);
 }
 
 namespace {
@@ -1608,16 +1582,7 @@ int stress_begin(pl_handle h, const char *who, const double *u, int32_t where, c
   if (h->dist.active) return fail(PL_ERR_STATE, std::string(who) + ": not available on a multi-GPU handle");
   if (!h->assembled) return fail(PL_ERR_STATE, std::string(who) + ": call pl_assemble first");
   if (where != 0 && where != 1) return fail(PL_ERR_ARG, std::string(who) + ": where must be 0 (all stations) or 1 (middle segment)");
-  if (!u && !(h->usol.p && h->usol_valid))
-    return fail(PL_ERR_STATE, std::string(who) + ": u = NULL needs a pl_solve on this handle first");
-  PL_HIP(hipSetDevice(h->opt.device));
-  *u_dev = h->usol.p;
-  if (u) {
-    std::vector<double> stage;
-    if (int rc = upload6(h, u, h->tmp.p, stage)) return rc;
-    *u_dev = h->tmp.p;
-  }
-  return PL_OK;
+  return state_on_device(h, who, u, u_dev);
 }
 // PL_TIMING in the environment: HIP-event times of a call's device stages on stderr, "[<who>] <stage> <ms> ms" with four
 // decimals (tools/time_*.py read this format).  mark(stage) records an event on the stream; a stage runs from its mark to the
@@ -1672,82 +1637,78 @@ int pl_stress(pl_handle h, const double *u, int32_t where, double *station, doub
                      peak ? h->st_dr.p : (double *)nullptr, (double *)nullptr, (double *)nullptr);
   PL_HIP(hipGetLastError());
   timer.stop();
-  if (station) {
-    std::vector<double> tmp((size_t)B * 20);
-    PL_HIP(hipMemcpyAsync(tmp.data(), d_station.p, tmp.size() * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-    PL_HIP(hipStreamSynchronize(h->stream));
-    pl::parallel_for(B, [&](int64_t b0, int64_t b1, unsigned) {
-      for (int64_t b = b0; b < b1; ++b) std::memcpy(station + 20 * (size_t)h->bperm[b], &tmp[20 * (size_t)b], 20 * sizeof(double));
-    }, 1 << 14);
-  }
-  if (peak) {
-    double *stg = nullptr;
-    if (int rc = stagingB(h, &stg)) return rc;
-    PL_HIP(hipMemcpyAsync(stg, h->st_dr.p, B * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-    PL_HIP(hipStreamSynchronize(h->stream));
-    pl::parallel_for(B, [&](int64_t b0, int64_t b1, unsigned) {
-      for (int64_t b = b0; b < b1; ++b) peak[h->bperm[b]] = stg[b];
-    }, 1 << 16);
-  }
+  if (station)
+    if (int rc = download_struts(h, d_station.p, station, 20)) return rc;
+  if (peak)
+    if (int rc = download_struts(h, h->st_dr.p, peak)) return rc;
   return PL_OK;
 }
 
-int pl_stress_pnorm(pl_handle h, const double *u, int32_t where, double p, double *phi, double *sigma_max, double *dphi_du,
-                    double *dphi_dr) {
-  const double *u_dev = nullptr;
-  if (int rc = stress_begin(h, "pl_stress_pnorm", u, where, &u_dev)) return rc;
-  if (!(p >= 1.0) || !std::isfinite(p)) return fail(PL_ERR_ARG, "pl_stress_pnorm: p must be >= 1");
-  if (!phi && !sigma_max && !dphi_du && !dphi_dr) return fail(PL_ERR_ARG, "pl_stress_pnorm: every output pointer is NULL");
+extern "C++" {   // (a template)
+namespace {
+// What pl_stress_pnorm and pl_buckling_pnorm share after their own checks: the checks of p and the outputs, the work arrays
+// (st_vm4 = the measure's per-strut values, one stream, every call ends with its downloads), the passes
+//     values -> fold<max> -> p-sum -> fold<sum> [-> grad<DR> [-> k_stress_gather]]
+// between the marks of the PL_TIMING line, red = (max, p-sum, p-norm) and the downloads.  The measure gives its three
+// launches: values(grid) fills st_vm4 and the block maxima in st_part, psum(grid) the block sums in st_part, and
+// grad(grid, std::bool_constant<DR>) G[b][6] in st_G and, with DR, d/dr in st_dr.  A new per-strut aggregate is one such triple.
+template <class Values, class Psum, class Grad>
+int pnorm_call(pl_handle h, const char *who, double p, double *value, double *value_max, double *d_du, double *d_dr,
+               Values values, Psum psum, Grad grad) {
+  if (!(p >= 1.0) || !std::isfinite(p)) return fail(PL_ERR_ARG, std::string(who) + ": p must be >= 1");
+  if (!value && !value_max && !d_du && !d_dr) return fail(PL_ERR_ARG, std::string(who) + ": every output pointer is NULL");
   const int64_t B = h->B, N = h->N;
   const unsigned grid = grid_for(B);
   if (!h->st_vm4.p) PL_HIP(h->st_vm4.alloc((size_t)B * 4));
   if (!h->st_part.p) PL_HIP(h->st_part.alloc(std::max<size_t>(grid, 1)));
   if (!h->st_red.p) PL_HIP(h->st_red.alloc(4));
-  const bool grad = dphi_du || dphi_dr;
-  if (grad && !h->st_G.p) PL_HIP(h->st_G.alloc((size_t)B * 6));
-  if (dphi_dr && !h->st_dr.p) PL_HIP(h->st_dr.alloc((size_t)B));
-  EventTimer timer("pl_stress_pnorm", h->stream, "kernel_hip_event");
-  hipLaunchKernelGGL(pl::k_stress_stations, dim3(grid), dim3(pl::kBlock), 0, h->stream, B, h->conn.p, h->rec.p, h->radius.p,
-                     h->seg_len.p, h->mult.p, h->mat.pen, (int)where, u_dev, (double *)nullptr, (double *)nullptr,
-                     h->st_vm4.p, h->st_part.p);
+  if ((d_du || d_dr) && !h->st_G.p) PL_HIP(h->st_G.alloc((size_t)B * 6));
+  if (d_dr && !h->st_dr.p) PL_HIP(h->st_dr.alloc((size_t)B));
+  EventTimer timer(who, h->stream, "kernel_hip_event");
+  values(grid);
   hipLaunchKernelGGL(pl::k_stress_fold<true>, dim3(1), dim3(pl::kBlock), 0, h->stream, (int64_t)grid, h->st_part.p, p,
                      h->st_red.p);
-  hipLaunchKernelGGL(pl::k_stress_psum, dim3(grid), dim3(pl::kBlock), 0, h->stream, B, h->st_vm4.p, h->st_red.p, p,
-                     h->st_part.p);
+  psum(grid);
   hipLaunchKernelGGL(pl::k_stress_fold<false>, dim3(1), dim3(pl::kBlock), 0, h->stream, (int64_t)grid, h->st_part.p, p,
                      h->st_red.p);
-  if (grad) {
-    if (dphi_dr)
-      hipLaunchKernelGGL(pl::k_stress_grad<true>, dim3(grid), dim3(pl::kBlock), 0, h->stream, B, h->conn.p, h->rec.p,
-                         h->radius.p, h->seg_len.p, h->seg_nsub.p, h->mult.p, h->mat, (int)where, p, u_dev, h->st_red.p,
-                         h->st_G.p, h->st_dr.p);
-    else
-      hipLaunchKernelGGL(pl::k_stress_grad<false>, dim3(grid), dim3(pl::kBlock), 0, h->stream, B, h->conn.p, h->rec.p,
-                         h->radius.p, h->seg_len.p, h->seg_nsub.p, h->mult.p, h->mat, (int)where, p, u_dev, h->st_red.p,
-                         h->st_G.p, (double *)nullptr);
-    if (dphi_du)   // (tmp2 is free: u sits in tmp or usol)
-      hipLaunchKernelGGL(pl::k_stress_gather, dim3(grid_for(N)), dim3(pl::kBlock), 0, h->stream, N, pl::kWave / h->lpn,
-                         h->slice_ptr.p, h->ent.p, h->rec.p, h->st_G.p, h->tmp2.p);
-  }
+  if (d_dr) grad(grid, std::true_type{});
+  else if (d_du) grad(grid, std::false_type{});
+  if (d_du)   // (tmp2 is free: u sits in tmp or usol)
+    hipLaunchKernelGGL(pl::k_stress_gather, dim3(grid_for(N)), dim3(pl::kBlock), 0, h->stream, N, pl::kWave / h->lpn,
+                       h->slice_ptr.p, h->ent.p, h->rec.p, h->st_G.p, h->tmp2.p);
   PL_HIP(hipGetLastError());
   timer.stop();
   double red[3] = {0, 0, 0};
   PL_HIP(hipMemcpyAsync(red, h->st_red.p, sizeof(red), hipMemcpyDeviceToHost, h->stream));
   PL_HIP(hipStreamSynchronize(h->stream));
-  if (sigma_max) *sigma_max = red[0];
-  if (phi) *phi = red[2];
-  if (dphi_du)
-    if (int rc = download6(h, h->tmp2.p, dphi_du)) return rc;
-  if (dphi_dr) {
-    double *stg = nullptr;
-    if (int rc = stagingB(h, &stg)) return rc;
-    PL_HIP(hipMemcpyAsync(stg, h->st_dr.p, B * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-    PL_HIP(hipStreamSynchronize(h->stream));
-    pl::parallel_for(B, [&](int64_t b0, int64_t b1, unsigned) {
-      for (int64_t b = b0; b < b1; ++b) dphi_dr[h->bperm[b]] = stg[b];
-    }, 1 << 16);
-  }
+  if (value_max) *value_max = red[0];
+  if (value) *value = red[2];
+  if (d_du)
+    if (int rc = download6(h, h->tmp2.p, d_du)) return rc;
+  if (d_dr)
+    if (int rc = download_struts(h, h->st_dr.p, d_dr)) return rc;
   return PL_OK;
+}
+}  // namespace
+}  // extern "C++"
+
+int pl_stress_pnorm(pl_handle h, const double *u, int32_t where, double p, double *phi, double *sigma_max, double *dphi_du,
+                    double *dphi_dr) {
+  const double *u_dev = nullptr;
+  if (int rc = stress_begin(h, "pl_stress_pnorm", u, where, &u_dev)) return rc;
+  const int64_t B = h->B;
+  return pnorm_call(h, "pl_stress_pnorm", p, phi, sigma_max, dphi_du, dphi_dr, [&](unsigned grid) {
+    hipLaunchKernelGGL(pl::k_stress_stations, dim3(grid), dim3(pl::kBlock), 0, h->stream, B, h->conn.p, h->rec.p, h->radius.p,
+                       h->seg_len.p, h->mult.p, h->mat.pen, (int)where, u_dev, (double *)nullptr, (double *)nullptr,
+                       h->st_vm4.p, h->st_part.p);
+  }, [&](unsigned grid) {
+    hipLaunchKernelGGL((pl::k_pnorm_psum<4, true>), dim3(grid), dim3(pl::kBlock), 0, h->stream, B, h->st_vm4.p, h->st_red.p, p,
+                       h->st_part.p);
+  }, [&](unsigned grid, auto dr) {
+    hipLaunchKernelGGL(pl::k_stress_grad<decltype(dr)::value>, dim3(grid), dim3(pl::kBlock), 0, h->stream, B, h->conn.p,
+                       h->rec.p, h->radius.p, h->seg_len.p, h->seg_nsub.p, h->mult.p, h->mat, (int)where, p, u_dev, h->st_red.p,
+                       h->st_G.p, dr ? h->st_dr.p : (double *)nullptr);
+  });
 }
 
 namespace {
@@ -1760,17 +1721,6 @@ int buckling_begin(pl_handle h, const char *who, const double *u, int32_t length
   if (shear != 0 && shear != 1) return fail(PL_ERR_ARG, std::string(who) + ": shear must be 0 (Euler) or 1 (Engesser)");
   if (!(k_eff > 0.0) || !std::isfinite(k_eff)) return fail(PL_ERR_ARG, std::string(who) + ": k_eff must be positive and finite");
   return stress_begin(h, who, u, 0, u_dev);
-}
-// one [B] array from the device to the caller's strut numbering
-int download_struts(pl_handle h, const double *dev, double *host) {
-  double *stg = nullptr;
-  if (int rc = stagingB(h, &stg)) return rc;
-  PL_HIP(hipMemcpyAsync(stg, dev, h->B * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-  PL_HIP(hipStreamSynchronize(h->stream));
-  pl::parallel_for(h->B, [&](int64_t b0, int64_t b1, unsigned) {
-    for (int64_t b = b0; b < b1; ++b) host[h->bperm[b]] = stg[b];
-  }, 1 << 16);
-  return PL_OK;
 }
 }  // namespace
 
@@ -1802,52 +1752,19 @@ int pl_buckling_pnorm(pl_handle h, const double *u, int32_t length, double k_eff
                       double *util_max, double *dbp_du, double *dbp_dr) {
   const double *u_dev = nullptr;
   if (int rc = buckling_begin(h, "pl_buckling_pnorm", u, length, k_eff, shear, &u_dev)) return rc;
-  if (!(p >= 1.0) || !std::isfinite(p)) return fail(PL_ERR_ARG, "pl_buckling_pnorm: p must be >= 1");
-  if (!bp && !util_max && !dbp_du && !dbp_dr) return fail(PL_ERR_ARG, "pl_buckling_pnorm: every output pointer is NULL");
-  const int64_t B = h->B, N = h->N;
-  const unsigned grid = grid_for(B);
-  // the stress pass's work arrays serve here too (one stream, every call ends with its downloads): beta in st_vm4
-  if (!h->st_vm4.p) PL_HIP(h->st_vm4.alloc((size_t)B * 4));
-  if (!h->st_part.p) PL_HIP(h->st_part.alloc(std::max<size_t>(grid, 1)));
-  if (!h->st_red.p) PL_HIP(h->st_red.alloc(4));
-  const bool grad = dbp_du || dbp_dr;
-  if (grad && !h->st_G.p) PL_HIP(h->st_G.alloc((size_t)B * 6));
-  if (dbp_dr && !h->st_dr.p) PL_HIP(h->st_dr.alloc((size_t)B));
-  EventTimer timer("pl_buckling_pnorm", h->stream, "kernel_hip_event");
-  hipLaunchKernelGGL(pl::k_buckling_util, dim3(grid), dim3(pl::kBlock), 0, h->stream, B, h->conn.p, h->rec.p, h->radius.p,
-                     h->seg_len.p, h->mult.p, h->mat, (int)length, k_eff, (int)shear, u_dev, h->st_vm4.p, (double *)nullptr,
-                     (double *)nullptr, h->st_part.p);
-  hipLaunchKernelGGL(pl::k_stress_fold<true>, dim3(1), dim3(pl::kBlock), 0, h->stream, (int64_t)grid, h->st_part.p, p,
-                     h->st_red.p);
-  hipLaunchKernelGGL(pl::k_buckling_psum, dim3(grid), dim3(pl::kBlock), 0, h->stream, B, h->st_vm4.p, h->st_red.p, p,
-                     h->st_part.p);
-  hipLaunchKernelGGL(pl::k_stress_fold<false>, dim3(1), dim3(pl::kBlock), 0, h->stream, (int64_t)grid, h->st_part.p, p,
-                     h->st_red.p);
-  if (grad) {
-    if (dbp_dr)
-      hipLaunchKernelGGL(pl::k_buckling_grad<true>, dim3(grid), dim3(pl::kBlock), 0, h->stream, B, h->conn.p, h->rec.p,
-                         h->radius.p, h->seg_len.p, h->seg_nsub.p, h->mult.p, h->mat, (int)length, k_eff, (int)shear, p, u_dev,
-                         h->st_red.p, h->st_G.p, h->st_dr.p);
-    else
-      hipLaunchKernelGGL(pl::k_buckling_grad<false>, dim3(grid), dim3(pl::kBlock), 0, h->stream, B, h->conn.p, h->rec.p,
-                         h->radius.p, h->seg_len.p, h->seg_nsub.p, h->mult.p, h->mat, (int)length, k_eff, (int)shear, p, u_dev,
-                         h->st_red.p, h->st_G.p, (double *)nullptr);
-    if (dbp_du)   // (tmp2 is free: u sits in tmp or usol)
-      hipLaunchKernelGGL(pl::k_stress_gather, dim3(grid_for(N)), dim3(pl::kBlock), 0, h->stream, N, pl::kWave / h->lpn,
-                         h->slice_ptr.p, h->ent.p, h->rec.p, h->st_G.p, h->tmp2.p);
-  }
-  PL_HIP(hipGetLastError());
-  timer.stop();
-  double red[3] = {0, 0, 0};
-  PL_HIP(hipMemcpyAsync(red, h->st_red.p, sizeof(red), hipMemcpyDeviceToHost, h->stream));
-  PL_HIP(hipStreamSynchronize(h->stream));
-  if (util_max) *util_max = red[0];
-  if (bp) *bp = red[2];
-  if (dbp_du)
-    if (int rc = download6(h, h->tmp2.p, dbp_du)) return rc;
-  if (dbp_dr)
-    if (int rc = download_struts(h, h->st_dr.p, dbp_dr)) return rc;
-  return PL_OK;
+  const int64_t B = h->B;
+  return pnorm_call(h, "pl_buckling_pnorm", p, bp, util_max, dbp_du, dbp_dr, [&](unsigned grid) {   // beta in st_vm4
+    hipLaunchKernelGGL(pl::k_buckling_util, dim3(grid), dim3(pl::kBlock), 0, h->stream, B, h->conn.p, h->rec.p, h->radius.p,
+                       h->seg_len.p, h->mult.p, h->mat, (int)length, k_eff, (int)shear, u_dev, h->st_vm4.p, (double *)nullptr,
+                       (double *)nullptr, h->st_part.p);
+  }, [&](unsigned grid) {
+    hipLaunchKernelGGL((pl::k_pnorm_psum<1, false>), dim3(grid), dim3(pl::kBlock), 0, h->stream, B, h->st_vm4.p, h->st_red.p, p,
+                       h->st_part.p);
+  }, [&](unsigned grid, auto dr) {
+    hipLaunchKernelGGL(pl::k_buckling_grad<decltype(dr)::value>, dim3(grid), dim3(pl::kBlock), 0, h->stream, B, h->conn.p,
+                       h->rec.p, h->radius.p, h->seg_len.p, h->seg_nsub.p, h->mult.p, h->mat, (int)length, k_eff, (int)shear, p,
+                       u_dev, h->st_red.p, h->st_G.p, dr ? h->st_dr.p : (double *)nullptr);
+  });
 }
 
 int pl_energy(pl_handle h, const double *u, double *energy) {
@@ -2062,15 +1979,8 @@ namespace {
 // what the two geometric calls share after their argument checks: the handle checks and the geometric records of u
 int geom_begin(pl_handle h, const char *who, const double *u, bool need_bc, GeomWs **g) {
   if (int rc = multi_check_handle(h, who, need_bc)) return rc;
-  if (!u && !(h->usol.p && h->usol_valid))
-    return fail(PL_ERR_STATE, std::string(who) + ": u = NULL needs a pl_solve on this handle first");
-  PL_HIP(hipSetDevice(h->opt.device));
-  const double *u_dev = h->usol.p;
-  if (u) {
-    std::vector<double> stage;
-    if (int rc = upload6(h, u, h->tmp.p, stage)) return rc;
-    u_dev = h->tmp.p;
-  }
+  const double *u_dev = nullptr;
+  if (int rc = state_on_device(h, who, u, &u_dev)) return rc;
   if (int rc = geom_ws(h, g)) return rc;
   return launch_geom_records(h, *g, u_dev);
 }
@@ -3109,10 +3019,8 @@ int pl_get_records(pl_handle h, double *rec) {
   if (!valid(h) || !rec) return fail(PL_ERR_ARG, "pl_get_records: null argument");
   if (!h->assembled) return fail(PL_ERR_STATE, "pl_get_records: call pl_assemble first");
   PL_HIP(hipSetDevice(h->opt.device));
-  std::vector<pl::Record> tmp(h->B);
-  PL_HIP(hipMemcpy(tmp.data(), h->rec.p, h->B * sizeof(pl::Record), hipMemcpyDeviceToHost));
-  for (int64_t b = 0; b < h->B; ++b) std::memcpy(rec + 8 * (size_t)h->bperm[b], &tmp[b], sizeof(pl::Record));
-  return PL_OK;
+  static_assert(sizeof(pl::Record) == 8 * sizeof(double), "a record is a row of eight doubles");
+  return download_struts(h, reinterpret_cast<const double *>(h->rec.p), rec, 8);
 }
 
 int pl_debug_partition(pl_handle h, int32_t *tile_of_node, int32_t *agg_of_node, int32_t *local_agg_of_node,

@@ -54,13 +54,7 @@ __global__ __launch_bounds__(kBlock) void k_buckling_util(int64_t B, const int32
   const int64_t b = (int64_t)blockIdx.x * kBlock + threadIdx.x;
   double pk = 0.0;
   if (b < B) {
-    const int64_t ia = conn[2 * b], ib = conn[2 * b + 1];
-    const Record r = load_record(rec, b);
-    V3 uA, tA, uB, tB, F, M;
-    load6(u + 6 * ia, uA, tA);
-    load6(u + 6 * ib, uB, tB);
-    tip_force(r, uA, tA, uB, tB, F, M);
-    const StressStrut s = stress_strut(r, mult ? mult[b] : 1.0, F, M);
+    const StressStrut s = load_strut(b, conn, rec, mult, u).q;
     const double l2 = seg_len[3 * b + 1];
     const bool on = length == 0 || l2 > 0.0;
     const double nan = __longlong_as_double(0x7ff8000000000000ll);
@@ -76,22 +70,6 @@ __global__ __launch_bounds__(kBlock) void k_buckling_util(int64_t B, const int32
     const double m = stress_block_fold<true>(pk, smem);
     if (threadIdx.x == 0) part_max[blockIdx.x] = m;
   }
-}
-
-// First stage of the p-sum: (beta / beta_max)^p of every present strut, one partial per block (red[0] = beta_max).
-__global__ __launch_bounds__(kBlock) void k_buckling_psum(int64_t B, const double *__restrict__ util,
-                                                          const double *__restrict__ red, double p,
-                                                          double *__restrict__ part_sum) {
-  __shared__ double smem[kBlock];
-  const int64_t b = (int64_t)blockIdx.x * kBlock + threadIdx.x;
-  const double bmax = red[0];
-  double acc = 0.0;
-  if (b < B && bmax > 0.0) {
-    const double v = util[b];
-    if (v > 0.0) acc = pow(v / bmax, p);      // (NaN marks an absent strut; beta = 0 adds nothing)
-  }
-  const double t = stress_block_fold<false>(acc, smem);
-  if (threadIdx.x == 0) part_sum[blockIdx.x] = t;
 }
 
 // ---------------------------------------------------------------------------------------------------------
@@ -111,14 +89,8 @@ __global__ __launch_bounds__(kBlock) void k_buckling_grad(int64_t B, const int32
   const int64_t b = (int64_t)blockIdx.x * kBlock + threadIdx.x;
   if (b >= B) return;
   const double bmax = red[0], bsum = red[1];
-  const int64_t ia = conn[2 * b], ib = conn[2 * b + 1];
-  const Record r = load_record(rec, b);
-  V3 uA, tA, uB, tB, F, M;
-  load6(u + 6 * ia, uA, tA);
-  load6(u + 6 * ib, uB, tB);
-  tip_force(r, uA, tA, uB, tB, F, M);
-  const double k = mult ? mult[b] : 1.0;
-  const StressStrut s = stress_strut(r, k, F, M);
+  const StrutState st = load_strut(b, conn, rec, mult, u);
+  const StressStrut &s = st.q;
   const double len[3] = {seg_len[3 * b], seg_len[3 * b + 1], seg_len[3 * b + 2]};
   const bool on = length == 0 || len[1] > 0.0;
   const double rr = radius[b];
@@ -128,22 +100,9 @@ __global__ __launch_bounds__(kBlock) void k_buckling_grad(int64_t B, const int32
   const double beta = live ? -s.N / ncr : 0.0;
   const double w = live ? pow(beta / bmax, p - 1.0) * pow(bsum, 1.0 / p - 1.0) : 0.0;
   const V3 gF = (live ? -w * s.invk / ncr : 0.0) * s.t;
-  const V3 zero = {0, 0, 0};
-  V3 Gu, Gth;
-  tip_force(r, zero, zero, gF, zero, Gu, Gth);
-  double2 *o = reinterpret_cast<double2 *>(G + 6 * b);
-  o[0] = {Gu.x, Gu.y};
-  o[1] = {Gu.z, Gth.x};
-  o[2] = {Gth.y, Gth.z};
-  if (DR) {
-    const int ns[3] = {seg_nsub[3 * b], seg_nsub[3 * b + 1], seg_nsub[3 * b + 2]};
-    const Material mk = scaled(mat, k);
-    const V3 d = {r.dx, r.dy, r.dz};
-    const Record dr = make_record(dscalars_dr(strut_flexibility(rr, len, ns, mk), rr), d);
-    V3 dF, dM;
-    tip_force(dr, uA, tA, uB, tB, dF, dM);
-    dbp_dr[b] = live ? dot(gF, dF) - w * beta * (4.0 - 2.0 * q / (1.0 + q)) / rr : 0.0;
-  }
+  V3 dF, dM;
+  grad_epilogue<DR>(st, b, rr, len, seg_nsub, mat, gF, V3{0, 0, 0}, G, dF, dM);
+  if (DR) dbp_dr[b] = live ? dot(gF, dF) - w * beta * (4.0 - 2.0 * q / (1.0 + q)) / rr : 0.0;
 }
 
 }  // namespace pl

@@ -377,4 +377,46 @@ int download6(pl_context *c, const double *dev, double *host) {
   return PL_OK;
 }
 
+// [B][width] per-strut rows from the device's strut order (stg, on the host) to the caller's: the one place that applies
+// bperm to downloaded values.
+void struts_to_caller(const pl_context *c, const double *stg, double *host, int width = 1) {
+  const size_t w = (size_t)width;
+  pl::parallel_for(c->B, [&](int64_t b0, int64_t b1, unsigned) {
+    for (int64_t b = b0; b < b1; ++b)
+      for (size_t k = 0; k < w; ++k) host[w * (size_t)c->bperm[b] + k] = stg[w * (size_t)b + k];
+  }, width == 1 ? 1 << 16 : 1 << 14);
+}
+
+// ... from the device: single values through the pinned per-strut buffer, wider rows through pageable memory.
+int download_struts(pl_context *c, const double *dev, double *host, int width = 1) {
+  const size_t w = (size_t)width;
+  std::vector<double> wide;
+  double *stg = nullptr;
+  if (width == 1) {
+    if (int rc = stagingB(c, &stg)) return rc;
+  } else {
+    wide.resize((size_t)c->B * w);
+    stg = wide.data();
+  }
+  PL_HIP(hipMemcpyAsync(stg, dev, (size_t)c->B * w * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+  PL_HIP(hipStreamSynchronize(c->stream));
+  struts_to_caller(c, stg, host, width);
+  return PL_OK;
+}
+
+// u == NULL means the solution of the last pl_solve, still on the device (a design loop evaluates the derived quantities of
+// the field it has just computed: no 6N-vector upload); any other u is uploaded to tmp.
+int state_on_device(pl_context *c, const char *who, const double *u, const double **u_dev) {
+  if (!u && !(c->usol.p && c->usol_valid))
+    return fail(PL_ERR_STATE, std::string(who) + ": u = NULL needs a pl_solve on this handle first");
+  PL_HIP(hipSetDevice(c->opt.device));
+  *u_dev = c->usol.p;
+  if (u) {
+    std::vector<double> stage;
+    if (int rc = upload6(c, u, c->tmp.p, stage)) return rc;
+    *u_dev = c->tmp.p;
+  }
+  return PL_OK;
+}
+
 }  // namespace

@@ -114,6 +114,12 @@ __device__ __forceinline__ void load6(const double *__restrict__ p, V3 &u, V3 &t
   u = {a.x, a.y, b.x};
   t = {b.y, c.x, c.y};
 }
+__device__ __forceinline__ void store6(double *__restrict__ p, V3 u, V3 t) {
+  double2 *q = reinterpret_cast<double2 *>(p);
+  q[0] = {u.x, u.y};
+  q[1] = {u.z, t.x};
+  q[2] = {t.y, t.z};
+}
 
 // fp32-stored vectors (opts.precision = 1 / 2): rows are 24 B, read as three float2; all arithmetic stays fp64.
 __device__ __forceinline__ void load6(const float *__restrict__ p, V3 &u, V3 &t) {

@@ -94,6 +94,46 @@ __device__ __forceinline__ StressStrut stress_strut(const Record &r, double k, V
   return q;
 }
 
+// Strut b under the field u: record, end vectors, (F, M_B) = tip_force(record, u), multiplicity k, and what its stations share.
+struct StrutState {
+  Record r;
+  V3 uA, tA, uB, tB, F, M;
+  double k;
+  StressStrut q;
+};
+
+__device__ __forceinline__ StrutState load_strut(int64_t b, const int32_t *__restrict__ conn, const Record *__restrict__ rec,
+                                                 const double *__restrict__ mult, const double *__restrict__ u) {
+  StrutState s;
+  const int64_t ia = conn[2 * b], ib = conn[2 * b + 1];
+  s.r = load_record(rec, b);
+  load6(u + 6 * ia, s.uA, s.tA);
+  load6(u + 6 * ib, s.uB, s.tB);
+  tip_force(s.r, s.uA, s.tA, s.uB, s.tB, s.F, s.M);
+  s.k = mult ? mult[b] : 1.0;
+  s.q = stress_strut(s.r, s.k, s.F, s.M);
+  return s;
+}
+
+// Close of a p-norm grad kernel (k_stress_grad, k_buckling_grad): G[b][6] = K_tip (g_F, g_M), the tip block applied to the
+// aggregate's derivative with respect to (F, M_B).  With DR also (dF, dM) = d(F, M_B)/dr at fixed u and segment geometry, so
+// that the caller's d/dr = g_F.dF + g_M.dM + its own section term.
+template <bool DR>
+__device__ __forceinline__ void grad_epilogue(const StrutState &s, int64_t b, double rr, const double *len,
+                                              const int32_t *__restrict__ seg_nsub, const Material &mat, V3 gF, V3 gM,
+                                              double *__restrict__ G, V3 &dF, V3 &dM) {
+  const V3 zero = {0, 0, 0};
+  V3 Gu, Gth;
+  tip_force(s.r, zero, zero, gF, gM, Gu, Gth);
+  store6(G + 6 * b, Gu, Gth);
+  if (DR) {
+    const int ns[3] = {seg_nsub[3 * b], seg_nsub[3 * b + 1], seg_nsub[3 * b + 2]};
+    const V3 d = {s.r.dx, s.r.dy, s.r.dz};
+    const Record dr = strut_drecord(rr, len, ns, scaled(mat, s.k), d);
+    tip_force(dr, s.uA, s.tA, s.uB, s.tB, dF, dM);
+  }
+}
+
 // Section constants of radius R: 1 / S, R / I, R / J.
 __device__ __forceinline__ void stress_section(double R, double &iS, double &RI, double &RJ) {
   const double PI = 3.14159265358979323846;
@@ -120,13 +160,7 @@ __global__ __launch_bounds__(kBlock) void k_stress_stations(int64_t B, const int
   const int64_t b = (int64_t)blockIdx.x * kBlock + threadIdx.x;
   double pk = 0.0;
   if (b < B) {
-    const int64_t ia = conn[2 * b], ib = conn[2 * b + 1];
-    const Record r = load_record(rec, b);
-    V3 uA, tA, uB, tB, F, M;
-    load6(u + 6 * ia, uA, tA);
-    load6(u + 6 * ib, uB, tB);
-    tip_force(r, uA, tA, uB, tB, F, M);
-    const StressStrut q = stress_strut(r, mult ? mult[b] : 1.0, F, M);
+    const StressStrut q = load_strut(b, conn, rec, mult, u).q;
     const StressStations s = stress_stations(seg_len[3 * b], seg_len[3 * b + 1], seg_len[3 * b + 2], q.L, pen, where);
     const double rr = radius[b];
     const double nan = __longlong_as_double(0x7ff8000000000000ll);
@@ -182,22 +216,26 @@ __global__ __launch_bounds__(kBlock) void k_stress_fold(int64_t n, const double 
   }
 }
 
-// First stage of the p-sum: per strut sum over its present stations of (sigma_vm / sigma_max)^p, one partial per block.
-__global__ __launch_bounds__(kBlock) void k_stress_psum(int64_t B, const double *__restrict__ vm4,
-                                                        const double *__restrict__ red, double p,
-                                                        double *__restrict__ part_sum) {
+// First stage of the p-sum: per strut the sum over its W values (stress: 4 stations, buckling: 1 utilisation) of
+// (v / v_max)^p, one partial per block; red[0] = v_max.  NaN marks an absent value, and like a zero it adds nothing.
+// RECIP: the ratio is formed as v * (1 / v_max) (the stress pass), else as v / v_max (the buckling pass) - each as its grad
+// kernel forms it.
+template <int W, bool RECIP>
+__global__ __launch_bounds__(kBlock) void k_pnorm_psum(int64_t B, const double *__restrict__ val /*[B][W]*/,
+                                                       const double *__restrict__ red, double p,
+                                                       double *__restrict__ part_sum) {
   __shared__ double smem[kBlock];
   const int64_t b = (int64_t)blockIdx.x * kBlock + threadIdx.x;
-  const double smax = red[0];
+  const double vmax = red[0];
   double acc = 0.0;
-  if (b < B && smax > 0.0) {
-    const double2 *q = reinterpret_cast<const double2 *>(vm4 + 4 * b);
-    const double2 a = q[0], c = q[1];
-    const double inv = 1.0 / smax;
-    if (a.x == a.x) acc += pow(a.x * inv, p);      // (NaN marks an absent station)
-    if (a.y == a.y) acc += pow(a.y * inv, p);
-    if (c.x == c.x) acc += pow(c.x * inv, p);
-    if (c.y == c.y) acc += pow(c.y * inv, p);
+  if (b < B && vmax > 0.0) {
+    double v[W];
+#pragma unroll
+    for (int i = 0; i < W; ++i) v[i] = val[W * b + i];
+    const double inv = 1.0 / vmax;
+#pragma unroll
+    for (int i = 0; i < W; ++i)
+      if (v[i] > 0.0) acc += pow(RECIP ? v[i] * inv : v[i] / vmax, p);
   }
   const double t = stress_block_fold<false>(acc, smem);
   if (threadIdx.x == 0) part_sum[blockIdx.x] = t;
@@ -226,14 +264,8 @@ __global__ __launch_bounds__(kBlock) void k_stress_grad(int64_t B, const int32_t
   const int64_t b = (int64_t)blockIdx.x * kBlock + threadIdx.x;
   if (b >= B) return;
   const double smax = red[0], ssum = red[1];
-  const int64_t ia = conn[2 * b], ib = conn[2 * b + 1];
-  const Record r = load_record(rec, b);
-  V3 uA, tA, uB, tB, F, M;
-  load6(u + 6 * ia, uA, tA);
-  load6(u + 6 * ib, uB, tB);
-  tip_force(r, uA, tA, uB, tB, F, M);
-  const double k = mult ? mult[b] : 1.0;
-  const StressStrut q = stress_strut(r, k, F, M);
+  const StrutState st = load_strut(b, conn, rec, mult, u);
+  const StressStrut &q = st.q;
   const double len[3] = {seg_len[3 * b], seg_len[3 * b + 1], seg_len[3 * b + 2]};
   const StressStations s = stress_stations(len[0], len[1], len[2], q.L, mat.pen, where);
   const double rr = radius[b];
@@ -259,22 +291,9 @@ __global__ __launch_bounds__(kBlock) void k_stress_grad(int64_t B, const int32_t
       dsec -= (ws * (2.0 * sgN + 3.0 * sgB) + wt * 3.0 * ta) / rr;
     }
   }
-  const V3 zero = {0, 0, 0};
-  V3 Gu, Gth;
-  tip_force(r, zero, zero, gF, gM, Gu, Gth);
-  double2 *o = reinterpret_cast<double2 *>(G + 6 * b);
-  o[0] = {Gu.x, Gu.y};
-  o[1] = {Gu.z, Gth.x};
-  o[2] = {Gth.y, Gth.z};
-  if (DR) {
-    const int ns[3] = {seg_nsub[3 * b], seg_nsub[3 * b + 1], seg_nsub[3 * b + 2]};
-    const Material mk = scaled(mat, k);
-    const V3 d = {r.dx, r.dy, r.dz};
-    const Record dr = make_record(dscalars_dr(strut_flexibility(rr, len, ns, mk), rr), d);
-    V3 dF, dM;
-    tip_force(dr, uA, tA, uB, tB, dF, dM);
-    dphi_dr[b] = dot(gF, dF) + dot(gM, dM) + dsec;
-  }
+  V3 dF, dM;
+  grad_epilogue<DR>(st, b, rr, len, seg_nsub, mat, gF, gM, G, dF, dM);
+  if (DR) dphi_dr[b] = dot(gF, dF) + dot(gM, dM) + dsec;
 }
 
 // dPhi/du by a per-node gather over the sliced-ELL incidence of k_spmv_gather (SN = 64 / lanes-per-node nodes per slice,
@@ -305,10 +324,7 @@ __global__ __launch_bounds__(kBlock) void k_stress_gather(int64_t N, int SN, con
       at = at + gt;
     }
   }
-  double2 *o = reinterpret_cast<double2 *>(out + 6 * i);
-  o[0] = {au.x, au.y};
-  o[1] = {au.z, at.x};
-  o[2] = {at.y, at.z};
+  store6(out + 6 * i, au, at);
 }
 
 }  // namespace pl

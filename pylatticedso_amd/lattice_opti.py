@@ -320,6 +320,12 @@ class LatticeOpti(LatticeSim):
             _, self._model = solve_FEM_FenicsX(self)
         self._sim_is_current = True
 
+    def _equilibrium_at(self, r):
+        """The design r set and its equilibrium solved, unless the last solve is already that of r."""
+        self.set_optimization_parameters(r)
+        if not self._sim_is_current:
+            self._simulate_lattice_equilibrium()
+
     def compute_compliance(self):
         """C = sum_k f_k u_k over loaded dofs (lattice_opti.py:645-663)."""
         return float((self.applied_force * self.displacement_vector).sum())
@@ -377,9 +383,7 @@ class LatticeOpti(LatticeSim):
         return u_in, u_out, q
 
     def objective(self, r):
-        self.set_optimization_parameters(r)
-        if not self._sim_is_current:
-            self._simulate_lattice_equilibrium()
+        self._equilibrium_at(r)
         objective = self.calculate_objective()
         self.denorm_objective = objective
         val = self.normalize_objective(objective)
@@ -588,9 +592,7 @@ class LatticeOpti(LatticeSim):
 
     def gradient(self, r):
         """d(normalised objective)/d(theta) (lattice_opti.py:701-731)."""
-        self.set_optimization_parameters(r)
-        if not self._sim_is_current:
-            self._simulate_lattice_equilibrium()
+        self._equilibrium_at(r)
         g = -self.calculate_gradient()
         if self.objective_function == "max":
             g = -g        # objective() negates the (normalised) value for 'max'; keep the pair consistent
@@ -635,18 +637,14 @@ class LatticeOpti(LatticeSim):
 
     def stress_constraint(self, r):
         """Phi_p / s_allow - 1 (<= 0 when feasible; Phi_p >= the largest von Mises stress of any strut station)."""
-        self.set_optimization_parameters(r)
-        if not self._sim_is_current:
-            self._simulate_lattice_equilibrium()
+        self._equilibrium_at(r)
         return self.strut_stress_aggregate()[0] / self._stress_settings()[0] - 1.0
 
     def stress_constraint_gradient(self, r):
         """d(stress_constraint)/d(theta): dPhi/dr_b = dPhi/dr_b at fixed u - lam^T (dK/dr_b) u with K lam = dPhi/du on the free
         dofs (lam = 0 on prescribed ones, which take no load), chained through Cell.get_radius and the parameterisation
         as the objective's gradient is."""
-        self.set_optimization_parameters(r)
-        if not self._sim_is_current:
-            self._simulate_lattice_equilibrium()
+        self._equilibrium_at(r)
         s_allow = self._stress_settings()[0]
         _, _, dphi_du, dphi_dr = self.strut_stress_aggregate(want_grad=True)
         return self._aggregate_gradient(dphi_du, dphi_dr) / s_allow
@@ -687,17 +685,13 @@ class LatticeOpti(LatticeSim):
 
     def buckling_constraint(self, r):
         """B_p / beta_allow - 1 (<= 0 when feasible; B_p >= the largest utilisation max(0, -N) / N_cr of any strut)."""
-        self.set_optimization_parameters(r)
-        if not self._sim_is_current:
-            self._simulate_lattice_equilibrium()
+        self._equilibrium_at(r)
         return self.strut_buckling_aggregate()[0] / self._buckling_settings()[0] - 1.0
 
     def buckling_constraint_gradient(self, r):
         """d(buckling_constraint)/d(theta) by the adjoint chain of stress_constraint_gradient: dB/dr_b at fixed u -
         lam^T (dK/dr_b) u with K lam = dB/du on the free dofs."""
-        self.set_optimization_parameters(r)
-        if not self._sim_is_current:
-            self._simulate_lattice_equilibrium()
+        self._equilibrium_at(r)
         b_allow = self._buckling_settings()[0]
         _, _, dbp_du, dbp_dr = self.strut_buckling_aggregate(want_grad=True)
         return self._aggregate_gradient(dbp_du, dbp_dr) / b_allow
@@ -724,16 +718,12 @@ class LatticeOpti(LatticeSim):
     def global_buckling_constraint(self, r):
         """lambda_min J_p - 1 (<= 0 when feasible: J_p >= 1 / lambda_1, so lambda_1 >= lambda_min then; -1 when no positive load
         factor exists)."""
-        self.set_optimization_parameters(r)
-        if not self._sim_is_current:
-            self._simulate_lattice_equilibrium()
+        self._equilibrium_at(r)
         return self._global_buckling_settings()[0] * self.global_buckling_aggregate()[0] - 1.0
 
     def global_buckling_constraint_gradient(self, r):
         """d(global_buckling_constraint)/d(theta): lambda_min dJ/dr_b through the tail of _aggregate_gradient."""
-        self.set_optimization_parameters(r)
-        if not self._sim_is_current:
-            self._simulate_lattice_equilibrium()
+        self._equilibrium_at(r)
         _, _, dJ_dr = self.global_buckling_aggregate(want_grad=True)
         return self._global_buckling_settings()[0] * self._strut_gradient_to_parameters(dJ_dr)
 
@@ -757,16 +747,12 @@ class LatticeOpti(LatticeSim):
 
     def frequency_constraint(self, r):
         """(2 pi f_min)^2 J_p - 1 (<= 0 when feasible: J_p >= 1 / omega_1^2, so f_1 >= f_min then)."""
-        self.set_optimization_parameters(r)
-        if not self._sim_is_current:
-            self._simulate_lattice_equilibrium()
+        self._equilibrium_at(r)
         return (2.0 * np.pi * self._frequency_settings()[0]) ** 2 * self.frequency_aggregate()[0] - 1.0
 
     def frequency_constraint_gradient(self, r):
         """d(frequency_constraint)/d(theta): (2 pi f_min)^2 dJ/dr_b through _strut_gradient_to_parameters."""
-        self.set_optimization_parameters(r)
-        if not self._sim_is_current:
-            self._simulate_lattice_equilibrium()
+        self._equilibrium_at(r)
         _, _, dJ_dr = self.frequency_aggregate(want_grad=True)
         return (2.0 * np.pi * self._frequency_settings()[0]) ** 2 * self._strut_gradient_to_parameters(dJ_dr)
 
@@ -796,16 +782,12 @@ class LatticeOpti(LatticeSim):
 
     def peak_displacement_constraint(self, r):
         """J_p / max_displacement - 1 (<= 0 when feasible: J_p >= max_n |y_n|, so the peak stays below max_displacement then)."""
-        self.set_optimization_parameters(r)
-        if not self._sim_is_current:
-            self._simulate_lattice_equilibrium()
+        self._equilibrium_at(r)
         return self.peak_displacement_aggregate()[0] / self._peak_displacement_settings()[0] - 1.0
 
     def peak_displacement_constraint_gradient(self, r):
         """d(peak_displacement_constraint)/d(theta): dJ/dr_b / max_displacement through _strut_gradient_to_parameters."""
-        self.set_optimization_parameters(r)
-        if not self._sim_is_current:
-            self._simulate_lattice_equilibrium()
+        self._equilibrium_at(r)
         return self._strut_gradient_to_parameters(self.peak_displacement_aggregate()[2]) / self._peak_displacement_settings()[0]
 
     # -- driver (SciPy SLSQP, as the reference) ---------------------------------------------------------------------

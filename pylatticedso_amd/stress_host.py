@@ -168,6 +168,19 @@ def pnorm(sigma_vm, p):
     return smax * float(((s / smax) ** p).sum()) ** (1.0 / p), smax
 
 
+def scatter_tip_gradient(rec, conn, node_count, gF, gM):
+    """(N, 6) derivative with respect to u of a scalar whose derivatives with respect to the struts' (F, M_B) are (gF, gM):
+    the symmetric tip block applied to (g_F, g_M), added to end B and, moved to end A with reversed sign, to end A."""
+    a, c, e1, e2, e3 = (rec[:, i:i + 1] for i in range(5))
+    d = rec[:, 5:8]
+    Gu = a * gF + e1 * _dot(gF, d)[:, None] * d + e2 * np.cross(d, gM)
+    Gth = c * gM + e3 * _dot(gM, d)[:, None] * d - e2 * np.cross(d, gF)
+    du = np.zeros((node_count, 6))
+    np.add.at(du, conn[:, 1], np.column_stack([Gu, Gth]))
+    np.add.at(du, conn[:, 0], np.column_stack([-Gu, -Gth - np.cross(d, Gu)]))
+    return du
+
+
 def stress_pnorm(rec, node_count, beam_conn, radius, seg_len, seg_nsub, u, p, young, poisson, kappa=0.9, pen_coef=1.5,
                  mult=None, where=0, want_grad=True):
     """(phi, sigma_max, dphi_du (N, 6), dphi_dr (B,)) - the outputs of pl_stress_pnorm with the formulas of its kernels;
@@ -195,13 +208,8 @@ def stress_pnorm(rec, node_count, beam_conn, radius, seg_len, seg_nsub, u, p, yo
     gM = ((ws * ev["RI"])[:, :, None] * mh).sum(axis=1) * ik[:, None] + ((wt * ev["RJ"]).sum(axis=1) * sT * ik)[:, None] * t
     dsec = -((ws * (2.0 * ev["sgN"] + 3.0 * ev["sgB"]) + wt * 3.0 * ev["tau"]).sum(axis=1)) / ev["r"]
     rec = np.asarray(rec, dtype=float).reshape(-1, 8)
-    a, c, e1, e2, e3 = (rec[:, i:i + 1] for i in range(5))
     d = rec[:, 5:8]
-    Gu = a * gF + e1 * _dot(gF, d)[:, None] * d + e2 * np.cross(d, gM)       # the symmetric tip block applied to (g_F, g_M)
-    Gth = c * gM + e3 * _dot(gM, d)[:, None] * d - e2 * np.cross(d, gF)
-    du = np.zeros((node_count, 6))
-    np.add.at(du, conn[:, 1], np.column_stack([Gu, Gth]))
-    np.add.at(du, conn[:, 0], np.column_stack([-Gu, -Gth - np.cross(d, Gu)]))
+    du = scatter_tip_gradient(rec, conn, node_count, gF, gM)
     f = flexibility(radius, seg_len, seg_nsub, young, poisson, kappa, pen_coef, mult)
     drec = _record(_dscalars_dr(f, ev["r"]), d)
     dF, dM = tip_force(drec, conn, u)
