@@ -574,6 +574,34 @@ int pl_transient_sens(pl_handle h, int32_t n_steps, double dt, double beta, doub
                       double *J, double *y /*[n_steps+1] or NULL*/, double *dJ_dr /*[B], caller's strut numbering*/,
                       int32_t *iters /*[2][n_steps+1] or NULL: forward, adjoint*/);
 
+/* ---- frequency response (csrc/pl_harm.h) -------------------------------------------------------------
+ * The steady state u e^{iwt} under the load f e^{iwt} on the free dofs of pl_set_bc, the supports held at zero:
+ *     A(w) u = f,   A(w) = c_K K + c_M M,   c_K = 1 + i w ray_k,   c_M = i w ray_m - w^2
+ * with K, M and the Rayleigh damping of pl_transient.  A is complex symmetric; each frequency is solved by the conjugate
+ * orthogonal CG (unconjugated bilinear form, Jacobi-preconditioned with the complex diagonal, zero start), the frequencies of a
+ * pass in lock step, one fused gather per iteration.  Complex arrays are complex128: (re, im) pairs.  COCG has no convergence
+ * guarantee: lightly damped systems slow down or fail at frequencies with many modes below them, and at an undamped resonance
+ * the system is singular - status tells which frequency.  Both calls: PL_ERR_STATE on DDM and multi-rank handles, before
+ * pl_set_mass, before pl_assemble and with pl_set_periodic constraints.  The handle's single-column state is left untouched. */
+/* y_k = (cK_k K + cM_k M) x_k in ONE gather (masked != 0: P (...) P x_k, needs pl_set_bc), k < n_freq <= PL_MULTI_MAX / 2;
+ * coef[n_freq][4] = Re cK, Im cK, Re cM, Im cM; x, y: [n_freq][6N] complex128 host arrays. */
+int pl_harm_spmv(pl_handle h, int32_t n_freq, const double *coef, int masked, const double *x, double *y);
+/* One solve per omega[k] >= 0 (0: the static solve), k < n_freq, in passes of `block` frequencies (0 = PL_MULTI_MAX / 2, the
+ * most).  The load load_re + i load_im is read with the fixed dofs zeroed.  A frequency stops when ||r|| <= rtol ||f||
+ * (status 0), at max_iter (1), or at a breakdown - a zero or non-finite p^T A p or r^T z (2).  probe_out: the six complex
+ * dofs of the probe_nodes (caller numbering); fields: the whole complex fields; power: Re f^T u, Im f^T u (unconjugated),
+ * u^H K u, u^H M u, so that Re f^T u = u^H K u - w^2 u^H M u and -Im f^T u = w (ray_m u^H M u + ray_k u^H K u) is twice the
+ * dissipated power over w.  PL_ERR_ARG: n_freq < 1, a negative omega or Rayleigh coefficient, rtol or max_iter not positive,
+ * block outside 0 ... PL_MULTI_MAX / 2, a probe index out of range, a NULL omega, load_re, iters, relres or status.
+ * PL_ERR_STATE also before pl_set_bc and when the handle holds non-zero prescribed displacements.  PL_ERR_NOCONV when any
+ * frequency ends with status != 0; every output is still written. */
+int pl_harmonic(pl_handle h, int32_t n_freq, const double *omega /*[n_freq]*/, double ray_m, double ray_k,
+                const double *load_re /*[6N]*/, const double *load_im /*[6N] or NULL = 0*/, int32_t n_probe,
+                const int32_t *probe_nodes /*[n_probe]*/, double rtol, int32_t max_iter, int32_t block,
+                double *probe_out /*[n_freq][n_probe][6] complex*/, double *fields /*[n_freq][6N] complex, or NULL*/,
+                double *power /*[n_freq][4], or NULL*/, int32_t *iters /*[n_freq]*/, double *relres /*[n_freq]*/,
+                int32_t *status /*[n_freq]: 0 ok, 1 max_iter, 2 breakdown*/);
+
 /* The same condensation, exact and batched, without a handle: n_inst small lattices of ONE topology (a unit cell at
  * several radius sets - the exact DDM mode, Schur datasets), each condensed by a dense Cholesky of K_II in one workgroup
  * of a single launch.  Material, pen_coef and device come from o (stamped by pl_default_opts; the solver fields are

@@ -25,7 +25,7 @@ EXPORTS = ["pl_default_opts", "pl_opts_size", "pl_stats_size", "pl_abi_version",
            "pl_stress", "pl_stress_pnorm", "pl_buckling", "pl_buckling_pnorm",
            "pl_spmv_multi", "pl_solve_multi", "pl_schur_block", "pl_geom_spmv_multi", "pl_buckling_modes", "pl_buckling_modes_sens",
            "pl_set_mass", "pl_mass_spmv_multi", "pl_vibration_modes", "pl_vibration_modes_sens",
-           "pl_dyn_spmv_multi", "pl_transient", "pl_transient_sens",
+           "pl_dyn_spmv_multi", "pl_transient", "pl_transient_sens", "pl_harm_spmv", "pl_harmonic",
            "pl_schur_cells", "pl_cells_recover", "pl_get_records", "pl_debug_partition", "pl_time_kernel", "pl_algorithmic_bytes", "pl_node_words_info", "pl_forget_history", "pl_debug_spd_solve", "pl_dist_unique_id_bytes",
            "pl_dist_unique_id", "pl_dist_loopback_id", "pl_dist_abort", "pl_dist_init", "pl_dist_set_peers", "pl_generate_lattice", "pl_lattice_fetch",
            "pl_lattice_free", "pl_penalize", "pl_boundary_index", "pl_boundary_index_rows"]
@@ -107,6 +107,8 @@ def load_library(path: str | None = None):
            "pl_dyn_spmv_multi": [V, D, D, I32, I32, V, V],
            "pl_transient": [V, I32, D, D, D, D, D, I32, V, V, V, V, D, I32, I32, V, V, V, I32, V, V, V],
            "pl_transient_sens": [V, I32, D, D, D, D, D, I32, V, V, V, V, V, V, D, I32, V, I32, D, V, V, V, V, V],
+           "pl_harm_spmv": [V, I32, V, I32, V, V],
+           "pl_harmonic": [V, I32, V, D, D, V, V, I32, V, D, I32, I32, V, V, V, V, V, V],
            "pl_schur_cells": [V, I32, I32, I32, V, I32, V, V, V, V, V, V, V],
            "pl_cells_recover": [V, I32, I32, I32, V, I32, V, V, V, V, V, V, V, V, V, V, V],
            "pl_get_records": [V, V], "pl_debug_partition": [V, V, V, V, V], "pl_time_kernel": [V, I32, I32, V],
@@ -1080,6 +1082,67 @@ class HipLattice:
                                       patterns, amp, base_dir, base_acc, u0, v0, beta, gamma, ray_m, ray_k, solve)
 
     # -- measurement ------------------------------------------------------------------------------------
+    # -- frequency response -------------------------------------------------------------------------------
+    def harm_spmv(self, coef, X, masked=False):
+        """Y[k] = (cK[k] K + cM[k] M) X[k] for k complex vectors in one fused gather (pl_harm_spmv).  coef (k, 2) complex =
+        (cK, cM) per vector, or (k, 4) real = Re cK, Im cK, Re cM, Im cM; X (k, N, 6) or (k, 6 N) complex; masked: P (...) P X[k]
+        under the mask of set_bc.  Returns (k, N, 6) complex."""
+        n6 = 6 * self.n_nodes
+        x = np.ascontiguousarray(np.asarray(X, dtype=np.complex128)).reshape(-1, n6)
+        k = x.shape[0]
+        c = np.asarray(coef)
+        c = (np.ascontiguousarray(c, dtype=np.complex128).reshape(k, 2).view(np.float64) if np.iscomplexobj(c)
+             else np.ascontiguousarray(c, dtype=np.float64))
+        if c.size != 4 * k:
+            raise ValueError(f"coef must have shape ({k}, 2) complex or ({k}, 4) real")
+        c = np.ascontiguousarray(c.reshape(k, 4))
+        y = np.empty_like(x)
+        _check(self._lib, self._lib.pl_harm_spmv(self._h, k, _ptr(c), int(bool(masked)), _ptr(x), _ptr(y)))
+        return y.reshape(k, self.n_nodes, 6)
+
+    def harmonic(self, omegas, load, ray_m=0.0, ray_k=0.0, probes=None, fields=False, rtol=1e-10, max_iter=20000, block=0,
+                 raise_on_noconv=True):
+        """The steady state u e^{iwt} under load e^{iwt} for every w of ``omegas`` (pl_harmonic):
+        ((1 + i w ray_k) K + (i w ray_m - w^2) M) u = load on the free dofs of set_bc, one Jacobi-preconditioned COCG solve per
+        frequency, ``block`` frequencies in lock step per pass (0 = 32).  load (N, 6) real or complex; probes: node indices.
+        Returns a dict: omega (n_freq,), probe (n_freq, n_probe, 6) complex, power (n_freq, 4) = Re f^T u, Im f^T u, u^H K u,
+        u^H M u, iters, relres and status (n_freq,; 0 converged, 1 max_iter, 2 breakdown), and fields (n_freq, N, 6) complex if
+        ``fields``.  Without raise_on_noconv a frequency that did not converge only shows in status."""
+        w = np.ascontiguousarray(np.atleast_1d(np.asarray(omegas, dtype=np.float64)).reshape(-1))
+        nf, n6 = w.size, 6 * self.n_nodes
+        ld = np.asarray(load)
+        if ld.size != n6:
+            raise ValueError(f"load must have shape ({self.n_nodes}, 6)")
+        lre = np.ascontiguousarray(ld.real, dtype=np.float64).reshape(-1)
+        lim = np.ascontiguousarray(ld.imag, dtype=np.float64).reshape(-1) if np.iscomplexobj(ld) else None
+        pr = np.zeros(0, np.int32) if probes is None else np.ascontiguousarray(np.asarray(probes).reshape(-1), dtype=np.int32)
+        probe = np.zeros((nf, pr.size, 6), np.complex128)
+        fld = np.zeros((nf, self.n_nodes, 6), np.complex128) if fields else None
+        power = np.zeros((nf, 4), np.float64)
+        iters = np.zeros(nf, np.int32)
+        relres = np.zeros(nf, np.float64)
+        status = np.zeros(nf, np.int32)
+        rc = self._lib.pl_harmonic(self._h, nf, _ptr(w), float(ray_m), float(ray_k), _ptr(lre), _ptr(lim), pr.size,
+                                   _ptr(pr) if pr.size else None, float(rtol), int(max_iter), int(block),
+                                   _ptr(probe) if pr.size else None, _ptr(fld), _ptr(power), _ptr(iters), _ptr(relres),
+                                   _ptr(status))
+        _check(self._lib, rc, allow=() if raise_on_noconv else (PL_ERR_NOCONV,))
+        out = {"omega": w, "probe": probe, "power": power, "iters": iters, "relres": relres, "status": status}
+        if fields:
+            out["fields"] = fld
+        return out
+
+    def harmonic_host(self, fixed, omegas, load, ray_m=0.0, ray_k=0.0, solver=None):
+        """The numpy / scipy restatement of ``harmonic`` (dynamics_host.harmonic) on this handle's own BSR K and the restated M
+        of its mass model.  fixed (N, 6): the mask that was given to set_bc."""
+        import scipy.sparse as sp
+        from . import dynamics_host as DH
+        self.assemble_bsr(False)
+        rowptr, col, vals = self.get_bsr()
+        K = sp.bsr_matrix((vals, col, rowptr), shape=(6 * self.n_nodes, 6 * self.n_nodes)).tocsr()
+        K.sum_duplicates()
+        return DH.harmonic(K, self.mass_matrix_host(), fixed, omegas, load, ray_m, ray_k, solver)
+
     def time_kernel(self, which, reps=20):
         ms = C.c_double()
         _check(self._lib, self._lib.pl_time_kernel(self._h, int(which), int(reps), C.byref(ms)))

@@ -10,6 +10,7 @@
 #include "pl_geom.h"
 #include "pl_mass.h"
 #include "pl_dyn.h"
+#include "pl_harm.h"
 #include "pl_dyn_sens.h"
 #include "pl_sensgram.h"
 
@@ -2801,6 +2802,142 @@ int pl_transient_sens(pl_handle h, int32_t n_steps, double dt, double beta, doub
     std::fprintf(stderr, "[%s] %-28s %10.4f ms\n", who, "k_transient_sens", ms_sens);
     std::fprintf(stderr, "[%s] %-28s %10.2f %%\n", who, "k_transient_sens_share", 100.0 * ms_sens / ms);
   }
+  return PL_OK;
+}
+
+// ---- frequency response (pl_harm.h) ------------------------------------------------------------------------------------
+int pl_harm_spmv(pl_handle h, int32_t n_freq, const double *coef, int masked, const double *x, double *y) {
+  const char *who = "pl_harm_spmv";
+  if (!valid(h) || !coef || !x || !y) return fail(PL_ERR_ARG, "pl_harm_spmv: null argument");
+  if (n_freq < 1 || n_freq > kHarmMaxFreq) return fail(PL_ERR_ARG, "pl_harm_spmv: n_freq must be 1 ... PL_MULTI_MAX / 2");
+  for (int i = 0; i < 4 * n_freq; ++i)
+    if (!std::isfinite(coef[i])) return fail(PL_ERR_ARG, "pl_harm_spmv: the coefficients must be finite");
+  MassWs *m = nullptr;
+  if (int rc = mass_begin(h, who, masked != 0, &m)) return rc;
+  const MultiShape s = harm_shape(h, n_freq);
+  MultiWs *w = nullptr;
+  if (int rc = multi_ws(h, s, false, &w)) return rc;
+  HarmWs *hw = nullptr;
+  if (int rc = harm_ws(h, &hw)) return rc;
+  PL_HIP(hipMemcpyAsync(hw->coef.p, coef, (size_t)4 * n_freq * sizeof(double), hipMemcpyHostToDevice, h->stream));
+  if (int rc = harm_upload(h, w, n_freq, x, nullptr, false, w->F.p, masked ? -1 : 0)) return rc;
+  EventTimer timer(who, h->stream, "kernel_hip_event");
+  if (int rc = launch_harm_multi(h, m, s, hw->coef.p, w->F.p, w->U.p, masked != 0)) return rc;
+  timer.stop();
+  return harm_download(h, w, n_freq, w->U.p, y);
+}
+
+int pl_harmonic(pl_handle h, int32_t n_freq, const double *omega, double ray_m, double ray_k, const double *load_re,
+                const double *load_im, int32_t n_probe, const int32_t *probe_nodes, double rtol, int32_t max_iter, int32_t block,
+                double *probe_out, double *fields, double *power, int32_t *iters, double *relres, int32_t *status) {
+  const char *who = "pl_harmonic";
+  if (!valid(h) || !omega || !load_re || !iters || !relres || !status) return fail(PL_ERR_ARG, "pl_harmonic: null argument");
+  if (n_freq < 1) return fail(PL_ERR_ARG, "pl_harmonic: n_freq must be at least 1");
+  for (int i = 0; i < n_freq; ++i)
+    if (!(omega[i] >= 0.0) || !std::isfinite(omega[i])) return fail(PL_ERR_ARG, "pl_harmonic: omega must be finite and not negative");
+  if (!(ray_m >= 0.0) || !(ray_k >= 0.0) || !std::isfinite(ray_m) || !std::isfinite(ray_k))
+    return fail(PL_ERR_ARG, "pl_harmonic: the Rayleigh coefficients must be finite and not negative");
+  if (!(rtol > 0.0) || max_iter <= 0) return fail(PL_ERR_ARG, "pl_harmonic: rtol and max_iter must be positive");
+  if (block < 0 || block > kHarmMaxFreq) return fail(PL_ERR_ARG, "pl_harmonic: block must be 0 ... PL_MULTI_MAX / 2");
+  if (n_probe < 0 || (n_probe > 0 && (!probe_nodes || !probe_out)))
+    return fail(PL_ERR_ARG, "pl_harmonic: n_probe > 0 needs probe_nodes and probe_out");
+  const int64_t N = h->N, n6 = N * 6;
+  for (int i = 0; i < n_probe; ++i)
+    if (probe_nodes[i] < 0 || probe_nodes[i] >= N) return fail(PL_ERR_ARG, "pl_harmonic: probe node index out of range");
+  MassWs *m = nullptr;
+  if (int rc = transient_begin(h, who, &m)) return rc;
+  const int nb = std::min<int>(block == 0 ? kHarmMaxFreq : block, n_freq);
+  MultiWs *w = nullptr;
+  if (int rc = multi_ws(h, harm_shape(h, nb), true, &w)) return rc;
+  HarmWs *hw = nullptr;
+  if (int rc = harm_ws(h, &hw)) return rc;
+  // the probed nodes, each once: slot of the node in the device's probe block
+  std::vector<int32_t> slot_of((size_t)N, -1), probe_to_slot((size_t)n_probe);
+  int n_slot = 0;
+  for (int i = 0; i < n_probe; ++i) {
+    const int64_t di = h->iperm[probe_nodes[i]];
+    if (slot_of[(size_t)di] < 0) slot_of[(size_t)di] = n_slot++;
+    probe_to_slot[(size_t)i] = slot_of[(size_t)di];
+  }
+  PL_HIP(dyn_grow(hw->probe, (size_t)nb * std::max(n_slot, 1) * 12));
+  PL_HIP(hipMemcpyAsync(hw->probe_slot.p, slot_of.data(), (size_t)N * sizeof(int32_t), hipMemcpyHostToDevice, h->stream));
+  if (int rc = harm_upload(h, w, 1, load_re, load_im, true, w->F.p, -1)) return rc;   // (its wait covers slot_of too)
+  // diag K and diag M, real, once per call
+  MultiOp op;
+  op.mass = m;
+  op.c_K = 1.0; op.c_M = 0.0;
+  if (int rc = launch_dyn_diag(h, op, h->fixedbits.p, hw->diagK.p, nullptr)) return rc;
+  op.c_K = 0.0; op.c_M = 1.0;
+  if (int rc = launch_dyn_diag(h, op, h->fixedbits.p, hw->diagM.p, nullptr)) return rc;
+
+  const bool timing = std::getenv("PL_TIMING") != nullptr;
+  const auto t_begin = std::chrono::steady_clock::now();
+  const dim3 gs(harm_grid(n6));
+  std::vector<double> coef((size_t)4 * nb), st((size_t)pl::H_ST_COUNT * nb), pw((size_t)nb * pl::H_PW_COUNT * pl::kSlots);
+  std::vector<double> ph((size_t)nb * std::max(n_slot, 1) * 12);
+  int bad = 0;
+  for (int f0 = 0; f0 < n_freq; f0 += nb) {
+    const int nf = std::min(nb, n_freq - f0);
+    const MultiShape s = harm_shape(h, nf);
+    for (int j = 0; j < nf; ++j) {
+      const double wj = omega[f0 + j];
+      coef[(size_t)4 * j] = 1.0;
+      coef[(size_t)4 * j + 1] = wj * ray_k;
+      coef[(size_t)4 * j + 2] = -wj * wj;
+      coef[(size_t)4 * j + 3] = wj * ray_m;
+    }
+    PL_HIP(hipMemcpyAsync(hw->coef.p, coef.data(), (size_t)4 * nf * sizeof(double), hipMemcpyHostToDevice, h->stream));
+    PL_HIP(hipStreamSynchronize(h->stream));         // (coef is pageable host memory, rewritten by the next pass)
+    const auto t0 = std::chrono::steady_clock::now();
+    int launched = 0;
+    if (int rc = cocg_solve(h, w, hw, m, s, rtol, max_iter, st.data(), &launched)) return rc;
+    const double ms_pass = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    // K u and M u of the fields, then the probes and the power sums
+    if (int rc = launch_spmv_multi(h, s, h->fixedbits.p, w->X.p, w->KU.p, true, nullptr)) return rc;
+    if (int rc = launch_mass_multi(h, m, s, w->X.p, w->AP.p, true)) return rc;
+    PL_HIP(hipMemsetAsync(hw->power.p, 0, (size_t)nf * pl::H_PW_COUNT * pl::kSlots * sizeof(double), h->stream));
+    hipLaunchKernelGGL(pl::k_harm_epilogue, dim3(gs.x, (unsigned)nf), dim3(pl::kBlock), 0, h->stream, n6, (const double *)w->F.p,
+                       (const double *)w->X.p, (const double *)w->KU.p, (const double *)w->AP.p,
+                       (const int32_t *)hw->probe_slot.p, n_slot, hw->probe.p, hw->power.p, s.stride);
+    PL_HIP(hipGetLastError());
+    PL_HIP(hipMemcpyAsync(pw.data(), hw->power.p, (size_t)nf * pl::H_PW_COUNT * pl::kSlots * sizeof(double),
+                          hipMemcpyDeviceToHost, h->stream));
+    if (n_slot > 0)
+      PL_HIP(hipMemcpyAsync(ph.data(), hw->probe.p, (size_t)nf * n_slot * 12 * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+    PL_HIP(hipStreamSynchronize(h->stream));
+    long pass_iters = 0;
+    for (int j = 0; j < nf; ++j) {
+      const double rr = st[(size_t)pl::H_ST_RR * nf + j], bb = st[(size_t)pl::H_ST_BB * nf + j];
+      const int state = (int)st[(size_t)pl::H_ST_STATE * nf + j];
+      iters[f0 + j] = (int32_t)st[(size_t)pl::H_ST_ITER * nf + j];
+      relres[f0 + j] = bb > 0.0 ? std::sqrt(rr / bb) : 0.0;
+      status[f0 + j] = state == 1 ? 0 : (state == 2 ? 2 : 1);
+      if (status[f0 + j] != 0) ++bad;
+      pass_iters += iters[f0 + j];
+      if (power)
+        for (int k = 0; k < pl::H_PW_COUNT; ++k) {
+          double t = 0.0;
+          for (int q = 0; q < pl::kSlots; ++q) t += pw[((size_t)j * pl::H_PW_COUNT + k) * pl::kSlots + q];
+          power[(size_t)(f0 + j) * pl::H_PW_COUNT + k] = t;
+        }
+      for (int i = 0; i < n_probe; ++i)
+        std::memcpy(probe_out + ((size_t)(f0 + j) * n_probe + i) * 12,
+                    ph.data() + ((size_t)j * n_slot + probe_to_slot[(size_t)i]) * 12, 12 * sizeof(double));
+    }
+    if (fields)
+      if (int rc = harm_download(h, w, nf, w->X.p, fields + (size_t)f0 * 2 * n6)) return rc;
+    if (timing) {
+      std::fprintf(stderr, "[%s] %-28s %10d\n", who, "pass_frequencies", nf);
+      std::fprintf(stderr, "[%s] %-28s %10.4f ms\n", who, "iteration_mean_host_clock", launched > 0 ? ms_pass / launched : 0.0);
+      std::fprintf(stderr, "[%s] %-28s %10.2f\n", who, "iterations_per_frequency", (double)pass_iters / nf);
+    }
+  }
+  if (timing) {
+    const double ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_begin).count();
+    std::fprintf(stderr, "[%s] %-28s %10.4f ms\n", who, "whole_call_host_clock", ms);
+  }
+  if (bad)
+    return fail(PL_ERR_NOCONV, "pl_harmonic: " + std::to_string(bad) + " frequencies ended without convergence (see status)");
   return PL_OK;
 }
 

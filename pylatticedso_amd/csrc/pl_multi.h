@@ -579,14 +579,22 @@ int multi_download(pl_context *c, MultiWs *w, const MultiShape &s, const double 
 // y_j = A x_j (masked: P A x_j), A the operator of `term`, for every column of the shape: one launch of k_gather_multi at the
 // handle's lanes per node, the shape's column block and the mask.  A column block wider than the term is built for is an
 // error: there is no other path.
+// the narrowest column block a term is built for: Term::kMinKB where it has one (HarmTerm, pl_harm.h), 1 otherwise
+template <class Term, class = void>
+struct term_min_kb : std::integral_constant<int, 1> {};
+template <class Term>
+struct term_min_kb<Term, std::void_t<decltype(Term::kMinKB)>> : std::integral_constant<int, Term::kMinKB> {};
+
 template <class Term>
 int launch_gather_multi(pl_context *c, const MultiShape &s, Term term, const uint8_t *fixedbits, const double *x, double *y,
                         bool masked, double *dot_dev) {
-  if (s.KB > Term::kMaxKB) return fail(PL_ERR_ARG, "the product is not built for column blocks of " + std::to_string(s.KB));
+  constexpr int kMinKB = term_min_kb<Term>::value;
+  if (s.KB > Term::kMaxKB || s.KB < kMinKB)
+    return fail(PL_ERR_ARG, "the product is not built for column blocks of " + std::to_string(s.KB));
   const dim3 g(grid_for(c->n_slices, pl::kBlock / pl::kWave), (unsigned)s.ncb);   // one wave per ELL slice and column block
   auto go = [&](auto lpn, auto kb) {
     constexpr int LPN = decltype(lpn)::value, KB = decltype(kb)::value;
-    if constexpr (KB <= Term::kMaxKB) {
+    if constexpr (KB <= Term::kMaxKB && KB >= term_min_kb<Term>::value) {
       const auto kernel = masked ? pl::k_gather_multi<LPN, KB, true, Term> : pl::k_gather_multi<LPN, KB, false, Term>;
       hipLaunchKernelGGL(kernel, g, dim3(pl::kBlock), 0, c->stream, c->N, (const int64_t *)c->slice_ptr.p, (const int2 *)c->ent.p,
                          term, fixedbits, x, y, dot_dev, s.stride);

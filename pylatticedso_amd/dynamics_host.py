@@ -6,7 +6,10 @@ Step n -> n + 1 with dt:
     (M (1 + gamma dt ray_m) + K (beta dt^2 + gamma dt ray_k)) a_{n+1} = f_{n+1} - K ut - C vt
     u_{n+1} = ut + beta dt^2 a_{n+1},   v_{n+1} = vt + gamma dt a_{n+1}
 and M a_0 = f_0 - K u_0 - C v_0.  With beta = 1/4, gamma = 1/2 (the average acceleration) an undamped mode of frequency omega
-is carried with its amplitude kept and the phase ``newmark_phase(omega, dt)`` per step."""
+is carried with its amplitude kept and the phase ``newmark_phase(omega, dt)`` per step.
+
+``harmonic`` restates the frequency response (csrc/pl_harm.h, pl_harmonic): the steady state under
+f e^{iwt}, one complex symmetric system per frequency, with ``jacobi_cocg`` the device's solver."""
 import numpy as np
 import scipy.linalg
 import scipy.sparse as sp
@@ -230,3 +233,99 @@ def newmark_sensitivity(K, M, fixed, conn, drec_dr, dM_dr, dt, n_steps, out_vec,
         we = np.concatenate([wM[n][ia], wM[n][ib]], axis=1)
         grad += GH._pairing(drec, conn, wK[n], lam3[n]) + np.einsum("bi,bij,bj->b", le, dM, we)
     return {"J": J, "y": y, "dJ_dr": grad, "lam": lam3, "c": c}
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# Frequency response: the steady state under a harmonic load (csrc/pl_harm.h, pl_harmonic)
+# ---------------------------------------------------------------------------------------------------------------------
+def harmonic_coefficients(omegas, ray_m=0.0, ray_k=0.0):
+    """(c_K, c_M) of A(w) = c_K K + c_M M: c_K = 1 + i w ray_k, c_M = i w ray_m - w^2, with the argument checks of pl_harmonic."""
+    w = np.atleast_1d(np.asarray(omegas, float)).reshape(-1)
+    if w.size < 1:
+        raise ValueError("at least one frequency is needed")
+    if not (np.isfinite(w).all() and (w >= 0.0).all()):
+        raise ValueError("omega must be finite and not negative")
+    if not (ray_m >= 0.0 and ray_k >= 0.0 and np.isfinite(ray_m) and np.isfinite(ray_k)):
+        raise ValueError("the Rayleigh coefficients must be finite and not negative")
+    return w, 1.0 + 1j * w * ray_k, 1j * w * ray_m - w * w
+
+
+def jacobi_cocg(rtol, max_iter=100000, counts=None):
+    """A ``solver`` for ``harmonic``: the device's algorithm, the conjugate orthogonal CG (CG with the unconjugated form
+    x^T y) on the complex symmetric A, preconditioned with its diagonal, from a zero start to ||r|| <= rtol ||b||.
+    counts: a list that receives (iterations, status) of every solve; status 0 converged, 1 max_iter, 2 breakdown (a zero or
+    non-finite p^T A p or r^T z)."""
+    counts = [] if counts is None else counts
+
+    def bad(v):
+        return not np.isfinite(v) or v == 0.0
+
+    def solve(A, b):
+        d = A.diagonal()
+        dinv = np.where(d != 0.0, 1.0 / np.where(d != 0.0, d, 1.0), 0.0)
+        b = np.asarray(b, complex)
+        x = np.zeros_like(b)
+        r = b.copy()
+        bb = float(np.vdot(r, r).real)
+        it, status = 0, 0
+        if bb > 0.0:
+            z = dinv * r
+            p = z.copy()
+            rho = r @ z
+            status = 1
+            while it < max_iter:
+                Ap = A @ p
+                sigma = p @ Ap
+                if bad(rho) or bad(sigma):
+                    it += 1
+                    status = 2
+                    break
+                alpha = rho / sigma
+                x += alpha * p
+                r -= alpha * Ap
+                it += 1
+                if float(np.vdot(r, r).real) <= rtol * rtol * bb:
+                    status = 0
+                    break
+                z = dinv * r
+                rho_new = r @ z
+                if bad(rho_new):
+                    status = 2
+                    break
+                p = z + (rho_new / rho) * p
+                rho = rho_new
+        counts.append((it, status))
+        return x
+    solve.counts = counts
+    return solve
+
+
+def harmonic(K, M, fixed, omegas, f, ray_m=0.0, ray_k=0.0, solver=None):
+    """The arrays of pl_harmonic from the matrices K, M (6N x 6N, dense or sparse) and the mask fixed (N, 6) / (6N,):
+    ((1 + i w ray_k) K + (i w ray_m - w^2) M) u = f on the free dofs for every w of ``omegas``, the fixed dofs at zero.
+
+    f (6N,) or (N, 6), real or complex, is read with the fixed dofs zeroed.  solver(A, b): the solver of the reduced complex
+    system (A sparse); None = a dense solve.  Returns a dict: omega (n_freq,), u (n_freq, N, 6) complex and power (n_freq, 4)
+    = Re f^T u, Im f^T u (unconjugated), u^H K u, u^H M u; with a ``jacobi_cocg`` solver also iterations and status (n_freq,)."""
+    w, cK, cM = harmonic_coefficients(omegas, ray_m, ray_k)
+    fx = np.asarray(fixed).reshape(-1) != 0
+    n6 = fx.size
+    free = np.flatnonzero(~fx)
+    K, M = sp.csr_matrix(K), sp.csr_matrix(M)
+    Kf, Mf = K[free][:, free].tocsr(), M[free][:, free].tocsr()
+    ff = np.asarray(f, complex).reshape(-1)[free]
+    U = np.zeros((w.size, n6), complex)
+    power = np.zeros((w.size, 4))
+    counts = getattr(solver, "counts", None)
+    n0 = 0 if counts is None else len(counts)
+    for k in range(w.size):
+        A = (cK[k] * Kf + cM[k] * Mf).tocsr()
+        u = np.linalg.solve(A.toarray(), ff) if solver is None else solver(A, ff)
+        U[k, free] = u
+        fu = ff @ u
+        power[k] = fu.real, fu.imag, np.vdot(u, Kf @ u).real, np.vdot(u, Mf @ u).real
+    out = {"omega": w, "u": U.reshape(w.size, n6 // 6, 6), "power": power}
+    if counts is not None:
+        out["iterations"] = np.array([c[0] for c in counts[n0:]], int)
+        out["status"] = np.array([c[1] for c in counts[n0:]], int)
+    return out

@@ -749,14 +749,18 @@ class LatticeSim(LatticeViews):
         self._transient_settings = s
         return out
 
-    def _transient_setup(self, who, dt, n_steps, density, amplitude, base_acceleration, damping, rotary, node_mass, kw):
-        """The checks of ``transient_response``, the mass model on the device, and the settings of the run as a dict: what
-        ``transient_sensitivity`` runs again."""
+    def _dynamics_guard(self, who):
+        """What the dynamic responses ask of the lattice: the default strut model, a FEM handle, a solve behind it."""
         if getattr(self, "_compat_rows", False) or self.domain_decomposition_solver:
             raise NotImplementedError(f"{who}: the default strut model on a FEM lattice only (no reference_compat "
                                       "rows, no domain decomposition)")
         if self._device is None:
             raise RuntimeError(f"{who} needs a solve_FEM_FenicsX on this lattice first")
+
+    def _transient_setup(self, who, dt, n_steps, density, amplitude, base_acceleration, damping, rotary, node_mass, kw):
+        """The checks of ``transient_response``, the mass model on the device, and the settings of the run as a dict: what
+        ``transient_sensitivity`` runs again."""
+        self._dynamics_guard(who)
         n, rows = self.lattice.n_nodes, int(n_steps) + 1
         self._device.set_mass(density, rotary, node_mass)
         time = float(dt) * np.arange(rows)
@@ -819,6 +823,63 @@ class LatticeSim(LatticeViews):
         u_dyn = np.linalg.norm(self.transient_probe[:, 0, :, :3], axis=2).max(axis=0)
         u_static = np.linalg.norm(np.asarray(self.displacement_vector)[self._transient_probes, :3], axis=1)
         return u_dyn / u_static
+
+    def frequency_response(self, frequencies_hz, density, damping=(0.0, 0.0), probes=None, base_acceleration=None,
+                           rotary=True, node_mass=None, **kw):
+        """Steady-state response to a harmonic load under the supports of the last solve_FEM_FenicsX, on the device
+        (pl_set_mass, pl_harmonic): for every frequency f (Hz), w = 2 pi f, the complex amplitudes u of
+        (K + i w C - w^2 M) u = load, M the consistent mass of the struts at ``density`` (as ``natural_frequencies``),
+        C = damping[0] M + damping[1] K.  The load is the force set of the solve; with ``base_acceleration`` = direction (3,)
+        or an axis 0 / 1 / 2 it is the inertia load -M e_direction of a base shaken with unit acceleration amplitude, the
+        response then being relative to the base.  probes: node indices (default: the nodes of the force set).  Keyword
+        arguments (rtol, max_iter, block, fields, raise_on_noconv) go to ``HipLattice.harmonic``.  Sets ``frf_frequency`` (n_freq,) in Hz, ``frf_probe``
+        (n_freq, n_probe, 6) complex, ``frf_power`` (n_freq, 4) = Re f^T u, Im f^T u, u^H K u, u^H M u, ``frf_iterations``
+        (n_freq,), with a base acceleration ``frf_transmissibility`` (n_freq, n_probe, 3) = absolute over base displacement
+        (else None), and returns the device call's dict."""
+        self._dynamics_guard("frequency_response")
+        dev, n = self._device, self.lattice.n_nodes
+        hz = np.atleast_1d(np.asarray(frequencies_hz, float)).reshape(-1)
+        dev.set_mass(density, rotary, node_mass)
+        if base_acceleration is None:
+            load = np.zeros((n, 6))
+            load[:, :3] = np.asarray(self.applied_force)[:n, :3]      # (only the translational components are loads)
+            if probes is None:
+                probes = np.flatnonzero(np.abs(load).sum(axis=1) > 0)
+        else:
+            direction = (np.eye(3)[int(base_acceleration)] if np.ndim(base_acceleration) == 0
+                         else np.asarray(base_acceleration, float).reshape(3))
+            e = np.zeros((1, n, 6))
+            e[0, :, :3] = direction
+            load = -dev.mass_spmv_multi(e)[0]
+            if probes is None:
+                probes = np.flatnonzero(np.abs(np.asarray(self.applied_force)[:n, :3]).sum(axis=1) > 0)
+        probes = np.asarray(probes, int).reshape(-1)
+        out = dev.harmonic(2.0 * np.pi * hz, load, ray_m=float(damping[0]), ray_k=float(damping[1]), probes=probes, **kw)
+        self.frf_frequency, self.frf_probe = hz, out["probe"]
+        self.frf_power, self.frf_iterations = out["power"], out["iters"]
+        self._frf_probes = probes
+        # a base moving with x_b e^{iwt}, -w^2 x_b = 1: absolute over base displacement, e_direction - w^2 u (the rigid
+        # value e_direction at w = 0)
+        self.frf_transmissibility = None
+        if base_acceleration is not None:
+            w2 = (2.0 * np.pi * hz) ** 2
+            self.frf_transmissibility = direction[None, None, :] - w2[:, None, None] * out["probe"][:, :, :3]
+        return out
+
+    def dynamic_stiffness_peaks(self):
+        """The resonance peaks of the last ``frequency_response``: for every probe the local maxima of |u| over the
+        frequencies, |.| the norm of the three complex translations - a list (one entry per probe) of dicts with index,
+        frequency (Hz) and amplitude arrays.  The ends of the band count only if they lie above their one neighbour."""
+        if getattr(self, "frf_probe", None) is None:
+            raise RuntimeError("dynamic_stiffness_peaks needs a frequency_response on this lattice first")
+        amp = np.linalg.norm(self.frf_probe[:, :, :3], axis=2)           # (n_freq, n_probe)
+        pad = np.vstack([np.full((1, amp.shape[1]), -np.inf), amp, np.full((1, amp.shape[1]), -np.inf)])
+        top = (pad[1:-1] > pad[:-2]) & (pad[1:-1] >= pad[2:]) if amp.shape[0] > 1 else np.zeros_like(amp, bool)
+        peaks = []
+        for j in range(amp.shape[1]):
+            idx = np.flatnonzero(top[:, j])
+            peaks.append({"index": idx, "frequency": self.frf_frequency[idx], "amplitude": amp[idx, j]})
+        return peaks
 
     def natural_frequency_sensitivity(self, p=8, want_rows=True):
         """Derivatives of the omega^2 of the last ``natural_frequencies`` to the strut radii, on the device
