@@ -602,6 +602,32 @@ int pl_harmonic(pl_handle h, int32_t n_freq, const double *omega /*[n_freq]*/, d
                 double *power /*[n_freq][4], or NULL*/, int32_t *iters /*[n_freq]*/, double *relres /*[n_freq]*/,
                 int32_t *status /*[n_freq]: 0 ok, 1 max_iter, 2 breakdown*/);
 
+/* ---- frequency response sensitivities (csrc/pl_harm_sens.h) ------------------------------------------
+ * The solves of pl_harmonic (same systems, same solver, same preconditions and error codes; the fields are its bits), one
+ * complex output per frequency y_k = l^T u_k (unconjugated; out_vec = l real, read with the fixed dofs zeroed), a real
+ * objective of the outputs with weights w_k >= 0 (NULL = 1)
+ *     kind 0: J = -sum w_k Im y_k,   kind 1: J = 1/2 sum w_k |y_k|^2,   kind 2: J = (sum w_k |y_k|^p)^(1/p), p >= 2
+ * and dJ/dr_b for every strut radius at fixed segment geometry (the convention of pl_sens).  A(w) is complex symmetric, so
+ * the adjoint field solves A(w_k) lam_k = l with the matrix of the forward solve; it rides in the same pass as u_k, which
+ * therefore takes PL_MULTI_MAX / 4 frequencies at the most.  The load is load_re + i load_im (a dead load) plus, with
+ * base_dir, the load -P M e_dir of a base shaken with unit acceleration (e_dir: the rigid translation base_dir of ALL nodes),
+ * the only load that follows the design; load_re = NULL is legal with base_dir.  out_vec = NULL: l is the whole load, lam = u,
+ * no second solve (the dynamic compliance; with kind 0 and w_k = omega_k / 2 the mean dissipated power), and a pass takes
+ * PL_MULTI_MAX / 2 frequencies.  The fields of every frequency stay on the device for the call: 2 * 96 N n_freq bytes, half
+ * of it with out_vec = NULL.  No floating-point atomics in the contraction: two calls return the same bits, whatever `block`.
+ * iters, relres, status: row 0 the forward solves, row 1 the adjoint ones (zeros with out_vec = NULL).
+ * PL_ERR_ARG: the checks of pl_harmonic, kind outside 0 ... 2, p < 2 with kind 2, a negative or non-finite weight, a NULL J
+ * or dJ_dr, neither a load nor base_dir, block above the pass limit.  PL_ERR_STATE as pl_harmonic.  PL_ERR_NOCONV when any
+ * solve ends with status != 0: iters, relres and status are written, J, y and dJ_dr are not.  PL_ERR_NAN: the objective is
+ * not finite.  The handle's single-column state and its earlier results are left untouched. */
+int pl_harmonic_sens(pl_handle h, int32_t n_freq, const double *omega /*[n_freq]*/, double ray_m, double ray_k,
+                     const double *load_re /*[6N] or NULL with base_dir*/, const double *load_im /*[6N] or NULL = 0*/,
+                     const double *base_dir /*[3] or NULL*/, const double *out_vec /*[6N] real, or NULL = the load*/,
+                     int32_t kind, double p, const double *weight /*[n_freq] or NULL = 1*/, double rtol, int32_t max_iter,
+                     int32_t block /*0 = the most*/, double *J, double *y /*[n_freq] complex or NULL*/,
+                     double *dJ_dr /*[B], caller's strut numbering*/, int32_t *iters, double *relres,
+                     int32_t *status /*[2][n_freq]: forward, adjoint; or NULL*/);
+
 /* The same condensation, exact and batched, without a handle: n_inst small lattices of ONE topology (a unit cell at
  * several radius sets - the exact DDM mode, Schur datasets), each condensed by a dense Cholesky of K_II in one workgroup
  * of a single launch.  Material, pen_coef and device come from o (stamped by pl_default_opts; the solver fields are

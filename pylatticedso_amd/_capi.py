@@ -25,7 +25,7 @@ EXPORTS = ["pl_default_opts", "pl_opts_size", "pl_stats_size", "pl_abi_version",
            "pl_stress", "pl_stress_pnorm", "pl_buckling", "pl_buckling_pnorm",
            "pl_spmv_multi", "pl_solve_multi", "pl_schur_block", "pl_geom_spmv_multi", "pl_buckling_modes", "pl_buckling_modes_sens",
            "pl_set_mass", "pl_mass_spmv_multi", "pl_vibration_modes", "pl_vibration_modes_sens",
-           "pl_dyn_spmv_multi", "pl_transient", "pl_transient_sens", "pl_harm_spmv", "pl_harmonic",
+           "pl_dyn_spmv_multi", "pl_transient", "pl_transient_sens", "pl_harm_spmv", "pl_harmonic", "pl_harmonic_sens",
            "pl_schur_cells", "pl_cells_recover", "pl_get_records", "pl_debug_partition", "pl_time_kernel", "pl_algorithmic_bytes", "pl_node_words_info", "pl_forget_history", "pl_debug_spd_solve", "pl_dist_unique_id_bytes",
            "pl_dist_unique_id", "pl_dist_loopback_id", "pl_dist_abort", "pl_dist_init", "pl_dist_set_peers", "pl_generate_lattice", "pl_lattice_fetch",
            "pl_lattice_free", "pl_penalize", "pl_boundary_index", "pl_boundary_index_rows"]
@@ -109,6 +109,7 @@ def load_library(path: str | None = None):
            "pl_transient_sens": [V, I32, D, D, D, D, D, I32, V, V, V, V, V, V, D, I32, V, I32, D, V, V, V, V, V],
            "pl_harm_spmv": [V, I32, V, I32, V, V],
            "pl_harmonic": [V, I32, V, D, D, V, V, I32, V, D, I32, I32, V, V, V, V, V, V],
+           "pl_harmonic_sens": [V, I32, V, D, D, V, V, V, V, I32, D, V, D, I32, I32, V, V, V, V, V, V],
            "pl_schur_cells": [V, I32, I32, I32, V, I32, V, V, V, V, V, V, V],
            "pl_cells_recover": [V, I32, I32, I32, V, I32, V, V, V, V, V, V, V, V, V, V, V],
            "pl_get_records": [V, V], "pl_debug_partition": [V, V, V, V, V], "pl_time_kernel": [V, I32, I32, V],
@@ -1142,6 +1143,66 @@ class HipLattice:
         K = sp.bsr_matrix((vals, col, rowptr), shape=(6 * self.n_nodes, 6 * self.n_nodes)).tocsr()
         K.sum_duplicates()
         return DH.harmonic(K, self.mass_matrix_host(), fixed, omegas, load, ray_m, ray_k, solver)
+
+    def harmonic_sens(self, omegas, load, out_vec=None, kind=2, p=8.0, weight=None, base_dir=None, ray_m=0.0, ray_k=0.0,
+                      rtol=1e-10, max_iter=20000, block=0, raise_on_noconv=True):
+        """The solves of ``harmonic`` with one complex output per frequency y_k = out_vec^T u_k (unconjugated), the objective J
+        of the outputs (kind 0: -sum w Im y, 1: 1/2 sum w |y|^2, 2: (sum w |y|^p)^(1/p); weight (n_freq,) >= 0 or None = 1)
+        and dJ/dr for every strut radius (pl_harmonic_sens).  load (N, 6) real or complex, or None with base_dir; base_dir
+        (3,) adds the load -M e_dir of a base shaken with unit acceleration, which follows the design; out_vec (N, 6) real,
+        read with the fixed dofs zeroed, or None: the whole load (no second solve).  ``block`` frequencies per pass (0 = the
+        most: 16, or 32 with out_vec = None).  Returns a dict: omega, J, y (n_freq,) complex, dJ_dr (B,), iters, relres and
+        status (2, n_freq) = forward, adjoint.  Without raise_on_noconv a solve that did not converge only shows in status,
+        and J, y, dJ_dr are None."""
+        w = np.ascontiguousarray(np.atleast_1d(np.asarray(omegas, dtype=np.float64)).reshape(-1))
+        nf, n6 = w.size, 6 * self.n_nodes
+        lre = lim = None
+        if load is not None:
+            ld = np.asarray(load)
+            if ld.size != n6:
+                raise ValueError(f"load must have shape ({self.n_nodes}, 6)")
+            lre = np.ascontiguousarray(ld.real, dtype=np.float64).reshape(-1)
+            lim = np.ascontiguousarray(ld.imag, dtype=np.float64).reshape(-1) if np.iscomplexobj(ld) else None
+        bd = None if base_dir is None else _f64(np.asarray(base_dir).reshape(-1), 3)
+        lv = None if out_vec is None else _f64(np.asarray(out_vec).reshape(-1), n6)
+        wt = None if weight is None else _f64(np.asarray(weight).reshape(-1), nf)
+        J = C.c_double()
+        y = np.zeros(nf, np.complex128)
+        grad = np.zeros(self.n_beams, np.float64)
+        iters = np.zeros((2, nf), np.int32)
+        relres = np.zeros((2, nf), np.float64)
+        status = np.zeros((2, nf), np.int32)
+        rc = self._lib.pl_harmonic_sens(self._h, nf, _ptr(w), float(ray_m), float(ray_k), _ptr(lre), _ptr(lim), _ptr(bd),
+                                        _ptr(lv), int(kind), float(p), _ptr(wt), float(rtol), int(max_iter), int(block),
+                                        C.byref(J), _ptr(y), _ptr(grad), _ptr(iters), _ptr(relres), _ptr(status))
+        _check(self._lib, rc, allow=() if raise_on_noconv else (PL_ERR_NOCONV,))
+        ok = rc == PL_OK
+        return {"omega": w, "J": J.value if ok else None, "y": y if ok else None, "dJ_dr": grad if ok else None,
+                "iters": iters, "relres": relres, "status": status}
+
+    def harmonic_sens_host(self, fixed, omegas, load, out_vec=None, kind=2, p=8.0, weight=None, base_dir=None, ray_m=0.0,
+                           ray_k=0.0, solver=None):
+        """The numpy / scipy restatement of ``harmonic_sens`` (dynamics_host.harmonic_sensitivity) on this handle's own BSR K,
+        the restated M of its mass model and the restated record and mass derivatives.  fixed (N, 6): the mask that was given
+        to set_bc."""
+        import scipy.sparse as sp
+        from . import dynamics_host as DH
+        from . import mass_host as MH
+        from . import stress_host as SH
+        self.assemble_bsr(False)
+        rowptr, col, vals = self.get_bsr()
+        K = sp.bsr_matrix((vals, col, rowptr), shape=(6 * self.n_nodes, 6 * self.n_nodes)).tocsr()
+        K.sum_duplicates()
+        rho, rotary, nm = self._mass_model()
+        E, nu, kappa, pen = self._material
+        drec = SH.drecords_dr(self.node_xyz, self.beam_conn, self._radius, self._seg_len, self._seg_nsub, E, nu, kappa, pen,
+                              self._mult)
+        conn = np.asarray(self.beam_conn).reshape(-1, 2)
+        xyz = np.asarray(self.node_xyz, dtype=np.float64).reshape(-1, 3)
+        dM = MH.delement_matrix_dr(xyz[conn[:, 1]] - xyz[conn[:, 0]], np.asarray(self._radius, dtype=np.float64).reshape(-1),
+                                   rho, self._mult, rotary)
+        return DH.harmonic_sensitivity(K, self.mass_matrix_host(), fixed, conn, drec, dM, omegas, load, out_vec, kind, p,
+                                       weight, base_dir, ray_m, ray_k, solver)
 
     def time_kernel(self, which, reps=20):
         ms = C.c_double()

@@ -12,6 +12,7 @@
 #include "pl_dyn.h"
 #include "pl_harm.h"
 #include "pl_dyn_sens.h"
+#include "pl_harm_sens.h"
 #include "pl_sensgram.h"
 
 
@@ -2938,6 +2939,217 @@ int pl_harmonic(pl_handle h, int32_t n_freq, const double *omega, double ray_m, 
   }
   if (bad)
     return fail(PL_ERR_NOCONV, "pl_harmonic: " + std::to_string(bad) + " frequencies ended without convergence (see status)");
+  return PL_OK;
+}
+
+// ---- frequency response sensitivities (pl_harm_sens.h) -------------------------------------------------------------------
+int pl_harmonic_sens(pl_handle h, int32_t n_freq, const double *omega, double ray_m, double ray_k, const double *load_re,
+                     const double *load_im, const double *base_dir, const double *out_vec, int32_t kind, double p,
+                     const double *weight, double rtol, int32_t max_iter, int32_t block, double *J, double *y, double *dJ_dr,
+                     int32_t *iters, double *relres, int32_t *status) {
+  const char *who = "pl_harmonic_sens";
+  if (!valid(h) || !omega) return fail(PL_ERR_ARG, "pl_harmonic_sens: null argument");
+  if (!J || !dJ_dr) return fail(PL_ERR_ARG, "pl_harmonic_sens: J and dJ_dr must not be NULL");
+  if (!load_re && !base_dir) return fail(PL_ERR_ARG, "pl_harmonic_sens: neither a load nor base_dir");
+  if (load_im && !load_re) return fail(PL_ERR_ARG, "pl_harmonic_sens: load_im needs load_re");
+  if (n_freq < 1) return fail(PL_ERR_ARG, "pl_harmonic_sens: n_freq must be at least 1");
+  for (int i = 0; i < n_freq; ++i)
+    if (!(omega[i] >= 0.0) || !std::isfinite(omega[i]))
+      return fail(PL_ERR_ARG, "pl_harmonic_sens: omega must be finite and not negative");
+  if (!(ray_m >= 0.0) || !(ray_k >= 0.0) || !std::isfinite(ray_m) || !std::isfinite(ray_k))
+    return fail(PL_ERR_ARG, "pl_harmonic_sens: the Rayleigh coefficients must be finite and not negative");
+  if (!(rtol > 0.0) || max_iter <= 0) return fail(PL_ERR_ARG, "pl_harmonic_sens: rtol and max_iter must be positive");
+  const bool self_adjoint = out_vec == nullptr;
+  const int pass_max = self_adjoint ? kHarmMaxFreq : kHarmSensMaxFreq;
+  if (block < 0 || block > pass_max)
+    return fail(PL_ERR_ARG, "pl_harmonic_sens: block must be 0 ... PL_MULTI_MAX / 4 (PL_MULTI_MAX / 2 with out_vec = NULL)");
+  if (kind < 0 || kind > 2) return fail(PL_ERR_ARG, "pl_harmonic_sens: kind must be 0, 1 or 2");
+  if (kind == 2 && !(p >= 2.0 && std::isfinite(p))) return fail(PL_ERR_ARG, "pl_harmonic_sens: p must be at least 2 (and finite)");
+  if (base_dir)
+    for (int k = 0; k < 3; ++k)
+      if (!std::isfinite(base_dir[k])) return fail(PL_ERR_ARG, "pl_harmonic_sens: base_dir must be finite");
+  if (weight)
+    for (int k = 0; k < n_freq; ++k)
+      if (!(weight[k] >= 0.0) || !std::isfinite(weight[k]))
+        return fail(PL_ERR_ARG, "pl_harmonic_sens: the weights must be finite and not negative");
+  MassWs *m = nullptr;
+  if (int rc = transient_begin(h, who, &m)) return rc;
+  const int64_t N = h->N, n6 = N * 6, n12 = N * 12, B = h->B;
+  const int nb = std::min<int>(block == 0 ? pass_max : block, n_freq);     // frequencies per pass
+  const int per = self_adjoint ? 1 : 2;                                   // column blocks per frequency
+  MultiWs *w = nullptr;
+  if (int rc = multi_ws(h, harm_shape(h, per * nb), true, &w)) return rc;
+  HarmWs *hw = nullptr;
+  if (int rc = harm_ws(h, &hw)) return rc;
+  if (!h->harm_sens_ws) h->harm_sens_ws = std::make_shared<HarmSensWs>();
+  HarmSensWs *s = static_cast<HarmSensWs *>(h->harm_sens_ws.get());
+  PL_HIP(dyn_grow(s->U, (size_t)n_freq * n12));
+  if (!self_adjoint) PL_HIP(dyn_grow(s->L, (size_t)n_freq * n12));
+  PL_HIP(dyn_grow(s->fl, (size_t)2 * n12));
+  PL_HIP(dyn_grow(s->edir, (size_t)n6));
+  PL_HIP(dyn_grow(s->Me, (size_t)n6));
+  PL_HIP(dyn_grow(s->coef, (size_t)4 * n_freq));
+  PL_HIP(dyn_grow(s->g, (size_t)2 * n_freq));
+  PL_HIP(dyn_grow(s->yslots, (size_t)2 * n_freq * pl::kSlots));
+  PL_HIP(dyn_grow(s->acc, (size_t)pl::kHarmSensGroups * B));
+  PL_HIP(dyn_grow(s->grad, (size_t)B));
+  // the load f (0 on fixed dofs), with a base minus P M e_dir, and the output vector l
+  double *f_dev = s->fl.p, *l_dev = self_adjoint ? s->fl.p : s->fl.p + n12;
+  if (load_re) {
+    if (int rc = harm_upload(h, w, 1, load_re, load_im, true, f_dev, -1)) return rc;
+  } else {
+    PL_HIP(hipMemsetAsync(f_dev, 0, (size_t)n12 * sizeof(double), h->stream));
+  }
+  if (base_dir) {   // P M e_dir on the single-column gather
+    const MultiShape s1 = multi_shape(h, 1);
+    std::vector<double> e((size_t)n6, 0.0);
+    for (int64_t i = 0; i < N; ++i)
+      for (int k = 0; k < 3; ++k) e[(size_t)(6 * i + k)] = base_dir[k];
+    if (int rc = multi_upload(h, w, s1, e.data(), s->edir.p, 0)) return rc;
+    if (int rc = launch_mass_multi(h, m, s1, s->edir.p, s->Me.p, true)) return rc;
+    hipLaunchKernelGGL(pl::k_harm_base_load, dim3(grid_stream(n6)), dim3(pl::kBlock), 0, h->stream, n6, (const double *)s->Me.p,
+                       f_dev);
+    PL_HIP(hipGetLastError());
+  }
+  if (!self_adjoint)
+    if (int rc = harm_upload(h, w, 1, out_vec, nullptr, true, l_dev, -1)) return rc;
+  // diag K and diag M, real, once per call
+  MultiOp op;
+  op.mass = m;
+  op.c_K = 1.0; op.c_M = 0.0;
+  if (int rc = launch_dyn_diag(h, op, h->fixedbits.p, hw->diagK.p, nullptr)) return rc;
+  op.c_K = 0.0; op.c_M = 1.0;
+  if (int rc = launch_dyn_diag(h, op, h->fixedbits.p, hw->diagM.p, nullptr)) return rc;
+
+  const bool timing = std::getenv("PL_TIMING") != nullptr;
+  const auto t_begin = std::chrono::steady_clock::now();
+  std::vector<double> coef_all((size_t)4 * n_freq), coef((size_t)4 * per * nb), st((size_t)pl::H_ST_COUNT * per * nb);
+  std::vector<int32_t> its((size_t)2 * n_freq, 0), stat((size_t)2 * n_freq, 0);
+  std::vector<double> rres((size_t)2 * n_freq, 0.0);
+  for (int k = 0; k < n_freq; ++k) {
+    const double wk = omega[k];
+    coef_all[(size_t)4 * k] = 1.0;
+    coef_all[(size_t)4 * k + 1] = wk * ray_k;
+    coef_all[(size_t)4 * k + 2] = -wk * wk;
+    coef_all[(size_t)4 * k + 3] = wk * ray_m;
+  }
+  int bad = 0, filled = 0;
+  for (int f0 = 0; f0 < n_freq; f0 += nb) {
+    const int nf = std::min(nb, n_freq - f0), ncb = per * nf;
+    const MultiShape sh = harm_shape(h, ncb);
+    if (filled != nf) {   // every column block reads its own load: f for the fields, l for the adjoint fields
+      for (int j = 0; j < ncb; ++j)
+        PL_HIP(hipMemcpyAsync(w->F.p + (size_t)j * n12, j < nf ? f_dev : l_dev, (size_t)n12 * sizeof(double),
+                              hipMemcpyDeviceToDevice, h->stream));
+      filled = nf;
+    }
+    for (int q = 0; q < per; ++q)
+      std::memcpy(coef.data() + (size_t)4 * q * nf, coef_all.data() + (size_t)4 * f0, (size_t)4 * nf * sizeof(double));
+    PL_HIP(hipMemcpyAsync(hw->coef.p, coef.data(), (size_t)4 * ncb * sizeof(double), hipMemcpyHostToDevice, h->stream));
+    PL_HIP(hipStreamSynchronize(h->stream));         // (coef is pageable host memory, rewritten by the next pass)
+    const auto t0 = std::chrono::steady_clock::now();
+    int launched = 0;
+    if (int rc = cocg_solve(h, w, hw, m, sh, rtol, max_iter, st.data(), &launched, sh.stride)) return rc;
+    const double ms_pass = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    PL_HIP(hipMemcpyAsync(s->U.p + (size_t)f0 * n12, w->X.p, (size_t)nf * n12 * sizeof(double), hipMemcpyDeviceToDevice, h->stream));
+    if (!self_adjoint)
+      PL_HIP(hipMemcpyAsync(s->L.p + (size_t)f0 * n12, w->X.p + (size_t)nf * n12, (size_t)nf * n12 * sizeof(double),
+                            hipMemcpyDeviceToDevice, h->stream));
+    long pass_iters = 0;
+    for (int j = 0; j < ncb; ++j) {
+      const double rr = st[(size_t)pl::H_ST_RR * ncb + j], bb = st[(size_t)pl::H_ST_BB * ncb + j];
+      const int state = (int)st[(size_t)pl::H_ST_STATE * ncb + j];
+      const size_t o = (size_t)(j / nf) * n_freq + f0 + (j % nf);
+      its[o] = (int32_t)st[(size_t)pl::H_ST_ITER * ncb + j];
+      rres[o] = bb > 0.0 ? std::sqrt(rr / bb) : 0.0;
+      stat[o] = state == 1 ? 0 : (state == 2 ? 2 : 1);
+      if (stat[o] != 0) ++bad;
+      pass_iters += its[o];
+    }
+    if (timing) {
+      std::fprintf(stderr, "[%s] %-28s %10d\n", who, "pass_frequencies", nf);
+      std::fprintf(stderr, "[%s] %-28s %10d\n", who, "pass_column_blocks", ncb);
+      std::fprintf(stderr, "[%s] %-28s %10.4f ms\n", who, "iteration_mean_host_clock", launched > 0 ? ms_pass / launched : 0.0);
+      std::fprintf(stderr, "[%s] %-28s %10.2f\n", who, "iterations_per_solve", (double)pass_iters / ncb);
+    }
+  }
+  if (iters) std::memcpy(iters, its.data(), its.size() * sizeof(int32_t));
+  if (relres) std::memcpy(relres, rres.data(), rres.size() * sizeof(double));
+  if (status) std::memcpy(status, stat.data(), stat.size() * sizeof(int32_t));
+  if (bad) {
+    PL_HIP(hipStreamSynchronize(h->stream));
+    return fail(PL_ERR_NOCONV, "pl_harmonic_sens: " + std::to_string(bad) + " solves ended without convergence (see status)");
+  }
+  // the one host look between the solves and the contraction: y_k from its slots, J and g_k = dJ/dy_k
+  PL_HIP(hipMemsetAsync(s->yslots.p, 0, (size_t)2 * n_freq * pl::kSlots * sizeof(double), h->stream));
+  hipLaunchKernelGGL(pl::k_harm_output, dim3(harm_grid(n6), (unsigned)n_freq), dim3(pl::kBlock), 0, h->stream, n6,
+                     (const double *)l_dev, (const double *)s->U.p, s->yslots.p);
+  PL_HIP(hipGetLastError());
+  std::vector<double> yh((size_t)2 * n_freq), g((size_t)2 * n_freq, 0.0);
+  {
+    std::vector<double> ys((size_t)2 * n_freq * pl::kSlots);
+    PL_HIP(hipMemcpyAsync(ys.data(), s->yslots.p, ys.size() * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+    PL_HIP(hipStreamSynchronize(h->stream));
+    for (int k = 0; k < 2 * n_freq; ++k) {
+      double t = 0.0;
+      for (int q = 0; q < pl::kSlots; ++q) t += ys[(size_t)k * pl::kSlots + q];
+      yh[(size_t)k] = t;
+    }
+  }
+  double Jv = 0.0;
+  auto wt = [&](int k) { return weight ? weight[k] : 1.0; };
+  auto mag = [&](int k) { return std::hypot(yh[(size_t)2 * k], yh[(size_t)2 * k + 1]); };
+  if (kind == 0) {          // J = -sum w Im y, g = i w
+    for (int k = 0; k < n_freq; ++k) { Jv -= wt(k) * yh[(size_t)2 * k + 1]; g[(size_t)2 * k + 1] = wt(k); }
+  } else if (kind == 1) {   // J = 1/2 sum w |y|^2, g = w conj(y)
+    for (int k = 0; k < n_freq; ++k) {
+      const double re = yh[(size_t)2 * k], im = yh[(size_t)2 * k + 1];
+      Jv += wt(k) * (re * re + im * im);
+      g[(size_t)2 * k] = wt(k) * re;
+      g[(size_t)2 * k + 1] = -wt(k) * im;
+    }
+    Jv *= 0.5;
+  } else {                  // scaled by the largest |y|: |y|^p cannot overflow
+    double top = 0.0, sum = 0.0;
+    for (int k = 0; k < n_freq; ++k) top = std::max(top, mag(k));
+    if (top > 0.0)
+      for (int k = 0; k < n_freq; ++k) sum += wt(k) * std::pow(mag(k) / top, p);
+    const double Js = sum > 0.0 ? std::pow(sum, 1.0 / p) : 0.0;
+    Jv = top * Js;
+    if (Js > 0.0)
+      for (int k = 0; k < n_freq; ++k) {
+        const double a = mag(k) / top;
+        const double c = a > 0.0 ? std::pow(Js, 1.0 - p) * wt(k) * std::pow(a, p - 2.0) / top : 0.0;
+        g[(size_t)2 * k] = c * yh[(size_t)2 * k];
+        g[(size_t)2 * k + 1] = -c * yh[(size_t)2 * k + 1];
+      }
+  }
+  if (!std::isfinite(Jv)) return fail(PL_ERR_NAN, "pl_harmonic_sens: the objective is not finite");
+  for (double v : g)
+    if (!std::isfinite(v)) return fail(PL_ERR_NAN, "pl_harmonic_sens: the objective's derivative is not finite");
+  PL_HIP(hipMemcpyAsync(s->coef.p, coef_all.data(), coef_all.size() * sizeof(double), hipMemcpyHostToDevice, h->stream));
+  PL_HIP(hipMemcpyAsync(s->g.p, g.data(), g.size() * sizeof(double), hipMemcpyHostToDevice, h->stream));
+  float ms_sens = 0.0f;
+  if (timing) PL_HIP(hipEventRecord(h->ev0, h->stream));
+  const double sfac = base_dir ? (self_adjoint ? 2.0 : 1.0) : 0.0;
+  if (int rc = launch_harmonic_sens(h, m, s, self_adjoint, n_freq, sfac, base_dir)) return rc;
+  if (timing) {
+    PL_HIP(hipEventRecord(h->ev1, h->stream));
+    PL_HIP(hipEventSynchronize(h->ev1));
+    PL_HIP(hipEventElapsedTime(&ms_sens, h->ev0, h->ev1));
+  }
+  hipLaunchKernelGGL(pl::k_transient_sens_sum, dim3(grid_for(B)), dim3(pl::kBlock), 0, h->stream, B, (const double *)s->acc.p,
+                     s->grad.p);
+  PL_HIP(hipGetLastError());
+  if (int rc = download_struts(h, s->grad.p, dJ_dr)) return rc;   // (its wait covers coef_all and g too)
+  *J = Jv;
+  if (y) std::memcpy(y, yh.data(), yh.size() * sizeof(double));
+  if (timing) {
+    const double ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_begin).count();
+    std::fprintf(stderr, "[%s] %-28s %10.4f ms\n", who, "whole_call_host_clock", ms);
+    std::fprintf(stderr, "[%s] %-28s %10.4f ms\n", who, "k_harmonic_sens", (double)ms_sens);
+    std::fprintf(stderr, "[%s] %-28s %10.2f %%\n", who, "k_harmonic_sens_share", 100.0 * ms_sens / ms);
+  }
   return PL_OK;
 }
 

@@ -281,6 +281,7 @@ struct pl_context {
   std::shared_ptr<void> dyn_ws;     // state, loads and histories of pl_transient (pl_dyn.h), created by the first call
   std::shared_ptr<void> dyn_sens_ws;   // histories and adjoint state of pl_transient_sens (pl_dyn_sens.h), likewise
   std::shared_ptr<void> harm_ws;    // diagonals, coefficients, scalars and probes of pl_harmonic (pl_harm.h), likewise
+  std::shared_ptr<void> harm_sens_ws;   // kept fields and contraction data of pl_harmonic_sens (pl_harm_sens.h), likewise
   // pl_stress / pl_stress_pnorm (pl_stress.h), allocated by the first call: per-station sigma_vm [B][4], block partials of the
   // two reductions, (sigma_max, p-sum, Phi_p), per-strut dPhi/d(du, dth) [B][6] and dPhi/dr [B]
   // (pl_buckling / pl_buckling_pnorm, pl_buckling.h, use the same arrays: st_vm4 as [4][B] with beta, N, N_cr in rows 0..2)

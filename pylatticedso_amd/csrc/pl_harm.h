@@ -124,16 +124,19 @@ __device__ __forceinline__ Cplx harm_dinv(const double *__restrict__ diagK, cons
   return cdiv({1.0, 0.0}, d);
 }
 
-// r = P f ; z = r / d ; p = z ; x = 0 ; rho = r^T z ; bb = ||r||^2.  The load f [6N] complex is the same for every frequency.
+// r = P f ; z = r / d ; p = z ; x = 0 ; rho = r^T z ; bb = ||r||^2.  The load of column block cb is f + cb * fstride, [6N] complex:
+// fstride = 0 gives every frequency the same load (pl_harmonic), pl_harmonic_sens gives every block its own.
 __global__ __launch_bounds__(kBlock) void k_harm_init(int64_t n6, const double *__restrict__ f,
                                                       const uint8_t *__restrict__ fixedbits,
                                                       const double *__restrict__ diagK, const double *__restrict__ diagM,
                                                       const double *__restrict__ coef, double *__restrict__ x,
                                                       double *__restrict__ r, double *__restrict__ z, double *__restrict__ p,
-                                                      double *__restrict__ set0, double *__restrict__ bb, int nf, int64_t stride) {
+                                                      double *__restrict__ set0, double *__restrict__ bb, int nf, int64_t stride,
+                                                      int64_t fstride) {
   __shared__ double red[3][kBlock / kWave];
   const int cb = blockIdx.y;
   const size_t off = (size_t)cb * stride;
+  f += (size_t)cb * fstride;
   const Cplx cK = {coef[4 * cb], coef[4 * cb + 1]}, cM = {coef[4 * cb + 2], coef[4 * cb + 3]};
   double s[3] = {0.0, 0.0, 0.0};
   for (int64_t e = (int64_t)blockIdx.x * kBlock + threadIdx.x; e < n6; e += (int64_t)gridDim.x * kBlock) {
@@ -429,10 +432,11 @@ int harm_iteration(pl_context *c, MultiWs *w, HarmWs *hw, const MassWs *m, const
 }
 
 // A(w_cb) u_cb = f on the free dofs for the frequencies of the pass: hw->coef holds their coefficients, hw->diagK / diagM the
-// real diagonals, w->F the load (one complex vector, 0 on fixed dofs); w->X receives the fields (0 on fixed dofs).
+// real diagonals, w->F the load (0 on fixed dofs: one complex vector with fstride = 0, one per column block with fstride =
+// s.stride); w->X receives the fields (0 on fixed dofs).
 // status_host[H_ST_COUNT][ncb].  The host looks at the status block every check_every iterations; nothing else drains the stream.
 int cocg_solve(pl_context *c, MultiWs *w, HarmWs *hw, const MassWs *m, const MultiShape &s, double rtol, int max_iter,
-               double *status_host, int *launched) {
+               double *status_host, int *launched, int64_t fstride = 0) {
   const int64_t n6 = c->N * 6;
   const int nf = s.ncb;
   const HarmScal q = harm_scal(hw, nf);
@@ -441,7 +445,7 @@ int cocg_solve(pl_context *c, MultiWs *w, HarmWs *hw, const MassWs *m, const Mul
   const dim3 g(harm_grid(n6), (unsigned)nf);
   hipLaunchKernelGGL(pl::k_harm_init, g, dim3(pl::kBlock), 0, c->stream, n6, (const double *)w->F.p, (const uint8_t *)c->fixedbits.p,
                      (const double *)hw->diagK.p, (const double *)hw->diagM.p, (const double *)hw->coef.p, w->X.p, w->R.p, w->Z.p,
-                     w->P.p, q.set[0], q.bb, nf, s.stride);
+                     w->P.p, q.set[0], q.bb, nf, s.stride, fstride);
   hipLaunchKernelGGL(pl::k_harm_begin, dim3((unsigned)nf), dim3(pl::kWave), 0, c->stream, nf, rtol, (const double *)q.bb, q.thresh,
                      q.status, q.flag[0]);
   PL_HIP(hipGetLastError());

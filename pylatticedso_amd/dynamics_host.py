@@ -329,3 +329,113 @@ def harmonic(K, M, fixed, omegas, f, ray_m=0.0, ray_k=0.0, solver=None):
         out["iterations"] = np.array([c[0] for c in counts[n0:]], int)
         out["status"] = np.array([c[1] for c in counts[n0:]], int)
     return out
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# Radius sensitivities of the frequency response (csrc/pl_harm_sens.h, pl_harmonic_sens)
+# ---------------------------------------------------------------------------------------------------------------------
+def harmonic_objective(y, kind, p=8.0, weight=None):
+    """(J, g) with g_k = dJ/dy_k in the sense dJ = sum_k Re(g_k dy_k), for the complex outputs y (n_freq,) and weights w >= 0
+    (None = 1): kind 0: J = -sum w Im y (g = i w), 1: J = 1/2 sum w |y|^2 (g = w conj(y)), 2: J = (sum w |y|^p)^(1/p), p >= 2
+    (g = J^(1-p) w |y|^(p-2) conj(y), 0 where J = 0)."""
+    y = np.asarray(y, complex).reshape(-1)
+    w = np.ones(y.size) if weight is None else np.asarray(weight, float).reshape(-1)
+    if w.shape != y.shape or not np.isfinite(w).all() or (w < 0.0).any():
+        raise ValueError("weight must have one finite entry per frequency and must not be negative")
+    if kind == 0:
+        return -float(w @ y.imag), 1j * w
+    if kind == 1:
+        return 0.5 * float(w @ (np.abs(y) ** 2)), w * np.conj(y)
+    if kind == 2:
+        if not (p >= 2.0 and np.isfinite(p)):
+            raise ValueError("p must be at least 2")
+        # scaled by the largest |y|: no overflow of |y|^p
+        top = float(np.abs(y).max())
+        if top == 0.0:
+            return 0.0, np.zeros_like(y)
+        s = np.abs(y) / top
+        Js = float(w @ s ** p) ** (1.0 / p)
+        if Js == 0.0:
+            return 0.0, np.zeros_like(y)
+        c = np.where(s > 0.0, Js ** (1.0 - p) * w * np.where(s > 0.0, s, 1.0) ** (p - 2.0) / top, 0.0)
+        return top * Js, c * np.conj(y)
+    raise ValueError("kind must be 0, 1 or 2")
+
+
+def harmonic_sensitivity(K, M, fixed, conn, drec_dr, dM_dr, omegas, f=None, out_vec=None, kind=2, p=8.0, weight=None,
+                         base_dir=None, ray_m=0.0, ray_k=0.0, solver=None):
+    """What pl_harmonic_sens computes: J of the outputs y_k = l^T u_k (unconjugated) of ``harmonic`` and dJ/dr_b at fixed
+    segment geometry (discretise, then differentiate).
+
+    conn (B, 2), drec_dr (B, 8) the radius derivative of the condensed records (stress_host.drecords_dr) and dM_dr
+    (B, 12, 12) that of the mass elements (mass_host.delement_matrix_dr) give dK_e/dr_b and dM_e/dr_b.  f (6N,) or (N, 6),
+    real or complex, is a dead load (None = 0); base_dir (3,) adds the load -M e_dir of a base shaken with unit acceleration,
+    e_dir the rigid translation of ALL nodes: the only load that follows the design.  out_vec = l (6N,) or (N, 6) real, read
+    with the fixed dofs zeroed; None: l is the whole load.  Point masses have no derivative.
+
+    A_k = c_K K + c_M M is complex symmetric, so A_k lam_k = l has the matrix of the forward solve and
+        dy_k/dr_b = -[c_K lam_e^T dK_e u_e + c_M lam_e^T dM_e u_e + s lam_e^T dM_e e_dir,e]        s = 1 with base_dir, else 0
+    (out_vec = None: lam_k = u_k, no second solve, and s = 2: l follows the design too);  dJ/dr_b = sum_k Re(g_k dy_k/dr_b)
+    with (J, g) = ``harmonic_objective``.  Returns a dict: J, y (n_freq,) complex, dJ_dr (B,), dy_dr (n_freq, B) complex,
+    lam (n_freq, N, 6) complex, u (n_freq, N, 6) complex; with a ``jacobi_cocg`` solver also iterations and status
+    (2, n_freq) = forward, adjoint (zeros with out_vec = None)."""
+    from . import geometric_host as GH
+    w, cK, cM = harmonic_coefficients(omegas, ray_m, ray_k)
+    fx = np.asarray(fixed).reshape(-1) != 0
+    n6 = fx.size
+    N = n6 // 6
+    M = sp.csr_matrix(M)
+    if f is None and base_dir is None:
+        raise ValueError("neither a load nor base_dir")
+    load = np.zeros(n6, complex) if f is None else np.asarray(f, complex).reshape(-1).copy()
+    if load.size != n6:
+        raise ValueError(f"f must have {n6} entries")
+    e_dir = np.zeros((N, 6))
+    s = 0.0
+    if base_dir is not None:
+        e_dir[:, :3] = np.asarray(base_dir, float).reshape(3)
+        load = load - M @ e_dir.reshape(-1)
+        s = 1.0
+    load[fx] = 0.0
+    fwd = harmonic(K, M, fixed, w, load, ray_m, ray_k, solver)
+    U = fwd["u"]
+    its = np.zeros((2, w.size), int)
+    sts = np.zeros((2, w.size), int)
+    if "iterations" in fwd:
+        its[0], sts[0] = fwd["iterations"], fwd["status"]
+    if out_vec is None:
+        l = load
+        lam = U
+        s *= 2.0
+    else:
+        l = np.asarray(out_vec, float).reshape(-1)
+        if l.size != n6:
+            raise ValueError(f"out_vec must have {n6} entries")
+        l = np.where(fx, 0.0, l)
+        adj = harmonic(K, M, fixed, w, l, ray_m, ray_k, solver)
+        lam = adj["u"]
+        if "iterations" in adj:
+            its[1], sts[1] = adj["iterations"], adj["status"]
+    y = U.reshape(w.size, n6) @ l
+    J, g = harmonic_objective(y, kind, p, weight)
+
+    conn = np.asarray(conn).reshape(-1, 2)
+    drec = np.asarray(drec_dr, float).reshape(-1, 8)
+    dM = np.asarray(dM_dr, float).reshape(-1, 12, 12)
+    ia, ib = conn[:, 0], conn[:, 1]
+    ee = np.concatenate([e_dir[ia], e_dir[ib]], axis=1)
+    dy = np.zeros((w.size, len(conn)), complex)
+    for k in range(w.size):
+        u, la = U[k], lam[k]
+        qK = (GH._pairing(drec, conn, u.real, la.real) - GH._pairing(drec, conn, u.imag, la.imag)
+              + 1j * (GH._pairing(drec, conn, u.imag, la.real) + GH._pairing(drec, conn, u.real, la.imag)))
+        ue = np.concatenate([u[ia], u[ib]], axis=1)
+        le = np.concatenate([la[ia], la[ib]], axis=1)
+        qM = np.einsum("bi,bij,bj->b", le, dM, ue)
+        qE = np.einsum("bi,bij,bj->b", le, dM, ee)
+        dy[k] = -(cK[k] * qK + cM[k] * qM + s * qE)
+    grad = (g[:, None] * dy).real.sum(axis=0)
+    out = {"J": J, "y": y, "dJ_dr": grad, "dy_dr": dy, "lam": lam, "u": U, "g": g}
+    if "iterations" in fwd:
+        out["iterations"], out["status"] = its, sts
+    return out

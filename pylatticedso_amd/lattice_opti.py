@@ -72,6 +72,9 @@ class LatticeOpti(LatticeSim):
         if self._ddm_mode and "peak_displacement" in (info.get("constraints") or {}):
             raise NotImplementedError('the "peak_displacement" constraint needs simulation_type "FEM": the transient response '
                                       "of the recovered interiors of DDM cells is not implemented")
+        if self._ddm_mode and "resonance_peak" in (info.get("constraints") or {}):
+            raise NotImplementedError('the "resonance_peak" constraint needs simulation_type "FEM": the frequency response '
+                                      "of the recovered interiors of DDM cells is not implemented")
         comp = ((params.get("simulation_parameters", {}).get("DDM") or {}).get("schur_complement_computation") or {})
         if ddm_gradient is None:
             ddm_gradient = comp.get("gradient", "finite_difference") if self._ddm_mode else "finite_difference"
@@ -122,6 +125,10 @@ class LatticeOpti(LatticeSim):
         self._peak_cache = None             # (parameters, aggregate): the value and the gradient of one design share one call
         if "peak_displacement" in self.constraints_dict:
             self._history["peak_displacement"] = []
+        self._last_resonance_peak = None
+        self._resonance_cache = None        # (parameters, aggregate), as _peak_cache
+        if "resonance_peak" in self.constraints_dict:
+            self._history["resonance_peak"] = []
         self._set_number_parameters_optimization()
         # strut -> (cell, type) of the LAST cell that holds it: Cell.change_beam_radius (cell.py:896-917) is called
         # cell after cell, so a strut shared by several cells ends with the last one's radius
@@ -790,6 +797,41 @@ class LatticeOpti(LatticeSim):
         self._equilibrium_at(r)
         return self._strut_gradient_to_parameters(self.peak_displacement_aggregate()[2]) / self._peak_displacement_settings()[0]
 
+    # -- resonance peak constraint (FEM mode): p-norm over a band of one output of the frequency response, pl_harmonic_sens ---------
+    def _resonance_peak_settings(self):
+        c = self.constraints_dict["resonance_peak"]
+        run = dict(frequencies_hz=np.asarray(c["frequencies_hz"], float).reshape(-1), density=float(c["density"]),
+                   damping=tuple(c.get("damping", (0.0, 0.0))), base_acceleration=c.get("base_acceleration", None),
+                   rotary=bool(c.get("rotary", True)), node_mass=c.get("node_mass", None))
+        kw = {k: c[k] for k in ("rtol", "max_iter") if k in c}
+        return float(c["max_amplitude"]), run, kw, c.get("output", None), float(c.get("p", 8))
+
+    def resonance_peak_aggregate(self):
+        """(J_p, max_k |y_k|, dJ/dr_b) of the current design over the constraint's frequencies: y_k = l^T u_k the output at
+        frequency k, J_p = (sum_k |y_k|^p)^(1/p) >= max_k |y_k|.  One pl_harmonic_sens call gives all three (the fields and
+        the adjoint fields in the same passes); the value and the gradient of one design share it."""
+        key = tuple(map(float, self.actual_optimization_parameters)) if len(self.actual_optimization_parameters) else None
+        if self._resonance_cache is not None and key is not None and self._resonance_cache[0] == key:
+            return self._resonance_cache[1]
+        _, run, kw, output, p = self._resonance_peak_settings()
+        self._dynamics_guard("resonance_peak")
+        self._frf_settings = self._frf_setup(kw=kw, **run)
+        out = self.frequency_response_sensitivity(output, kind=2, p=p)
+        res = (out["J"], float(np.abs(out["y"]).max()), out["dJ_dr"])
+        self._last_resonance_peak = res[:2]
+        self._resonance_cache = (key, res)
+        return res
+
+    def resonance_peak_constraint(self, r):
+        """J_p / max_amplitude - 1 (<= 0 when feasible: J_p >= max_k |y_k|, so the peak stays below max_amplitude then)."""
+        self._equilibrium_at(r)
+        return self.resonance_peak_aggregate()[0] / self._resonance_peak_settings()[0] - 1.0
+
+    def resonance_peak_constraint_gradient(self, r):
+        """d(resonance_peak_constraint)/d(theta): dJ/dr_b / max_amplitude through _strut_gradient_to_parameters."""
+        self._equilibrium_at(r)
+        return self._strut_gradient_to_parameters(self.resonance_peak_aggregate()[2]) / self._resonance_peak_settings()[0]
+
     # -- driver (SciPy SLSQP, as the reference) ---------------------------------------------------------------------
     def _initialize_optimization_solver(self):
         from scipy.optimize import Bounds
@@ -826,6 +868,9 @@ class LatticeOpti(LatticeSim):
         if "peak_displacement" in self._history:
             self._history["peak_displacement"].append(None if self._last_peak_displacement is None
                                                       else self._last_peak_displacement[1])
+        if "resonance_peak" in self._history:
+            self._history["resonance_peak"].append(None if self._last_resonance_peak is None
+                                                   else self._last_resonance_peak[1])
         self._history["parameters"].append(list(map(float, r)))
         self._history["timestamp"].append(time.time())
 
@@ -857,6 +902,9 @@ class LatticeOpti(LatticeSim):
         if "peak_displacement" in self.constraints_dict:
             jac = {"jac": self.peak_displacement_constraint_gradient} if self.enable_gradient_computing else {}
             self.constraints.append(NonlinearConstraint(self.peak_displacement_constraint, -np.inf, 0.0, **jac))
+        if "resonance_peak" in self.constraints_dict:
+            jac = {"jac": self.resonance_peak_constraint_gradient} if self.enable_gradient_computing else {}
+            self.constraints.append(NonlinearConstraint(self.resonance_peak_constraint, -np.inf, 0.0, **jac))
         kw = dict(fun=self.objective, x0=self.initial_parameters, method="SLSQP", bounds=self.bounds,
                   constraints=self.constraints, callback=self.callback_function,
                   options={"maxiter": self.optim_max_iteration, "ftol": self.optim_ftol, "disp": self.optim_disp,

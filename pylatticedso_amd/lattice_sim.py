@@ -858,6 +858,7 @@ class LatticeSim(LatticeViews):
         self.frf_frequency, self.frf_probe = hz, out["probe"]
         self.frf_power, self.frf_iterations = out["power"], out["iters"]
         self._frf_probes = probes
+        self._frf_settings = self._frf_setup(hz, density, damping, base_acceleration, rotary, node_mass, kw)
         # a base moving with x_b e^{iwt}, -w^2 x_b = 1: absolute over base displacement, e_direction - w^2 u (the rigid
         # value e_direction at w = 0)
         self.frf_transmissibility = None
@@ -865,6 +866,48 @@ class LatticeSim(LatticeViews):
             w2 = (2.0 * np.pi * hz) ** 2
             self.frf_transmissibility = direction[None, None, :] - w2[:, None, None] * out["probe"][:, :, :3]
         return out
+
+    def _frf_setup(self, frequencies_hz, density, damping, base_acceleration, rotary, node_mass, kw):
+        """The settings of a ``frequency_response`` as a dict: what ``frequency_response_sensitivity`` runs again.  The load
+        is the force set of the last solve, or (base_acceleration: a direction (3,) or an axis 0 / 1 / 2) that of a base
+        shaken with unit acceleration, which the device forms itself because it follows the design."""
+        n = self.lattice.n_nodes
+        load = direction = None
+        if base_acceleration is None:
+            load = np.zeros((n, 6))
+            load[:, :3] = np.asarray(self.applied_force)[:n, :3]      # (only the translational components are loads)
+        else:
+            direction = (np.eye(3)[int(base_acceleration)] if np.ndim(base_acceleration) == 0
+                         else np.asarray(base_acceleration, float).reshape(3))
+        return dict(hz=np.atleast_1d(np.asarray(frequencies_hz, float)).reshape(-1), density=density, rotary=rotary,
+                    node_mass=node_mass, damping=(float(damping[0]), float(damping[1])), load=load, base_dir=direction,
+                    run={q: kw[q] for q in ("rtol", "max_iter", "block") if q in kw})
+
+    def frequency_response_sensitivity(self, output=None, kind=2, p=8, weight=None):
+        """Radius derivatives of an objective of the last ``frequency_response``, on the device (pl_harmonic_sens: the sweep
+        again with the same frequencies, density, load or base acceleration, damping and solver settings, the adjoint fields
+        in the same passes).  One complex output per frequency y_k = l^T u_k: ``output`` is l as an (n_nodes, 6) array, a
+        (node, dof) pair, or None = the load itself (the dynamic compliance: no second solve).  J of the outputs with the
+        weights ``weight`` (n_freq,) or None = 1: kind 0 -sum w Im y, 1 1/2 sum w |y|^2, 2 (sum w |y|^p)^(1/p) >= max |y| for
+        w = 1.  Returns a dict with J, y (n_freq,) complex and dJ_dr (n_beams,) at fixed segment geometry, plus iters, relres
+        and status (2, n_freq) of the forward and the adjoint solves."""
+        if getattr(self, "_compat_rows", False) or self.domain_decomposition_solver:
+            raise NotImplementedError("frequency_response_sensitivity: the default strut model on a FEM lattice only (no "
+                                      "reference_compat rows, no domain decomposition)")
+        s = getattr(self, "_frf_settings", None)
+        if s is None or self._device is None:
+            raise RuntimeError("frequency_response_sensitivity needs a frequency_response on this lattice first")
+        n = self.lattice.n_nodes
+        if output is None:
+            l = None
+        elif np.ndim(output) == 1 and np.size(output) == 2:
+            l = np.zeros((n, 6))
+            l[int(output[0]), int(output[1])] = 1.0
+        else:
+            l = np.asarray(output, float).reshape(n, 6)
+        self._device.set_mass(s["density"], s["rotary"], s["node_mass"])
+        return self._device.harmonic_sens(2.0 * np.pi * s["hz"], s["load"], l, kind, p, weight, s["base_dir"],
+                                          ray_m=s["damping"][0], ray_k=s["damping"][1], **s["run"])
 
     def dynamic_stiffness_peaks(self):
         """The resonance peaks of the last ``frequency_response``: for every probe the local maxima of |u| over the
