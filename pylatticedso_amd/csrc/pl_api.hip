@@ -13,6 +13,7 @@
 #include "pl_harm.h"
 #include "pl_dyn_sens.h"
 #include "pl_harm_sens.h"
+#include "pl_objective.h"
 #include "pl_sensgram.h"
 
 
@@ -1611,13 +1612,18 @@ struct EventTimer {
     if (n < 2 || hipEventSynchronize(ev[n - 1]) != hipSuccess) return;
     for (int i = 0; i + 1 < n; ++i) {
       float ms = 0.f;
-      if (hipEventElapsedTime(&ms, ev[i], ev[i + 1]) == hipSuccess)
-        std::fprintf(stderr, "[%s] %-28s %10.4f ms\n", who, stage[i], (double)ms);
+      if (hipEventElapsedTime(&ms, ev[i], ev[i + 1]) == hipSuccess) timing_ms(who, stage[i], (double)ms);
     }
   }
   void stop() {   // closes the running stage and prints
     mark();
     report();
+  }
+  double lap() {  // closes the running stage and returns its time, for a caller that adds laps up and prints the sum itself
+    mark();
+    float ms = 0.f;
+    if (n >= 2 && hipEventSynchronize(ev[n - 1]) == hipSuccess) (void)hipEventElapsedTime(&ms, ev[n - 2], ev[n - 1]);
+    return ms;
   }
   ~EventTimer() {
     for (int i = 0; i < n; ++i) (void)hipEventDestroy(ev[i]);
@@ -2423,12 +2429,10 @@ int transient_check(pl_handle h, const std::string &who, const TransientRun &a) 
   if (!(a.gamma >= 0.5) || !std::isfinite(a.gamma)) return fail(PL_ERR_ARG, who + ": gamma must be at least 1/2");
   if (!(a.beta >= 0.25 * (0.5 + a.gamma) * (0.5 + a.gamma)) || !std::isfinite(a.beta))
     return fail(PL_ERR_ARG, who + ": beta must be at least (1/2 + gamma)^2 / 4 (unconditionally stable schemes only)");
-  if (!(a.ray_m >= 0.0) || !(a.ray_k >= 0.0) || !std::isfinite(a.ray_m) || !std::isfinite(a.ray_k))
-    return fail(PL_ERR_ARG, who + ": the Rayleigh coefficients must be finite and not negative");
+  if (int rc = check_rayleigh(who, a.ray_m, a.ray_k)) return rc;
   if (a.n_pat < 0 || a.n_pat > 4) return fail(PL_ERR_ARG, who + ": n_pat must be 0 ... 4");
   if (a.n_pat > 0 && (!a.pattern || !a.amp)) return fail(PL_ERR_ARG, who + ": n_pat > 0 needs pattern and amp");
-  if (!(a.rtol > 0.0) || a.max_iter <= 0) return fail(PL_ERR_ARG, who + ": rtol and max_iter must be positive");
-  return PL_OK;
+  return check_solve(who, a.rtol, a.max_iter);
 }
 
 // the handle checks, the mass records of the current radii, and supports held at zero: prescribed values are refused
@@ -2454,8 +2458,8 @@ struct TransientClock {              // what the PL_TIMING lines of the callers 
 int transient_forward(pl_handle h, const char *who, MassWs *m, const TransientRun &a, const std::vector<int32_t> &slot_of,
                       int n_slot, int snap_every, int n_snap, int32_t *iters, const DynHistory *hist, MultiWs **w_out,
                       DynWs **d_out, TransientClock *clk) {
-  const int32_t n_steps = a.n_steps, n_pat = a.n_pat, max_iter = a.max_iter;
-  const double dt = a.dt, beta = a.beta, gamma = a.gamma, ray_m = a.ray_m, ray_k = a.ray_k, rtol = a.rtol;
+  const int32_t n_steps = a.n_steps, n_pat = a.n_pat;
+  const double dt = a.dt, beta = a.beta, gamma = a.gamma, ray_m = a.ray_m, ray_k = a.ray_k;
   const double *pattern = a.pattern, *amp = a.amp, *u0 = a.u0, *v0 = a.v0;
   const int64_t N = h->N, n6 = N * 6;
   const int rows = n_steps + 1;
@@ -2493,13 +2497,8 @@ int transient_forward(pl_handle h, const char *who, MassWs *m, const TransientRu
   }
   if (n_pat > 0)
     if (int rc = multi_upload(h, w, sp, pattern, d->pattern.p, -1)) return rc;
-  if (base) {   // P M e_dir on the single-column gather; its amplitude column carries -a_g
-    std::vector<double> e((size_t)n6, 0.0);
-    for (int64_t i = 0; i < N; ++i)
-      for (int k = 0; k < 3; ++k) e[(size_t)(6 * i + k)] = hist->base_dir[k];
-    if (int rc = multi_upload(h, w, s1, e.data(), hist->s->edir.p, 0)) return rc;
-    if (int rc = launch_mass_multi(h, m, s1, hist->s->edir.p, d->pattern.p + (size_t)n_pat * n6, true)) return rc;
-  }
+  if (base)     // P M e_dir behind the caller's patterns; its amplitude column carries -a_g
+    if (int rc = base_load(h, w, m, hist->base_dir, hist->s->edir.p, d->pattern.p + (size_t)n_pat * n6)) return rc;
   if (n_pat_dev > 0)
     PL_HIP(hipMemcpyAsync(d->amp.p, amp, (size_t)rows * n_pat_dev * sizeof(double), hipMemcpyHostToDevice, h->stream));
   if (hist) {
@@ -2512,11 +2511,8 @@ int transient_forward(pl_handle h, const char *who, MassWs *m, const TransientRu
   PL_HIP(hipMemsetAsync(d->energy.p, 0, (size_t)rows * pl::DYN_E_COUNT * pl::kSlots * sizeof(double), h->stream));
   PL_HIP(hipMemsetAsync(w->UB.p, 0, (size_t)n6 * sizeof(double), h->stream));      // zero prescribed values in every solve
 
-  const auto t_begin = std::chrono::steady_clock::now();
-  double ms_solve = 0.0;
-  long total_iters = 0;
+  clk->t_begin = std::chrono::steady_clock::now();
   const dim3 gs(grid_stream(n6));
-  std::vector<double> status((size_t)pl::M_ST_COUNT * s1.ncol);
   MultiOp op;
   op.mass = m;
   // K and M on the state, then the energies of row erow; form: the predictors, the load of row erow + 1 and the right-hand side
@@ -2536,18 +2532,12 @@ int transient_forward(pl_handle h, const char *who, MassWs *m, const TransientRu
     op.c_M = 1.0 + gamma * q.dt * ray_m;
     op.c_K = beta * q.dt * q.dt + gamma * q.dt * ray_k;
     if (int rc = products_and_predict(q, true, row - 1)) return rc;
-    const auto t0 = std::chrono::steady_clock::now();
-    if (int rc = pcg_solve_multi(h, w, s1, h->fixedbits.p, w->F.p, rtol, max_iter, status.data(), op)) return rc;
-    ms_solve += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-    const double rr = status[pl::M_ST_RR * s1.ncol], bb = status[pl::M_ST_BB * s1.ncol];
-    const int its = (int)status[pl::M_ST_ITER * s1.ncol];
-    total_iters += its;
+    int its = 0;
+    const int rc = transient_solve(h, w, op, a.rtol, a.max_iter, who, hist ? "the forward solve of step" : "the solve of step", row,
+                                   &its, &clk->ms_solve);
+    clk->total_iters += its;
     if (iters) iters[row] = its;
-    if (!std::isfinite(rr) || !std::isfinite(bb))
-      return fail(PL_ERR_NAN, std::string(who) + ": NaN/Inf in a residual norm of step " + std::to_string(row));
-    if (!(rr <= rtol * rtol * bb))
-      return fail(PL_ERR_NOCONV, std::string(who) + (hist ? ": the forward solve of step " : ": the solve of step ") +
-                                     std::to_string(row) + " did not reach rtol within max_iter");
+    if (rc) return rc;
     double *snap = nullptr;
     if (n_snap > 0 && row > 0 && row % snap_every == 0) snap = d->snaps.p + (size_t)(row / snap_every - 1) * n6;
     hipLaunchKernelGGL(pl::k_newmark_correct, gs, dim3(pl::kBlock), 0, h->stream, n6, (const double *)d->ut.p,
@@ -2567,9 +2557,6 @@ int transient_forward(pl_handle h, const char *who, MassWs *m, const TransientRu
     const pl::NewmarkCoef q = {dt, beta, gamma, ray_m, ray_k};
     if (int rc = products_and_predict(q, false, n_steps)) return rc;
   }
-  clk->t_begin = t_begin;
-  clk->ms_solve = ms_solve;
-  clk->total_iters = total_iters;
   *w_out = w;
   *d_out = d;
   return PL_OK;
@@ -2585,21 +2572,13 @@ int pl_transient(pl_handle h, int32_t n_steps, double dt, double beta, double ga
   if (int rc = transient_check(h, who, a)) return rc;
   if (n_probe < 0 || (n_probe > 0 && (!probe_nodes || !probe))) return fail(PL_ERR_ARG, "pl_transient: n_probe > 0 needs probe_nodes and probe");
   if (snap_every < 0 || (snaps && snap_every < 1)) return fail(PL_ERR_ARG, "pl_transient: snaps needs snap_every >= 1");
-  const int64_t N = h->N, n6 = N * 6;
-  for (int i = 0; i < n_probe; ++i)
-    if (probe_nodes[i] < 0 || probe_nodes[i] >= N) return fail(PL_ERR_ARG, "pl_transient: probe node index out of range");
+  if (int rc = check_probes(who, n_probe, probe_nodes, h->N)) return rc;
   MassWs *m = nullptr;
   if (int rc = transient_begin(h, who, &m)) return rc;
-  const int rows = n_steps + 1;
+  const int64_t n6 = h->N * 6;
+  std::vector<int32_t> slot_of, probe_to_slot;
+  const int rows = n_steps + 1, n_slot = probe_map(h, n_probe, probe_nodes, slot_of, probe_to_slot);
   const int n_snap = snaps ? n_steps / snap_every : 0;
-  // the probed nodes, each once: slot of the node in the device's probe block
-  std::vector<int32_t> slot_of((size_t)N, -1), probe_to_slot((size_t)n_probe);
-  int n_slot = 0;
-  for (int i = 0; i < n_probe; ++i) {
-    const int64_t di = h->iperm[probe_nodes[i]];
-    if (slot_of[(size_t)di] < 0) slot_of[(size_t)di] = n_slot++;
-    probe_to_slot[(size_t)i] = slot_of[(size_t)di];
-  }
   MultiWs *w = nullptr;
   DynWs *d = nullptr;
   TransientClock clk;
@@ -2607,17 +2586,9 @@ int pl_transient(pl_handle h, int32_t n_steps, double dt, double beta, double ga
   const MultiShape s4 = {3, 4, 1, 4, n6 * 4};
   // histories come down once
   if (energy) {
-    std::vector<double> eh((size_t)rows * pl::DYN_E_COUNT * pl::kSlots);
-    PL_HIP(hipMemcpyAsync(eh.data(), d->energy.p, eh.size() * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-    PL_HIP(hipStreamSynchronize(h->stream));
-    double work = 0.0;
-    for (int r = 0; r < rows; ++r)
-      for (int k = 0; k < pl::DYN_E_COUNT; ++k) {
-        double t = 0.0;
-        for (int q = 0; q < pl::kSlots; ++q) t += eh[((size_t)r * pl::DYN_E_COUNT + k) * pl::kSlots + q];
-        if (k == pl::DYN_E_WORK) t = (work += t);
-        energy[(size_t)r * 3 + k] = t;
-      }
+    const size_t ne = pl::DYN_E_COUNT;
+    if (int rc = download_slot_sums(h, d->energy.p, rows * ne, energy)) return rc;
+    for (int r = 1; r < rows; ++r) energy[r * ne + pl::DYN_E_WORK] += energy[(r - 1) * ne + pl::DYN_E_WORK];   // the work done so far
   }
   if (n_probe > 0) {
     std::vector<double> ph((size_t)rows * 18 * n_slot);
@@ -2634,11 +2605,11 @@ int pl_transient(pl_handle h, int32_t n_steps, double dt, double beta, double ga
   if (std::getenv("PL_TIMING") != nullptr) {
     PL_HIP(hipStreamSynchronize(h->stream));
     const double ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - clk.t_begin).count();
-    std::fprintf(stderr, "[%s] %-28s %10.4f ms\n", who, "whole_call_host_clock", ms);
-    std::fprintf(stderr, "[%s] %-28s %10d\n", who, "steps", (int)n_steps);
-    std::fprintf(stderr, "[%s] %-28s %10.4f ms\n", who, "step_mean_host_clock", ms / rows);
-    std::fprintf(stderr, "[%s] %-28s %10.4f ms\n", who, "inner_solve_mean_host_clock", clk.ms_solve / rows);
-    std::fprintf(stderr, "[%s] %-28s %10.2f\n", who, "iterations_per_step", (double)clk.total_iters / rows);
+    timing_ms(who, "whole_call_host_clock", ms);
+    timing_count(who, "steps", (int)n_steps);
+    timing_ms(who, "step_mean_host_clock", ms / rows);
+    timing_ms(who, "inner_solve_mean_host_clock", clk.ms_solve / rows);
+    timing_mean(who, "iterations_per_step", (double)clk.total_iters / rows);
   }
   return PL_OK;
 }
@@ -2651,17 +2622,13 @@ int pl_transient_sens(pl_handle h, int32_t n_steps, double dt, double beta, doub
   TransientRun a = {n_steps, dt, beta, gamma, ray_m, ray_k, n_pat, pattern, amp, u0, v0, rtol, max_iter};
   if (int rc = transient_check(h, who, a)) return rc;
   if (!out_vec || !J || !dJ_dr) return fail(PL_ERR_ARG, "pl_transient_sens: out_vec, J and dJ_dr must not be NULL");
-  if (kind < 0 || kind > 2) return fail(PL_ERR_ARG, "pl_transient_sens: kind must be 0, 1 or 2");
-  if (kind == 2 && !(p >= 2.0 && std::isfinite(p))) return fail(PL_ERR_ARG, "pl_transient_sens: p must be at least 2 (and finite)");
+  if (int rc = check_kind(who, kind, p)) return rc;
   if (base_dir && !base_acc) return fail(PL_ERR_ARG, "pl_transient_sens: base_dir needs base_acc");
   const int rows = n_steps + 1;
-  if (weight)
-    for (int n = 0; n < rows; ++n)
-      if (!(weight[n] >= 0.0) || !std::isfinite(weight[n]))
-        return fail(PL_ERR_ARG, "pl_transient_sens: the weights must be finite and not negative");
+  if (int rc = check_weights(who, weight, rows)) return rc;
   MassWs *m = nullptr;
   if (int rc = transient_begin(h, who, &m)) return rc;
-  const int64_t N = h->N, n6 = N * 6, B = h->B;
+  const int64_t n6 = h->N * 6, B = h->B;
   if (!h->dyn_sens_ws) h->dyn_sens_ws = std::make_shared<DynSensWs>();
   DynSensWs *s = static_cast<DynSensWs *>(h->dyn_sens_ws.get());
   PL_HIP(dyn_grow(s->wK, (size_t)rows * n6));
@@ -2679,60 +2646,27 @@ int pl_transient_sens(pl_handle h, int32_t n_steps, double dt, double beta, doub
     if (base_dir) amp_dev[(size_t)n * n_pat_dev + n_pat] = -base_acc[n];
   }
   a.amp = amp_dev.data();
-  DynHistory hist;
-  hist.s = s;
-  hist.l_host = out_vec;
-  hist.base_dir = base_dir;
-  hist.base_acc = base_acc;
-  const std::vector<int32_t> no_probe((size_t)N, -1);
+  const DynHistory hist = {s, out_vec, base_dir, base_acc};
   std::vector<int32_t> its((size_t)2 * rows, 0);
   MultiWs *w = nullptr;
   DynWs *d = nullptr;
   TransientClock clk;
+  const std::vector<int32_t> no_probe((size_t)h->N, -1);
   if (int rc = transient_forward(h, who, m, a, no_probe, 0, 0, 0, its.data(), &hist, &w, &d, &clk)) return rc;
   // the one host look between the passes: y_n from its slots, J and c_n = dJ/dy_n
-  std::vector<double> yh((size_t)rows), c((size_t)rows, 0.0);
-  {
-    std::vector<double> ys((size_t)rows * pl::kSlots);
-    PL_HIP(hipMemcpyAsync(ys.data(), s->yslots.p, ys.size() * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-    PL_HIP(hipStreamSynchronize(h->stream));
-    for (int n = 0; n < rows; ++n) {
-      double t = 0.0;
-      for (int q = 0; q < pl::kSlots; ++q) t += ys[(size_t)n * pl::kSlots + q];
-      yh[(size_t)n] = t;
-    }
-  }
-  const bool timing = std::getenv("PL_TIMING") != nullptr;
+  std::vector<double> yh((size_t)rows), c((size_t)rows);
+  if (int rc = download_slot_sums(h, s->yslots.p, (size_t)rows, yh.data())) return rc;
   const double ms_forward = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - clk.t_begin).count();
-  double Jv = 0.0;
-  auto wt = [&](int n) { return weight ? weight[n] : 1.0; };
-  if (kind == 0) {
-    for (int n = 0; n < rows; ++n) { Jv += wt(n) * yh[n]; c[n] = wt(n); }
-  } else if (kind == 1) {
-    for (int n = 0; n < rows; ++n) { Jv += wt(n) * yh[n] * yh[n]; c[n] = wt(n) * yh[n]; }
-    Jv *= 0.5;
-  } else {   // scaled by the largest |y|: |y|^p cannot overflow
-    double top = 0.0, sum = 0.0;
-    for (int n = 0; n < rows; ++n) top = std::max(top, std::fabs(yh[n]));
-    if (top > 0.0)
-      for (int n = 0; n < rows; ++n) sum += wt(n) * std::pow(std::fabs(yh[n]) / top, p);
-    const double Js = sum > 0.0 ? std::pow(sum, 1.0 / p) : 0.0;
-    Jv = top * Js;
-    if (Js > 0.0)
-      for (int n = 0; n < rows; ++n) {
-        const double sgn = yh[n] > 0.0 ? 1.0 : (yh[n] < 0.0 ? -1.0 : 0.0);
-        c[n] = std::pow(Js, 1.0 - p) * wt(n) * std::pow(std::fabs(yh[n]) / top, p - 1.0) * sgn;
-      }
-  }
+  const double Jv = objective_real(rows, yh.data(), kind, p, weight, c.data());
   if (!std::isfinite(Jv)) return fail(PL_ERR_NAN, "pl_transient_sens: the objective is not finite");
   // the backward sweep
   const double c2 = dt * dt * (0.5 - beta), c3 = dt * (1.0 - gamma), cu = beta * dt * dt, cv = gamma * dt;
   const double ca = cu + cv * dt + c2, cb = cv + c3;
   const dim3 gs(grid_stream(n6));
   const MultiShape s1 = multi_shape(h, 1);
-  std::vector<double> status((size_t)pl::M_ST_COUNT * s1.ncol);
   MultiOp op;
   op.mass = m;
+  const bool timing = std::getenv("PL_TIMING") != nullptr;
   double ms_solve = 0.0, ms_sens = 0.0;
   long adj_iters = 0;
   PL_HIP(hipMemsetAsync(s->acc.p, 0, (size_t)pl::kSensGroups * B * sizeof(double), h->stream));
@@ -2741,36 +2675,15 @@ int pl_transient_sens(pl_handle h, int32_t n_steps, double dt, double beta, doub
                        (const double *)s->Ml.p, (const double *)s->l.p, dt, ray_m, ray_k, c_cur, a_, b_, cl_next, s->mu.p,
                        s->nu.p, w->F.p, s->lam.p + (size_t)(row % pl::kSensChunk) * n6);
   };
-  auto contract = [&](int row0) -> int {   // the chunk whose first row is row0
-    const int nrows = std::min(pl::kSensChunk, rows - row0);
-    if (timing) PL_HIP(hipEventRecord(h->ev0, h->stream));
-    if (int rc = launch_transient_sens(h, m, s, row0, nrows)) return rc;
-    if (timing) {
-      float t = 0.0f;
-      PL_HIP(hipEventRecord(h->ev1, h->stream));
-      PL_HIP(hipEventSynchronize(h->ev1));
-      PL_HIP(hipEventElapsedTime(&t, h->ev0, h->ev1));
-      ms_sens += t;
-    }
-    return PL_OK;
-  };
   adjoint(nullptr, 0.0, ca, cb, cu * c[(size_t)n_steps], 0);     // mu = nu = 0 and the right-hand side of row n_steps
   PL_HIP(hipGetLastError());
   for (int row = n_steps; row >= 0; --row) {
     const double qdt = row == 0 ? 0.0 : dt;
     op.c_M = 1.0 + gamma * qdt * ray_m;
     op.c_K = beta * qdt * qdt + gamma * qdt * ray_k;
-    const auto t0 = std::chrono::steady_clock::now();
-    if (int rc = pcg_solve_multi(h, w, s1, h->fixedbits.p, w->F.p, rtol, max_iter, status.data(), op)) return rc;
-    ms_solve += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-    const double rr = status[pl::M_ST_RR * s1.ncol], bb = status[pl::M_ST_BB * s1.ncol];
-    its[(size_t)rows + row] = (int)status[pl::M_ST_ITER * s1.ncol];
+    if (int rc = transient_solve(h, w, op, rtol, max_iter, who, "the adjoint solve of step", row, &its[(size_t)rows + row], &ms_solve))
+      return rc;
     adj_iters += its[(size_t)rows + row];
-    if (!std::isfinite(rr) || !std::isfinite(bb))
-      return fail(PL_ERR_NAN, "pl_transient_sens: NaN/Inf in a residual norm of the adjoint solve of step " + std::to_string(row));
-    if (!(rr <= rtol * rtol * bb))
-      return fail(PL_ERR_NOCONV, "pl_transient_sens: the adjoint solve of step " + std::to_string(row) +
-                                     " did not reach rtol within max_iter");
     if (row > 0) {
       if (int rc = launch_spmv_multi(h, s1, h->fixedbits.p, w->U.p, s->Kl.p, true, nullptr)) return rc;
       if (int rc = launch_mass_multi(h, m, s1, w->U.p, s->Ml.p, true)) return rc;
@@ -2780,8 +2693,11 @@ int pl_transient_sens(pl_handle h, int32_t n_steps, double dt, double beta, doub
     } else {
       PL_HIP(hipMemcpyAsync(s->lam.p, w->U.p, (size_t)n6 * sizeof(double), hipMemcpyDeviceToDevice, h->stream));
     }
-    if (row % pl::kSensChunk == 0)
-      if (int rc = contract(row)) return rc;
+    if (row % pl::kSensChunk == 0) {   // the chunk whose first row this is
+      EventTimer timer(who, h->stream, "k_transient_sens");
+      if (int rc = launch_transient_sens(h, m, s, row, std::min(pl::kSensChunk, rows - row))) return rc;
+      ms_sens += timer.lap();
+    }
   }
   hipLaunchKernelGGL(pl::k_transient_sens_sum, dim3(grid_for(B)), dim3(pl::kBlock), 0, h->stream, B, (const double *)s->acc.p,
                      s->grad.p);
@@ -2793,15 +2709,15 @@ int pl_transient_sens(pl_handle h, int32_t n_steps, double dt, double beta, doub
   if (timing) {
     PL_HIP(hipStreamSynchronize(h->stream));
     const double ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - clk.t_begin).count();
-    std::fprintf(stderr, "[%s] %-28s %10.4f ms\n", who, "whole_call_host_clock", ms);
-    std::fprintf(stderr, "[%s] %-28s %10d\n", who, "steps", (int)n_steps);
-    std::fprintf(stderr, "[%s] %-28s %10.4f ms\n", who, "forward_pass_host_clock", ms_forward);
-    std::fprintf(stderr, "[%s] %-28s %10.4f ms\n", who, "adjoint_pass_host_clock", ms - ms_forward);
-    std::fprintf(stderr, "[%s] %-28s %10.4f ms\n", who, "inner_solve_mean_host_clock", (clk.ms_solve + ms_solve) / (2 * rows));
-    std::fprintf(stderr, "[%s] %-28s %10.2f\n", who, "forward_iterations_per_step", (double)clk.total_iters / rows);
-    std::fprintf(stderr, "[%s] %-28s %10.2f\n", who, "adjoint_iterations_per_step", (double)adj_iters / rows);
-    std::fprintf(stderr, "[%s] %-28s %10.4f ms\n", who, "k_transient_sens", ms_sens);
-    std::fprintf(stderr, "[%s] %-28s %10.2f %%\n", who, "k_transient_sens_share", 100.0 * ms_sens / ms);
+    timing_ms(who, "whole_call_host_clock", ms);
+    timing_count(who, "steps", (int)n_steps);
+    timing_ms(who, "forward_pass_host_clock", ms_forward);
+    timing_ms(who, "adjoint_pass_host_clock", ms - ms_forward);
+    timing_ms(who, "inner_solve_mean_host_clock", (clk.ms_solve + ms_solve) / (2 * rows));
+    timing_mean(who, "forward_iterations_per_step", (double)clk.total_iters / rows);
+    timing_mean(who, "adjoint_iterations_per_step", (double)adj_iters / rows);
+    timing_ms(who, "k_transient_sens", ms_sens);
+    timing_mean(who, "k_transient_sens_share", 100.0 * ms_sens / ms, " %");
   }
   return PL_OK;
 }
@@ -2833,67 +2749,35 @@ int pl_harmonic(pl_handle h, int32_t n_freq, const double *omega, double ray_m, 
                 double *probe_out, double *fields, double *power, int32_t *iters, double *relres, int32_t *status) {
   const char *who = "pl_harmonic";
   if (!valid(h) || !omega || !load_re || !iters || !relres || !status) return fail(PL_ERR_ARG, "pl_harmonic: null argument");
-  if (n_freq < 1) return fail(PL_ERR_ARG, "pl_harmonic: n_freq must be at least 1");
-  for (int i = 0; i < n_freq; ++i)
-    if (!(omega[i] >= 0.0) || !std::isfinite(omega[i])) return fail(PL_ERR_ARG, "pl_harmonic: omega must be finite and not negative");
-  if (!(ray_m >= 0.0) || !(ray_k >= 0.0) || !std::isfinite(ray_m) || !std::isfinite(ray_k))
-    return fail(PL_ERR_ARG, "pl_harmonic: the Rayleigh coefficients must be finite and not negative");
-  if (!(rtol > 0.0) || max_iter <= 0) return fail(PL_ERR_ARG, "pl_harmonic: rtol and max_iter must be positive");
+  if (int rc = check_omega(who, n_freq, omega)) return rc;
+  if (int rc = check_rayleigh(who, ray_m, ray_k)) return rc;
+  if (int rc = check_solve(who, rtol, max_iter)) return rc;
   if (block < 0 || block > kHarmMaxFreq) return fail(PL_ERR_ARG, "pl_harmonic: block must be 0 ... PL_MULTI_MAX / 2");
   if (n_probe < 0 || (n_probe > 0 && (!probe_nodes || !probe_out)))
     return fail(PL_ERR_ARG, "pl_harmonic: n_probe > 0 needs probe_nodes and probe_out");
-  const int64_t N = h->N, n6 = N * 6;
-  for (int i = 0; i < n_probe; ++i)
-    if (probe_nodes[i] < 0 || probe_nodes[i] >= N) return fail(PL_ERR_ARG, "pl_harmonic: probe node index out of range");
+  if (int rc = check_probes(who, n_probe, probe_nodes, h->N)) return rc;
   MassWs *m = nullptr;
   if (int rc = transient_begin(h, who, &m)) return rc;
+  const int64_t N = h->N, n6 = N * 6;
   const int nb = std::min<int>(block == 0 ? kHarmMaxFreq : block, n_freq);
   MultiWs *w = nullptr;
   if (int rc = multi_ws(h, harm_shape(h, nb), true, &w)) return rc;
   HarmWs *hw = nullptr;
   if (int rc = harm_ws(h, &hw)) return rc;
-  // the probed nodes, each once: slot of the node in the device's probe block
-  std::vector<int32_t> slot_of((size_t)N, -1), probe_to_slot((size_t)n_probe);
-  int n_slot = 0;
-  for (int i = 0; i < n_probe; ++i) {
-    const int64_t di = h->iperm[probe_nodes[i]];
-    if (slot_of[(size_t)di] < 0) slot_of[(size_t)di] = n_slot++;
-    probe_to_slot[(size_t)i] = slot_of[(size_t)di];
-  }
+  std::vector<int32_t> slot_of, probe_to_slot;
+  const int n_slot = probe_map(h, n_probe, probe_nodes, slot_of, probe_to_slot);
   PL_HIP(dyn_grow(hw->probe, (size_t)nb * std::max(n_slot, 1) * 12));
   PL_HIP(hipMemcpyAsync(hw->probe_slot.p, slot_of.data(), (size_t)N * sizeof(int32_t), hipMemcpyHostToDevice, h->stream));
   if (int rc = harm_upload(h, w, 1, load_re, load_im, true, w->F.p, -1)) return rc;   // (its wait covers slot_of too)
-  // diag K and diag M, real, once per call
-  MultiOp op;
-  op.mass = m;
-  op.c_K = 1.0; op.c_M = 0.0;
-  if (int rc = launch_dyn_diag(h, op, h->fixedbits.p, hw->diagK.p, nullptr)) return rc;
-  op.c_K = 0.0; op.c_M = 1.0;
-  if (int rc = launch_dyn_diag(h, op, h->fixedbits.p, hw->diagM.p, nullptr)) return rc;
 
-  const bool timing = std::getenv("PL_TIMING") != nullptr;
-  const auto t_begin = std::chrono::steady_clock::now();
   const dim3 gs(harm_grid(n6));
-  std::vector<double> coef((size_t)4 * nb), st((size_t)pl::H_ST_COUNT * nb), pw((size_t)nb * pl::H_PW_COUNT * pl::kSlots);
   std::vector<double> ph((size_t)nb * std::max(n_slot, 1) * 12);
+  const std::vector<double> coef = harm_coef(n_freq, omega, ray_m, ray_k);
   int bad = 0;
-  for (int f0 = 0; f0 < n_freq; f0 += nb) {
-    const int nf = std::min(nb, n_freq - f0);
+  std::chrono::steady_clock::time_point t_begin;
+  // after the solves of a pass: K u and M u of the fields, then the probes and the power sums
+  auto products_and_outputs = [&](int f0, int nf) -> int {
     const MultiShape s = harm_shape(h, nf);
-    for (int j = 0; j < nf; ++j) {
-      const double wj = omega[f0 + j];
-      coef[(size_t)4 * j] = 1.0;
-      coef[(size_t)4 * j + 1] = wj * ray_k;
-      coef[(size_t)4 * j + 2] = -wj * wj;
-      coef[(size_t)4 * j + 3] = wj * ray_m;
-    }
-    PL_HIP(hipMemcpyAsync(hw->coef.p, coef.data(), (size_t)4 * nf * sizeof(double), hipMemcpyHostToDevice, h->stream));
-    PL_HIP(hipStreamSynchronize(h->stream));         // (coef is pageable host memory, rewritten by the next pass)
-    const auto t0 = std::chrono::steady_clock::now();
-    int launched = 0;
-    if (int rc = cocg_solve(h, w, hw, m, s, rtol, max_iter, st.data(), &launched)) return rc;
-    const double ms_pass = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-    // K u and M u of the fields, then the probes and the power sums
     if (int rc = launch_spmv_multi(h, s, h->fixedbits.p, w->X.p, w->KU.p, true, nullptr)) return rc;
     if (int rc = launch_mass_multi(h, m, s, w->X.p, w->AP.p, true)) return rc;
     PL_HIP(hipMemsetAsync(hw->power.p, 0, (size_t)nf * pl::H_PW_COUNT * pl::kSlots * sizeof(double), h->stream));
@@ -2901,42 +2785,24 @@ int pl_harmonic(pl_handle h, int32_t n_freq, const double *omega, double ray_m, 
                        (const double *)w->X.p, (const double *)w->KU.p, (const double *)w->AP.p,
                        (const int32_t *)hw->probe_slot.p, n_slot, hw->probe.p, hw->power.p, s.stride);
     PL_HIP(hipGetLastError());
-    PL_HIP(hipMemcpyAsync(pw.data(), hw->power.p, (size_t)nf * pl::H_PW_COUNT * pl::kSlots * sizeof(double),
-                          hipMemcpyDeviceToHost, h->stream));
     if (n_slot > 0)
       PL_HIP(hipMemcpyAsync(ph.data(), hw->probe.p, (size_t)nf * n_slot * 12 * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-    PL_HIP(hipStreamSynchronize(h->stream));
-    long pass_iters = 0;
-    for (int j = 0; j < nf; ++j) {
-      const double rr = st[(size_t)pl::H_ST_RR * nf + j], bb = st[(size_t)pl::H_ST_BB * nf + j];
-      const int state = (int)st[(size_t)pl::H_ST_STATE * nf + j];
-      iters[f0 + j] = (int32_t)st[(size_t)pl::H_ST_ITER * nf + j];
-      relres[f0 + j] = bb > 0.0 ? std::sqrt(rr / bb) : 0.0;
-      status[f0 + j] = state == 1 ? 0 : (state == 2 ? 2 : 1);
-      if (status[f0 + j] != 0) ++bad;
-      pass_iters += iters[f0 + j];
-      if (power)
-        for (int k = 0; k < pl::H_PW_COUNT; ++k) {
-          double t = 0.0;
-          for (int q = 0; q < pl::kSlots; ++q) t += pw[((size_t)j * pl::H_PW_COUNT + k) * pl::kSlots + q];
-          power[(size_t)(f0 + j) * pl::H_PW_COUNT + k] = t;
-        }
+    if (power) {   // (its wait covers ph too)
+      if (int rc = download_slot_sums(h, hw->power.p, (size_t)nf * pl::H_PW_COUNT, power + (size_t)f0 * pl::H_PW_COUNT)) return rc;
+    } else {
+      PL_HIP(hipStreamSynchronize(h->stream));
+    }
+    for (int j = 0; j < nf; ++j)
       for (int i = 0; i < n_probe; ++i)
         std::memcpy(probe_out + ((size_t)(f0 + j) * n_probe + i) * 12,
                     ph.data() + ((size_t)j * n_slot + probe_to_slot[(size_t)i]) * 12, 12 * sizeof(double));
-    }
-    if (fields)
-      if (int rc = harm_download(h, w, nf, w->X.p, fields + (size_t)f0 * 2 * n6)) return rc;
-    if (timing) {
-      std::fprintf(stderr, "[%s] %-28s %10d\n", who, "pass_frequencies", nf);
-      std::fprintf(stderr, "[%s] %-28s %10.4f ms\n", who, "iteration_mean_host_clock", launched > 0 ? ms_pass / launched : 0.0);
-      std::fprintf(stderr, "[%s] %-28s %10.2f\n", who, "iterations_per_frequency", (double)pass_iters / nf);
-    }
-  }
-  if (timing) {
-    const double ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_begin).count();
-    std::fprintf(stderr, "[%s] %-28s %10.4f ms\n", who, "whole_call_host_clock", ms);
-  }
+    return fields ? harm_download(h, w, nf, w->X.p, fields + (size_t)f0 * 2 * n6) : PL_OK;
+  };
+  if (int rc = harm_passes(h, w, hw, m, who, n_freq, coef.data(), nb, 1, nullptr, rtol, max_iter, nullptr, "iterations_per_frequency",
+                           iters, relres, status, &bad, &t_begin, products_and_outputs))
+    return rc;
+  if (std::getenv("PL_TIMING") != nullptr)
+    timing_ms(who, "whole_call_host_clock", std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_begin).count());
   if (bad)
     return fail(PL_ERR_NOCONV, "pl_harmonic: " + std::to_string(bad) + " frequencies ended without convergence (see status)");
   return PL_OK;
@@ -2952,29 +2818,21 @@ int pl_harmonic_sens(pl_handle h, int32_t n_freq, const double *omega, double ra
   if (!J || !dJ_dr) return fail(PL_ERR_ARG, "pl_harmonic_sens: J and dJ_dr must not be NULL");
   if (!load_re && !base_dir) return fail(PL_ERR_ARG, "pl_harmonic_sens: neither a load nor base_dir");
   if (load_im && !load_re) return fail(PL_ERR_ARG, "pl_harmonic_sens: load_im needs load_re");
-  if (n_freq < 1) return fail(PL_ERR_ARG, "pl_harmonic_sens: n_freq must be at least 1");
-  for (int i = 0; i < n_freq; ++i)
-    if (!(omega[i] >= 0.0) || !std::isfinite(omega[i]))
-      return fail(PL_ERR_ARG, "pl_harmonic_sens: omega must be finite and not negative");
-  if (!(ray_m >= 0.0) || !(ray_k >= 0.0) || !std::isfinite(ray_m) || !std::isfinite(ray_k))
-    return fail(PL_ERR_ARG, "pl_harmonic_sens: the Rayleigh coefficients must be finite and not negative");
-  if (!(rtol > 0.0) || max_iter <= 0) return fail(PL_ERR_ARG, "pl_harmonic_sens: rtol and max_iter must be positive");
+  if (int rc = check_omega(who, n_freq, omega)) return rc;
+  if (int rc = check_rayleigh(who, ray_m, ray_k)) return rc;
+  if (int rc = check_solve(who, rtol, max_iter)) return rc;
   const bool self_adjoint = out_vec == nullptr;
   const int pass_max = self_adjoint ? kHarmMaxFreq : kHarmSensMaxFreq;
   if (block < 0 || block > pass_max)
     return fail(PL_ERR_ARG, "pl_harmonic_sens: block must be 0 ... PL_MULTI_MAX / 4 (PL_MULTI_MAX / 2 with out_vec = NULL)");
-  if (kind < 0 || kind > 2) return fail(PL_ERR_ARG, "pl_harmonic_sens: kind must be 0, 1 or 2");
-  if (kind == 2 && !(p >= 2.0 && std::isfinite(p))) return fail(PL_ERR_ARG, "pl_harmonic_sens: p must be at least 2 (and finite)");
+  if (int rc = check_kind(who, kind, p)) return rc;
   if (base_dir)
     for (int k = 0; k < 3; ++k)
       if (!std::isfinite(base_dir[k])) return fail(PL_ERR_ARG, "pl_harmonic_sens: base_dir must be finite");
-  if (weight)
-    for (int k = 0; k < n_freq; ++k)
-      if (!(weight[k] >= 0.0) || !std::isfinite(weight[k]))
-        return fail(PL_ERR_ARG, "pl_harmonic_sens: the weights must be finite and not negative");
+  if (int rc = check_weights(who, weight, n_freq)) return rc;
   MassWs *m = nullptr;
   if (int rc = transient_begin(h, who, &m)) return rc;
-  const int64_t N = h->N, n6 = N * 6, n12 = N * 12, B = h->B;
+  const int64_t n6 = h->N * 6, n12 = h->N * 12, B = h->B;
   const int nb = std::min<int>(block == 0 ? pass_max : block, n_freq);     // frequencies per pass
   const int per = self_adjoint ? 1 : 2;                                   // column blocks per frequency
   MultiWs *w = nullptr;
@@ -3000,79 +2858,31 @@ int pl_harmonic_sens(pl_handle h, int32_t n_freq, const double *omega, double ra
   } else {
     PL_HIP(hipMemsetAsync(f_dev, 0, (size_t)n12 * sizeof(double), h->stream));
   }
-  if (base_dir) {   // P M e_dir on the single-column gather
-    const MultiShape s1 = multi_shape(h, 1);
-    std::vector<double> e((size_t)n6, 0.0);
-    for (int64_t i = 0; i < N; ++i)
-      for (int k = 0; k < 3; ++k) e[(size_t)(6 * i + k)] = base_dir[k];
-    if (int rc = multi_upload(h, w, s1, e.data(), s->edir.p, 0)) return rc;
-    if (int rc = launch_mass_multi(h, m, s1, s->edir.p, s->Me.p, true)) return rc;
+  if (base_dir) {
+    if (int rc = base_load(h, w, m, base_dir, s->edir.p, s->Me.p)) return rc;
     hipLaunchKernelGGL(pl::k_harm_base_load, dim3(grid_stream(n6)), dim3(pl::kBlock), 0, h->stream, n6, (const double *)s->Me.p,
                        f_dev);
     PL_HIP(hipGetLastError());
   }
   if (!self_adjoint)
     if (int rc = harm_upload(h, w, 1, out_vec, nullptr, true, l_dev, -1)) return rc;
-  // diag K and diag M, real, once per call
-  MultiOp op;
-  op.mass = m;
-  op.c_K = 1.0; op.c_M = 0.0;
-  if (int rc = launch_dyn_diag(h, op, h->fixedbits.p, hw->diagK.p, nullptr)) return rc;
-  op.c_K = 0.0; op.c_M = 1.0;
-  if (int rc = launch_dyn_diag(h, op, h->fixedbits.p, hw->diagM.p, nullptr)) return rc;
 
-  const bool timing = std::getenv("PL_TIMING") != nullptr;
-  const auto t_begin = std::chrono::steady_clock::now();
-  std::vector<double> coef_all((size_t)4 * n_freq), coef((size_t)4 * per * nb), st((size_t)pl::H_ST_COUNT * per * nb);
+  const std::vector<double> coef_all = harm_coef(n_freq, omega, ray_m, ray_k);
   std::vector<int32_t> its((size_t)2 * n_freq, 0), stat((size_t)2 * n_freq, 0);
   std::vector<double> rres((size_t)2 * n_freq, 0.0);
-  for (int k = 0; k < n_freq; ++k) {
-    const double wk = omega[k];
-    coef_all[(size_t)4 * k] = 1.0;
-    coef_all[(size_t)4 * k + 1] = wk * ray_k;
-    coef_all[(size_t)4 * k + 2] = -wk * wk;
-    coef_all[(size_t)4 * k + 3] = wk * ray_m;
-  }
-  int bad = 0, filled = 0;
-  for (int f0 = 0; f0 < n_freq; f0 += nb) {
-    const int nf = std::min(nb, n_freq - f0), ncb = per * nf;
-    const MultiShape sh = harm_shape(h, ncb);
-    if (filled != nf) {   // every column block reads its own load: f for the fields, l for the adjoint fields
-      for (int j = 0; j < ncb; ++j)
-        PL_HIP(hipMemcpyAsync(w->F.p + (size_t)j * n12, j < nf ? f_dev : l_dev, (size_t)n12 * sizeof(double),
-                              hipMemcpyDeviceToDevice, h->stream));
-      filled = nf;
-    }
-    for (int q = 0; q < per; ++q)
-      std::memcpy(coef.data() + (size_t)4 * q * nf, coef_all.data() + (size_t)4 * f0, (size_t)4 * nf * sizeof(double));
-    PL_HIP(hipMemcpyAsync(hw->coef.p, coef.data(), (size_t)4 * ncb * sizeof(double), hipMemcpyHostToDevice, h->stream));
-    PL_HIP(hipStreamSynchronize(h->stream));         // (coef is pageable host memory, rewritten by the next pass)
-    const auto t0 = std::chrono::steady_clock::now();
-    int launched = 0;
-    if (int rc = cocg_solve(h, w, hw, m, sh, rtol, max_iter, st.data(), &launched, sh.stride)) return rc;
-    const double ms_pass = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+  const double *loads[2] = {f_dev, l_dev};   // every column block reads its own load: f for the fields, l for the adjoint fields
+  int bad = 0;
+  std::chrono::steady_clock::time_point t_begin;
+  auto keep_fields = [&](int f0, int nf) -> int {
     PL_HIP(hipMemcpyAsync(s->U.p + (size_t)f0 * n12, w->X.p, (size_t)nf * n12 * sizeof(double), hipMemcpyDeviceToDevice, h->stream));
     if (!self_adjoint)
       PL_HIP(hipMemcpyAsync(s->L.p + (size_t)f0 * n12, w->X.p + (size_t)nf * n12, (size_t)nf * n12 * sizeof(double),
                             hipMemcpyDeviceToDevice, h->stream));
-    long pass_iters = 0;
-    for (int j = 0; j < ncb; ++j) {
-      const double rr = st[(size_t)pl::H_ST_RR * ncb + j], bb = st[(size_t)pl::H_ST_BB * ncb + j];
-      const int state = (int)st[(size_t)pl::H_ST_STATE * ncb + j];
-      const size_t o = (size_t)(j / nf) * n_freq + f0 + (j % nf);
-      its[o] = (int32_t)st[(size_t)pl::H_ST_ITER * ncb + j];
-      rres[o] = bb > 0.0 ? std::sqrt(rr / bb) : 0.0;
-      stat[o] = state == 1 ? 0 : (state == 2 ? 2 : 1);
-      if (stat[o] != 0) ++bad;
-      pass_iters += its[o];
-    }
-    if (timing) {
-      std::fprintf(stderr, "[%s] %-28s %10d\n", who, "pass_frequencies", nf);
-      std::fprintf(stderr, "[%s] %-28s %10d\n", who, "pass_column_blocks", ncb);
-      std::fprintf(stderr, "[%s] %-28s %10.4f ms\n", who, "iteration_mean_host_clock", launched > 0 ? ms_pass / launched : 0.0);
-      std::fprintf(stderr, "[%s] %-28s %10.2f\n", who, "iterations_per_solve", (double)pass_iters / ncb);
-    }
-  }
+    return PL_OK;
+  };
+  if (int rc = harm_passes(h, w, hw, m, who, n_freq, coef_all.data(), nb, per, loads, rtol, max_iter, "pass_column_blocks",
+                           "iterations_per_solve", its.data(), rres.data(), stat.data(), &bad, &t_begin, keep_fields))
+    return rc;
   if (iters) std::memcpy(iters, its.data(), its.size() * sizeof(int32_t));
   if (relres) std::memcpy(relres, rres.data(), rres.size() * sizeof(double));
   if (status) std::memcpy(status, stat.data(), stat.size() * sizeof(int32_t));
@@ -3085,70 +2895,29 @@ int pl_harmonic_sens(pl_handle h, int32_t n_freq, const double *omega, double ra
   hipLaunchKernelGGL(pl::k_harm_output, dim3(harm_grid(n6), (unsigned)n_freq), dim3(pl::kBlock), 0, h->stream, n6,
                      (const double *)l_dev, (const double *)s->U.p, s->yslots.p);
   PL_HIP(hipGetLastError());
-  std::vector<double> yh((size_t)2 * n_freq), g((size_t)2 * n_freq, 0.0);
-  {
-    std::vector<double> ys((size_t)2 * n_freq * pl::kSlots);
-    PL_HIP(hipMemcpyAsync(ys.data(), s->yslots.p, ys.size() * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-    PL_HIP(hipStreamSynchronize(h->stream));
-    for (int k = 0; k < 2 * n_freq; ++k) {
-      double t = 0.0;
-      for (int q = 0; q < pl::kSlots; ++q) t += ys[(size_t)k * pl::kSlots + q];
-      yh[(size_t)k] = t;
-    }
-  }
-  double Jv = 0.0;
-  auto wt = [&](int k) { return weight ? weight[k] : 1.0; };
-  auto mag = [&](int k) { return std::hypot(yh[(size_t)2 * k], yh[(size_t)2 * k + 1]); };
-  if (kind == 0) {          // J = -sum w Im y, g = i w
-    for (int k = 0; k < n_freq; ++k) { Jv -= wt(k) * yh[(size_t)2 * k + 1]; g[(size_t)2 * k + 1] = wt(k); }
-  } else if (kind == 1) {   // J = 1/2 sum w |y|^2, g = w conj(y)
-    for (int k = 0; k < n_freq; ++k) {
-      const double re = yh[(size_t)2 * k], im = yh[(size_t)2 * k + 1];
-      Jv += wt(k) * (re * re + im * im);
-      g[(size_t)2 * k] = wt(k) * re;
-      g[(size_t)2 * k + 1] = -wt(k) * im;
-    }
-    Jv *= 0.5;
-  } else {                  // scaled by the largest |y|: |y|^p cannot overflow
-    double top = 0.0, sum = 0.0;
-    for (int k = 0; k < n_freq; ++k) top = std::max(top, mag(k));
-    if (top > 0.0)
-      for (int k = 0; k < n_freq; ++k) sum += wt(k) * std::pow(mag(k) / top, p);
-    const double Js = sum > 0.0 ? std::pow(sum, 1.0 / p) : 0.0;
-    Jv = top * Js;
-    if (Js > 0.0)
-      for (int k = 0; k < n_freq; ++k) {
-        const double a = mag(k) / top;
-        const double c = a > 0.0 ? std::pow(Js, 1.0 - p) * wt(k) * std::pow(a, p - 2.0) / top : 0.0;
-        g[(size_t)2 * k] = c * yh[(size_t)2 * k];
-        g[(size_t)2 * k + 1] = -c * yh[(size_t)2 * k + 1];
-      }
-  }
+  std::vector<double> yh((size_t)2 * n_freq), g((size_t)2 * n_freq);
+  if (int rc = download_slot_sums(h, s->yslots.p, (size_t)2 * n_freq, yh.data())) return rc;
+  const double Jv = objective_complex(n_freq, yh.data(), kind, p, weight, g.data());
   if (!std::isfinite(Jv)) return fail(PL_ERR_NAN, "pl_harmonic_sens: the objective is not finite");
   for (double v : g)
     if (!std::isfinite(v)) return fail(PL_ERR_NAN, "pl_harmonic_sens: the objective's derivative is not finite");
   PL_HIP(hipMemcpyAsync(s->coef.p, coef_all.data(), coef_all.size() * sizeof(double), hipMemcpyHostToDevice, h->stream));
   PL_HIP(hipMemcpyAsync(s->g.p, g.data(), g.size() * sizeof(double), hipMemcpyHostToDevice, h->stream));
-  float ms_sens = 0.0f;
-  if (timing) PL_HIP(hipEventRecord(h->ev0, h->stream));
+  EventTimer sens_timer(who, h->stream, "k_harmonic_sens");
   const double sfac = base_dir ? (self_adjoint ? 2.0 : 1.0) : 0.0;
   if (int rc = launch_harmonic_sens(h, m, s, self_adjoint, n_freq, sfac, base_dir)) return rc;
-  if (timing) {
-    PL_HIP(hipEventRecord(h->ev1, h->stream));
-    PL_HIP(hipEventSynchronize(h->ev1));
-    PL_HIP(hipEventElapsedTime(&ms_sens, h->ev0, h->ev1));
-  }
+  const double ms_sens = sens_timer.lap();
   hipLaunchKernelGGL(pl::k_transient_sens_sum, dim3(grid_for(B)), dim3(pl::kBlock), 0, h->stream, B, (const double *)s->acc.p,
                      s->grad.p);
   PL_HIP(hipGetLastError());
   if (int rc = download_struts(h, s->grad.p, dJ_dr)) return rc;   // (its wait covers coef_all and g too)
   *J = Jv;
   if (y) std::memcpy(y, yh.data(), yh.size() * sizeof(double));
-  if (timing) {
+  if (sens_timer.on) {
     const double ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_begin).count();
-    std::fprintf(stderr, "[%s] %-28s %10.4f ms\n", who, "whole_call_host_clock", ms);
-    std::fprintf(stderr, "[%s] %-28s %10.4f ms\n", who, "k_harmonic_sens", (double)ms_sens);
-    std::fprintf(stderr, "[%s] %-28s %10.2f %%\n", who, "k_harmonic_sens_share", 100.0 * ms_sens / ms);
+    timing_ms(who, "whole_call_host_clock", ms);
+    timing_ms(who, "k_harmonic_sens", ms_sens);
+    timing_mean(who, "k_harmonic_sens_share", 100.0 * ms_sens / ms, " %");
   }
   return PL_OK;
 }

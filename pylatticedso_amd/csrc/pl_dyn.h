@@ -254,4 +254,93 @@ hipError_t dyn_grow(DevBuf<T> &b, size_t n) {
   return b.n < n ? b.alloc(n) : hipSuccess;
 }
 
+// ---- what the response calls (pl_transient, pl_harmonic, their _sens) share; first a PL_TIMING line (tools/time_*.py read it) ----
+inline void timing_ms(const char *who, const char *label, double ms) { std::fprintf(stderr, "[%s] %-28s %10.4f ms\n", who, label, ms); }
+inline void timing_count(const char *who, const char *label, int n) { std::fprintf(stderr, "[%s] %-28s %10d\n", who, label, n); }
+inline void timing_mean(const char *who, const char *label, double v, const char *unit = "") {
+  std::fprintf(stderr, "[%s] %-28s %10.2f%s\n", who, label, v, unit);
+}
+inline int check_rayleigh(const std::string &who, double ray_m, double ray_k) {
+  if (!(ray_m >= 0.0) || !(ray_k >= 0.0) || !std::isfinite(ray_m) || !std::isfinite(ray_k))
+    return fail(PL_ERR_ARG, who + ": the Rayleigh coefficients must be finite and not negative");
+  return PL_OK;
+}
+inline int check_solve(const std::string &who, double rtol, int32_t max_iter) {
+  if (!(rtol > 0.0) || max_iter <= 0) return fail(PL_ERR_ARG, who + ": rtol and max_iter must be positive");
+  return PL_OK;
+}
+inline int check_omega(const std::string &who, int32_t n_freq, const double *omega) {
+  if (n_freq < 1) return fail(PL_ERR_ARG, who + ": n_freq must be at least 1");
+  for (int i = 0; i < n_freq; ++i)
+    if (!(omega[i] >= 0.0) || !std::isfinite(omega[i])) return fail(PL_ERR_ARG, who + ": omega must be finite and not negative");
+  return PL_OK;
+}
+inline int check_kind(const std::string &who, int32_t kind, double p) {
+  if (kind < 0 || kind > 2) return fail(PL_ERR_ARG, who + ": kind must be 0, 1 or 2");
+  if (kind == 2 && !(p >= 2.0 && std::isfinite(p))) return fail(PL_ERR_ARG, who + ": p must be at least 2 (and finite)");
+  return PL_OK;
+}
+inline int check_weights(const std::string &who, const double *weight, int rows) {
+  for (int n = 0; weight && n < rows; ++n)
+    if (!(weight[n] >= 0.0) || !std::isfinite(weight[n])) return fail(PL_ERR_ARG, who + ": the weights must be finite and not negative");
+  return PL_OK;
+}
+inline int check_probes(const std::string &who, int32_t n_probe, const int32_t *probe_nodes, int64_t N) {
+  for (int i = 0; i < n_probe; ++i)
+    if (probe_nodes[i] < 0 || probe_nodes[i] >= N) return fail(PL_ERR_ARG, who + ": probe node index out of range");
+  return PL_OK;
+}
+
+// The probed nodes, each once: their rows in the device's probe block by device node (-1: not probed) and by probe; returns the rows
+inline int probe_map(const pl_context *c, int32_t n_probe, const int32_t *probe_nodes, std::vector<int32_t> &slot_of,
+                     std::vector<int32_t> &probe_to_slot) {
+  int n_slot = 0;
+  slot_of.assign((size_t)c->N, -1);
+  probe_to_slot.resize((size_t)n_probe);
+  for (int i = 0; i < n_probe; ++i) {
+    const int64_t di = c->iperm[probe_nodes[i]];
+    if (slot_of[(size_t)di] < 0) slot_of[(size_t)di] = n_slot++;
+    probe_to_slot[(size_t)i] = slot_of[(size_t)di];
+  }
+  return n_slot;
+}
+
+// sum[r] of `rows` reduction scalars on the device: their kSlots partial sums added in ascending order (the sums keep their bits)
+inline int download_slot_sums(pl_context *c, const double *slots_dev, size_t rows, double *sum) {
+  std::vector<double> sl(rows * pl::kSlots);
+  PL_HIP(hipMemcpyAsync(sl.data(), slots_dev, sl.size() * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+  PL_HIP(hipStreamSynchronize(c->stream));
+  for (size_t r = 0; r < rows; ++r) sum[r] = std::accumulate(&sl[r * pl::kSlots], &sl[r * pl::kSlots] + pl::kSlots, 0.0);
+  return PL_OK;
+}
+
+// e_dir, the rigid translation of ALL nodes along dir[3] (supports included), into edir_dev and P M e_dir into out_dev
+inline int base_load(pl_context *c, MultiWs *w, const MassWs *m, const double *dir, double *edir_dev, double *out_dev) {
+  const MultiShape s1 = multi_shape(c, 1);
+  std::vector<double> e((size_t)c->N * 6, 0.0);
+  for (int64_t i = 0; i < c->N; ++i)
+    for (int k = 0; k < 3; ++k) e[(size_t)(6 * i + k)] = dir[k];
+  if (int rc = multi_upload(c, w, s1, e.data(), edir_dev, 0)) return rc;
+  return launch_mass_multi(c, m, s1, edir_dev, out_dev, true);
+}
+
+// One solve of a transient row, (c_K K + c_M M) w->U = w->F.  `what` names it where it misses rtol ("the [forward | adjoint ]solve
+// of step"); where a norm is not a number only the adjoint is named in full.  *ms gains the host time of the solve.
+inline int transient_solve(pl_context *c, MultiWs *w, const MultiOp &op, double rtol, int32_t max_iter, const std::string &who,
+                           const char *what, int row, int *iters, double *ms) {
+  const MultiShape s1 = multi_shape(c, 1);
+  std::vector<double> status((size_t)pl::M_ST_COUNT * s1.ncol);
+  const auto t0 = std::chrono::steady_clock::now();
+  if (int rc = pcg_solve_multi(c, w, s1, c->fixedbits.p, w->F.p, rtol, max_iter, status.data(), op)) return rc;
+  *ms += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+  const double rr = status[pl::M_ST_RR * s1.ncol], bb = status[pl::M_ST_BB * s1.ncol];
+  *iters = (int)status[pl::M_ST_ITER * s1.ncol];
+  if (!std::isfinite(rr) || !std::isfinite(bb))
+    return fail(PL_ERR_NAN, who + ": NaN/Inf in a residual norm of " + (std::strstr(what, "adjoint") ? what : "step") + " " +
+                                std::to_string(row));
+  if (!(rr <= rtol * rtol * bb))
+    return fail(PL_ERR_NOCONV, who + ": " + what + " " + std::to_string(row) + " did not reach rtol within max_iter");
+  return PL_OK;
+}
+
 }  // namespace

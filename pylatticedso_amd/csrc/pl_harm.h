@@ -471,4 +471,76 @@ int cocg_solve(pl_context *c, MultiWs *w, HarmWs *hw, const MassWs *m, const Mul
   return PL_OK;
 }
 
+// {Re c_K, Im c_K, Re c_M, Im c_M} of every frequency: c_K = 1 + i w ray_k, c_M = i w ray_m - w^2
+inline std::vector<double> harm_coef(int n_freq, const double *omega, double ray_m, double ray_k) {
+  std::vector<double> coef((size_t)4 * n_freq);
+  for (int k = 0; k < n_freq; ++k) {
+    const double wk = omega[k];
+    coef[(size_t)4 * k] = 1.0;
+    coef[(size_t)4 * k + 1] = wk * ray_k;
+    coef[(size_t)4 * k + 2] = -wk * wk;
+    coef[(size_t)4 * k + 3] = wk * ray_m;
+  }
+  return coef;
+}
+
+// The passes of pl_harmonic and pl_harmonic_sens: diag K and diag M (real, once per call), then nb frequencies per pass with
+// `per` column blocks each (block q * nf + j: frequency j).  loads = null: w->F holds the one load of every block; else block
+// q * nf + j reads loads[q], copied into w->F when the pass size changes.  iters / relres / status are [per][n_freq]; after the
+// solves step(f0, nf) takes what the caller needs from w->X.  The labels name the PL_TIMING lines in which the two calls differ.
+template <class Step>
+int harm_passes(pl_context *c, MultiWs *w, HarmWs *hw, const MassWs *m, const char *who, int n_freq, const double *coef_all, int nb,
+                int per, const double *const *loads, double rtol, int max_iter, const char *blocks_label,
+                const char *iterations_label, int32_t *iters, double *relres, int32_t *status, int *bad,
+                std::chrono::steady_clock::time_point *t_begin, Step step) {
+  MultiOp op;
+  op.mass = m;
+  op.c_K = 1.0; op.c_M = 0.0;
+  if (int rc = launch_dyn_diag(c, op, c->fixedbits.p, hw->diagK.p, nullptr)) return rc;
+  op.c_K = 0.0; op.c_M = 1.0;
+  if (int rc = launch_dyn_diag(c, op, c->fixedbits.p, hw->diagM.p, nullptr)) return rc;
+
+  const bool timing = std::getenv("PL_TIMING") != nullptr;
+  *t_begin = std::chrono::steady_clock::now();
+  std::vector<double> coef((size_t)4 * per * nb), st((size_t)pl::H_ST_COUNT * per * nb);
+  int filled = 0;
+  for (int f0 = 0; f0 < n_freq; f0 += nb) {
+    const int nf = std::min(nb, n_freq - f0), ncb = per * nf;
+    const MultiShape s = harm_shape(c, ncb);
+    if (loads && filled != nf) {
+      for (int j = 0; j < ncb; ++j)
+        PL_HIP(hipMemcpyAsync(w->F.p + (size_t)j * s.stride, loads[j / nf], (size_t)s.stride * sizeof(double),
+                              hipMemcpyDeviceToDevice, c->stream));
+      filled = nf;
+    }
+    for (int q = 0; q < per; ++q)
+      std::memcpy(coef.data() + (size_t)4 * q * nf, coef_all + (size_t)4 * f0, (size_t)4 * nf * sizeof(double));
+    PL_HIP(hipMemcpyAsync(hw->coef.p, coef.data(), (size_t)4 * ncb * sizeof(double), hipMemcpyHostToDevice, c->stream));
+    PL_HIP(hipStreamSynchronize(c->stream));         // (coef is pageable host memory, rewritten by the next pass)
+    const auto t0 = std::chrono::steady_clock::now();
+    int launched = 0;
+    if (int rc = cocg_solve(c, w, hw, m, s, rtol, max_iter, st.data(), &launched, loads ? s.stride : 0)) return rc;
+    const double ms_pass = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    long pass_iters = 0;
+    for (int j = 0; j < ncb; ++j) {
+      const double rr = st[(size_t)pl::H_ST_RR * ncb + j], bb = st[(size_t)pl::H_ST_BB * ncb + j];
+      const int state = (int)st[(size_t)pl::H_ST_STATE * ncb + j];
+      const size_t o = (size_t)(j / nf) * n_freq + f0 + (j % nf);
+      iters[o] = (int32_t)st[(size_t)pl::H_ST_ITER * ncb + j];
+      relres[o] = bb > 0.0 ? std::sqrt(rr / bb) : 0.0;
+      status[o] = state == 1 ? 0 : (state == 2 ? 2 : 1);
+      if (status[o] != 0) ++*bad;
+      pass_iters += iters[o];
+    }
+    if (int rc = step(f0, nf)) return rc;
+    if (timing) {
+      timing_count(who, "pass_frequencies", nf);
+      if (blocks_label) timing_count(who, blocks_label, ncb);
+      timing_ms(who, "iteration_mean_host_clock", launched > 0 ? ms_pass / launched : 0.0);
+      timing_mean(who, iterations_label, (double)pass_iters / ncb);
+    }
+  }
+  return PL_OK;
+}
+
 }  // namespace

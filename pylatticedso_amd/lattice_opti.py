@@ -20,6 +20,7 @@ direct strut-volume formula instead.
 from __future__ import annotations
 
 import time
+from typing import Callable, NamedTuple
 
 import numpy as np
 
@@ -28,6 +29,52 @@ from .lattice_sim import LatticeSim, open_lattice_parameters
 from .utils_simulation import solve_FEM_FenicsX
 
 _DOF = {"X": 0, "Y": 1, "Z": 2, "RX": 3, "RY": 4, "RZ": 5}
+
+
+class _ResponseConstraint(NamedTuple):
+    """One response constraint of the preset (FEM mode).  `stem` names its methods and attributes: _<stem>_settings (whose first
+    entry is the limit), <stem>_constraint, <stem>_constraint_gradient and _last_<stem>, the (aggregate, peak) of the last
+    evaluation, whose peak goes into _history[history] per iteration.  The aggregate method returns (q, peak, ...); the
+    constraint is scale(q, limit) - 1 <= 0 and its gradient scale(dq/dtheta, limit).  gradient: "partials" - aggregate(want_grad)
+    ends with (dq/du, dq/dr at fixed u) for _aggregate_gradient; "total" - it ends with dq/dr_b for
+    _strut_gradient_to_parameters; "shared" - aggregate() gives the value and dq/dr_b in one call.  reason: why DDM mode refuses."""
+    key: str
+    stem: str
+    history: str
+    reason: str
+    aggregate: str
+    scale: Callable
+    gradient: str
+
+
+def _over(q, limit):
+    return q / limit
+
+
+def _times(q, limit):
+    return limit * q
+
+
+def _times_circular_squared(q, limit):
+    return (2.0 * np.pi * limit) ** 2 * q
+
+
+_INTERIORS = "the recovered interiors of DDM cells"
+# in the order they are handed to SLSQP
+_RESPONSE_CONSTRAINTS = (
+    _ResponseConstraint("max_stress", "stress", "max_stress", f"strut stresses on {_INTERIORS} are not implemented",
+                        "strut_stress_aggregate", _over, "partials"),
+    _ResponseConstraint("buckling", "buckling", "max_buckling", f"strut forces on {_INTERIORS} are not implemented",
+                        "strut_buckling_aggregate", _over, "partials"),
+    _ResponseConstraint("global_buckling", "global_buckling", "min_load_factor",
+                        f"the geometric stiffness of {_INTERIORS} is not implemented", "global_buckling_aggregate", _times, "total"),
+    _ResponseConstraint("frequency", "frequency", "min_frequency", f"the mass of {_INTERIORS} is not implemented",
+                        "frequency_aggregate", _times_circular_squared, "total"),
+    _ResponseConstraint("peak_displacement", "peak_displacement", "peak_displacement",
+                        f"the transient response of {_INTERIORS} is not implemented", "peak_displacement_aggregate", _over, "shared"),
+    _ResponseConstraint("resonance_peak", "resonance_peak", "resonance_peak",
+                        f"the frequency response of {_INTERIORS} is not implemented", "resonance_peak_aggregate", _over, "shared"),
+)
 
 
 class LatticeOpti(LatticeSim):
@@ -57,24 +104,9 @@ class LatticeOpti(LatticeSim):
         # lattice_opti.py:96-103: simulation_type "DDM" runs every equilibrium through solve_DDM with the cell Schur
         # complements (exact or surrogate) and contracts their derivatives dS/dr for the gradient
         self._ddm_mode = info.get("simulation_type", None) == "DDM"
-        if self._ddm_mode and "max_stress" in (info.get("constraints") or {}):
-            raise NotImplementedError('the "max_stress" constraint needs simulation_type "FEM": strut stresses on the '
-                                      "recovered interiors of DDM cells are not implemented")
-        if self._ddm_mode and "buckling" in (info.get("constraints") or {}):
-            raise NotImplementedError('the "buckling" constraint needs simulation_type "FEM": strut forces on the '
-                                      "recovered interiors of DDM cells are not implemented")
-        if self._ddm_mode and "global_buckling" in (info.get("constraints") or {}):
-            raise NotImplementedError('the "global_buckling" constraint needs simulation_type "FEM": the geometric stiffness of '
-                                      "the recovered interiors of DDM cells is not implemented")
-        if self._ddm_mode and "frequency" in (info.get("constraints") or {}):
-            raise NotImplementedError('the "frequency" constraint needs simulation_type "FEM": the mass of the recovered '
-                                      "interiors of DDM cells is not implemented")
-        if self._ddm_mode and "peak_displacement" in (info.get("constraints") or {}):
-            raise NotImplementedError('the "peak_displacement" constraint needs simulation_type "FEM": the transient response '
-                                      "of the recovered interiors of DDM cells is not implemented")
-        if self._ddm_mode and "resonance_peak" in (info.get("constraints") or {}):
-            raise NotImplementedError('the "resonance_peak" constraint needs simulation_type "FEM": the frequency response '
-                                      "of the recovered interiors of DDM cells is not implemented")
+        for c in _RESPONSE_CONSTRAINTS:
+            if self._ddm_mode and c.key in (info.get("constraints") or {}):
+                raise NotImplementedError(f'the "{c.key}" constraint needs simulation_type "FEM": {c.reason}')
         comp = ((params.get("simulation_parameters", {}).get("DDM") or {}).get("schur_complement_computation") or {})
         if ddm_gradient is None:
             ddm_gradient = comp.get("gradient", "finite_difference") if self._ddm_mode else "finite_difference"
@@ -109,26 +141,12 @@ class LatticeOpti(LatticeSim):
                          "parameters": [], "timestamp": []}
         lat = self.lattice
         self._get_optimization_parameters(name_file)
-        self._last_stress = None
-        if "max_stress" in self.constraints_dict:
-            self._history["max_stress"] = []
-        self._last_buckling = None
-        if "buckling" in self.constraints_dict:
-            self._history["max_buckling"] = []
-        self._last_global_buckling = None
-        if "global_buckling" in self.constraints_dict:
-            self._history["min_load_factor"] = []
-        self._last_frequency = None
-        if "frequency" in self.constraints_dict:
-            self._history["min_frequency"] = []
-        self._last_peak_displacement = None
-        self._peak_cache = None             # (parameters, aggregate): the value and the gradient of one design share one call
-        if "peak_displacement" in self.constraints_dict:
-            self._history["peak_displacement"] = []
-        self._last_resonance_peak = None
-        self._resonance_cache = None        # (parameters, aggregate), as _peak_cache
-        if "resonance_peak" in self.constraints_dict:
-            self._history["resonance_peak"] = []
+        for c in _RESPONSE_CONSTRAINTS:
+            setattr(self, "_last_" + c.stem, None)
+            if c.key in self.constraints_dict:
+                self._history[c.history] = []
+        # (parameters, aggregate) of peak_displacement and resonance_peak: the value and the gradient of one design share one call
+        self._peak_cache = self._resonance_cache = None
         self._set_number_parameters_optimization()
         # strut -> (cell, type) of the LAST cell that holds it: Cell.change_beam_radius (cell.py:896-917) is called
         # cell after cell, so a strut shared by several cells ends with the last one's radius
@@ -644,17 +662,40 @@ class LatticeOpti(LatticeSim):
 
     def stress_constraint(self, r):
         """Phi_p / s_allow - 1 (<= 0 when feasible; Phi_p >= the largest von Mises stress of any strut station)."""
-        self._equilibrium_at(r)
-        return self.strut_stress_aggregate()[0] / self._stress_settings()[0] - 1.0
+        return self._constraint_value("max_stress", r)
 
     def stress_constraint_gradient(self, r):
         """d(stress_constraint)/d(theta): dPhi/dr_b = dPhi/dr_b at fixed u - lam^T (dK/dr_b) u with K lam = dPhi/du on the free
         dofs (lam = 0 on prescribed ones, which take no load), chained through Cell.get_radius and the parameterisation
         as the objective's gradient is."""
+        return self._constraint_gradient("max_stress", r)
+
+    # -- what the response constraints share (_RESPONSE_CONSTRAINTS) -------------------------------------------------------
+    def _constraint_limit(self, c):
+        return getattr(self, f"_{c.stem}_settings")()[0]
+
+    def _constraint_value(self, key, r):
+        c = next(c for c in _RESPONSE_CONSTRAINTS if c.key == key)
         self._equilibrium_at(r)
-        s_allow = self._stress_settings()[0]
-        _, _, dphi_du, dphi_dr = self.strut_stress_aggregate(want_grad=True)
-        return self._aggregate_gradient(dphi_du, dphi_dr) / s_allow
+        return c.scale(getattr(self, c.aggregate)()[0], self._constraint_limit(c)) - 1.0
+
+    def _constraint_gradient(self, key, r):
+        c = next(c for c in _RESPONSE_CONSTRAINTS if c.key == key)
+        self._equilibrium_at(r)
+        aggregate = getattr(self, c.aggregate)
+        out = aggregate() if c.gradient == "shared" else aggregate(want_grad=True)
+        g = self._aggregate_gradient(out[2], out[3]) if c.gradient == "partials" else self._strut_gradient_to_parameters(out[2])
+        return c.scale(g, self._constraint_limit(c))
+
+    def _cached_aggregate(self, cache, compute):
+        """compute() for the current design, unless the one-entry cache (an attribute's name) already holds it."""
+        key = tuple(map(float, self.actual_optimization_parameters)) if len(self.actual_optimization_parameters) else None
+        hit = getattr(self, cache)
+        if hit is not None and key is not None and hit[0] == key:
+            return hit[1]
+        res = compute()
+        setattr(self, cache, (key, res))
+        return res
 
     def _aggregate_gradient(self, dq_du, dq_dr):
         """dq/d(theta) of a scalar q(u(r), r) of the equilibrium from its partial derivatives: dq/dr_b = dq/dr_b at fixed u -
@@ -692,16 +733,12 @@ class LatticeOpti(LatticeSim):
 
     def buckling_constraint(self, r):
         """B_p / beta_allow - 1 (<= 0 when feasible; B_p >= the largest utilisation max(0, -N) / N_cr of any strut)."""
-        self._equilibrium_at(r)
-        return self.strut_buckling_aggregate()[0] / self._buckling_settings()[0] - 1.0
+        return self._constraint_value("buckling", r)
 
     def buckling_constraint_gradient(self, r):
         """d(buckling_constraint)/d(theta) by the adjoint chain of stress_constraint_gradient: dB/dr_b at fixed u -
         lam^T (dK/dr_b) u with K lam = dB/du on the free dofs."""
-        self._equilibrium_at(r)
-        b_allow = self._buckling_settings()[0]
-        _, _, dbp_du, dbp_dr = self.strut_buckling_aggregate(want_grad=True)
-        return self._aggregate_gradient(dbp_du, dbp_dr) / b_allow
+        return self._constraint_gradient("buckling", r)
 
     # -- global buckling constraint (FEM mode): p-norm of 1 / lambda_i, pl_buckling_modes + pl_buckling_modes_sens ------------
     def _global_buckling_settings(self):
@@ -725,14 +762,11 @@ class LatticeOpti(LatticeSim):
     def global_buckling_constraint(self, r):
         """lambda_min J_p - 1 (<= 0 when feasible: J_p >= 1 / lambda_1, so lambda_1 >= lambda_min then; -1 when no positive load
         factor exists)."""
-        self._equilibrium_at(r)
-        return self._global_buckling_settings()[0] * self.global_buckling_aggregate()[0] - 1.0
+        return self._constraint_value("global_buckling", r)
 
     def global_buckling_constraint_gradient(self, r):
         """d(global_buckling_constraint)/d(theta): lambda_min dJ/dr_b through the tail of _aggregate_gradient."""
-        self._equilibrium_at(r)
-        _, _, dJ_dr = self.global_buckling_aggregate(want_grad=True)
-        return self._global_buckling_settings()[0] * self._strut_gradient_to_parameters(dJ_dr)
+        return self._constraint_gradient("global_buckling", r)
 
     # -- frequency constraint (FEM mode): p-norm of 1 / omega_i^2, pl_vibration_modes + pl_vibration_modes_sens -------------------
     def _frequency_settings(self):
@@ -754,14 +788,11 @@ class LatticeOpti(LatticeSim):
 
     def frequency_constraint(self, r):
         """(2 pi f_min)^2 J_p - 1 (<= 0 when feasible: J_p >= 1 / omega_1^2, so f_1 >= f_min then)."""
-        self._equilibrium_at(r)
-        return (2.0 * np.pi * self._frequency_settings()[0]) ** 2 * self.frequency_aggregate()[0] - 1.0
+        return self._constraint_value("frequency", r)
 
     def frequency_constraint_gradient(self, r):
         """d(frequency_constraint)/d(theta): (2 pi f_min)^2 dJ/dr_b through _strut_gradient_to_parameters."""
-        self._equilibrium_at(r)
-        _, _, dJ_dr = self.frequency_aggregate(want_grad=True)
-        return (2.0 * np.pi * self._frequency_settings()[0]) ** 2 * self._strut_gradient_to_parameters(dJ_dr)
+        return self._constraint_gradient("frequency", r)
 
     # -- peak displacement constraint (FEM mode): p-norm over time of one output of the transient response, pl_transient_sens ------
     def _peak_displacement_settings(self):
@@ -776,26 +807,22 @@ class LatticeOpti(LatticeSim):
         """(J_p, max_n |y_n|, dJ/dr_b) of the current design under the constraint's transient run: y_n = l . u_n the output of
         row n, J_p = (sum_n |y_n|^p)^(1/p) >= max_n |y_n|.  One pl_transient_sens call gives all three (the forward pass and
         the adjoint sweep); the value and the gradient of one design share it."""
-        key = tuple(map(float, self.actual_optimization_parameters)) if len(self.actual_optimization_parameters) else None
-        if self._peak_cache is not None and key is not None and self._peak_cache[0] == key:
-            return self._peak_cache[1]
-        _, run, kw, output, p = self._peak_displacement_settings()
-        self._transient_settings = self._transient_setup("peak_displacement", kw=kw, **run)
-        out = self.transient_sensitivity(output, kind=2, p=p)
-        res = (out["J"], float(np.abs(out["y"]).max()), out["dJ_dr"])
-        self._last_peak_displacement = res[:2]
-        self._peak_cache = (key, res)
-        return res
+        def run_once():
+            _, run, kw, output, p = self._peak_displacement_settings()
+            self._transient_settings = self._transient_setup("peak_displacement", kw=kw, **run)
+            out = self.transient_sensitivity(output, kind=2, p=p)
+            res = (out["J"], float(np.abs(out["y"]).max()), out["dJ_dr"])
+            self._last_peak_displacement = res[:2]
+            return res
+        return self._cached_aggregate("_peak_cache", run_once)
 
     def peak_displacement_constraint(self, r):
         """J_p / max_displacement - 1 (<= 0 when feasible: J_p >= max_n |y_n|, so the peak stays below max_displacement then)."""
-        self._equilibrium_at(r)
-        return self.peak_displacement_aggregate()[0] / self._peak_displacement_settings()[0] - 1.0
+        return self._constraint_value("peak_displacement", r)
 
     def peak_displacement_constraint_gradient(self, r):
         """d(peak_displacement_constraint)/d(theta): dJ/dr_b / max_displacement through _strut_gradient_to_parameters."""
-        self._equilibrium_at(r)
-        return self._strut_gradient_to_parameters(self.peak_displacement_aggregate()[2]) / self._peak_displacement_settings()[0]
+        return self._constraint_gradient("peak_displacement", r)
 
     # -- resonance peak constraint (FEM mode): p-norm over a band of one output of the frequency response, pl_harmonic_sens ---------
     def _resonance_peak_settings(self):
@@ -810,27 +837,23 @@ class LatticeOpti(LatticeSim):
         """(J_p, max_k |y_k|, dJ/dr_b) of the current design over the constraint's frequencies: y_k = l^T u_k the output at
         frequency k, J_p = (sum_k |y_k|^p)^(1/p) >= max_k |y_k|.  One pl_harmonic_sens call gives all three (the fields and
         the adjoint fields in the same passes); the value and the gradient of one design share it."""
-        key = tuple(map(float, self.actual_optimization_parameters)) if len(self.actual_optimization_parameters) else None
-        if self._resonance_cache is not None and key is not None and self._resonance_cache[0] == key:
-            return self._resonance_cache[1]
-        _, run, kw, output, p = self._resonance_peak_settings()
-        self._dynamics_guard("resonance_peak")
-        self._frf_settings = self._frf_setup(kw=kw, **run)
-        out = self.frequency_response_sensitivity(output, kind=2, p=p)
-        res = (out["J"], float(np.abs(out["y"]).max()), out["dJ_dr"])
-        self._last_resonance_peak = res[:2]
-        self._resonance_cache = (key, res)
-        return res
+        def run_once():
+            _, run, kw, output, p = self._resonance_peak_settings()
+            self._dynamics_guard("resonance_peak")
+            self._frf_settings = self._frf_setup(kw=kw, **run)
+            out = self.frequency_response_sensitivity(output, kind=2, p=p)
+            res = (out["J"], float(np.abs(out["y"]).max()), out["dJ_dr"])
+            self._last_resonance_peak = res[:2]
+            return res
+        return self._cached_aggregate("_resonance_cache", run_once)
 
     def resonance_peak_constraint(self, r):
         """J_p / max_amplitude - 1 (<= 0 when feasible: J_p >= max_k |y_k|, so the peak stays below max_amplitude then)."""
-        self._equilibrium_at(r)
-        return self.resonance_peak_aggregate()[0] / self._resonance_peak_settings()[0] - 1.0
+        return self._constraint_value("resonance_peak", r)
 
     def resonance_peak_constraint_gradient(self, r):
         """d(resonance_peak_constraint)/d(theta): dJ/dr_b / max_amplitude through _strut_gradient_to_parameters."""
-        self._equilibrium_at(r)
-        return self._strut_gradient_to_parameters(self.resonance_peak_aggregate()[2]) / self._resonance_peak_settings()[0]
+        return self._constraint_gradient("resonance_peak", r)
 
     # -- driver (SciPy SLSQP, as the reference) ---------------------------------------------------------------------
     def _initialize_optimization_solver(self):
@@ -856,21 +879,10 @@ class LatticeOpti(LatticeSim):
         self._history["objective_norm"].append(self.actual_objective)
         self._history["objective"].append(self.denorm_objective)
         self._history["relative_density"].append(self.relative_density())
-        if "max_stress" in self._history:
-            self._history["max_stress"].append(None if self._last_stress is None else self._last_stress[1])
-        if "max_buckling" in self._history:
-            self._history["max_buckling"].append(None if self._last_buckling is None else self._last_buckling[1])
-        if "min_load_factor" in self._history:
-            self._history["min_load_factor"].append(None if self._last_global_buckling is None
-                                                    else self._last_global_buckling[1])
-        if "min_frequency" in self._history:
-            self._history["min_frequency"].append(None if self._last_frequency is None else self._last_frequency[1])
-        if "peak_displacement" in self._history:
-            self._history["peak_displacement"].append(None if self._last_peak_displacement is None
-                                                      else self._last_peak_displacement[1])
-        if "resonance_peak" in self._history:
-            self._history["resonance_peak"].append(None if self._last_resonance_peak is None
-                                                   else self._last_resonance_peak[1])
+        for c in _RESPONSE_CONSTRAINTS:
+            if c.history in self._history:
+                last = getattr(self, "_last_" + c.stem)
+                self._history[c.history].append(None if last is None else last[1])
         self._history["parameters"].append(list(map(float, r)))
         self._history["timestamp"].append(time.time())
 
@@ -887,24 +899,10 @@ class LatticeOpti(LatticeSim):
             mode = self.constraints_dict["relative_density"].get("mode", "upper")
             lb, ub = {"upper": (-np.inf, 0.0), "lower": (0.0, np.inf), "eq": (0.0, 0.0)}.get(mode, (-np.inf, 0.0))
             self.constraints.append(NonlinearConstraint(self.density_constraint, lb, ub))
-        if "max_stress" in self.constraints_dict:
-            jac = {"jac": self.stress_constraint_gradient} if self.enable_gradient_computing else {}
-            self.constraints.append(NonlinearConstraint(self.stress_constraint, -np.inf, 0.0, **jac))
-        if "buckling" in self.constraints_dict:
-            jac = {"jac": self.buckling_constraint_gradient} if self.enable_gradient_computing else {}
-            self.constraints.append(NonlinearConstraint(self.buckling_constraint, -np.inf, 0.0, **jac))
-        if "global_buckling" in self.constraints_dict:
-            jac = {"jac": self.global_buckling_constraint_gradient} if self.enable_gradient_computing else {}
-            self.constraints.append(NonlinearConstraint(self.global_buckling_constraint, -np.inf, 0.0, **jac))
-        if "frequency" in self.constraints_dict:
-            jac = {"jac": self.frequency_constraint_gradient} if self.enable_gradient_computing else {}
-            self.constraints.append(NonlinearConstraint(self.frequency_constraint, -np.inf, 0.0, **jac))
-        if "peak_displacement" in self.constraints_dict:
-            jac = {"jac": self.peak_displacement_constraint_gradient} if self.enable_gradient_computing else {}
-            self.constraints.append(NonlinearConstraint(self.peak_displacement_constraint, -np.inf, 0.0, **jac))
-        if "resonance_peak" in self.constraints_dict:
-            jac = {"jac": self.resonance_peak_constraint_gradient} if self.enable_gradient_computing else {}
-            self.constraints.append(NonlinearConstraint(self.resonance_peak_constraint, -np.inf, 0.0, **jac))
+        for c in _RESPONSE_CONSTRAINTS:
+            if c.key in self.constraints_dict:
+                jac = {"jac": getattr(self, c.stem + "_constraint_gradient")} if self.enable_gradient_computing else {}
+                self.constraints.append(NonlinearConstraint(getattr(self, c.stem + "_constraint"), -np.inf, 0.0, **jac))
         kw = dict(fun=self.objective, x0=self.initial_parameters, method="SLSQP", bounds=self.bounds,
                   constraints=self.constraints, callback=self.callback_function,
                   options={"maxiter": self.optim_max_iteration, "ftol": self.optim_ftol, "disp": self.optim_disp,
