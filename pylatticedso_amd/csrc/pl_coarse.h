@@ -1740,11 +1740,62 @@ __global__ __launch_bounds__(kBlock) void k_pcg_direction_coarse(const int32_t *
 
 // The same update with a flat mapping (no rank-local level): one lane per PAIR of vector entries (three lanes per
 // node), so a wave's loads and stores of r, p, x are 1 KB contiguous (the per-tile kernel strides lanes by 48 bytes and
-// leaves the last wave of a 152-node tile at 24 of 64 lanes); the tile's and the aggregate's coefficients come through
-// the caches, the same address for almost every lane of a wave.  50^3 Octet: iteration 99.4 -> 97.0 us.
+// leaves the last wave of a 152-node tile at 24 of 64 lanes).  50^3 Octet: iteration 99.4 -> 97.0 us.
+// Two levels of loads.  Level 1, requested together before anything is waited for: the scalar slots, the node's tile and
+// word, and the pairs of r, p, x (with node elimination keep[slot] comes one level earlier).  Level 2: the coefficients,
+// through the scalar path.  A wave covers 21 nodes, a tile holds about 152, so most waves lie in one tile: the wave takes the
+// tile of its first lane that has none yet (v_readlane), fetches agg_of_tile, the aggregate's row of y_c and the tile's row
+// of y_t with scalar loads - twelve values in SGPRs instead of twelve loads of one address by 64 lanes - and hands
+// C = y_c + y_t to the lanes of that tile; a wave that straddles tiles goes round once per tile (two or three times on the
+// 16-node tiles of the tests).  One text, one arithmetic, whatever the tile size; the lever-arm products follow the loop.
+// What is fixed for a handle is a template parameter, chosen in launch_direction_flat: ARMS = where the lever arms come
+// from (bytes of the node word / rel32 / xyz - cen), DTAB = D^-1 from the class table of the node words, YT = a tile
+// level, KEEP = node elimination, SHARED = several ranks (nodes shared with other ranks take no tile coefficients).
+// The arithmetic is the same text in every variant.
+// Lanes past the end repeat the last pair's loads and store nothing, so that no load sits behind a divergent branch.
+// The scalar path rests on two things no test can see - the results are the same without them, only slower: the casts
+// of the three tables to the constant address space (uniform_ptr) and the copy of t0 behind an empty asm in the loop.  How to
+// notice that a compiler has folded the loads back into per-lane ones: `make resource-usage` of the headline instantiation
+// <double, double, 12, kArmsBytes, true, true, false, false> says 60 VGPRs, 66 SGPRs, no scratch, 8 waves per SIMD (per-lane
+// coefficient loads: 71 - 82 VGPRs, under 50 SGPRs), its disassembly holds s_load_dwordx4 / x8 / x16 inside the loop and
+// 10 global_load, and the kernel takes 21.6 us at 50^3 Octet (24.4 us before).  Cost of the variants: 96
+// instantiations, 8 s of the 80 s the library takes to compile.  With SHARED `own` differs from lane to lane, the sum
+// C = y_c + y_t is formed in vector registers before it is handed out, and those variants hold 82 - 90 VGPRs (5 waves per
+// SIMD); the multi-rank path is covered by the loopback tests for its results, its time has not been measured.
 // (All six components are formed and the lane's pair selected afterwards: an if / else-if chain over the pair index with
 // the strain terms inside was miscompiled by hipcc 7.2 for TM = 12 - components 4, 5 came out as 0 / garbage.)
-template <typename PT, typename RT, int TM>
+constexpr int kArmsBytes = 0, kArmsRel32 = 1, kArmsXyz = 2;
+// (the constant address space, with an index the compiler knows to be wave-uniform: scalar loads)
+template <typename T>
+using uniform_ptr = const __attribute__((address_space(4))) T *;
+// C = y_c (+ y_t where add_tile) of tile tt (wave-uniform), a = the tile's aggregate
+template <int TM, bool YT>
+__device__ __forceinline__ void flat_coefficients(int tt, uniform_ptr<int32_t> agg_of_tile, uniform_ptr<double> yc,
+                                                  uniform_ptr<double> yt, int cm, bool add_tile, int &a, double (&C)[12]) {
+  a = agg_of_tile[tt];
+  uniform_ptr<double> y = yc + cm * a;
+#pragma unroll
+  for (int m = 0; m < 6; ++m) C[m] = y[m];
+#pragma unroll
+  for (int m = 6; m < 12; ++m) C[m] = 0.0;
+  if constexpr (TM == 12) {
+    const bool strains = cm == 12;                 // (12-mode dense level: the aggregate's strains; else the row ends at 6)
+    uniform_ptr<double> ys = y + (strains ? 6 : 0);
+#pragma unroll
+    for (int m = 0; m < 6; ++m) {
+      const double v = ys[m];
+      C[6 + m] = strains ? v : 0.0;
+    }
+  }
+  if constexpr (YT) {                  // same reference point: the tile's coefficients add to the aggregate's (several
+    uniform_ptr<double> w = yt + TM * (size_t)tt;   // GPUs: on this rank's own nodes only, as in k_pcg_direction_coarse)
+    if (add_tile) {
+#pragma unroll
+      for (int m = 0; m < TM; ++m) C[m] += w[m];
+    }
+  }
+}
+template <typename PT, typename RT, int TM, int ARMS, bool DTAB, bool YT, bool KEEP, bool SHARED>
 __global__ __launch_bounds__(kBlock) void k_pcg_direction_flat(int64_t N, const int32_t *__restrict__ tile_of_node,
                                                                const RT *__restrict__ r,
                                                                const float *__restrict__ dinv32,
@@ -1752,80 +1803,100 @@ __global__ __launch_bounds__(kBlock) void k_pcg_direction_flat(int64_t N, const 
                                                                const int32_t *__restrict__ agg_of_tile,
                                                                const double *__restrict__ cen,
                                                                const double *__restrict__ yc,
-                                                               const double *__restrict__ yt /* may be null */,
+                                                               const double *__restrict__ yt /* YT */,
                                                                const uint8_t *__restrict__ fixedbits,
                                                                PT *__restrict__ p, RT *__restrict__ x,
                                                                const double *__restrict__ scal,
                                                                double *__restrict__ scal_next,
                                                                double *__restrict__ hist, int k,
                                                                double *__restrict__ rc, int ncp,
-                                                               const int32_t *__restrict__ keep /* may be null */,
-                                                               int cm, const uint8_t *__restrict__ shared /* may be null */,
-                                                               const float *__restrict__ rel32 = nullptr /* Coarse::rel32 */,
-                                                               const uint32_t *__restrict__ nword = nullptr,
-                                                               const uint32_t *__restrict__ dtab = nullptr,
-                                                               double rscale = 0.0 /* as in k_pcg_update_tile */) {
+                                                               const int32_t *__restrict__ keep /* KEEP */,
+                                                               int cm, const uint8_t *__restrict__ shared /* SHARED */,
+                                                               const float *__restrict__ rel32 /* Coarse::rel32 */,
+                                                               const uint32_t *__restrict__ nword,
+                                                               const uint32_t *__restrict__ dtab /* DTAB */,
+                                                               double rscale /* as in k_pcg_update_tile */) {
   // keep: with node elimination (opts.condense) N counts the nodes that stay unknowns and keep[] lists them - the lanes
   // map onto those only (a flag test per node left half of the lanes of a BCC lattice idle: 80 us for 1.03 M kept nodes at
   // 100^3 against 26 us for 0.5 M nodes of the Octet lattice)
-  double old, rz_new, pap;
-  scalar_read3(scal, S_RZ_OLD, S_RZ_NEW, S_PAP, old, rz_new, pap);
-  const double beta = (old != 0.0) ? rz_new / old : 0.0;
-  const double alpha = (pap != 0.0) ? old / pap : 0.0;
-  if (blockIdx.x == 1 || gridDim.x == 1)
-    for (int e = threadIdx.x; e < ncp; e += blockDim.x) rc[e] = 0.0;
-  if (blockIdx.x == 0 && threadIdx.x < kWave) {
-    const int s = threadIdx.x;
-    double rr = 0.0;
-    for (int q = s; q < kSlots; q += kWave) rr += rc[ncp + q];
-    rr = wave_sum(rr);
-    if (s == 0) hist[k] = rr;
-    for (int q = s; q < kSlots; q += kWave) {
-      rc[ncp + q] = 0.0;
-      rc[ncp + kSlots + q] = 0.0;
-      scal_next[S_RZ_OLD * kSlots + q] = scal[S_RZ_NEW * kSlots + q];
-      scal_next[S_RZ_NEW * kSlots + q] = 0.0;
-      scal_next[S_PAP * kSlots + q] = 0.0;
-    }
-  }
-  const int64_t lane_pair = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (lane_pair >= 3 * N) return;
-  const int64_t slot = lane_pair / 3;
-  const int q = (int)(lane_pair - 3 * slot);
-  const int64_t i = keep ? (int64_t)keep[slot] : slot;
+  // (the 64-bit division by three on the block's first pair, in scalar registers; the lane's share of it in 32 bits)
+  const int64_t pair0 = (int64_t)blockIdx.x * kBlock;
+  const int64_t slot0 = pair0 / 3;
+  const int local = (int)(pair0 - 3 * slot0) + (int)threadIdx.x;
+  const bool live = pair0 + threadIdx.x < 3 * N;
+  const int64_t slot = live ? slot0 + local / 3 : N - 1;
+  const int q = live ? local % 3 : 2;
+  const int64_t i = KEEP ? (int64_t)keep[slot] : slot;
   const int64_t pair = 3 * i + q;
+  // level 1
+  const ScalarSlots3 slots = scalar_slots3(scal, S_RZ_OLD, S_RZ_NEW, S_PAP);      // (reduced below: scalar_sum3)
   const int t = tile_of_node[i];
-  const int a = agg_of_tile[t];
-  const double *y = yc + cm * a;
-  double C[12];
-#pragma unroll
-  for (int m = 0; m < 6; ++m) C[m] = y[m];
-#pragma unroll
-  for (int m = 6; m < 12; ++m) C[m] = 0.0;
-  if constexpr (TM == 12) {
-    if (cm == 12) {
-#pragma unroll
-      for (int m = 6; m < 12; ++m) C[m] = y[m];
-    }
-  }
-  if (yt && !(shared && shared[i])) {   // same reference point: the tile's coefficients add to the aggregate's (several
-    const double *w = yt + TM * (size_t)t;   // GPUs: on this rank's own nodes only, as in k_pcg_direction_coarse)
-#pragma unroll
-    for (int m = 0; m < TM; ++m) C[m] += w[m];
-  }
-  const uint32_t nw = nword ? nword[i] : 0u;
+  const uint32_t nw = (ARMS == kArmsBytes || DTAB) ? nword[i] : 0u;
+  const double2 rr = load_pair(r, pair);
+  double2 pp = load_pair(p, pair);
+  double2 xx = load_pair(x, pair);
+  bool own = true;
+  if constexpr (SHARED) own = !shared[i];
   double rx, ry, rz;
-  if (rscale != 0.0) {
+  if constexpr (ARMS == kArmsBytes) {
     nword_rel(nw, rscale, rx, ry, rz);
-  } else if (rel32) {
+  } else if constexpr (ARMS == kArmsRel32) {
     rx = (double)rel32[3 * i];
     ry = (double)rel32[3 * i + 1];
     rz = (double)rel32[3 * i + 2];
   } else {
-    rx = xyz[3 * i] - cen[3 * a];
-    ry = xyz[3 * i + 1] - cen[3 * a + 1];
-    rz = xyz[3 * i + 2] - cen[3 * a + 2];
+    rx = xyz[3 * i];
+    ry = xyz[3 * i + 1];
+    rz = xyz[3 * i + 2];
   }
+  unsigned fb;
+  float2 dd;
+  if constexpr (!DTAB) {
+    fb = (unsigned)fixedbits[i];
+    dd = reinterpret_cast<const float2 *>(dinv32)[pair];
+  }
+  if constexpr (DTAB) {
+    const uint32_t *row = dtab + 8 * (nw >> 24);                         // (the class row carries the Dirichlet bits too)
+    fb = row[6];
+    dd = reinterpret_cast<const float2 *>(row)[q];
+  }
+  // level 2: one round per tile of the wave (every lane stays in the loop: the mask of lanes without coefficients is uniform)
+  double C[12], cx = 0.0, cy = 0.0, cz = 0.0;
+#pragma unroll
+  for (int m = 0; m < 12; ++m) C[m] = 0.0;
+  uint64_t rest = __builtin_amdgcn_ballot_w64(true);
+  do {
+    const int t0 = __builtin_amdgcn_readlane(t, (int)__builtin_ctzll(rest));
+    // (compared through a copy the compiler cannot see through: knowing t == t0 inside the branch it would form the
+    // addresses from the lane's own t and turn the scalar loads into per-lane ones)
+    int t0_seen = t0;
+    asm volatile("" : "+s"(t0_seen));
+    const bool mine = t == t0_seen;
+    int a0;
+    double C0[12];
+    flat_coefficients<TM, YT>(t0, (uniform_ptr<int32_t>)agg_of_tile, (uniform_ptr<double>)yc, (uniform_ptr<double>)yt, cm, own,
+                              a0, C0);
+    if (mine) {
+#pragma unroll
+      for (int m = 0; m < 12; ++m) C[m] = C0[m];
+      if constexpr (ARMS == kArmsXyz) {
+        uniform_ptr<double> ce = (uniform_ptr<double>)cen + 3 * a0;
+        cx = ce[0];
+        cy = ce[1];
+        cz = ce[2];
+      }
+    }
+    rest &= ~__builtin_amdgcn_ballot_w64(mine);
+  } while (rest != 0);
+  if constexpr (ARMS == kArmsXyz) {
+    rx -= cx;
+    ry -= cy;
+    rz -= cz;
+  }
+  double old, rz_new, pap;
+  scalar_sum3(slots, old, rz_new, pap);
+  const double beta = (old != 0.0) ? rz_new / old : 0.0;
+  const double alpha = (pap != 0.0) ? old / pap : 0.0;
   double zc[6] = {C[0] + (C[4] * rz - C[5] * ry), C[1] + (C[5] * rx - C[3] * rz), C[2] + (C[3] * ry - C[4] * rx),
                   C[3], C[4], C[5]};
   if constexpr (TM == 12) {
@@ -1835,20 +1906,33 @@ __global__ __launch_bounds__(kBlock) void k_pcg_direction_flat(int64_t N, const 
   }
   double z0 = q == 0 ? zc[0] : (q == 1 ? zc[2] : zc[4]);
   double z1 = q == 0 ? zc[1] : (q == 1 ? zc[3] : zc[5]);
-  const uint32_t *row = dtab ? dtab + 8 * (nw >> 24) : nullptr;          // (the class row carries the Dirichlet bits too)
-  const unsigned fb = dtab ? row[6] : (unsigned)fixedbits[i];
-  const float2 dd = dtab ? reinterpret_cast<const float2 *>(row)[q] : reinterpret_cast<const float2 *>(dinv32)[pair];
-  const double2 rr = load_pair(r, pair);
-  double2 pp = load_pair(p, pair);
-  double2 xx = load_pair(x, pair);
   xx.x += alpha * pp.x;
   xx.y += alpha * pp.y;
-  store_pair(x, pair, xx);
   z0 = dd.x * rr.x + (((fb >> (2 * q)) & 1u) ? 0.0 : z0);
   z1 = dd.y * rr.y + (((fb >> (2 * q + 1)) & 1u) ? 0.0 : z1);
   pp.x = z0 + beta * pp.x;
   pp.y = z1 + beta * pp.y;
-  store_pair(p, pair, pp);
+  if (live) {
+    store_pair(x, pair, xx);
+    store_pair(p, pair, pp);
+  }
+  // housekeeping of the iteration, behind the streamed work: only blocks 0 and 1 ever wait for it
+  if (blockIdx.x == 1 || gridDim.x == 1)
+    for (int e = threadIdx.x; e < ncp; e += blockDim.x) rc[e] = 0.0;
+  if (blockIdx.x == 0 && threadIdx.x < kWave) {
+    const int s = threadIdx.x;
+    double sum = 0.0;
+    for (int e = s; e < kSlots; e += kWave) sum += rc[ncp + e];
+    sum = wave_sum(sum);
+    if (s == 0) hist[k] = sum;
+    for (int e = s; e < kSlots; e += kWave) {
+      rc[ncp + e] = 0.0;
+      rc[ncp + kSlots + e] = 0.0;
+      scal_next[S_RZ_OLD * kSlots + e] = scal[S_RZ_NEW * kSlots + e];
+      scal_next[S_RZ_NEW * kSlots + e] = 0.0;
+      scal_next[S_PAP * kSlots + e] = 0.0;
+    }
+  }
 }
 
 }  // namespace pl

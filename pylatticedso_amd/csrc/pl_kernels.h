@@ -85,13 +85,24 @@ __device__ __forceinline__ void scalar_read2(const double *scal, int a, int b, d
   va = wave_sum(xa);
   vb = wave_sum(xb);
 }
-__device__ __forceinline__ void scalar_read3(const double *scal, int a, int b, int c, double &va, double &vb, double &vc) {
+// The two halves of scalar_read3 for a kernel that has other loads to request between them: the lane's slot of each scalar
+// (three loads, nothing waited for), and the totals.  One definition of how a scalar is summed: every kernel that forms
+// alpha or beta must form the same bits from the same slots.
+struct ScalarSlots3 {
+  double a, b, c;
+};
+__device__ __forceinline__ ScalarSlots3 scalar_slots3(const double *scal, int a, int b, int c) {
   static_assert(kSlots == kWave, "one slot per lane");
   const int lane = threadIdx.x & 63;
-  const double xa = scal[a * kSlots + lane], xb = scal[b * kSlots + lane], xc = scal[c * kSlots + lane];
-  va = wave_sum(xa);
-  vb = wave_sum(xb);
-  vc = wave_sum(xc);
+  return {scal[a * kSlots + lane], scal[b * kSlots + lane], scal[c * kSlots + lane]};
+}
+__device__ __forceinline__ void scalar_sum3(const ScalarSlots3 &s, double &va, double &vb, double &vc) {
+  va = wave_sum(s.a);
+  vb = wave_sum(s.b);
+  vc = wave_sum(s.c);
+}
+__device__ __forceinline__ void scalar_read3(const double *scal, int a, int b, int c, double &va, double &vb, double &vc) {
+  scalar_sum3(scalar_slots3(scal, a, b, c), va, vb, vc);
 }
 
 // Sum over the block, result valid in thread 0.

@@ -54,6 +54,12 @@ inline void with_tile_modes(const pl_context *c, F &&f) {
   if (tile_modes_now(c) == 12) f(Int<12>{});
   else f(Int<6>{});
 }
+// f(flag): a run-time yes / no as a compile-time constant
+template <typename F>
+inline void with_flag(bool b, F &&f) {
+  if (b) f(std::true_type{});
+  else f(std::false_type{});
+}
 // f(tm, multi, local): MULTI = several ranks or a rank-local dense level, LOCAL = the rank-local level (k_pcg_update_tile)
 template <typename F>
 inline void with_tail_variant(const pl_context *c, F &&f) {
@@ -120,13 +126,33 @@ void launch_direction_flat(pl_context *c, Int<TM>, PT *p, RT *x, const RT *r, do
                            const NodeWords &nw) {
   pl::Coarse &cs = c->coarse;
   const int64_t n_flat = c->cond_use ? c->N - c->n_cond : c->N;       // nodes that are unknowns of this CG
-  hipLaunchKernelGGL((pl::k_pcg_direction_flat<PT, RT, TM>), dim3((unsigned)((3 * n_flat + pl::kBlock - 1) / pl::kBlock)),
-                     dim3(pl::kBlock), 0, c->stream, n_flat, cs.tile_of_node.p, r, cs.dinv32, c->xyz.p, cs.agg_of_tile.p,
-                     cs.cen.p, cs.yc, cs.tile_level ? (const double *)cs.yt : (const double *)nullptr, c->fixedbits.p, p, x,
-                     cur, nxt, c->hist.p, hist_slot, cs.rc, cs.ncp,
-                     c->cond_use ? (const int32_t *)c->ckeep.p : (const int32_t *)nullptr, cs.cm,
-                     c->dist.active ? (const uint8_t *)c->sharedbits.p : (const uint8_t *)nullptr, nw.rel32, nw.nword, nw.dtab,
-                     nw.rscale);
+  // what is fixed for the handle is compiled in: where the lever arms come from, the class table, the tile level, node
+  // elimination, several ranks
+  auto go = [&](auto arms, auto dt, auto yt, auto keep, auto sh) {
+    hipLaunchKernelGGL((pl::k_pcg_direction_flat<PT, RT, TM, decltype(arms)::value, decltype(dt)::value, decltype(yt)::value,
+                                                 decltype(keep)::value, decltype(sh)::value>),
+                       dim3((unsigned)((3 * n_flat + pl::kBlock - 1) / pl::kBlock)), dim3(pl::kBlock), 0, c->stream, n_flat,
+                       cs.tile_of_node.p, r, cs.dinv32, c->xyz.p, cs.agg_of_tile.p, cs.cen.p, cs.yc,
+                       cs.tile_level ? (const double *)cs.yt : (const double *)nullptr, c->fixedbits.p, p, x, cur, nxt,
+                       c->hist.p, hist_slot, cs.rc, cs.ncp,
+                       c->cond_use ? (const int32_t *)c->ckeep.p : (const int32_t *)nullptr, cs.cm,
+                       c->dist.active ? (const uint8_t *)c->sharedbits.p : (const uint8_t *)nullptr, nw.rel32, nw.nword,
+                       nw.dtab, nw.rscale);
+  };
+  auto with_arms = [&](auto &&f) {
+    if (nw.rscale != 0.0) f(Int<pl::kArmsBytes>{});
+    else if (nw.rel32) f(Int<pl::kArmsRel32>{});
+    else f(Int<pl::kArmsXyz>{});
+  };
+  with_arms([&](auto arms) {
+    with_flag(nw.dtab != nullptr, [&](auto dt) {
+      with_flag(cs.tile_level, [&](auto yt) {
+        with_flag(c->cond_use, [&](auto keep) {
+          with_flag(c->dist.active, [&](auto sh) { go(arms, dt, yt, keep, sh); });
+        });
+      });
+    });
+  });
 }
 
 // Everything of a two-level PCG iteration after K*p: update + restriction, coarse solve, new direction.
@@ -146,9 +172,14 @@ int pcg_tail_coarse_t(pl_context *c, double *cur, double *nxt, int hist_slot, PT
   pl::coarse_apply(cs, cs.rc, cs.tv, cs.yc, cur + pl::S_RZ_NEW * pl::kSlots, cs.rc + cs.ncp + pl::kSlots, c->stream);
   // flat mapping: fp64 p without a rank-local level (measured on one box, 50^3 Octet: 26.2 -> 24.5 us;
   // fp32 p / fp64 r the same either way, fp32 p / fp32 r 19.0 -> 22.0 us - 8-byte loads per lane are too few in flight)
-  if (!useL && sizeof(PT) == 8)
-    with_tile_modes(c, [&](auto tm) { launch_direction_flat(c, tm, p, x, (const RT *)r, cur, nxt, hist_slot, nw); });
-  else
+  bool flat = false;
+  if constexpr (sizeof(PT) == 8) {
+    if (!useL) {
+      flat = true;
+      with_tile_modes(c, [&](auto tm) { launch_direction_flat(c, tm, p, x, (const RT *)r, cur, nxt, hist_slot, nw); });
+    }
+  }
+  if (!flat)
     with_tail_variant(c, [&](auto tm, auto multi, auto local) {
       launch_direction_coarse(c, tm, multi, local, p, x, (const RT *)r, cur, nxt, hist_slot, nw);
     });
