@@ -43,22 +43,17 @@ inline void converged_at(pl_stats_t *st, int iterations, double stop_reason) {
 
 // ----------------------------------------------------------------------------------------------------------
 // Launches of the iteration's tail kernels: every kernel's argument list is written once, in its launch_* function, and the
-// compile-time variant is chosen by one of the two dispatchers below, which hand it to a generic lambda as constants.
+// compile-time variant is chosen by a dispatcher (pl_dispatch.h and the two below), which hands it to a generic lambda as
+// constants.
 // ----------------------------------------------------------------------------------------------------------
-template <int V>
-using Int = std::integral_constant<int, V>;
+using pl::Int;
+using pl::with_flag;
 
 // f(tm): modes of the tile level, 6 or 12
 template <typename F>
 inline void with_tile_modes(const pl_context *c, F &&f) {
   if (tile_modes_now(c) == 12) f(Int<12>{});
   else f(Int<6>{});
-}
-// f(flag): a run-time yes / no as a compile-time constant
-template <typename F>
-inline void with_flag(bool b, F &&f) {
-  if (b) f(std::true_type{});
-  else f(std::false_type{});
 }
 // f(tm, multi, local): MULTI = several ranks or a rank-local dense level, LOCAL = the rank-local level (k_pcg_update_tile)
 template <typename F>
@@ -279,14 +274,14 @@ int small_iteration(pl_context *c, int k) {
   const pl::Rec5 *r5 = stream_form ? reinterpret_cast<const pl::Rec5 *>(c->rec5.p) : (const pl::Rec5 *)nullptr;
   if (c->cond_use) {   // (the first pass of S p with the direction formed in the kernel, the second as in apply_operator)
     const pl::CondSolve cs = cond_solve(c, pl::kEndsCondensedSolve);
-    if (!pl::launch_tile_spmv_lds_defer(c->tile, vw, tab, n_tab, r5, nullptr, df.p_new, nullptr, c->stream,
-                                        pl::kEndsCondensedSolve, c->cflag.p, cs, df))
+    if (!pl::launch_tile_spmv_lds<double>(c->tile, vw, tab, n_tab, r5, nullptr, nullptr, df.p_new, nullptr, c->stream,
+                                          pl::kEndsCondensedSolve, c->cflag.p, cs, nullptr, 0, &df))
       return fail(PL_ERR_STATE, "short iteration: the LDS-resident K*p does not fit this lattice");
     int rc = launch_spmv(c, df.p_new, c->Ap.p, true, dot, c->maskC.p, pl::kEndsOthers);
     if (rc) return rc;
   } else {
-    if (!pl::launch_tile_spmv_lds_defer(c->tile, vw, tab, n_tab, r5, c->fixedbits.p, c->Ap.p, dot, c->stream, pl::kEndsAll,
-                                        nullptr, pl::CondSolve(), df))
+    if (!pl::launch_tile_spmv_lds<double>(c->tile, vw, tab, n_tab, r5, c->fixedbits.p, nullptr, c->Ap.p, dot, c->stream,
+                                          pl::kEndsAll, nullptr, pl::CondSolve(), nullptr, 0, &df))
       return fail(PL_ERR_STATE, "short iteration: the LDS-resident K*p does not fit this lattice");
   }
   return small_tail(c, k, k);

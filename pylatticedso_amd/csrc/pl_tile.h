@@ -24,6 +24,7 @@
 #include <type_traits>
 #include <vector>
 
+#include "pl_dispatch.h"
 #include "pl_kernels.h"
 #include "pl_parallel.h"
 
@@ -518,6 +519,58 @@ __device__ __forceinline__ void tile_strut(int64_t b, const int2 c, const unsign
   }
 }
 
+// Everything after the second barrier of a tile kernel, for all three of them: the tile's rows of the LDS accumulator ys
+// become rows of y.  kEndsCondensedSolve: v = -K_cc^-1 (accumulated row) for each condensed node of the tile (sbase: the
+// nodes' blocks in cs.inv, staged before the strut loops - no dependent load here).  Every other pass: the rows of the
+// pass's kind, the Dirichlet mask, the store, and the fused dot x.y reduced over the workgroup into one slot of dot_out.
+// What differs between the kernels comes as arguments: `condensed(node)` = the node's flag from wherever the kernel keeps
+// it (cflag in global memory / sflag in LDS), `xpair(i)` = pair i of the tile's rows of x (global memory / the staged
+// rows), BLOCK = the workgroup size (red: BLOCK / kWave doubles of LDS).
+template <bool MASK, bool DOT, int ENDS, int BLOCK, typename VT, typename Condensed, typename XPair>
+__device__ __forceinline__ void tile_epilogue(const double *ys, int stride, int n0, int nn, const int32_t *sbase,
+                                              const CondSolve &cs, const uint8_t *fixedbits, VT *y, double *dot_out, double *red,
+                                              Condensed condensed, XPair xpair) {
+  if (ENDS == kEndsCondensedSolve) {
+    for (int i = threadIdx.x; i < nn * 6; i += BLOCK) {
+      const int node = i / 6, k = i - 6 * node;
+      const int32_t b0 = sbase[node];
+      if (b0 < 0) continue;
+      const double *A = cs.inv + b0 + 6 * k;
+      double v = 0.0;
+#pragma unroll
+      for (int j = 0; j < 6; ++j) v += A[j] * ys[j * stride + node];
+      y[6 * (int64_t)(n0 + node) + k] = (VT)(-v);
+    }
+    return;
+  }
+  double acc = 0.0;
+  const int64_t pair0 = 3 * (int64_t)n0;
+  for (int i = threadIdx.x; i < nn * 3; i += BLOCK) {
+    const int node = i / 3, part = i - 3 * node;
+    if (ENDS != kEndsAll && (condensed(node) != (ENDS == kEndsCondensed))) continue;   // rows of the other kind
+    double2 v = {ys[(2 * part) * stride + node], ys[(2 * part + 1) * stride + node]};
+    if (MASK) {
+      const unsigned fb = fixedbits[n0 + node] >> (2 * part);
+      if (fb & 1u) v.x = 0.0;
+      if (fb & 2u) v.y = 0.0;
+    }
+    store_pair(y, pair0 + i, v);
+    if (DOT) {
+      const double2 xv = xpair(i);
+      acc += xv.x * v.x + xv.y * v.y;
+    }
+  }
+  if (DOT) {
+    double s = wave_sum(acc);
+    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = s;
+    __syncthreads();
+    s = 0.0;
+    if (threadIdx.x == 0)
+      for (int q = 0; q < BLOCK / kWave; ++q) s += red[q];
+    if (threadIdx.x == 0) unsafeAtomicAdd(dot_out + (blockIdx.x & (kSlots - 1)), s);
+  }
+}
+
 // Workgroup size of the tile K*p.  Measured on the 50^3 Octet (256-node tiles): 128 / 256 / 384 / 512 / 640 / 768 / 1024
 // threads -> 45.9 / 40.6 / 39.7 / 36.2 / 47.8 / 42.8 / 55.0 us: with 512 a tile's ~1900 strut visits are 3-4 per thread, so a
 // workgroup lives half as long while 4 of them still fit a CU.  (End of round 2, 152-node tiles of ~1 080 visits:
@@ -620,45 +673,9 @@ __global__ __launch_bounds__(kTileBlock) void k_spmv_tile(const int32_t *__restr
   PL_STAMP(3);
   __syncthreads();
   PL_STAMP(4);
-  if (ENDS == kEndsCondensedSolve) {
-    for (int i = threadIdx.x; i < nn * 6; i += kTileBlock) {
-      const int node = i / 6, k = i - 6 * node;
-      const int32_t b0 = sbase[node];
-      if (b0 < 0) continue;
-      const double *A = cs.inv + b0 + 6 * k;
-      double v = 0.0;
-#pragma unroll
-      for (int j = 0; j < 6; ++j) v += A[j] * ys[j * stride + node];
-      y[6 * (int64_t)(n0 + node) + k] = (VT)(-v);
-    }
-    return;
-  }
-  double acc = 0.0;
-  const int64_t pair0 = 3 * (int64_t)n0;
-  for (int i = threadIdx.x; i < nn * 3; i += kTileBlock) {
-    const int node = i / 3, part = i - 3 * node;
-    if (ENDS != kEndsAll && ((cflag[n0 + node] != 0) != (ENDS == kEndsCondensed))) continue;   // rows of the other kind
-    double2 v = {ys[(2 * part) * stride + node], ys[(2 * part + 1) * stride + node]};
-    if (MASK) {
-      const unsigned fb = fixedbits[n0 + node] >> (2 * part);
-      if (fb & 1u) v.x = 0.0;
-      if (fb & 2u) v.y = 0.0;
-    }
-    store_pair(y, pair0 + i, v);
-    if (DOT) {
-      const double2 xv = load_pair(x, pair0 + i);
-      acc += xv.x * v.x + xv.y * v.y;
-    }
-  }
-  if (DOT) {
-    double s = wave_sum(acc);
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = s;
-    __syncthreads();
-    s = 0.0;
-    if (threadIdx.x == 0)
-      for (int q = 0; q < kTileBlock / kWave; ++q) s += red[q];
-    if (threadIdx.x == 0) unsafeAtomicAdd(dot_out + (blockIdx.x & (kSlots - 1)), s);
-  }
+  tile_epilogue<MASK, DOT, ENDS, kTileBlock>(
+      ys, stride, n0, nn, sbase, cs, fixedbits, y, dot_out, red, [=](int node) { return cflag[n0 + node] != 0; },
+      [=](int i) { return load_pair(x, 3 * (int64_t)n0 + i); });
   PL_STAMP(5);
 }
 
@@ -744,16 +761,46 @@ struct Defer {
   double *p_new = nullptr, *xsol = nullptr;
   const double *sc_prev = nullptr, *sc_cur = nullptr;
 };
-template <bool MASK, bool DOT, int REC, typename VT, int ENDS = kEndsAll, bool DEFER = false>
-__global__ __launch_bounds__(kLdsBlock) __attribute__((amdgpu_waves_per_eu(DEFER ? 1 : (REC == kRecPalette ? PL_LDS_WAVES : PL_LDS_WAVES_STREAM), 8)))
-void k_spmv_tile_lds_t(const TileDesc *__restrict__ tdesc, const uint32_t *__restrict__ vword,
-                       const int32_t *__restrict__ vother, const double2 *__restrict__ tab, int n_tab,
-                     const Rec5 *__restrict__ rec5, const int32_t *__restrict__ foreign_idx,
-                     const uint8_t *__restrict__ fixedbits, const VT *__restrict__ x, VT *__restrict__ y,
-                     double *__restrict__ dot_out, int stride, const uint8_t *__restrict__ cflag = nullptr,
-                     CondSolve cs = CondSolve(), const int32_t *__restrict__ tile_list = nullptr, Defer df = Defer()) {
+
+// The one body of the LDS-resident K*p: every form (palette, streaming, deferred) is this text, inlined into its entry point
+// below.  The palette form once spilled 20 B per lane from a shared template and was kept as a hand copy for that.  The cause
+// was the two visit loops written as by-reference closures (`auto interior_visits = [&]() {...}`) and called in either order
+// from an `if constexpr`: put back, they bring the 20 B back (12 B in the fused first pass), whatever else changes.  With the
+// loops written in the body every palette instantiation holds 64 VGPRs without scratch - with or without the scheduling fence
+// and the per-visit record copy of the other forms (compile-time figures: profiles/r18_kp_one_body_resource_usage.txt).
+template <bool MASK, bool DOT, int REC, typename VT, int ENDS, bool DEFER>
+__device__ __forceinline__ void tile_lds_body(const TileDesc *__restrict__ tdesc, const uint32_t *__restrict__ vword,
+                                              const int32_t *__restrict__ vother, const double2 *__restrict__ tab, int n_tab,
+                                              const Rec5 *__restrict__ rec5, const int32_t *__restrict__ foreign_idx,
+                                              const uint8_t *__restrict__ fixedbits, const VT *__restrict__ x,
+                                              VT *__restrict__ y, double *__restrict__ dot_out, int stride,
+                                              const uint8_t *__restrict__ cflag, const CondSolve &cs,
+                                              const int32_t *__restrict__ tile_list, const Defer &df) {
+  static_assert(REC == kRecPalette || REC == kRecCompact, "records come from the LDS palette or from the compact stream");
   static_assert(!DEFER || sizeof(VT) == 8, "the deferred direction is an fp64 path");
   constexpr bool kToCondensed = ENDS == kEndsCondensed || ENDS == kEndsCondensedSolve;
+  constexpr bool kStream = REC == kRecCompact;
+  // crossing visits run first in the streaming form: their record and out-of-tile row are requested before the barrier, and
+  // nothing of them then stays live across the interior visits, which hold the next visit's record in registers instead
+  constexpr bool kCrossFirst = kStream || PL_LDS_CROSS_FIRST;
+  // The shortcut for a strut with ONE eliminated end (interior visits of the fused first pass) is active in the palette form
+  // with a stored operand only, as it was before the forms shared this body; the streaming and deferred forms take such a
+  // visit through the general arithmetic.
+  constexpr bool kOneEndShortcut = ENDS == kEndsCondensedSolve && !kStream && !DEFER;
+  // A scheduling fence behind each unrolled interior visit: in the streaming and deferred forms, which were launched with it
+  // before the forms shared this body, and not in the palette form with a stored operand, which was launched without.  The
+  // resource table does not decide it - registers, scratch and occupancy of every form are the same with the fence in all
+  // forms, in none, and as here; only the order of the instructions moves - so each form keeps the schedule it was timed with.
+  constexpr bool kVisitFence = kStream || DEFER;
+  constexpr int kSrcChunks = kStream ? 2 : 4, kTabChunks = kStream ? 2 : kPalLdsChunks;
+  struct NoRec {};
+  using RQ = typename std::conditional<kStream, Rec5, NoRec>::type;      // a visit's streamed scalars (nothing in the palette form)
+  extern __shared__ double ys[];                                        // [6][stride] accumulator, component-major
+  double2 *xs2 = reinterpret_cast<double2 *>(ys + 6 * stride);          // [stride][3]: the tile's rows of x, node-major
+  double2 *ps2 = xs2 + 3 * stride;                                      // [n_tab][kTabChunks]: record / direction palette
+  uint8_t *sflag = reinterpret_cast<uint8_t *>(ps2 + kTabChunks * n_tab);      // [stride] condensed flags (ENDS != All)
+  __shared__ double red[kLdsBlock / kWave];
+  __shared__ int32_t sbase[ENDS == kEndsCondensedSolve ? kTileMaxNodes : 1];
   double d_alpha = 0.0, d_beta = 0.0;
   if constexpr (DEFER) {
     const double rz_prev = scalar_read(df.sc_prev, 0 /* S_RZ_OLD */), pap_prev = scalar_read(df.sc_prev, 1 /* S_PAP */);
@@ -765,33 +812,23 @@ void k_spmv_tile_lds_t(const TileDesc *__restrict__ tdesc, const uint32_t *__res
   auto load_other = [&](int32_t node, V3 &u, V3 &t) {
     if constexpr (DEFER) {
       V3 uz, tz, up, tp;
-      load6(reinterpret_cast<const double *>(df.z) + 6 * (int64_t)node, uz, tz);
-      load6(reinterpret_cast<const double *>(df.p_old) + 6 * (int64_t)node, up, tp);
+      load6(df.z + 6 * (int64_t)node, uz, tz);
+      load6(df.p_old + 6 * (int64_t)node, up, tp);
       u = uz + d_beta * up;
       t = tz + d_beta * tp;
     } else {
       load6(x + 6 * (int64_t)node, u, t);
     }
   };
-  constexpr bool kStream = REC == kRecCompact;
-  constexpr int kSrcChunks = kStream ? 2 : 4, kTabChunks = kStream ? 2 : kPalLdsChunks;
-  struct NoRec {};
-  using RQ = typename std::conditional<kStream, Rec5, NoRec>::type;      // a visit's streamed scalars (nothing in the palette form)
-  extern __shared__ double ys[];                                        // [6][stride] accumulator, component-major
-  double2 *xs2 = reinterpret_cast<double2 *>(ys + 6 * stride);          // [stride][3]: the tile's rows of x, node-major
-  double2 *ps2 = xs2 + 3 * stride;                                      // [n_tab][kTabChunks]: record / direction palette
-  uint8_t *sflag = reinterpret_cast<uint8_t *>(ps2 + kTabChunks * n_tab);      // [stride] condensed flags (ENDS != All)
-  __shared__ double red[kLdsBlock / kWave];
-  __shared__ int32_t sbase[ENDS == kEndsCondensedSolve ? kTileMaxNodes : 1];
   PL_STAMP(0);
   unsigned t = xcd_block(blockIdx.x, gridDim.x);
   if (tile_list) t = (unsigned)tile_list[t];
   const TileDesc td = tdesc[t];
   const int n0 = td.n0, nn = td.n1 - td.n0;
   // this thread's first kLdsPre interior visits and its first crossing visit: requested together with the rows of x, so
-  // that the interior visits hold no load of a visit word at all (a load inside a loop makes the compiler wait for
+  // that the unrolled interior visits hold no load of a visit word at all (a load inside a loop makes the compiler wait for
   // vmcnt(0) at the top of every iteration - for the word it has just requested AND for whatever else is meant to stay
-  // in flight behind the loop)
+  // in flight behind the loop: the crossing visit's row in the palette form, the next record in the streaming form)
   unsigned wv[kLdsPre];
 #pragma unroll
   for (int j = 0; j < kLdsPre; ++j) {
@@ -827,9 +864,9 @@ void k_spmv_tile_lds_t(const TileDesc *__restrict__ tdesc, const uint32_t *__res
     // (fused first pass of the condensed operator: a condensed node's row is being rewritten by its tile - it counts as
     // zero and is not read)
     double2 val = {0.0, 0.0};
-    if constexpr (DEFER) {
-      if (!(ENDS == kEndsCondensedSolve && f)) {
-        const int64_t pr = 3 * (int64_t)n0 + i;
+    if (!(ENDS == kEndsCondensedSolve && f)) {
+      const int64_t pr = 3 * (int64_t)n0 + i;
+      if constexpr (DEFER) {
         const double2 zz = load_pair(df.z, pr), po = load_pair(df.p_old, pr);
         double2 xx = load_pair(df.xsol, pr);
         val.x = zz.x + d_beta * po.x;
@@ -838,15 +875,15 @@ void k_spmv_tile_lds_t(const TileDesc *__restrict__ tdesc, const uint32_t *__res
         xx.y += d_alpha * po.y;
         store_pair(df.p_new, pr, val);
         store_pair(df.xsol, pr, xx);
+      } else {
+        val = load_pair(x, pr);
       }
-    } else {
-      if (!(ENDS == kEndsCondensedSolve && f)) val = load_pair(x, 3 * (int64_t)n0 + i);
     }
     xs2[i] = val;
   }
   for (int i = threadIdx.x; i < kSrcChunks * n_tab; i += kLdsBlock)
     ps2[(i / kSrcChunks) * kTabChunks + (i % kSrcChunks)] = tab[i];
-  if (ENDS == kEndsCondensedSolve)
+  if (ENDS == kEndsCondensedSolve)           // fetched now, needed after the strut loops: no dependent load in the tail
     for (int i = threadIdx.x; i < nn; i += kLdsBlock) sbase[i] = cs.base[n0 + i];
   // a crossing visit: is the tile's own end of the kind this pass accumulates, and does the other end's row count?
   auto cross_take = [&](unsigned cwv) -> bool {
@@ -884,6 +921,12 @@ void k_spmv_tile_lds_t(const TileDesc *__restrict__ tdesc, const uint32_t *__res
     }
     return r;
   };
+  auto row_of = [&](int l, V3 &u, V3 &th) {      // a staged row of x
+    const double2 *p = xs2 + 3 * l;
+    const double2 p0 = p[0], p1 = p[1], p2 = p[2];
+    u = {p0.x, p0.y, p1.x};
+    th = {p1.y, p2.x, p2.y};
+  };
   auto interior = [&](unsigned w, const RQ &q) {
     const int la = (int)(w & ((1u << kVisRowBits) - 1)), lb = (int)((w >> kVisRowBits) & ((1u << kVisRowBits) - 1));
     bool takeA = true, takeB = true;
@@ -891,252 +934,34 @@ void k_spmv_tile_lds_t(const TileDesc *__restrict__ tdesc, const uint32_t *__res
       takeA = (((w >> kVisCendShift) & 1u) != 0) == kToCondensed;
       takeB = (((w >> kVisCendShift) & 2u) != 0) == kToCondensed;
     }
-    if (takeA || takeB) {
-      const Record r = record_of((w >> kVisPidShift) & 0xFFu, q);
-      const double2 *pa = xs2 + 3 * la, *pb = xs2 + 3 * lb;
-      const double2 a0 = pa[0], a1 = pa[1], a2 = pa[2], b0 = pb[0], b1 = pb[1], b2 = pb[2];
-      const V3 uA = {a0.x, a0.y, a1.x}, tA = {a1.y, a2.x, a2.y}, uB = {b0.x, b0.y, b1.x}, tB = {b1.y, b2.x, b2.y};
-      V3 F, M;
-      tip_force(r, uA, tA, uB, tB, F, M);
-      if (takeB) lds_add6(ys + lb, stride, F, M);
-      if (takeA) {
-        const V3 d = {r.dx, r.dy, r.dz};
-        lds_add6(ys + la, stride, (-1.0) * F, (-1.0) * M - cross(d, F));
-      }
-    }
-  };
-  auto interior_visits = [&]() {
-#pragma unroll
-    for (int j = 0; j < kLdsPre; ++j) {
-      const RQ qc = qn;
-      if constexpr (kStream)
-        if (j + 1 < kLdsPre && wv[j + 1] != kNoVisit)
-          qn = load_rec5(rec5, td.h0 + (int64_t)threadIdx.x + (j + 1) * kLdsBlock);
-      if (wv[j] != kNoVisit) interior(wv[j], qc);
-      __builtin_amdgcn_sched_barrier(0);      // (visits interleaved by the scheduler cost 14 more registers: spills at 64)
-    }
-    for (int k = (int)threadIdx.x + kLdsPre * kLdsBlock; k < td.n_int; k += kLdsBlock) {      // large tiles
-      RQ q = RQ();
-      if constexpr (kStream) q = load_rec5(rec5, td.h0 + k);
-      interior(vword[td.v0 + k], q);
-    }
-  };
-  auto crossing_visits = [&]() {
-    while (clive) {
-      const int kn = kc + kLdsBlock;
-      const bool live_n = kn < td.n_cross;
-      unsigned cw_n = 0;
-      int32_t co_n = 0;
-      int64_t cb_n = 0;
-      (void)cb_n;
-      if (live_n) {
-        cw_n = vword[vc0 + kn];
-        co_n = vother[td.c0 + kn];
-        if constexpr (kStream) cb_n = cross_strut(kn);
-      }
-      if (cross_take(cw)) {
-        const int lo = (int)(cw & ((1u << kVisRowBits) - 1));
-        const bool ownB = (cw >> kVisRowBits) & 1u;
-        const Record r = record_of((cw >> kVisPidShift) & 0xFFu, cq);
-        const double2 *po = xs2 + 3 * lo;
-        const double2 a0 = po[0], a1 = po[1], a2 = po[2];
-        const V3 uW = {a0.x, a0.y, a1.x}, tW = {a1.y, a2.x, a2.y};
-        V3 F, M;
-        if (ownB) {
-          tip_force(r, uO, tO, uW, tW, F, M);
-          lds_add6(ys + lo, stride, F, M);
-        } else {
-          tip_force(r, uW, tW, uO, tO, F, M);
-          const V3 d = {r.dx, r.dy, r.dz};
-          lds_add6(ys + lo, stride, (-1.0) * F, (-1.0) * M - cross(d, F));
-        }
-      }
-      uO = {0, 0, 0};
-      tO = {0, 0, 0};
-      if (live_n && cross_take(cw_n)) {
-        if (!other_zero(cw_n)) load_other(co_n, uO, tO);
-        if constexpr (kStream) cq = load_rec5(rec5, cb_n);
-      }
-      kc = kn;
-      cw = cw_n;
-      clive = live_n;
-    }
-  };
-  if constexpr (kStream || PL_LDS_CROSS_FIRST) {
-    crossing_visits();
-    interior_visits();
-  } else {
-    interior_visits();
-    crossing_visits();
-  }
-  PL_STAMP(3);
-  __syncthreads();
-  PL_STAMP(4);
-  if (ENDS == kEndsCondensedSolve) {
-    for (int i = threadIdx.x; i < nn * 6; i += kLdsBlock) {
-      const int node = i / 6, k = i - 6 * node;
-      const int32_t b0 = sbase[node];
-      if (b0 < 0) continue;
-      const double *A = cs.inv + b0 + 6 * k;
-      double vv = 0.0;
-#pragma unroll
-      for (int j = 0; j < 6; ++j) vv += A[j] * ys[j * stride + node];
-      y[6 * (int64_t)(n0 + node) + k] = (VT)(-vv);
-    }
-    return;
-  }
-  double acc = 0.0;
-  const int64_t pair0 = 3 * (int64_t)n0;
-  for (int i = threadIdx.x; i < nn * 3; i += kLdsBlock) {
-    const int node = i / 3, part = i - 3 * node;
-    if (ENDS != kEndsAll && ((sflag[node] != 0) != (ENDS == kEndsCondensed))) continue;   // rows of the other kind
-    double2 val = {ys[(2 * part) * stride + node], ys[(2 * part + 1) * stride + node]};
-    if (MASK) {
-      const unsigned fb = fixedbits[n0 + node] >> (2 * part);
-      if (fb & 1u) val.x = 0.0;
-      if (fb & 2u) val.y = 0.0;
-    }
-    store_pair(y, pair0 + i, val);
-    if (DOT) {
-      const double2 xv = xs2[i];
-      acc += xv.x * val.x + xv.y * val.y;
-    }
-  }
-  if (DOT) {
-    double s = wave_sum(acc);
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = s;
-    __syncthreads();
-    s = 0.0;
-    if (threadIdx.x == 0)
-      for (int q = 0; q < kLdsBlock / kWave; ++q) s += red[q];
-    if (threadIdx.x == 0) unsafeAtomicAdd(dot_out + (blockIdx.x & (kSlots - 1)), s);
-  }
-  PL_STAMP(5);
-}
-
-// The palette form as its own function: the same text as k_spmv_tile_lds_t<.., kRecPalette, ..>, which the register allocator
-// fits into 64 VGPRs here and spills from there (16 VGPRs of the crossing visit's row to scratch: 2 x 27 MB of traffic per
-// launch at 50^3, K*p 33.7 -> 36.4 us) - the streaming form is held to 6 waves per SIMD instead.
-template <bool MASK, bool DOT, typename VT, int ENDS = kEndsAll>
-__global__ __launch_bounds__(kLdsBlock) __attribute__((amdgpu_waves_per_eu(PL_LDS_WAVES, 8))) void k_spmv_tile_lds(const TileDesc *__restrict__ tdesc,
-                                                         const uint32_t *__restrict__ vword,
-                                                         const int32_t *__restrict__ vother,
-                                                         const Record *__restrict__ pal_dense, int n_pal,
-                                                         const uint8_t *__restrict__ fixedbits,
-                                                         const VT *__restrict__ x, VT *__restrict__ y,
-                                                         double *__restrict__ dot_out, int stride,
-                                                         const uint8_t *__restrict__ cflag = nullptr,
-                                                         CondSolve cs = CondSolve(),
-                                                         const int32_t *__restrict__ tile_list = nullptr) {
-  constexpr bool kToCondensed = ENDS == kEndsCondensed || ENDS == kEndsCondensedSolve;
-  extern __shared__ double ys[];                                        // [6][stride] accumulator, component-major
-  double2 *xs2 = reinterpret_cast<double2 *>(ys + 6 * stride);          // [stride][3]: the tile's rows of x, node-major
-  double2 *ps2 = xs2 + 3 * stride;                                      // [n_pal][kPalLdsChunks]: the record palette
-  uint8_t *sflag = reinterpret_cast<uint8_t *>(ps2 + kPalLdsChunks * n_pal);   // [stride] condensed flags (ENDS != All)
-  __shared__ double red[kLdsBlock / kWave];
-  __shared__ int32_t sbase[ENDS == kEndsCondensedSolve ? kTileMaxNodes : 1];
-  PL_STAMP(0);
-  unsigned t = xcd_block(blockIdx.x, gridDim.x);
-  if (tile_list) t = (unsigned)tile_list[t];
-  const TileDesc td = tdesc[t];
-  const int n0 = td.n0, nn = td.n1 - td.n0;
-  // this thread's first kLdsPre interior visits and its first crossing visit: requested together with the rows of x, so
-  // that the interior loop holds no load from global memory at all (a load inside it makes the compiler wait for
-  // vmcnt(0) at the top of every iteration - for the word it has just requested AND for the crossing visit's row, which
-  // is meant to stay in flight behind the loop)
-  unsigned wv[kLdsPre];
-#pragma unroll
-  for (int j = 0; j < kLdsPre; ++j) {
-    const int k = (int)threadIdx.x + j * kLdsBlock;
-    wv[j] = k < td.n_int ? vword[td.v0 + k] : kNoVisit;
-  }
-  int kc = threadIdx.x;
-  bool clive = kc < td.n_cross;
-  unsigned cw = 0;
-  int32_t co = 0;
-  const int64_t vc0 = td.v0 + td.n_int;
-  if (clive) {
-    cw = vword[vc0 + kc];
-    co = vother[td.c0 + kc];
-  }
-  for (int i = threadIdx.x; i < 6 * stride; i += kLdsBlock) ys[i] = 0.0;
-  for (int i = threadIdx.x; i < 3 * nn; i += kLdsBlock) {               // own rows: 16 B per lane, contiguous
-    uint8_t f = 0;
-    if (ENDS != kEndsAll) {
-      const int node = i / 3;
-      f = cflag[n0 + node];
-      if (i - 3 * node == 0) sflag[node] = f;
-    }
-    // (fused first pass of the condensed operator: a condensed node's row is being rewritten by its tile - it counts as
-    // zero and is not read)
-    double2 val = {0.0, 0.0};
-    if (!(ENDS == kEndsCondensedSolve && f)) val = load_pair(x, 3 * (int64_t)n0 + i);
-    xs2[i] = val;
-  }
-  for (int i = threadIdx.x; i < 4 * n_pal; i += kLdsBlock)
-    ps2[(i >> 2) * kPalLdsChunks + (i & 3)] = reinterpret_cast<const double2 *>(pal_dense)[i];
-  if (ENDS == kEndsCondensedSolve)
-    for (int i = threadIdx.x; i < nn; i += kLdsBlock) sbase[i] = cs.base[n0 + i];
-  // a crossing visit: is the tile's own end of the kind this pass accumulates, and does the other end's row count?
-  auto cross_take = [&](unsigned cwv) -> bool {
-    if (ENDS == kEndsAll) return true;
-    const bool ownB = (cwv >> kVisRowBits) & 1u;
-    return (((cwv >> (kVisCendShift + (ownB ? 1 : 0))) & 1u) != 0) == kToCondensed;
-  };
-  auto other_zero = [&](unsigned cwv) -> bool {        // (first pass: condensed rows count as zero)
-    if (ENDS != kEndsCondensedSolve) return false;
-    const bool ownB = (cwv >> kVisRowBits) & 1u;
-    return ((cwv >> (kVisCendShift + (ownB ? 0 : 1))) & 1u) != 0;
-  };
-  // the first crossing visit's out-of-tile row: in flight during the barrier and the interior loop
-  V3 uO = {0, 0, 0}, tO = {0, 0, 0};
-  if (clive && cross_take(cw) && !other_zero(cw)) load6(x + 6 * (int64_t)co, uO, tO);
-  PL_STAMP(1);
-  __syncthreads();
-  PL_STAMP(2);
-  auto record_of = [&](unsigned id) -> Record {
-    const double2 *q = ps2 + kPalLdsChunks * id;
-    const double2 r0 = q[0], r1 = q[1], r2 = q[2], r3 = q[3];
-    Record r;
-    r.a = r0.x; r.c = r0.y; r.e1 = r1.x; r.e2 = r1.y; r.e3 = r2.x; r.dx = r2.y; r.dy = r3.x; r.dz = r3.y;
-    return r;
-  };
-  auto interior = [&](unsigned w) {
-    const int la = (int)(w & ((1u << kVisRowBits) - 1)), lb = (int)((w >> kVisRowBits) & ((1u << kVisRowBits) - 1));
-    bool takeA = true, takeB = true;
-    if (ENDS != kEndsAll) {
-      takeA = (((w >> kVisCendShift) & 1u) != 0) == kToCondensed;
-      takeB = (((w >> kVisCendShift) & 2u) != 0) == kToCondensed;
-    }
-    if (ENDS == kEndsCondensedSolve && takeA != takeB) {
+    if (kOneEndShortcut && takeA != takeB) {
       // first pass of the condensed operator, strut with ONE eliminated end (every strut of a bipartite lattice): that
       // end's row counts as zero - it is neither read nor carried through the arithmetic, and only its force is wanted.
       // (Visits are sorted by direction, so which end it is, is uniform over nearly every wave.)
-      const Record r = record_of((w >> kVisPidShift) & 0xFFu);
+      const Record r = record_of((w >> kVisPidShift) & 0xFFu, q);
       const V3 d = {r.dx, r.dy, r.dz};
+      // (One text for the force law with the branch only around the row and the add was timed: 0.5 us slower on the 75-us
+      // pass at 100^3 BCC, so each branch keeps its own.)
       V3 F, M;
       if (takeA) {        // A eliminated: du = u_B, dth = th_B; force on A = -(F, M + d x F)
-        const double2 *pb = xs2 + 3 * lb;
-        const double2 b0 = pb[0], b1 = pb[1], b2 = pb[2];
-        const V3 du = {b0.x, b0.y, b1.x}, dth = {b1.y, b2.x, b2.y};
+        V3 du, dth;
+        row_of(lb, du, dth);
         F = r.a * du + (r.e1 * dot(du, d)) * d + r.e2 * cross(d, dth);
         M = r.c * dth + (r.e3 * dot(dth, d)) * d - r.e2 * cross(d, du);
         lds_add6(ys + la, stride, (-1.0) * F, (-1.0) * M - cross(d, F));
       } else {            // B eliminated: du = -u_A + d x th_A, dth = -th_A; force on B = (F, M)
-        const double2 *pa = xs2 + 3 * la;
-        const double2 a0 = pa[0], a1 = pa[1], a2 = pa[2];
-        const V3 uA = {a0.x, a0.y, a1.x}, tA = {a1.y, a2.x, a2.y};
+        V3 uA, tA;
+        row_of(la, uA, tA);
         const V3 du = cross(d, tA) - uA, dth = (-1.0) * tA;
         F = r.a * du + (r.e1 * dot(du, d)) * d + r.e2 * cross(d, dth);
         M = r.c * dth + (r.e3 * dot(dth, d)) * d - r.e2 * cross(d, du);
         lds_add6(ys + lb, stride, F, M);
       }
     } else if (takeA || takeB) {
-      const Record r = record_of((w >> kVisPidShift) & 0xFFu);
-      const double2 *pa = xs2 + 3 * la, *pb = xs2 + 3 * lb;
-      const double2 a0 = pa[0], a1 = pa[1], a2 = pa[2], b0 = pb[0], b1 = pb[1], b2 = pb[2];
-      const V3 uA = {a0.x, a0.y, a1.x}, tA = {a1.y, a2.x, a2.y}, uB = {b0.x, b0.y, b1.x}, tB = {b1.y, b2.x, b2.y};
-      V3 F, M;
+      const Record r = record_of((w >> kVisPidShift) & 0xFFu, q);
+      V3 uA, tA, uB, tB, F, M;
+      row_of(la, uA, tA);
+      row_of(lb, uB, tB);
       tip_force(r, uA, tA, uB, tB, F, M);
       if (takeB) lds_add6(ys + lb, stride, F, M);
       if (takeA) {
@@ -1145,164 +970,159 @@ __global__ __launch_bounds__(kLdsBlock) __attribute__((amdgpu_waves_per_eu(PL_LD
       }
     }
   };
+  // The two visit loops stand in the body itself, in the order kCrossFirst gives them (a two-pass loop, unrolled).
 #pragma unroll
-  for (int j = 0; j < kLdsPre; ++j)
-    if (wv[j] != kNoVisit) interior(wv[j]);
-  for (int k = (int)threadIdx.x + kLdsPre * kLdsBlock; k < td.n_int; k += kLdsBlock) interior(vword[td.v0 + k]);   // large tiles
-  while (clive) {
-    const int kn = kc + kLdsBlock;
-    const bool live_n = kn < td.n_cross;
-    unsigned cw_n = 0;
-    int32_t co_n = 0;
-    if (live_n) {
-      cw_n = vword[vc0 + kn];
-      co_n = vother[td.c0 + kn];
-    }
-    if (cross_take(cw)) {
-      const int lo = (int)(cw & ((1u << kVisRowBits) - 1));
-      const bool ownB = (cw >> kVisRowBits) & 1u;
-      const Record r = record_of((cw >> kVisPidShift) & 0xFFu);
-      const double2 *po = xs2 + 3 * lo;
-      const double2 a0 = po[0], a1 = po[1], a2 = po[2];
-      const V3 uW = {a0.x, a0.y, a1.x}, tW = {a1.y, a2.x, a2.y};
-      V3 F, M;
-      if (ownB) {
-        tip_force(r, uO, tO, uW, tW, F, M);
-        lds_add6(ys + lo, stride, F, M);
-      } else {
-        tip_force(r, uW, tW, uO, tO, F, M);
-        const V3 d = {r.dx, r.dy, r.dz};
-        lds_add6(ys + lo, stride, (-1.0) * F, (-1.0) * M - cross(d, F));
+  for (int phase = 0; phase < 2; ++phase) {
+    if ((phase == 1) == kCrossFirst) {
+      // interior visits: the pre-fetched ones, then (large tiles) the rest
+#pragma unroll
+      for (int j = 0; j < kLdsPre; ++j) {
+        if constexpr (kStream) {
+          const RQ qc = qn;
+          if (j + 1 < kLdsPre && wv[j + 1] != kNoVisit)
+            qn = load_rec5(rec5, td.h0 + (int64_t)threadIdx.x + (j + 1) * kLdsBlock);
+          if (wv[j] != kNoVisit) interior(wv[j], qc);
+        } else {
+          if (wv[j] != kNoVisit) interior(wv[j], RQ());
+        }
+        if constexpr (kVisitFence) __builtin_amdgcn_sched_barrier(0);
+      }
+      for (int k = (int)threadIdx.x + kLdsPre * kLdsBlock; k < td.n_int; k += kLdsBlock) {
+        RQ q = RQ();
+        if constexpr (kStream) q = load_rec5(rec5, td.h0 + k);
+        interior(vword[td.v0 + k], q);
+      }
+    } else {
+      // crossing visits: the next one's words, then this one's arithmetic, then the next one's row (and record)
+      while (clive) {
+        const int kn = kc + kLdsBlock;
+        const bool live_n = kn < td.n_cross;
+        unsigned cw_n = 0;
+        int32_t co_n = 0;
+        int64_t cb_n = 0;
+        (void)cb_n;
+        if (live_n) {
+          cw_n = vword[vc0 + kn];
+          co_n = vother[td.c0 + kn];
+          if constexpr (kStream) cb_n = cross_strut(kn);
+        }
+        if (cross_take(cw)) {
+          const int lo = (int)(cw & ((1u << kVisRowBits) - 1));
+          const bool ownB = (cw >> kVisRowBits) & 1u;
+          const Record r = record_of((cw >> kVisPidShift) & 0xFFu, cq);
+          V3 uW, tW, F, M;
+          row_of(lo, uW, tW);
+          if (ownB) {
+            tip_force(r, uO, tO, uW, tW, F, M);
+            lds_add6(ys + lo, stride, F, M);
+          } else {
+            tip_force(r, uW, tW, uO, tO, F, M);
+            const V3 d = {r.dx, r.dy, r.dz};
+            lds_add6(ys + lo, stride, (-1.0) * F, (-1.0) * M - cross(d, F));
+          }
+        }
+        uO = {0, 0, 0};
+        tO = {0, 0, 0};
+        if (live_n && cross_take(cw_n)) {
+          if (!other_zero(cw_n)) load_other(co_n, uO, tO);
+          if constexpr (kStream) cq = load_rec5(rec5, cb_n);
+        }
+        kc = kn;
+        cw = cw_n;
+        clive = live_n;
       }
     }
-    uO = {0, 0, 0};
-    tO = {0, 0, 0};
-    if (live_n && cross_take(cw_n) && !other_zero(cw_n)) load6(x + 6 * (int64_t)co_n, uO, tO);
-    kc = kn;
-    cw = cw_n;
-    clive = live_n;
   }
   PL_STAMP(3);
   __syncthreads();
   PL_STAMP(4);
-  if (ENDS == kEndsCondensedSolve) {
-    for (int i = threadIdx.x; i < nn * 6; i += kLdsBlock) {
-      const int node = i / 6, k = i - 6 * node;
-      const int32_t b0 = sbase[node];
-      if (b0 < 0) continue;
-      const double *A = cs.inv + b0 + 6 * k;
-      double vv = 0.0;
-#pragma unroll
-      for (int j = 0; j < 6; ++j) vv += A[j] * ys[j * stride + node];
-      y[6 * (int64_t)(n0 + node) + k] = (VT)(-vv);
-    }
-    return;
-  }
-  double acc = 0.0;
-  const int64_t pair0 = 3 * (int64_t)n0;
-  for (int i = threadIdx.x; i < nn * 3; i += kLdsBlock) {
-    const int node = i / 3, part = i - 3 * node;
-    if (ENDS != kEndsAll && ((sflag[node] != 0) != (ENDS == kEndsCondensed))) continue;   // rows of the other kind
-    double2 val = {ys[(2 * part) * stride + node], ys[(2 * part + 1) * stride + node]};
-    if (MASK) {
-      const unsigned fb = fixedbits[n0 + node] >> (2 * part);
-      if (fb & 1u) val.x = 0.0;
-      if (fb & 2u) val.y = 0.0;
-    }
-    store_pair(y, pair0 + i, val);
-    if (DOT) {
-      const double2 xv = xs2[i];
-      acc += xv.x * val.x + xv.y * val.y;
-    }
-  }
-  if (DOT) {
-    double s = wave_sum(acc);
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = s;
-    __syncthreads();
-    s = 0.0;
-    if (threadIdx.x == 0)
-      for (int q = 0; q < kLdsBlock / kWave; ++q) s += red[q];
-    if (threadIdx.x == 0) unsafeAtomicAdd(dot_out + (blockIdx.x & (kSlots - 1)), s);
-  }
+  tile_epilogue<MASK, DOT, ENDS, kLdsBlock>(
+      ys, stride, n0, nn, sbase, cs, fixedbits, y, dot_out, red, [=](int node) { return sflag[node] != 0; },
+      [=](int i) { return xs2[i]; });
   PL_STAMP(5);
 }
 
+// The entry points: the palette form with a stored operand (tab = the dense record palette, Record[n_pal]) at PL_LDS_WAVES
+// waves per SIMD, and every other form - streaming (REC = kRecCompact) at PL_LDS_WAVES_STREAM, deferred (either REC) with the
+// occupancy left to the compiler.  Profiles, tools and pl_stats_t.kp_form tell the forms apart by these two names.
+template <bool MASK, bool DOT, typename VT, int ENDS = kEndsAll>
+__global__ __launch_bounds__(kLdsBlock) __attribute__((amdgpu_waves_per_eu(PL_LDS_WAVES, 8)))
+void k_spmv_tile_lds(const TileDesc *__restrict__ tdesc, const uint32_t *__restrict__ vword,
+                     const int32_t *__restrict__ vother, const Record *__restrict__ pal_dense, int n_pal,
+                     const uint8_t *__restrict__ fixedbits, const VT *__restrict__ x, VT *__restrict__ y,
+                     double *__restrict__ dot_out, int stride, const uint8_t *__restrict__ cflag = nullptr,
+                     CondSolve cs = CondSolve(), const int32_t *__restrict__ tile_list = nullptr) {
+  tile_lds_body<MASK, DOT, kRecPalette, VT, ENDS, false>(tdesc, vword, vother, reinterpret_cast<const double2 *>(pal_dense),
+                                                         n_pal, nullptr, nullptr, fixedbits, x, y, dot_out, stride, cflag, cs,
+                                                         tile_list, Defer());
+}
+template <bool MASK, bool DOT, int REC, typename VT, int ENDS = kEndsAll, bool DEFER = false>
+__global__ __launch_bounds__(kLdsBlock) __attribute__((amdgpu_waves_per_eu(DEFER ? 1 : (REC == kRecPalette ? PL_LDS_WAVES : PL_LDS_WAVES_STREAM), 8)))
+void k_spmv_tile_lds_t(const TileDesc *__restrict__ tdesc, const uint32_t *__restrict__ vword,
+                       const int32_t *__restrict__ vother, const double2 *__restrict__ tab, int n_tab,
+                       const Rec5 *__restrict__ rec5, const int32_t *__restrict__ foreign_idx,
+                       const uint8_t *__restrict__ fixedbits, const VT *__restrict__ x, VT *__restrict__ y,
+                       double *__restrict__ dot_out, int stride, const uint8_t *__restrict__ cflag = nullptr,
+                       CondSolve cs = CondSolve(), const int32_t *__restrict__ tile_list = nullptr, Defer df = Defer()) {
+  static_assert(DEFER || REC != kRecPalette, "the palette form with a stored operand is k_spmv_tile_lds");
+  tile_lds_body<MASK, DOT, REC, VT, ENDS, DEFER>(tdesc, vword, vother, tab, n_tab, rec5, foreign_idx, fixedbits, x, y, dot_out,
+                                                 stride, cflag, cs, tile_list, df);
+}
+
+// f(ends, mask, dot): the pass over strut ends, "Dirichlet mask" and "fused dot" of a tile launch as compile-time constants.
+// The fused first pass of the condensed operator (kEndsCondensedSolve) writes unmasked rows and has no dot.
+template <typename F>
+inline void with_tile_pass(int ends, bool mask, bool dot, F &&f) {
+  if (ends == kEndsCondensedSolve) return f(Int<kEndsCondensedSolve>{}, std::false_type{}, std::false_type{});
+  with_flag(mask, [&](auto m) {
+    with_flag(dot, [&](auto d) {
+      if (ends == kEndsCondensed) f(Int<kEndsCondensed>{}, m, d);
+      else if (ends == kEndsOthers) f(Int<kEndsOthers>{}, m, d);
+      else f(Int<kEndsAll>{}, m, d);
+    });
+  });
+}
 
 // false: this launch does not fit the LDS-resident kernel (the caller falls back to launch_tile_spmv).
 // rec5 == nullptr: palette form (tab = dense record palette); else streaming form (tab = the plan's direction palette).
+// df: the operand is formed in the kernel (Defer, short form of the PCG iteration; x is not read) - fp64, all tiles, and only
+// the two passes that start an operator application: kEndsAll masked and with the dot, or kEndsCondensedSolve.
 template <typename VT>
 inline bool launch_tile_spmv_lds(const TilePlan &plan, const uint32_t *vword, const void *tab, int n_tab,
                                  const Rec5 *rec5, const uint8_t *fixedbits, const VT *x, VT *y, double *dot_dev,
                                  hipStream_t s, int ends = kEndsAll, const uint8_t *cflag = nullptr,
-                                 CondSolve cs = CondSolve(), const int32_t *tile_list = nullptr, int64_t n_list = 0) {
+                                 CondSolve cs = CondSolve(), const int32_t *tile_list = nullptr, int64_t n_list = 0,
+                                 const Defer *df = nullptr) {
   if (!plan.vis_ready || !vword || n_tab <= 0 || n_tab > kPalDenseMax) return false;
+  constexpr bool kFp64 = std::is_same<VT, double>::value;
+  if (df && !(kFp64 && !tile_list && (ends == kEndsCondensedSolve || (ends == kEndsAll && fixedbits && dot_dev)))) return false;
   const int stride = plan.max_nodes | 1;
   const size_t lds = (size_t)stride * 96 + (size_t)n_tab * 16 * (rec5 ? 2 : kPalLdsChunks) + (ends != kEndsAll ? (size_t)stride : 0);
   if (lds > 60 * 1024) return false;
   if (tile_list && n_list <= 0) return true;
-  const int64_t n_units = tile_list ? n_list : plan.n_tiles;
-  const dim3 g((unsigned)n_units), blk(kLdsBlock);
+  const dim3 g((unsigned)(tile_list ? n_list : plan.n_tiles)), blk(kLdsBlock);
   const double2 *tab2 = static_cast<const double2 *>(tab);
-#define PL_T(M, D, R, E)                                                                                              \
-  do {                                                                                                                \
-    if (R == kRecPalette)                                                                                             \
-      hipLaunchKernelGGL((k_spmv_tile_lds<M, D, VT, E>), g, blk, lds, s, plan.tdesc.p, vword, plan.vother.p,          \
-                         static_cast<const Record *>(tab), n_tab, fixedbits, x, y, dot_dev, stride, cflag, cs,        \
-                         tile_list);                                                                                  \
-    else                                                                                                              \
-      hipLaunchKernelGGL((k_spmv_tile_lds_t<M, D, kRecCompact, VT, E>), g, blk, lds, s, plan.tdesc.p, vword,          \
-                         plan.vother.p, tab2, n_tab, rec5, plan.foreign_idx.p, fixedbits, x, y, dot_dev, stride,      \
-                         cflag, cs, tile_list);                                                                       \
-  } while (0)
-#define PL_TT(R, E)                                           \
-  do {                                                        \
-    if (fixedbits && dot_dev) PL_T(true, true, R, E);         \
-    else if (fixedbits) PL_T(true, false, R, E);              \
-    else if (dot_dev) PL_T(false, true, R, E);                \
-    else PL_T(false, false, R, E);                            \
-  } while (0)
-#define PL_TE(R)                                                                       \
-  do {                                                                                 \
-    if (ends == kEndsCondensed) PL_TT(R, kEndsCondensed);                              \
-    else if (ends == kEndsCondensedSolve) PL_T(false, false, R, kEndsCondensedSolve);  \
-    else if (ends == kEndsOthers) PL_TT(R, kEndsOthers);                               \
-    else PL_TT(R, kEndsAll);                                                           \
-  } while (0)
-  if (rec5) PL_TE(kRecCompact);
-  else PL_TE(kRecPalette);
-#undef PL_TE
-#undef PL_TT
-#undef PL_T
-  return true;
-}
-
-// The same launch with the operand formed in the kernel (Defer, short form of the PCG iteration): fp64, all tiles, and only
-// the two passes that start an operator application - ends = kEndsAll (masked, with the dot) or kEndsCondensedSolve.
-inline bool launch_tile_spmv_lds_defer(const TilePlan &plan, const uint32_t *vword, const void *tab, int n_tab,
-                                       const Rec5 *rec5, const uint8_t *fixedbits, double *y, double *dot_dev, hipStream_t s,
-                                       int ends, const uint8_t *cflag, CondSolve cs, const Defer &df) {
-  if (!plan.vis_ready || !vword || n_tab <= 0 || n_tab > kPalDenseMax) return false;
-  if (ends != kEndsAll && ends != kEndsCondensedSolve) return false;
-  const int stride = plan.max_nodes | 1;
-  const size_t lds = (size_t)stride * 96 + (size_t)n_tab * 16 * (rec5 ? 2 : kPalLdsChunks) + (ends != kEndsAll ? (size_t)stride : 0);
-  if (lds > 60 * 1024) return false;
-  const dim3 g((unsigned)plan.n_tiles), blk(kLdsBlock);
-  const double2 *tab2 = static_cast<const double2 *>(tab);
-  const double *x = nullptr;
-#define PL_TD(R)                                                                                                          \
-  do {                                                                                                                    \
-    if (ends == kEndsCondensedSolve)                                                                                      \
-      hipLaunchKernelGGL((k_spmv_tile_lds_t<false, false, R, double, kEndsCondensedSolve, true>), g, blk, lds, s,         \
-                         plan.tdesc.p, vword, plan.vother.p, tab2, n_tab, rec5, plan.foreign_idx.p, fixedbits, x, y,      \
-                         dot_dev, stride, cflag, cs, (const int32_t *)nullptr, df);                                       \
-    else                                                                                                                  \
-      hipLaunchKernelGGL((k_spmv_tile_lds_t<true, true, R, double, kEndsAll, true>), g, blk, lds, s, plan.tdesc.p, vword, \
-                         plan.vother.p, tab2, n_tab, rec5, plan.foreign_idx.p, fixedbits, x, y, dot_dev, stride, cflag,   \
-                         cs, (const int32_t *)nullptr, df);                                                               \
-  } while (0)
-  if (rec5) PL_TD(kRecCompact);
-  else PL_TD(kRecPalette);
-#undef PL_TD
+  with_tile_pass(ends, fixedbits != nullptr, dot_dev != nullptr, [&](auto e, auto m, auto d) {
+    with_flag(rec5 != nullptr, [&](auto stream) {
+      constexpr int E = decltype(e)::value, R = decltype(stream)::value ? kRecCompact : kRecPalette;
+      constexpr bool M = decltype(m)::value, D = decltype(d)::value;
+      constexpr bool kDeferPass = kFp64 && (E == kEndsCondensedSolve || (E == kEndsAll && M && D));
+      if constexpr (kDeferPass) {
+        if (df) {
+          hipLaunchKernelGGL((k_spmv_tile_lds_t<M, D, R, VT, E, true>), g, blk, lds, s, plan.tdesc.p, vword, plan.vother.p,
+                             tab2, n_tab, rec5, plan.foreign_idx.p, fixedbits, x, y, dot_dev, stride, cflag, cs, tile_list,
+                             *df);
+          return;
+        }
+      }
+      if constexpr (R == kRecPalette)
+        hipLaunchKernelGGL((k_spmv_tile_lds<M, D, VT, E>), g, blk, lds, s, plan.tdesc.p, vword, plan.vother.p,
+                           static_cast<const Record *>(tab), n_tab, fixedbits, x, y, dot_dev, stride, cflag, cs, tile_list);
+      else
+        hipLaunchKernelGGL((k_spmv_tile_lds_t<M, D, R, VT, E>), g, blk, lds, s, plan.tdesc.p, vword, plan.vother.p, tab2,
+                           n_tab, rec5, plan.foreign_idx.p, fixedbits, x, y, dot_dev, stride, cflag, cs, tile_list);
+    });
+  });
   return true;
 }
 
@@ -1322,35 +1142,20 @@ inline void launch_tile_spmv(const TilePlan &plan, const int32_t *conn, const Re
                              const double *xyz = nullptr, int ends = kEndsAll, const uint8_t *cflag = nullptr,
                              CondSolve cs = CondSolve(), const int32_t *tile_list = nullptr, int64_t n_list = 0) {
   if (tile_list && n_list <= 0) return;
-  const int64_t n_units = tile_list ? n_list : plan.n_tiles;
-  const dim3 g((unsigned)n_units), blk(kTileBlock);
+  const dim3 g((unsigned)(tile_list ? n_list : plan.n_tiles)), blk(kTileBlock);
   const int stride = plan.max_nodes | 1;                             // odd pitch of the component-major accumulator
   const size_t lds = (size_t)stride * 6 * sizeof(double);            // sized by the largest tile: more resident waves
   const int2 *conn2 = reinterpret_cast<const int2 *>(conn);
-#define PL_T(M, D, P, E)                                                                                          \
-  hipLaunchKernelGGL((k_spmv_tile<M, D, P, VT, E>), g, blk, lds, s, plan.tile_start.p, plan.home_ptr.p,           \
-                     plan.foreign_ptr.p, plan.foreign_idx.p, conn2, rec, pal, xyz, fixedbits, x, y, dot_dev, stride, cflag, cs, \
-                     tile_list)
-#define PL_TT(P, E)                                           \
-  do {                                                        \
-    if (fixedbits && dot_dev) PL_T(true, true, P, E);         \
-    else if (fixedbits) PL_T(true, false, P, E);              \
-    else if (dot_dev) PL_T(false, true, P, E);                \
-    else PL_T(false, false, P, E);                            \
-  } while (0)
-#define PL_TE(P)                                   \
-  do {                                             \
-    if (ends == kEndsCondensed) PL_TT(P, kEndsCondensed); \
-    else if (ends == kEndsCondensedSolve) PL_T(false, false, P, kEndsCondensedSolve); \
-    else if (ends == kEndsOthers) PL_TT(P, kEndsOthers);  \
-    else PL_TT(P, kEndsAll);                       \
-  } while (0)
-  if (pal) PL_TE(kRecPalette);
-  else if (xyz) PL_TE(kRecCompact);
-  else PL_TE(kRecAoS);
-#undef PL_TE
-#undef PL_TT
-#undef PL_T
+  auto launch = [&](auto r) {
+    with_tile_pass(ends, fixedbits != nullptr, dot_dev != nullptr, [&](auto e, auto m, auto d) {
+      hipLaunchKernelGGL((k_spmv_tile<decltype(m)::value, decltype(d)::value, decltype(r)::value, VT, decltype(e)::value>), g,
+                         blk, lds, s, plan.tile_start.p, plan.home_ptr.p, plan.foreign_ptr.p, plan.foreign_idx.p, conn2, rec,
+                         pal, xyz, fixedbits, x, y, dot_dev, stride, cflag, cs, tile_list);
+    });
+  };
+  if (pal) launch(Int<kRecPalette>{});
+  else if (xyz) launch(Int<kRecCompact>{});
+  else launch(Int<kRecAoS>{});
 }
 
 }  // namespace pl

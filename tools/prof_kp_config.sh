@@ -11,7 +11,7 @@ for set in "SQ_BUSY_CU_CYCLES SQ_WAVE_CYCLES SQ_ACTIVE_INST_VALU SQ_WAIT_INST_LD
            "SQ_INSTS_VALU SQ_INSTS_LDS SQ_LDS_BANK_CONFLICT SQ_LDS_IDX_ACTIVE SQ_WAVES" \
            "SQ_THREAD_CYCLES_VALU" "FETCH_SIZE" "WRITE_SIZE"; do
   i=$((i+1))
-  timeout -k 10 420 rocprofv3 --pmc $set --kernel-trace -d $O/p$i -o c --output-format csv -- python3 $R/tools/profile_config.py --config $CFG --precision $PREC --reps 5 > $O/p$i.out 2> $O/p$i.log || echo "pass $i failed"
+  timeout -k 10 420 rocprofv3 --pmc $set --kernel-trace -d $O/p$i -o c --output-format csv -- python3 $R/tools/profile_config.py --config $CFG --precision $PREC --reps 5 > $O/p$i.out 2> $O/p$i.log || { echo "pass $i failed: stopping"; exit 1; }
   echo "pass $i done"
 done
 python3 - $O $CFG $PREC $R/gpurun_out/$NAME.json <<'PY'
