@@ -716,6 +716,23 @@ int pl_forget_history(pl_handle h);
 int pl_debug_spd_solve(int device, int32_t n, const double *A, const double *b, double *x, double *quad,
                        int32_t fp32_factor);
 
+/* Test hook for the dense level with the switches of production (tests/test_gpu_dense_level.py): factors the host SPD matrix
+ * A[n*n] (row-major; padded to np = the next multiple of 64 with an identity diagonal) with block bandwidth bw_blocks
+ * (blocks (i, j), i - j > bw_blocks, must be zero; 0 = full), builds the inverse factor W = L^-1 in `storage` = 64, 32 or 16
+ * bits (fp64, fp32, bfloat16) - in one launch after the factorisation chain (trtri_rows = 0) or in ranges of at least
+ * trtri_rows block rows on a second stream behind it, as the assembly does with 3 - and applies it to r[n]:
+ * t = W r, y = W^T t, quad = t.t + the sum of add0[64] (a slotted scalar, as the PCG passes r.D^-1 r).  For storage 32 and
+ * 16 and np <= 2 048, also the explicit inverse Ainv = W^T W in fp32 and the one-GEMV form y_one = Ainv r,
+ * quad_one = r.y_one + sum(add0); *one_gemv says whether that ran (Ainv, y_one, quad_one are untouched otherwise).
+ * band_roundtrip != 0 first packs the block band of A and unpacks it again, as the multi-GPU assembly does around its
+ * all-reduce (needs 0 < bw_blocks < np / 64 - 1).  The calls are the assembly's and the preconditioner's own.
+ * W, Wt (= W^T as stored): [np*np], widened exactly to double; Ainv: [np*np]; t, y, y_one: [np]; info[2]: info[0] != 0 if a
+ * pivot was not positive (the outputs are then meaningless; the call still returns PL_OK). */
+int pl_debug_dense_level(int device, int32_t n, const double *A, int32_t bw_blocks, int32_t storage, int32_t trtri_rows,
+                         int32_t band_roundtrip, const double *r, const double *add0, double *W, double *Wt, float *Ainv,
+                         double *t, double *y, double *quad, double *y_one, double *quad_one, int32_t *one_gemv,
+                         int32_t *info);
+
 /* ---- multi-GPU (slab partition, RCCL) ---------------------------------------------------------------- */
 /* Size of the opaque RCCL unique id the ranks must share (rank 0 fills it with pl_dist_unique_id). */
 int pl_dist_unique_id_bytes(void);

@@ -26,7 +26,7 @@ EXPORTS = ["pl_default_opts", "pl_opts_size", "pl_stats_size", "pl_abi_version",
            "pl_spmv_multi", "pl_solve_multi", "pl_schur_block", "pl_geom_spmv_multi", "pl_buckling_modes", "pl_buckling_modes_sens",
            "pl_set_mass", "pl_mass_spmv_multi", "pl_vibration_modes", "pl_vibration_modes_sens",
            "pl_dyn_spmv_multi", "pl_transient", "pl_transient_sens", "pl_harm_spmv", "pl_harmonic", "pl_harmonic_sens",
-           "pl_schur_cells", "pl_cells_recover", "pl_get_records", "pl_debug_partition", "pl_time_kernel", "pl_algorithmic_bytes", "pl_node_words_info", "pl_forget_history", "pl_debug_spd_solve", "pl_dist_unique_id_bytes",
+           "pl_schur_cells", "pl_cells_recover", "pl_get_records", "pl_debug_partition", "pl_time_kernel", "pl_algorithmic_bytes", "pl_node_words_info", "pl_forget_history", "pl_debug_spd_solve", "pl_debug_dense_level", "pl_dist_unique_id_bytes",
            "pl_dist_unique_id", "pl_dist_loopback_id", "pl_dist_abort", "pl_dist_init", "pl_dist_set_peers", "pl_generate_lattice", "pl_lattice_fetch",
            "pl_lattice_free", "pl_penalize", "pl_boundary_index", "pl_boundary_index_rows"]
 
@@ -113,7 +113,8 @@ def load_library(path: str | None = None):
            "pl_schur_cells": [V, I32, I32, I32, V, I32, V, V, V, V, V, V, V],
            "pl_cells_recover": [V, I32, I32, I32, V, I32, V, V, V, V, V, V, V, V, V, V, V],
            "pl_get_records": [V, V], "pl_debug_partition": [V, V, V, V, V], "pl_time_kernel": [V, I32, I32, V],
-           "pl_algorithmic_bytes": [V, V], "pl_node_words_info": [V, V, V, V, V], "pl_forget_history": [V], "pl_debug_spd_solve": [I32, I32, V, V, V, V, I32], "pl_dist_unique_id_bytes": [], "pl_dist_unique_id": [V], "pl_dist_loopback_id": [V], "pl_dist_abort": [V],
+           "pl_algorithmic_bytes": [V, V], "pl_node_words_info": [V, V, V, V, V], "pl_forget_history": [V], "pl_debug_spd_solve": [I32, I32, V, V, V, V, I32],
+           "pl_debug_dense_level": [I32, I32, V, I32, I32, I32, I32] + [V] * 12, "pl_dist_unique_id_bytes": [], "pl_dist_unique_id": [V], "pl_dist_loopback_id": [V], "pl_dist_abort": [V],
            "pl_dist_init": [V, I32, I32, V, V, V, I32, I32], "pl_dist_set_peers": [V, V],
            "pl_generate_lattice": [I64, V, V, V, I32, I32, V, V, V, V], "pl_lattice_fetch": [V] * 12,
            "pl_lattice_free": [V], "pl_penalize": [I64, V, V, V, D, V, V, V],
@@ -176,6 +177,31 @@ def debug_spd_solve(A, b, device=0, fp32_factor=False):
     q = C.c_double()
     _check(lib, lib.pl_debug_spd_solve(device, len(b), _ptr(A), _ptr(b), _ptr(x), C.byref(q), int(bool(fp32_factor))))
     return x, q.value
+
+
+def debug_dense_level(A, r, bw_blocks, storage, trtri_rows=0, band_roundtrip=False, add0=None, device=0):
+    """The dense level as the assembly and the preconditioner run it (pl_debug_dense_level): block band, storage of the
+    inverse factor (64, 32 or 16 bits), row ranges on a second stream, band transfer, both forms of the apply.  Returns a
+    dict of arrays of the padded size np (next multiple of 64): W, Wt (np, np) as stored, widened to float64; t, y (np,);
+    quad; info (2,); and - where the one-GEMV form ran (``one_gemv``) - Ainv (np, np) float32, y_one, quad_one."""
+    lib = load_library()
+    r = _f64(r)
+    n = len(r)
+    A = _f64(A, n * n)
+    add0 = np.zeros(64) if add0 is None else _f64(add0, 64)
+    m = (n + 63) // 64 * 64
+    W, Wt, Ainv = np.empty((m, m)), np.empty((m, m)), np.zeros((m, m), np.float32)
+    t, y, y_one = np.empty(m), np.empty(m), np.zeros(m)
+    quad, quad_one, one = C.c_double(), C.c_double(), C.c_int32()
+    info = np.zeros(2, np.int32)
+    _check(lib, lib.pl_debug_dense_level(int(device), n, _ptr(A), int(bw_blocks), int(storage), int(trtri_rows),
+                                         int(bool(band_roundtrip)), _ptr(r), _ptr(add0), _ptr(W), _ptr(Wt), _ptr(Ainv),
+                                         _ptr(t), _ptr(y), C.byref(quad), _ptr(y_one), C.byref(quad_one), C.byref(one),
+                                         _ptr(info)))
+    out = {"W": W, "Wt": Wt, "t": t, "y": y, "quad": quad.value, "info": info, "one_gemv": bool(one.value)}
+    if one.value:
+        out.update(Ainv=Ainv, y_one=y_one, quad_one=quad_one.value)
+    return out
 
 
 # columns one pl_spmv_multi / pl_solve_multi call takes (PL_MULTI_MAX of include/pylattice_hip.h)

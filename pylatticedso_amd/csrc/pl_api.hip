@@ -74,6 +74,137 @@ int debug_spd_solve_t(int device, int32_t n, const double *A, const double *b, d
   return PL_OK;
 }
 
+// pl_debug_dense_level: the dense level as build_coarse_level and coarse_apply run it - the band, the row ranges of the
+// inverse factor on a second stream, the storage type, both forms of the apply - on a matrix of the caller's.
+inline double widen(double v) { return v; }
+inline double widen(float v) { return (double)v; }
+inline double widen(pl::bf16_t v) {
+  const uint32_t u = (uint32_t)v.v << 16;
+  float f;
+  std::memcpy(&f, &u, sizeof(f));
+  return (double)f;
+}
+struct DebugStreams {
+  hipStream_t main = nullptr, side = nullptr;
+  hipEvent_t go = nullptr, done = nullptr;
+  ~DebugStreams() {
+    if (go) (void)hipEventDestroy(go);
+    if (done) (void)hipEventDestroy(done);
+    if (side) (void)hipStreamDestroy(side);
+    if (main) (void)hipStreamDestroy(main);
+  }
+};
+template <typename WT>
+int debug_dense_level_t(int device, int32_t n, const double *A, int32_t bw_blocks, int32_t trtri_rows,
+                        int32_t band_roundtrip, const double *r, const double *add0, double *W_out, double *Wt_out,
+                        float *Ainv_out, double *t_out, double *y_out, double *quad, double *y_one, double *quad_one,
+                        int32_t *one_gemv, int32_t *info_out) {
+  int ndev = 0;
+  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return fail(PL_ERR_NODEVICE, "no HIP device visible");
+  if (device < 0 || device >= ndev) return fail(PL_ERR_ARG, "pl_debug_dense_level: bad device ordinal");
+  PL_HIP(hipSetDevice(device));
+  const int np = (n + pl::kNB - 1) / pl::kNB * pl::kNB, nb = np / pl::kNB;
+  if (band_roundtrip && !(bw_blocks > 0 && bw_blocks + 1 < nb))
+    return fail(PL_ERR_ARG, "pl_debug_dense_level: the band transfer needs 0 < bw_blocks < n / 64 - 1");
+  const size_t n2 = (size_t)np * np;
+  const bool one = !std::is_same<WT, double>::value && np <= pl::kOneGemvMaxDofs;
+  std::vector<double> Ap(n2, 0.0), rp(np, 0.0);
+  for (int i = 0; i < np; ++i) {
+    if (i < n) {
+      std::memcpy(&Ap[(size_t)i * np], A + (size_t)i * n, n * sizeof(double));
+      rp[i] = r[i];
+    } else {
+      Ap[(size_t)i * np + i] = 1.0;
+    }
+  }
+  DevBuf<double> dA, dL, dD, dr, dt, dy, dy1, dq, dq1, dadd;
+  DevBuf<WT> dW, dWt;
+  DevBuf<float> dG;
+  DevBuf<int> dinfo;
+  PL_HIP(dA.alloc(n2));
+  PL_HIP(dL.alloc(n2));
+  PL_HIP(dW.alloc(n2));
+  PL_HIP(dWt.alloc(n2));
+  PL_HIP(dD.alloc((size_t)np * pl::kNB));
+  PL_HIP(dr.alloc(np));
+  PL_HIP(dt.alloc(np));
+  PL_HIP(dy.alloc(np));
+  PL_HIP(dy1.alloc(np));
+  PL_HIP(dq.alloc(pl::kSlots));
+  PL_HIP(dq1.alloc(pl::kSlots));
+  PL_HIP(dadd.alloc(pl::kSlots));
+  PL_HIP(dinfo.alloc(2));
+  if (one) PL_HIP(dG.alloc(n2));
+  PL_HIP(hipMemcpy(dA.p, Ap.data(), n2 * sizeof(double), hipMemcpyHostToDevice));
+  PL_HIP(hipMemcpy(dr.p, rp.data(), np * sizeof(double), hipMemcpyHostToDevice));
+  PL_HIP(hipMemcpy(dadd.p, add0, pl::kSlots * sizeof(double), hipMemcpyHostToDevice));
+  PL_HIP(hipMemset(dL.p, 0, n2 * sizeof(double)));
+  PL_HIP(hipMemset(dW.p, 0, n2 * sizeof(WT)));
+  PL_HIP(hipMemset(dWt.p, 0, n2 * sizeof(WT)));
+  PL_HIP(hipMemset(dt.p, 0, np * sizeof(double)));
+  PL_HIP(hipMemset(dy.p, 0, np * sizeof(double)));
+  PL_HIP(hipMemset(dy1.p, 0, np * sizeof(double)));
+  PL_HIP(hipMemset(dq.p, 0, pl::kSlots * sizeof(double)));
+  PL_HIP(hipMemset(dq1.p, 0, pl::kSlots * sizeof(double)));
+  PL_HIP(hipMemset(dinfo.p, 0, 2 * sizeof(int)));
+  if (one) PL_HIP(hipMemset(dG.p, 0, n2 * sizeof(float)));
+  PL_HIP(hipDeviceSynchronize());                    // (the streams below do not wait for the null stream)
+  DebugStreams st;
+  PL_HIP(hipStreamCreateWithFlags(&st.main, hipStreamNonBlocking));
+  pl::TrtriPhases ph;
+  if (trtri_rows > 0) {
+    PL_HIP(hipStreamCreateWithFlags(&st.side, hipStreamNonBlocking));
+    PL_HIP(hipEventCreateWithFlags(&st.go, hipEventDisableTiming));
+    PL_HIP(hipEventCreateWithFlags(&st.done, hipEventDisableTiming));
+    ph.rows = trtri_rows;
+    ph.stream = st.side;
+    ph.ev_go = st.go;
+    ph.ev_done = st.done;
+  }
+  if (band_roundtrip) {
+    pl::band_pack(np, np, bw_blocks, dA.p, dL.p, st.main);
+    pl::band_unpack(np, np, bw_blocks, dL.p, dA.p, st.main);
+  }
+  pl::dense_factor_inverse(dA.p, dL.p, dW.p, dWt.p, dD.p, np, np, dinfo.p, bw_blocks, st.main, nullptr, (unsigned *)nullptr,
+                           ph);
+  pl::dense_apply(dW.p, dWt.p, np, np, dr.p, dt.p, dy.p, dq.p, dadd.p, st.main);
+  if constexpr (!std::is_same<WT, double>::value) {
+    if (one) {
+      pl::dense_explicit_inverse(np, (const WT *)dW.p, np, dG.p, st.main);
+      pl::dense_apply_one_gemv(dG.p, np, np, dr.p, dy1.p, dq1.p, dadd.p, st.main);
+    }
+  }
+  PL_HIP(hipGetLastError());
+  PL_HIP(hipStreamSynchronize(st.main));
+  if (st.side) PL_HIP(hipStreamSynchronize(st.side));
+  int info[2];
+  PL_HIP(hipMemcpy(info, dinfo.p, sizeof(info), hipMemcpyDeviceToHost));
+  info_out[0] = info[0];
+  info_out[1] = info[1];
+  {
+    std::vector<WT> w(n2);
+    PL_HIP(hipMemcpy(w.data(), dW.p, n2 * sizeof(WT), hipMemcpyDeviceToHost));
+    for (size_t e = 0; e < n2; ++e) W_out[e] = widen(w[e]);
+    PL_HIP(hipMemcpy(w.data(), dWt.p, n2 * sizeof(WT), hipMemcpyDeviceToHost));
+    for (size_t e = 0; e < n2; ++e) Wt_out[e] = widen(w[e]);
+  }
+  std::vector<double> q(pl::kSlots);
+  PL_HIP(hipMemcpy(t_out, dt.p, np * sizeof(double), hipMemcpyDeviceToHost));
+  PL_HIP(hipMemcpy(y_out, dy.p, np * sizeof(double), hipMemcpyDeviceToHost));
+  PL_HIP(hipMemcpy(q.data(), dq.p, pl::kSlots * sizeof(double), hipMemcpyDeviceToHost));
+  *quad = 0.0;
+  for (double v : q) *quad += v;
+  *one_gemv = one ? 1 : 0;
+  if (one) {
+    PL_HIP(hipMemcpy(Ainv_out, dG.p, n2 * sizeof(float), hipMemcpyDeviceToHost));
+    PL_HIP(hipMemcpy(y_one, dy1.p, np * sizeof(double), hipMemcpyDeviceToHost));
+    PL_HIP(hipMemcpy(q.data(), dq1.p, pl::kSlots * sizeof(double), hipMemcpyDeviceToHost));
+    *quad_one = 0.0;
+    for (double v : q) *quad_one += v;
+  }
+  return PL_OK;
+}
+
 // ---- multi-GPU ------------------------------------------------------------------------------------------
 }  // namespace
 
@@ -1179,13 +1310,8 @@ int pl_assemble(pl_handle h) {
         pl::coarse_factor(cs, n, h->stream, nullptr, (unsigned *)nullptr, ph);
         cs.ainv_ready = false;
         if (cs.Ainv) {
-          const long tiles = (long)(n / 32) * (n / 32 + 1) / 2;
-          if (cs.w16)
-            hipLaunchKernelGGL(pl::k_dense_explicit_inverse<pl::bf16_t>, dim3((unsigned)((tiles + 3) / 4)), dim3(256), 0,
-                               h->stream, n, reinterpret_cast<const pl::bf16_t *>(cs.W), n, cs.Ainv);
-          else
-            hipLaunchKernelGGL(pl::k_dense_explicit_inverse<float>, dim3((unsigned)((tiles + 3) / 4)), dim3(256), 0, h->stream,
-                               n, (const float *)cs.W, n, cs.Ainv);
+          if (cs.w16) pl::dense_explicit_inverse(n, reinterpret_cast<const pl::bf16_t *>(cs.W), n, cs.Ainv, h->stream);
+          else pl::dense_explicit_inverse(n, (const float *)cs.W, n, cs.Ainv, h->stream);
           cs.ainv_ready = true;
         }
         PL_HIP(hipMemcpyAsync(info2, cs.info, sizeof(info2), hipMemcpyDeviceToHost, h->stream));
@@ -3305,6 +3431,27 @@ int pl_debug_spd_solve(int device, int32_t n, const double *A, const double *b, 
                        int32_t fp32_factor) {
   return fp32_factor ? debug_spd_solve_t<float>(device, n, A, b, x, quad)
                      : debug_spd_solve_t<double>(device, n, A, b, x, quad);
+}
+
+int pl_debug_dense_level(int device, int32_t n, const double *A, int32_t bw_blocks, int32_t storage, int32_t trtri_rows,
+                         int32_t band_roundtrip, const double *r, const double *add0, double *W, double *Wt, float *Ainv,
+                         double *t, double *y, double *quad, double *y_one, double *quad_one, int32_t *one_gemv,
+                         int32_t *info) {
+  if (n <= 0 || !A || !r || !add0 || !W || !Wt || !Ainv || !t || !y || !quad || !y_one || !quad_one || !one_gemv || !info ||
+      bw_blocks < 0 || trtri_rows < 0)
+    return fail(PL_ERR_ARG, "pl_debug_dense_level: bad argument");
+  switch (storage) {
+    case 64:
+      return debug_dense_level_t<double>(device, n, A, bw_blocks, trtri_rows, band_roundtrip, r, add0, W, Wt, Ainv, t, y,
+                                         quad, y_one, quad_one, one_gemv, info);
+    case 32:
+      return debug_dense_level_t<float>(device, n, A, bw_blocks, trtri_rows, band_roundtrip, r, add0, W, Wt, Ainv, t, y,
+                                        quad, y_one, quad_one, one_gemv, info);
+    case 16:
+      return debug_dense_level_t<pl::bf16_t>(device, n, A, bw_blocks, trtri_rows, band_roundtrip, r, add0, W, Wt, Ainv, t,
+                                             y, quad, y_one, quad_one, one_gemv, info);
+  }
+  return fail(PL_ERR_ARG, "pl_debug_dense_level: storage must be 64, 32 or 16");
 }
 
 int pl_lzone(int device, int64_t n_nodes, int64_t n_beams, const double *node_xyz, const int32_t *beam_conn,

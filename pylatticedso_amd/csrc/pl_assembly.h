@@ -396,13 +396,10 @@ int build_coarse_level(pl_context *c, pl::Coarse &cs, const uint8_t *mask, bool 
   if (reduce && c->dist.active) {   // every rank holds the contribution of ITS struts; all ranks then factor the same matrix
     const int nb = n / pl::kNB;
     if (cs.bw_blocks > 0 && cs.bw_blocks + 1 < nb) {   // only the block band of the lower triangle travels (L_f is free)
-      const int64_t cnt = (int64_t)n * (cs.bw_blocks + 1) * pl::kNB;
-      hipLaunchKernelGGL(pl::k_band_pack, dim3((unsigned)((cnt + 255) / 256)), dim3(256), 0, c->stream, n, n,
-                         cs.bw_blocks, cs.Ac, cs.Lf);
-      if (pl::dist_sum_scalars(c->dist, cs.Lf, (int)cnt, c->stream))
+      pl::band_pack(n, n, cs.bw_blocks, cs.Ac, cs.Lf, c->stream);
+      if (pl::dist_sum_scalars(c->dist, cs.Lf, (int)pl::band_count(n, cs.bw_blocks), c->stream))
         return fail(PL_ERR_HIP, "RCCL all-reduce of the coarse operator failed");
-      hipLaunchKernelGGL(pl::k_band_unpack, dim3((unsigned)((cnt + 255) / 256)), dim3(256), 0, c->stream, n, n,
-                         cs.bw_blocks, cs.Lf, cs.Ac);
+      pl::band_unpack(n, n, cs.bw_blocks, cs.Lf, cs.Ac, c->stream);
     } else if (pl::dist_sum_scalars(c->dist, cs.Ac, n * n, c->stream)) {
       return fail(PL_ERR_HIP, "RCCL all-reduce of the coarse operator failed");
     }
@@ -425,13 +422,8 @@ int build_coarse_level(pl_context *c, pl::Coarse &cs, const uint8_t *mask, bool 
   if (&cs == &c->coarse && (small_wanted(c) || (n <= pl::kOneGemvMaxDofs && c->opkind == 0))) {
     if (!cs.Ainv && hipMalloc((void **)&cs.Ainv, (size_t)n * n * sizeof(float)) != hipSuccess)
       return fail(PL_ERR_HIP, "pl_assemble: out of device memory for the explicit inverse of the dense level");
-    const long tiles = (long)(n / 32) * (n / 32 + 1) / 2;
-    if (cs.w16)
-      hipLaunchKernelGGL(pl::k_dense_explicit_inverse<pl::bf16_t>, dim3((unsigned)((tiles + 3) / 4)), dim3(256), 0, c->stream, n,
-                         reinterpret_cast<const pl::bf16_t *>(cs.W), n, cs.Ainv);
-    else
-      hipLaunchKernelGGL(pl::k_dense_explicit_inverse<float>, dim3((unsigned)((tiles + 3) / 4)), dim3(256), 0, c->stream, n,
-                         (const float *)cs.W, n, cs.Ainv);
+    if (cs.w16) pl::dense_explicit_inverse(n, reinterpret_cast<const pl::bf16_t *>(cs.W), n, cs.Ainv, c->stream);
+    else pl::dense_explicit_inverse(n, (const float *)cs.W, n, cs.Ainv, c->stream);
     cs.ainv_ready = true;
   }
   if (tile_invert_pending) PL_HIP(hipStreamWaitEvent(c->stream, c->ev_t1, 0));

@@ -670,6 +670,14 @@ __global__ void k_band_unpack(int n, int ld, int bwb, const double *__restrict__
   const int i = (int)(e / W), j = (i / kNB - bwb) * kNB + (int)(e % W);
   if (j >= 0) A[(size_t)i * ld + j] = P[e];
 }
+// the band applies (and P = an n x ld matrix holds it) when bwb > 0 and bwb + 1 < n / kNB
+inline int64_t band_count(int n, int bwb) { return (int64_t)n * (bwb + 1) * kNB; }
+inline void band_pack(int n, int ld, int bwb, double *A, double *P, hipStream_t s) {
+  hipLaunchKernelGGL(k_band_pack, dim3((unsigned)((band_count(n, bwb) + 255) / 256)), dim3(256), 0, s, n, ld, bwb, A, P);
+}
+inline void band_unpack(int n, int ld, int bwb, const double *P, double *A, hipStream_t s) {
+  hipLaunchKernelGGL(k_band_unpack, dim3((unsigned)((band_count(n, bwb) + 255) / 256)), dim3(256), 0, s, n, ld, bwb, P, A);
+}
 
 __global__ __launch_bounds__(kBlock) void k_tile_blocks(const int32_t *__restrict__ tile_start,
                                                         const int64_t *__restrict__ home_ptr,
@@ -984,8 +992,7 @@ inline void coarse_apply(const Coarse &cs, const double *r, double *t, double *y
                          hipStream_t s) {
   static const bool one_off = [] { const char *e = std::getenv("PL_ONE_GEMV"); return e && e[0] == '0'; }();
   if (cs.ainv_ready && cs.Ainv && cs.ncp <= kOneGemvMaxDofs && !one_off) {
-    hipLaunchKernelGGL(k_full_gemv, dim3((cs.ncp + 3) / 4), dim3(kBlock), 0, s, cs.ncp, (const float *)cs.Ainv, cs.ncp, r, y,
-                       dot_out, add0);
+    dense_apply_one_gemv((const float *)cs.Ainv, cs.ncp, cs.ncp, r, y, dot_out, add0, s);
     return;
   }
   if (cs.w16)

@@ -777,5 +777,10 @@ inline void dense_apply(const WT *W, const WT *Wt, int n, int ld, const double *
   hipLaunchKernelGGL(k_tri_gemv<WT>, dim3((n + 3) / 4), dim3(kBlock), 0, s, n, W, ld, r, t, dot_out, add0);
   hipLaunchKernelGGL(k_tri_gemv_upper<WT>, dim3((n + 3) / 4), dim3(kBlock), 0, s, n, Wt, ld, t, y);
 }
+// the same through the explicit inverse G; dot_out[kSlots] += r.G r (+ *add0 once)
+inline void dense_apply_one_gemv(const float *G, int n, int ld, const double *r, double *y, double *dot_out,
+                                 const double *add0, hipStream_t s) {
+  hipLaunchKernelGGL(k_full_gemv, dim3((n + 3) / 4), dim3(kBlock), 0, s, n, G, ld, r, y, dot_out, add0);
+}
 
 }  // namespace pl

@@ -85,6 +85,11 @@ __global__ __launch_bounds__(256) void k_dense_explicit_inverse(int n, const WT 
         }
       }
 }
+template <typename WT>
+inline void dense_explicit_inverse(int n, const WT *W, int ld, float *Ainv, hipStream_t s) {
+  const long tiles = (long)(n / 32) * (n / 32 + 1) / 2;
+  hipLaunchKernelGGL(k_dense_explicit_inverse<WT>, dim3((unsigned)((tiles + 3) / 4)), dim3(256), 0, s, n, W, ld, Ainv);
+}
 
 // z = D^-1 r + P Z (y_c + y_t) for the rows of one tile, with y_c = the tile's aggregate's rows of A_c^-1 r_c computed here.
 // One workgroup per tile.  Also: r.z into the slots of the NEXT iteration's scalar set, ||r||^2 of this iteration into the
