@@ -404,6 +404,34 @@ int pl_buckling(pl_handle h, const double *u /*[6N] or NULL*/, int32_t length, d
 int pl_buckling_pnorm(pl_handle h, const double *u /*[6N] or NULL*/, int32_t length, double k_eff, int32_t shear, double p,
                       double *bp, double *util_max, double *dbp_du /*[6N] or NULL*/, double *dbp_dr /*[B] or NULL*/);
 
+/* ---- thermal loads: strut expansion forces, thermal stress and buckling, gradients -------------------------------------------
+ * The temperature rise is GIVEN per node (no heat conduction here), linear along a strut between its end values and uniform
+ * over the section (no thermal curvature).  Strut b = (A, B), d = x_B - x_A, L = |d|, t = d / L, expansion coefficient alpha_b:
+ *   free elongation     delta_b = alpha_b L (dT_A + dT_B) / 2    (no radius and no penalised segment enters)
+ *   restrained force    F_th,b = ka_b delta_b, ka_b = rec.a + rec.e1 L^2 the condensed axial stiffness of the record
+ *                       (multiplicity k of pl_set_multiplicity included); n_free_b = F_th,b / k is that of ONE copy
+ *   equivalent loads    f_th: +F_th t on the translations of B, -F_th t on those of A, no moments.  Equilibrium under a thermal
+ *                       load is K u = f_ext + f_th: the caller adds f_th to the f of pl_set_bc.
+ * While a thermal state is set, pl_stress, pl_stress_pnorm, pl_buckling and pl_buckling_pnorm evaluate the MECHANICAL section
+ * force F = K_tip (du, dth) - F_th t: N = (F.t - F_th) / k, while V, T, Mb are unchanged; dphi_du / dbp_du keep their form and
+ * dphi_dr / dbp_dr gain g_F . (-(2 ka / r) delta t) (d ka / dr = 2 ka / r at fixed segment geometry).  Without a thermal state
+ * these calls run the kernels and the arithmetic they ran before.  pl_buckling_modes, pl_buckling_modes_sens and
+ * pl_geom_spmv_multi build K_g from K_e u_e, which would ignore the thermal prestress: PL_ERR_STATE while a thermal state is set.
+ * pl_energy, pl_reactions, pl_node_mod, pl_sens and the dynamic calls do not read the thermal state.
+ *
+ * alpha_b = beam_alpha ? beam_alpha[b] : alpha; node_dT[N] in the caller's node numbering; node_dT == NULL clears the
+ * thermal state of the handle.  Non-finite values: PL_ERR_ARG.  Single-GPU FEM handles only (PL_ERR_STATE on
+ * pl_create_ddm / pl_dist_init handles, as pl_set_mass).  Survives pl_update_radii / pl_update_segments / pl_assemble. */
+int pl_set_thermal(pl_handle h, double alpha, const double *beam_alpha /*[B] or NULL*/, const double *node_dT /*[N] or NULL*/);
+/* f_th[6N] (caller's numbering) and/or n_free[B] = restrained force of ONE copy, from the records of the last pl_assemble.
+ * f_th is gathered per node without atomics: two calls return the same bits.
+ * PL_ERR_STATE before pl_set_thermal or before assembly; both outputs NULL: PL_ERR_ARG. */
+int pl_thermal_load(pl_handle h, double *f /*[6N] or NULL*/, double *n_free /*[B] or NULL*/);
+/* out[b] = lam^T d f_th / d r_b = (2 ka_b / r_b) delta_b t . (lam_u,B - lam_u,A) at fixed segment geometry; lam == NULL -> the
+ * solution of the last pl_solve (as pl_sens).  For a scalar q(u(r), r) with K lam = dq/du on the free dofs,
+ * dq/dr_b = dq/dr_b at fixed u - lam^T (dK/dr_b) u + lam^T d f_th / d r_b.  Errors as pl_thermal_load; out == NULL: PL_ERR_ARG. */
+int pl_thermal_sens(pl_handle h, const double *lam /*[6N] or NULL*/, double *out /*[B]*/);
+
 /* Strain energy 1/2 u^T K u (LatticeOpti.compute_compliance, lattice_opti.py:645-663 uses u^T K u). */
 int pl_energy(pl_handle h, const double *u, double *energy);
 

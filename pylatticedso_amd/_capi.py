@@ -23,6 +23,7 @@ EXPORTS = ["pl_default_opts", "pl_opts_size", "pl_stats_size", "pl_abi_version",
            "pl_update_radii", "pl_set_multiplicity", "pl_update_segments", "pl_assemble", "pl_assemble_bsr", "pl_get_bsr", "pl_spmv",
            "pl_spmv_free", "pl_spmv_bsr", "pl_solve", "pl_reactions", "pl_sens", "pl_sens_gram", "pl_energy", "pl_node_mod", "pl_schur",
            "pl_stress", "pl_stress_pnorm", "pl_buckling", "pl_buckling_pnorm",
+           "pl_set_thermal", "pl_thermal_load", "pl_thermal_sens",
            "pl_spmv_multi", "pl_solve_multi", "pl_schur_block", "pl_geom_spmv_multi", "pl_buckling_modes", "pl_buckling_modes_sens",
            "pl_set_mass", "pl_mass_spmv_multi", "pl_vibration_modes", "pl_vibration_modes_sens",
            "pl_dyn_spmv_multi", "pl_transient", "pl_transient_sens", "pl_harm_spmv", "pl_harmonic", "pl_harmonic_sens",
@@ -96,6 +97,7 @@ def load_library(path: str | None = None):
            "pl_reactions": [V, V, V], "pl_sens": [V, V, V, V], "pl_sens_gram": [V, I32, V, V], "pl_energy": [V, V, V], "pl_node_mod": [V, V, V],
            "pl_stress": [V, V, I32, V, V], "pl_stress_pnorm": [V, V, I32, D, V, V, V, V],
            "pl_buckling": [V, V, I32, D, I32, V, V, V], "pl_buckling_pnorm": [V, V, I32, D, I32, D, V, V, V, V],
+           "pl_set_thermal": [V, D, V, V], "pl_thermal_load": [V, V, V], "pl_thermal_sens": [V, V, V],
            "pl_schur": [V, V, I32, D, I32, V], "pl_spmv_multi": [V, I32, I32, V, V],
            "pl_solve_multi": [V, I32, V, V, D, I32, V, V], "pl_schur_block": [V, V, I32, D, I32, I32, V],
            "pl_geom_spmv_multi": [V, V, I32, I32, V, V],
@@ -443,6 +445,7 @@ class HipLattice:
         _check(self._lib, self._lib.pl_create(C.byref(mesh), C.byref(opts), C.byref(self._h)))
         self.last_stats = None
         self._mult = None
+        self._thermal = None
         if beam_mult is not None:
             self.set_multiplicity(beam_mult)
 
@@ -705,15 +708,17 @@ class HipLattice:
     def stress_host(self, u, where=0):
         """The numpy restatement of ``stress`` (stress_host.strut_stress) on this handle's records and segment data."""
         from . import stress_host as SH
-        return SH.strut_stress(self.records(), self.beam_conn, self._radius, self._seg_len, u, self._material[3],
-                               self._mult, where)
+        rec = self.records()
+        return SH.strut_stress(rec, self.beam_conn, self._radius, self._seg_len, u, self._material[3], self._mult, where,
+                               self._f_th_host(rec))
 
     def stress_pnorm_host(self, p, u, where=0, want_grad=True):
         """The numpy restatement of ``stress_pnorm`` (stress_host.stress_pnorm)."""
         from . import stress_host as SH
         E, nu, kappa, pen = self._material
-        return SH.stress_pnorm(self.records(), self.n_nodes, self.beam_conn, self._radius, self._seg_len, self._seg_nsub,
-                               u, p, E, nu, kappa, pen, self._mult, where, want_grad)
+        rec = self.records()
+        return SH.stress_pnorm(rec, self.n_nodes, self.beam_conn, self._radius, self._seg_len, self._seg_nsub,
+                               u, p, E, nu, kappa, pen, self._mult, where, want_grad, self._f_th_host(rec))
 
     def buckling(self, u=None, length=1, k_eff=1.0, shear=0):
         """Euler buckling utilisation of every strut (pl_buckling): dict with util = max(0, -N) / N_cr, n_axial (signed N of
@@ -734,15 +739,74 @@ class HipLattice:
         """The numpy restatement of ``buckling`` (buckling_host.strut_buckling) on this handle's records and segment data."""
         from . import buckling_host as BH
         E, nu, kappa, _ = self._material
-        return BH.strut_buckling(self.records(), self.beam_conn, self._radius, self._seg_len, u, E, nu, kappa, self._mult,
-                                 length, k_eff, shear)
+        rec = self.records()
+        return BH.strut_buckling(rec, self.beam_conn, self._radius, self._seg_len, u, E, nu, kappa, self._mult,
+                                 length, k_eff, shear, self._f_th_host(rec))
 
     def buckling_pnorm_host(self, p, u, length=1, k_eff=1.0, shear=0, want_grad=True):
         """The numpy restatement of ``buckling_pnorm`` (buckling_host.buckling_pnorm)."""
         from . import buckling_host as BH
         E, nu, kappa, pen = self._material
-        return BH.buckling_pnorm(self.records(), self.n_nodes, self.beam_conn, self._radius, self._seg_len, self._seg_nsub,
-                                 u, p, E, nu, kappa, pen, self._mult, length, k_eff, shear, want_grad)
+        rec = self.records()
+        return BH.buckling_pnorm(rec, self.n_nodes, self.beam_conn, self._radius, self._seg_len, self._seg_nsub,
+                                 u, p, E, nu, kappa, pen, self._mult, length, k_eff, shear, want_grad, self._f_th_host(rec))
+
+    # -- thermal loads ------------------------------------------------------------------------------------
+    def set_thermal(self, alpha, node_dT, beam_alpha=None):
+        """Thermal state of the handle (pl_set_thermal): expansion coefficient ``alpha`` of every strut, or beam_alpha (B,)
+        per strut, and the temperature rise node_dT (N,) of every node.  While it is set, ``stress``, ``stress_pnorm``,
+        ``buckling`` and ``buckling_pnorm`` evaluate the mechanical section force K_tip (du, dth) - ka delta t, and
+        ``buckling_modes`` / ``geom_spmv_multi`` refuse.  It survives update_radii / update_segments / assemble."""
+        dT = _f64(np.asarray(node_dT).reshape(-1), self.n_nodes)
+        ba = None if beam_alpha is None else _f64(np.asarray(beam_alpha).reshape(-1), self.n_beams)
+        _check(self._lib, self._lib.pl_set_thermal(self._h, float(alpha), _ptr(ba), _ptr(dT)))
+        self._thermal = (ba if ba is not None else float(alpha), dT)
+
+    def clear_thermal(self):
+        """Removes the thermal state (pl_set_thermal with node_dT = NULL)."""
+        _check(self._lib, self._lib.pl_set_thermal(self._h, 0.0, None, None))
+        self._thermal = None
+
+    def thermal_load(self):
+        """(f_th (N, 6), n_free (B,)) of the thermal state on the records of the last assemble() (pl_thermal_load): the
+        equivalent nodal loads, K u = f_ext + f_th, and the restrained force of one copy of every strut."""
+        f = np.empty((self.n_nodes, 6), np.float64)
+        n_free = np.empty(self.n_beams, np.float64)
+        _check(self._lib, self._lib.pl_thermal_load(self._h, _ptr(f), _ptr(n_free)))
+        return f, n_free
+
+    def thermal_sens(self, lam=None):
+        """(B,) lam^T d f_th / d r_b at fixed segment geometry (pl_thermal_sens); lam = None: the solution of the last
+        solve(), still on the device."""
+        out = np.empty(self.n_beams, np.float64)
+        _check(self._lib, self._lib.pl_thermal_sens(self._h, _ptr(self._opt_vec6(lam)), _ptr(out)))
+        return out
+
+    def _delta_host(self):
+        from . import thermal_host as TH
+        if getattr(self, "_thermal", None) is None:
+            return None
+        return TH.elongation(self.node_xyz, self.beam_conn, *self._thermal)
+
+    def _f_th_host(self, rec):
+        """Restrained thermal force of every record (thermal_host.restrained_force), None without a thermal state."""
+        from . import thermal_host as TH
+        delta = self._delta_host()
+        return None if delta is None else TH.restrained_force(rec, delta)
+
+    def thermal_load_host(self):
+        """The numpy restatement of ``thermal_load`` (thermal_host.thermal_load) on this handle's records."""
+        from . import thermal_host as TH
+        if self._thermal is None:
+            raise RuntimeError("thermal_load_host: call set_thermal first")
+        return TH.thermal_load(self.records(), self.beam_conn, self.n_nodes, self._delta_host(), self._mult)
+
+    def thermal_sens_host(self, lam):
+        """The numpy restatement of ``thermal_sens`` (thermal_host.thermal_sens)."""
+        from . import thermal_host as TH
+        if self._thermal is None:
+            raise RuntimeError("thermal_sens_host: call set_thermal first")
+        return TH.thermal_sens(self.records(), self.beam_conn, self._radius, self._delta_host(), lam)
 
     def energy(self, u):
         u = _f64(np.asarray(u).reshape(-1), 6 * self.n_nodes)

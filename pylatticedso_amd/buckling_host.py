@@ -33,7 +33,7 @@ def critical_load(radius, ell, young, poisson, kappa=0.9, k_eff=1.0, shear=0):
     return n_e / (1.0 + q), q
 
 
-def _evaluate(rec, conn, radius, seg_len, u, young, poisson, kappa, mult, length, k_eff, shear):
+def _evaluate(rec, conn, radius, seg_len, u, young, poisson, kappa, mult, length, k_eff, shear, f_th=None):
     if length not in (0, 1):
         raise ValueError("length must be 0 (node to node) or 1 (the middle segment)")
     conn = np.asarray(conn).reshape(-1, 2)
@@ -44,6 +44,8 @@ def _evaluate(rec, conn, radius, seg_len, u, young, poisson, kappa, mult, length
     span = np.sqrt(SH._dot(d, d))
     t = d / span[:, None]
     F, _ = SH.tip_force(rec, conn, u)
+    if f_th is not None:                                           # mechanical force under a thermal state: F - F_th t
+        F = F - np.asarray(f_th, dtype=float)[:, None] * t
     mid = np.asarray(seg_len, dtype=float).reshape(-1, 3)[:, 1]
     on = np.ones(len(r), bool) if length == 0 else mid > 0
     ell = span if length == 0 else np.where(on, mid, 1.0)
@@ -53,10 +55,11 @@ def _evaluate(rec, conn, radius, seg_len, u, young, poisson, kappa, mult, length
     return dict(conn=conn, rec=rec, r=r, k=k, d=d, t=t, on=on, N=N, n_cr=n_cr, q=q, beta=beta)
 
 
-def strut_buckling(rec, beam_conn, radius, seg_len, u, young, poisson, kappa=0.9, mult=None, length=1, k_eff=1.0, shear=0):
+def strut_buckling(rec, beam_conn, radius, seg_len, u, young, poisson, kappa=0.9, mult=None, length=1, k_eff=1.0, shear=0,
+                   f_th=None):
     """dict util (beta), n_axial (signed N of one copy), n_crit (N_cr), each (B,), NaN on absent struts - the outputs of
-    pl_buckling."""
-    ev = _evaluate(rec, beam_conn, radius, seg_len, u, young, poisson, kappa, mult, length, k_eff, shear)
+    pl_buckling.  f_th (B,): the restrained thermal force of every record (stress_host.strut_stress); None: no thermal state."""
+    ev = _evaluate(rec, beam_conn, radius, seg_len, u, young, poisson, kappa, mult, length, k_eff, shear, f_th)
     return {"util": np.where(ev["on"], ev["beta"], np.nan), "n_axial": np.where(ev["on"], ev["N"], np.nan),
             "n_crit": np.where(ev["on"], ev["n_cr"], np.nan)}
 
@@ -67,10 +70,11 @@ def pnorm(util, p):
 
 
 def buckling_pnorm(rec, node_count, beam_conn, radius, seg_len, seg_nsub, u, p, young, poisson, kappa=0.9, pen_coef=1.5,
-                   mult=None, length=1, k_eff=1.0, shear=0, want_grad=True):
+                   mult=None, length=1, k_eff=1.0, shear=0, want_grad=True, f_th=None):
     """(bp, util_max, dbp_du (N, 6), dbp_dr (B,)) - the outputs of pl_buckling_pnorm; dbp_dr at fixed u and segment geometry,
-    through the record (its radius derivative) and through N_cr(r)."""
-    ev = _evaluate(rec, beam_conn, radius, seg_len, u, young, poisson, kappa, mult, length, k_eff, shear)
+    through the record (its radius derivative) and through N_cr(r).  f_th: as in ``strut_buckling``; its radius derivative
+    (2 / r) f_th t enters dbp_dr."""
+    ev = _evaluate(rec, beam_conn, radius, seg_len, u, young, poisson, kappa, mult, length, k_eff, shear, f_th)
     on, beta = ev["on"], ev["beta"]
     bp, bmax = pnorm(np.where(on, beta, np.nan), p)
     if not want_grad:
@@ -87,6 +91,8 @@ def buckling_pnorm(rec, node_count, beam_conn, radius, seg_len, seg_nsub, u, p, 
     du = SH.scatter_tip_gradient(ev["rec"], conn, node_count, gF, np.zeros_like(gF))
     f = SH.flexibility(ev["r"], seg_len, seg_nsub, young, poisson, kappa, pen_coef, mult)
     dF, _ = SH.tip_force(SH._record(SH._dscalars_dr(f, ev["r"]), d), conn, u)
+    if f_th is not None:
+        dF = dF - (2.0 * np.asarray(f_th, dtype=float) / ev["r"])[:, None] * ev["t"]
     q = ev["q"]
     dbeta = -beta * (4.0 - 2.0 * q / (1.0 + q)) / ev["r"]                          # at fixed P: N_E ~ r^4, q ~ r^2
     return bp, bmax, du, np.where(live, SH._dot(gF, dF) + w * dbeta, 0.0)

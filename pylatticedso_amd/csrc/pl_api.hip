@@ -7,6 +7,7 @@
 #include "pl_multi.h"
 #include "pl_stress.h"
 #include "pl_buckling.h"
+#include "pl_thermal.h"
 #include "pl_geom.h"
 #include "pl_mass.h"
 #include "pl_dyn.h"
@@ -1755,6 +1756,34 @@ struct EventTimer {
     for (int i = 0; i < n; ++i) (void)hipEventDestroy(ev[i]);
   }
 };
+
+// Thermal state of the handle (pl_set_thermal): *t = null without one.  With one, delta[B] (and n_free[B] when asked for) is
+// rebuilt from the current records - k_thermal_strut, one thread per strut - so the state follows every pl_assemble.
+int thermal_refresh(pl_handle h, const char *who, bool want_n_free, ThermalWs **t) {
+  *t = static_cast<ThermalWs *>(h->thermal_ws.get());
+  if (!*t) return PL_OK;
+  EventTimer timer(who, h->stream, "kernel_hip_event");
+  hipLaunchKernelGGL(pl::k_thermal_strut, dim3(grid_for(h->B)), dim3(pl::kBlock), 0, h->stream, h->B, h->conn.p, h->rec.p,
+                     h->mult.p, (*t)->alpha.p, (*t)->dT.p, (*t)->delta.p, want_n_free ? (*t)->n_free.p : (double *)nullptr);
+  PL_HIP(hipGetLastError());
+  timer.stop();
+  return PL_OK;
+}
+// the free elongations the stress and buckling passes subtract: *delta = null without a thermal state (the plain kernels run)
+int thermal_delta(pl_handle h, const char *who, const double **delta) {
+  ThermalWs *t = nullptr;
+  if (int rc = thermal_refresh(h, who, false, &t)) return rc;
+  *delta = t ? t->delta.p : nullptr;
+  return PL_OK;
+}
+// runs launch(std::bool_constant<TH>): the thermal instantiation of a strut kernel exactly when delta is set
+extern "C++" {   // (a template)
+template <class Launch>
+void thermal_dispatch(const double *delta, Launch launch) {
+  if (delta) launch(std::true_type{});
+  else launch(std::false_type{});
+}
+}  // extern "C++"
 }  // namespace
 
 int pl_stress(pl_handle h, const double *u, int32_t where, double *station, double *peak) {
@@ -1765,10 +1794,14 @@ int pl_stress(pl_handle h, const double *u, int32_t where, double *station, doub
   DevBuf<double> d_station;
   if (station) PL_HIP(d_station.alloc((size_t)B * 20));
   if (peak && !h->st_dr.p) PL_HIP(h->st_dr.alloc((size_t)B));
+  const double *delta = nullptr;
+  if (int rc = thermal_delta(h, "pl_stress", &delta)) return rc;
   EventTimer timer("pl_stress", h->stream, "kernel_hip_event");
-  hipLaunchKernelGGL(pl::k_stress_stations, dim3(grid_for(B)), dim3(pl::kBlock), 0, h->stream, B, h->conn.p, h->rec.p,
-                     h->radius.p, h->seg_len.p, h->mult.p, h->mat.pen, (int)where, u_dev, d_station.p,
-                     peak ? h->st_dr.p : (double *)nullptr, (double *)nullptr, (double *)nullptr);
+  thermal_dispatch(delta, [&](auto th) {
+    hipLaunchKernelGGL(pl::k_stress_stations<decltype(th)::value>, dim3(grid_for(B)), dim3(pl::kBlock), 0, h->stream, B,
+                       h->conn.p, h->rec.p, h->radius.p, h->seg_len.p, h->mult.p, h->mat.pen, (int)where, u_dev, d_station.p,
+                       peak ? h->st_dr.p : (double *)nullptr, (double *)nullptr, (double *)nullptr, delta);
+  });
   PL_HIP(hipGetLastError());
   timer.stop();
   if (station)
@@ -1831,17 +1864,23 @@ int pl_stress_pnorm(pl_handle h, const double *u, int32_t where, double p, doubl
   const double *u_dev = nullptr;
   if (int rc = stress_begin(h, "pl_stress_pnorm", u, where, &u_dev)) return rc;
   const int64_t B = h->B;
+  const double *delta = nullptr;
+  if (int rc = thermal_delta(h, "pl_stress_pnorm", &delta)) return rc;
   return pnorm_call(h, "pl_stress_pnorm", p, phi, sigma_max, dphi_du, dphi_dr, [&](unsigned grid) {
-    hipLaunchKernelGGL(pl::k_stress_stations, dim3(grid), dim3(pl::kBlock), 0, h->stream, B, h->conn.p, h->rec.p, h->radius.p,
-                       h->seg_len.p, h->mult.p, h->mat.pen, (int)where, u_dev, (double *)nullptr, (double *)nullptr,
-                       h->st_vm4.p, h->st_part.p);
+    thermal_dispatch(delta, [&](auto th) {
+      hipLaunchKernelGGL(pl::k_stress_stations<decltype(th)::value>, dim3(grid), dim3(pl::kBlock), 0, h->stream, B, h->conn.p,
+                         h->rec.p, h->radius.p, h->seg_len.p, h->mult.p, h->mat.pen, (int)where, u_dev, (double *)nullptr,
+                         (double *)nullptr, h->st_vm4.p, h->st_part.p, delta);
+    });
   }, [&](unsigned grid) {
     hipLaunchKernelGGL((pl::k_pnorm_psum<4, true>), dim3(grid), dim3(pl::kBlock), 0, h->stream, B, h->st_vm4.p, h->st_red.p, p,
                        h->st_part.p);
   }, [&](unsigned grid, auto dr) {
-    hipLaunchKernelGGL(pl::k_stress_grad<decltype(dr)::value>, dim3(grid), dim3(pl::kBlock), 0, h->stream, B, h->conn.p,
-                       h->rec.p, h->radius.p, h->seg_len.p, h->seg_nsub.p, h->mult.p, h->mat, (int)where, p, u_dev, h->st_red.p,
-                       h->st_G.p, dr ? h->st_dr.p : (double *)nullptr);
+    thermal_dispatch(delta, [&](auto th) {
+      hipLaunchKernelGGL((pl::k_stress_grad<decltype(dr)::value, decltype(th)::value>), dim3(grid), dim3(pl::kBlock), 0,
+                         h->stream, B, h->conn.p, h->rec.p, h->radius.p, h->seg_len.p, h->seg_nsub.p, h->mult.p, h->mat,
+                         (int)where, p, u_dev, h->st_red.p, h->st_G.p, dr ? h->st_dr.p : (double *)nullptr, delta);
+    });
   });
 }
 
@@ -1866,11 +1905,15 @@ int pl_buckling(pl_handle h, const double *u, int32_t length, double k_eff, int3
   const int64_t B = h->B;
   if (!h->st_vm4.p) PL_HIP(h->st_vm4.alloc((size_t)B * 4));   // rows 0..2 of [4][B]: beta, N, N_cr
   double *d_util = h->st_vm4.p, *d_n = h->st_vm4.p + B, *d_cr = h->st_vm4.p + 2 * B;
+  const double *delta = nullptr;
+  if (int rc = thermal_delta(h, "pl_buckling", &delta)) return rc;
   EventTimer timer("pl_buckling", h->stream, "kernel_hip_event");
-  hipLaunchKernelGGL(pl::k_buckling_util, dim3(grid_for(B)), dim3(pl::kBlock), 0, h->stream, B, h->conn.p, h->rec.p,
-                     h->radius.p, h->seg_len.p, h->mult.p, h->mat, (int)length, k_eff, (int)shear, u_dev,
-                     util ? d_util : (double *)nullptr, n_axial ? d_n : (double *)nullptr,
-                     n_crit ? d_cr : (double *)nullptr, (double *)nullptr);
+  thermal_dispatch(delta, [&](auto th) {
+    hipLaunchKernelGGL(pl::k_buckling_util<decltype(th)::value>, dim3(grid_for(B)), dim3(pl::kBlock), 0, h->stream, B,
+                       h->conn.p, h->rec.p, h->radius.p, h->seg_len.p, h->mult.p, h->mat, (int)length, k_eff, (int)shear, u_dev,
+                       util ? d_util : (double *)nullptr, n_axial ? d_n : (double *)nullptr,
+                       n_crit ? d_cr : (double *)nullptr, (double *)nullptr, delta);
+  });
   PL_HIP(hipGetLastError());
   timer.stop();
   if (util)
@@ -1887,18 +1930,102 @@ int pl_buckling_pnorm(pl_handle h, const double *u, int32_t length, double k_eff
   const double *u_dev = nullptr;
   if (int rc = buckling_begin(h, "pl_buckling_pnorm", u, length, k_eff, shear, &u_dev)) return rc;
   const int64_t B = h->B;
+  const double *delta = nullptr;
+  if (int rc = thermal_delta(h, "pl_buckling_pnorm", &delta)) return rc;
   return pnorm_call(h, "pl_buckling_pnorm", p, bp, util_max, dbp_du, dbp_dr, [&](unsigned grid) {   // beta in st_vm4
-    hipLaunchKernelGGL(pl::k_buckling_util, dim3(grid), dim3(pl::kBlock), 0, h->stream, B, h->conn.p, h->rec.p, h->radius.p,
-                       h->seg_len.p, h->mult.p, h->mat, (int)length, k_eff, (int)shear, u_dev, h->st_vm4.p, (double *)nullptr,
-                       (double *)nullptr, h->st_part.p);
+    thermal_dispatch(delta, [&](auto th) {
+      hipLaunchKernelGGL(pl::k_buckling_util<decltype(th)::value>, dim3(grid), dim3(pl::kBlock), 0, h->stream, B, h->conn.p,
+                         h->rec.p, h->radius.p, h->seg_len.p, h->mult.p, h->mat, (int)length, k_eff, (int)shear, u_dev,
+                         h->st_vm4.p, (double *)nullptr, (double *)nullptr, h->st_part.p, delta);
+    });
   }, [&](unsigned grid) {
     hipLaunchKernelGGL((pl::k_pnorm_psum<1, false>), dim3(grid), dim3(pl::kBlock), 0, h->stream, B, h->st_vm4.p, h->st_red.p, p,
                        h->st_part.p);
   }, [&](unsigned grid, auto dr) {
-    hipLaunchKernelGGL(pl::k_buckling_grad<decltype(dr)::value>, dim3(grid), dim3(pl::kBlock), 0, h->stream, B, h->conn.p,
-                       h->rec.p, h->radius.p, h->seg_len.p, h->seg_nsub.p, h->mult.p, h->mat, (int)length, k_eff, (int)shear, p,
-                       u_dev, h->st_red.p, h->st_G.p, dr ? h->st_dr.p : (double *)nullptr);
+    thermal_dispatch(delta, [&](auto th) {
+      hipLaunchKernelGGL((pl::k_buckling_grad<decltype(dr)::value, decltype(th)::value>), dim3(grid), dim3(pl::kBlock), 0,
+                         h->stream, B, h->conn.p, h->rec.p, h->radius.p, h->seg_len.p, h->seg_nsub.p, h->mult.p, h->mat,
+                         (int)length, k_eff, (int)shear, p, u_dev, h->st_red.p, h->st_G.p, dr ? h->st_dr.p : (double *)nullptr,
+                         delta);
+    });
   });
+}
+
+// ---- thermal loads (pl_thermal.h) ----------------------------------------------------------------------------------------
+int pl_set_thermal(pl_handle h, double alpha, const double *beam_alpha, const double *node_dT) {
+  if (!valid(h)) return fail(PL_ERR_ARG, "pl_set_thermal: null handle");
+  if (h->opkind != 0) return fail(PL_ERR_STATE, "pl_set_thermal: not available on a DDM handle");
+  if (h->dist.active || h->opt.grid_nodes > 0)
+    return fail(PL_ERR_STATE, "pl_set_thermal: single-GPU handles only (this one belongs to a multi-rank run)");
+  if (!node_dT) {
+    h->thermal_ws.reset();
+    return PL_OK;
+  }
+  if (!beam_alpha && !std::isfinite(alpha)) return fail(PL_ERR_ARG, "pl_set_thermal: alpha must be finite");
+  if (beam_alpha)
+    for (int64_t b = 0; b < h->B; ++b)
+      if (!std::isfinite(beam_alpha[b])) return fail(PL_ERR_ARG, "pl_set_thermal: beam_alpha must be finite");
+  for (int64_t i = 0; i < h->N; ++i)
+    if (!std::isfinite(node_dT[i])) return fail(PL_ERR_ARG, "pl_set_thermal: node_dT must be finite");
+  PL_HIP(hipSetDevice(h->opt.device));
+  const size_t B = (size_t)h->B, N = (size_t)h->N;
+  auto t = std::make_shared<ThermalWs>();
+  PL_HIP(t->alpha.alloc(B));
+  PL_HIP(t->dT.alloc(N));
+  PL_HIP(t->delta.alloc(B));
+  PL_HIP(t->n_free.alloc(B));
+  PL_HIP(t->out.alloc(B));
+  std::vector<double> al(B), dt(N);
+  for (size_t b = 0; b < B; ++b) al[b] = beam_alpha ? beam_alpha[h->bperm[b]] : alpha;
+  for (size_t i = 0; i < N; ++i) dt[i] = node_dT[h->perm[i]];
+  PL_HIP(hipMemcpy(t->alpha.p, al.data(), B * sizeof(double), hipMemcpyHostToDevice));
+  PL_HIP(hipMemcpy(t->dT.p, dt.data(), N * sizeof(double), hipMemcpyHostToDevice));
+  h->thermal_ws = t;
+  return PL_OK;
+}
+
+namespace {
+// what pl_thermal_load and pl_thermal_sens share: the handle checks and the refreshed elongations
+int thermal_begin(pl_handle h, const char *who, bool want_n_free, ThermalWs **t) {
+  if (!valid(h)) return fail(PL_ERR_ARG, std::string(who) + ": null handle");
+  if (h->opkind != 0) return fail(PL_ERR_STATE, std::string(who) + ": not available on a DDM handle");
+  if (h->dist.active) return fail(PL_ERR_STATE, std::string(who) + ": not available on a multi-GPU handle");
+  if (!h->thermal_ws) return fail(PL_ERR_STATE, std::string(who) + ": call pl_set_thermal first");
+  if (!h->assembled) return fail(PL_ERR_STATE, std::string(who) + ": call pl_assemble first");
+  PL_HIP(hipSetDevice(h->opt.device));
+  return thermal_refresh(h, who, want_n_free, t);
+}
+}  // namespace
+
+int pl_thermal_load(pl_handle h, double *f, double *n_free) {
+  if (valid(h) && !f && !n_free) return fail(PL_ERR_ARG, "pl_thermal_load: every output pointer is NULL");
+  ThermalWs *t = nullptr;
+  if (int rc = thermal_begin(h, "pl_thermal_load", n_free != nullptr, &t)) return rc;
+  if (f) {   // (tmp2 is a work vector of the derived-quantity calls: pnorm_call gathers into it too)
+    EventTimer timer("pl_thermal_load", h->stream, "kernel_hip_event");
+    hipLaunchKernelGGL(pl::k_thermal_load, dim3(grid_for(h->N)), dim3(pl::kBlock), 0, h->stream, h->N, pl::kWave / h->lpn,
+                       h->slice_ptr.p, h->ent.p, h->rec.p, t->delta.p, h->tmp2.p);
+    PL_HIP(hipGetLastError());
+    timer.stop();
+    if (int rc = download6(h, h->tmp2.p, f)) return rc;
+  }
+  if (n_free)
+    if (int rc = download_struts(h, t->n_free.p, n_free)) return rc;
+  return PL_OK;
+}
+
+int pl_thermal_sens(pl_handle h, const double *lam, double *out) {
+  if (valid(h) && !out) return fail(PL_ERR_ARG, "pl_thermal_sens: null argument");
+  ThermalWs *t = nullptr;
+  if (int rc = thermal_begin(h, "pl_thermal_sens", false, &t)) return rc;
+  const double *lam_dev = nullptr;
+  if (int rc = state_on_device(h, "pl_thermal_sens", lam, &lam_dev)) return rc;
+  EventTimer timer("pl_thermal_sens", h->stream, "kernel_hip_event");
+  hipLaunchKernelGGL(pl::k_thermal_sens, dim3(grid_for(h->B)), dim3(pl::kBlock), 0, h->stream, h->B, h->conn.p, h->rec.p,
+                     h->radius.p, t->delta.p, lam_dev, t->out.p);
+  PL_HIP(hipGetLastError());
+  timer.stop();
+  return download_struts(h, t->out.p, out);
 }
 
 int pl_energy(pl_handle h, const double *u, double *energy) {
@@ -2113,6 +2240,9 @@ namespace {
 // what the two geometric calls share after their argument checks: the handle checks and the geometric records of u
 int geom_begin(pl_handle h, const char *who, const double *u, bool need_bc, GeomWs **g) {
   if (int rc = multi_check_handle(h, who, need_bc)) return rc;
+  if (h->thermal_ws)
+    return fail(PL_ERR_STATE, std::string(who) + ": K_g is built from K_e u_e and would ignore the thermal prestress of "
+                                                 "pl_set_thermal; clear the thermal state first");
   const double *u_dev = nullptr;
   if (int rc = state_on_device(h, who, u, &u_dev)) return rc;
   if (int rc = geom_ws(h, g)) return rc;

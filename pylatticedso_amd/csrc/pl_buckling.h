@@ -1,7 +1,8 @@
 // Euler buckling utilisation of every strut and its p-norm aggregate with derivatives (pl_buckling / pl_buckling_pnorm;
 // DESIGN.md section 10c).  gfx950 only.  The sibling of the stress pass (pl_stress.h), whose axial force it reads.
 //
-// Per strut b, with (F, M_B) = tip_force(record, u) and the multiplicity k of pl_set_multiplicity:
+// Per strut b, with (F, M_B) = tip_force(record, u) - under a thermal state of the handle (pl_set_thermal) the mechanical
+// force F - ka delta t of load_strut<true>, the TH instantiation of both kernels - and the multiplicity k of pl_set_multiplicity:
 //     N = F.t / k          signed axial force of ONE copy (tension > 0) - exactly the N of pl_stress (stress_strut)
 //     P = max(0, -N)       compressive force
 // Buckling length l:   length = 0: the node-to-node length |d|;
@@ -42,6 +43,7 @@ __device__ __forceinline__ double buckling_ncr(double r, double l, double k_eff,
 // Utilisation pass: one thread per strut, no scatter.  util[b] = beta, n_axial[b] = N of one copy (signed), n_crit[b] =
 // N_cr (all three NaN on an absent strut), part_max[block] = block maximum of beta.  Any output may be null.
 // ---------------------------------------------------------------------------------------------------------
+template <bool TH>
 __global__ __launch_bounds__(kBlock) void k_buckling_util(int64_t B, const int32_t *__restrict__ conn,
                                                           const Record *__restrict__ rec,
                                                           const double *__restrict__ radius,
@@ -49,12 +51,13 @@ __global__ __launch_bounds__(kBlock) void k_buckling_util(int64_t B, const int32
                                                           const double *__restrict__ mult, Material mat, int length,
                                                           double k_eff, int shear, const double *__restrict__ u,
                                                           double *__restrict__ util, double *__restrict__ n_axial,
-                                                          double *__restrict__ n_crit, double *__restrict__ part_max) {
+                                                          double *__restrict__ n_crit, double *__restrict__ part_max,
+                                                          const double *__restrict__ delta) {
   __shared__ double smem[kBlock];
   const int64_t b = (int64_t)blockIdx.x * kBlock + threadIdx.x;
   double pk = 0.0;
   if (b < B) {
-    const StressStrut s = load_strut(b, conn, rec, mult, u).q;
+    const StressStrut s = load_strut<TH>(b, conn, rec, mult, u, delta).q;
     const double l2 = seg_len[3 * b + 1];
     const bool on = length == 0 || l2 > 0.0;
     const double nan = __longlong_as_double(0x7ff8000000000000ll);
@@ -76,7 +79,7 @@ __global__ __launch_bounds__(kBlock) void k_buckling_util(int64_t B, const int32
 // Derivatives of B_p, one thread per strut, no scatter (header comment): G[b][6] and, with DR, dbp_dr[b].
 // red = (beta_max, sum (beta / beta_max)^p, B_p) of k_stress_fold.
 // ---------------------------------------------------------------------------------------------------------
-template <bool DR>
+template <bool DR, bool TH>
 __global__ __launch_bounds__(kBlock) void k_buckling_grad(int64_t B, const int32_t *__restrict__ conn,
                                                           const Record *__restrict__ rec,
                                                           const double *__restrict__ radius,
@@ -85,11 +88,12 @@ __global__ __launch_bounds__(kBlock) void k_buckling_grad(int64_t B, const int32
                                                           const double *__restrict__ mult, Material mat, int length,
                                                           double k_eff, int shear, double p,
                                                           const double *__restrict__ u, const double *__restrict__ red,
-                                                          double *__restrict__ G, double *__restrict__ dbp_dr) {
+                                                          double *__restrict__ G, double *__restrict__ dbp_dr,
+                                                          const double *__restrict__ delta) {
   const int64_t b = (int64_t)blockIdx.x * kBlock + threadIdx.x;
   if (b >= B) return;
   const double bmax = red[0], bsum = red[1];
-  const StrutState st = load_strut(b, conn, rec, mult, u);
+  const StrutState st = load_strut<TH>(b, conn, rec, mult, u, delta);
   const StressStrut &s = st.q;
   const double len[3] = {seg_len[3 * b], seg_len[3 * b + 1], seg_len[3 * b + 2]};
   const bool on = length == 0 || len[1] > 0.0;
@@ -101,7 +105,7 @@ __global__ __launch_bounds__(kBlock) void k_buckling_grad(int64_t B, const int32
   const double w = live ? pow(beta / bmax, p - 1.0) * pow(bsum, 1.0 / p - 1.0) : 0.0;
   const V3 gF = (live ? -w * s.invk / ncr : 0.0) * s.t;
   V3 dF, dM;
-  grad_epilogue<DR>(st, b, rr, len, seg_nsub, mat, gF, V3{0, 0, 0}, G, dF, dM);
+  grad_epilogue<DR, TH>(st, b, rr, len, seg_nsub, mat, gF, V3{0, 0, 0}, G, dF, dM);
   if (DR) dbp_dr[b] = live ? dot(gF, dF) - w * beta * (4.0 - 2.0 * q / (1.0 + q)) / rr : 0.0;
 }
 

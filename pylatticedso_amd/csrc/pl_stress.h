@@ -99,17 +99,28 @@ struct StrutState {
   Record r;
   V3 uA, tA, uB, tB, F, M;
   double k;
+  double fth;          // TH only: restrained thermal force ka delta of the record (pl_thermal.h)
   StressStrut q;
 };
 
+// TH: the handle has a thermal state (pl_set_thermal) and delta[b] is the strut's free elongation; F becomes the MECHANICAL
+// section force K_tip (du, dth) - ka delta t.  Without TH delta is not read and the arithmetic is that of the plain pass.
+template <bool TH>
 __device__ __forceinline__ StrutState load_strut(int64_t b, const int32_t *__restrict__ conn, const Record *__restrict__ rec,
-                                                 const double *__restrict__ mult, const double *__restrict__ u) {
+                                                 const double *__restrict__ mult, const double *__restrict__ u,
+                                                 const double *__restrict__ delta) {
   StrutState s;
   const int64_t ia = conn[2 * b], ib = conn[2 * b + 1];
   s.r = load_record(rec, b);
   load6(u + 6 * ia, s.uA, s.tA);
   load6(u + 6 * ib, s.uB, s.tB);
   tip_force(s.r, s.uA, s.tA, s.uB, s.tB, s.F, s.M);
+  if (TH) {
+    const V3 d = {s.r.dx, s.r.dy, s.r.dz};
+    const double L2 = dot(d, d);
+    s.fth = (s.r.a + s.r.e1 * L2) * delta[b];
+    s.F = s.F - (s.fth / sqrt(L2)) * d;
+  }
   s.k = mult ? mult[b] : 1.0;
   s.q = stress_strut(s.r, s.k, s.F, s.M);
   return s;
@@ -117,8 +128,8 @@ __device__ __forceinline__ StrutState load_strut(int64_t b, const int32_t *__res
 
 // Close of a p-norm grad kernel (k_stress_grad, k_buckling_grad): G[b][6] = K_tip (g_F, g_M), the tip block applied to the
 // aggregate's derivative with respect to (F, M_B).  With DR also (dF, dM) = d(F, M_B)/dr at fixed u and segment geometry, so
-// that the caller's d/dr = g_F.dF + g_M.dM + its own section term.
-template <bool DR>
+// that the caller's d/dr = g_F.dF + g_M.dM + its own section term; with TH the thermal shift of F is part of dF.
+template <bool DR, bool TH>
 __device__ __forceinline__ void grad_epilogue(const StrutState &s, int64_t b, double rr, const double *len,
                                               const int32_t *__restrict__ seg_nsub, const Material &mat, V3 gF, V3 gM,
                                               double *__restrict__ G, V3 &dF, V3 &dM) {
@@ -131,6 +142,7 @@ __device__ __forceinline__ void grad_epilogue(const StrutState &s, int64_t b, do
     const V3 d = {s.r.dx, s.r.dy, s.r.dz};
     const Record dr = strut_drecord(rr, len, ns, scaled(mat, s.k), d);
     tip_force(dr, s.uA, s.tA, s.uB, s.tB, dF, dM);
+    if (TH) dF = dF - (2.0 * s.fth / rr / sqrt(dot(d, d))) * d;   // d(ka delta t)/dr = (2 ka / r) delta t
   }
 }
 
@@ -146,8 +158,9 @@ __device__ __forceinline__ void stress_section(double R, double &iS, double &RI,
 // ---------------------------------------------------------------------------------------------------------
 // Station pass: one thread per strut, no scatter.  station[b][4][5] = N, V, T, Mb, sigma_vm (NaN where absent), peak[b] =
 // max sigma_vm (0 without a station), vm4[b][4] = sigma_vm per station (NaN where absent), part_max[block] = block maximum.
-// Any output may be null.
+// Any output may be null.  TH: the mechanical force under the handle's thermal state (load_strut).
 // ---------------------------------------------------------------------------------------------------------
+template <bool TH>
 __global__ __launch_bounds__(kBlock) void k_stress_stations(int64_t B, const int32_t *__restrict__ conn,
                                                             const Record *__restrict__ rec,
                                                             const double *__restrict__ radius,
@@ -155,12 +168,13 @@ __global__ __launch_bounds__(kBlock) void k_stress_stations(int64_t B, const int
                                                             const double *__restrict__ mult, double pen, int where,
                                                             const double *__restrict__ u, double *__restrict__ station,
                                                             double *__restrict__ peak, double *__restrict__ vm4,
-                                                            double *__restrict__ part_max) {
+                                                            double *__restrict__ part_max,
+                                                            const double *__restrict__ delta) {
   __shared__ double smem[kBlock];
   const int64_t b = (int64_t)blockIdx.x * kBlock + threadIdx.x;
   double pk = 0.0;
   if (b < B) {
-    const StressStrut q = load_strut(b, conn, rec, mult, u).q;
+    const StressStrut q = load_strut<TH>(b, conn, rec, mult, u, delta).q;
     const StressStations s = stress_stations(seg_len[3 * b], seg_len[3 * b + 1], seg_len[3 * b + 2], q.L, pen, where);
     const double rr = radius[b];
     const double nan = __longlong_as_double(0x7ff8000000000000ll);
@@ -252,7 +266,7 @@ __global__ __launch_bounds__(kBlock) void k_pnorm_psum(int64_t B, const double *
 // section constants' own dependence on R = fac r:  d sigma/dr = -(2 |N|/S + 3 Mb R/I) / r,  d tau/dr = -3 tau / r.
 // Derivatives of |N|, |T|, Mb at exactly zero are taken as zero.
 // ---------------------------------------------------------------------------------------------------------
-template <bool DR>
+template <bool DR, bool TH>
 __global__ __launch_bounds__(kBlock) void k_stress_grad(int64_t B, const int32_t *__restrict__ conn,
                                                         const Record *__restrict__ rec,
                                                         const double *__restrict__ radius,
@@ -260,11 +274,12 @@ __global__ __launch_bounds__(kBlock) void k_stress_grad(int64_t B, const int32_t
                                                         const int32_t *__restrict__ seg_nsub,
                                                         const double *__restrict__ mult, Material mat, int where, double p,
                                                         const double *__restrict__ u, const double *__restrict__ red,
-                                                        double *__restrict__ G, double *__restrict__ dphi_dr) {
+                                                        double *__restrict__ G, double *__restrict__ dphi_dr,
+                                                        const double *__restrict__ delta) {
   const int64_t b = (int64_t)blockIdx.x * kBlock + threadIdx.x;
   if (b >= B) return;
   const double smax = red[0], ssum = red[1];
-  const StrutState st = load_strut(b, conn, rec, mult, u);
+  const StrutState st = load_strut<TH>(b, conn, rec, mult, u, delta);
   const StressStrut &q = st.q;
   const double len[3] = {seg_len[3 * b], seg_len[3 * b + 1], seg_len[3 * b + 2]};
   const StressStations s = stress_stations(len[0], len[1], len[2], q.L, mat.pen, where);
@@ -292,7 +307,7 @@ __global__ __launch_bounds__(kBlock) void k_stress_grad(int64_t B, const int32_t
     }
   }
   V3 dF, dM;
-  grad_epilogue<DR>(st, b, rr, len, seg_nsub, mat, gF, gM, G, dF, dM);
+  grad_epilogue<DR, TH>(st, b, rr, len, seg_nsub, mat, gF, gM, G, dF, dM);
   if (DR) dphi_dr[b] = dot(gF, dF) + dot(gM, dM) + dsec;
 }
 

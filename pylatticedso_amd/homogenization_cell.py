@@ -305,6 +305,27 @@ class HomogenizedCell:
         d = HH.engineering_constants_sensitivity(self.homogenizeMatrix_raw, raw)
         return dict(zip(HH.CONSTANTS, self._per(d, per)))
 
+    # ---- homogenised thermal expansion (no counterpart in the reference) ------------------
+    def thermal_expansion(self, alpha, beam_alpha=None):
+        """alpha_hom (6,): the strain of the stress-free periodic cell per unit temperature, components in the order of the six
+        macro strains (xx, yy, zz, xy, xz, yz; shear as tensorial strain, like the macro strains themselves).  alpha: the
+        expansion coefficient of every strut, or beam_alpha (B,) per strut (a bi-material cell).  After
+        ``solve_full_homogenization`` (RuntimeError before it): with the six total fields u_k it kept, H_kl = u_k^T K u_l and
+        tau_k = u_k^T f_th at dT = 1, alpha_hom = H^-1 tau - the total fields are in equilibrium against every periodic
+        variation, so no further solve is needed: one thermal_load and the six products K u_k on the device.  The handle's thermal
+        state is left as it was found (cleared)."""
+        if self.saveDataToExport is None:
+            raise RuntimeError("thermal_expansion: call solve_full_homogenization first")
+        from . import thermal_host as TH
+        dev = self.device
+        U = np.stack(self.saveDataToExport)
+        dev.set_thermal(alpha, np.ones(dev.n_nodes), beam_alpha)
+        try:
+            f_th, _ = dev.thermal_load()
+        finally:
+            dev.clear_thermal()
+        return TH.expansion_from_fields(U, np.stack([dev.spmv(u) for u in U]), f_th)
+
     # ---- post-processing (:444-541) --------------------------------------------------------------------------
     def _engineering_constants(self):
         Hinv = np.linalg.inv(self.homogenizeMatrix)

@@ -59,6 +59,13 @@ def _times_circular_squared(q, limit):
     return (2.0 * np.pi * limit) ** 2 * q
 
 
+def _equilibrium_load(model):
+    """The load of the model's equilibrium problem: its external forces plus, under a temperature, the thermal loads
+    solve_problem composed (K u = f_ext + f_th)."""
+    f_th = getattr(model, "_f_th", None)
+    return model._f if f_th is None else model._f + f_th
+
+
 _INTERIORS = "the recovered interiors of DDM cells"
 # in the order they are handed to SLSQP
 _RESPONSE_CONSTRAINTS = (
@@ -118,6 +125,9 @@ class LatticeOpti(LatticeSim):
         if ddm_gradient == "analytic" and comp.get("type", None) != "exact":
             raise ValueError('ddm_gradient="analytic" needs exact Schur complements '
                              '(schur_complement_computation.type = "exact"): a surrogate has no strut model to differentiate')
+        if self._ddm_mode and (params.get("simulation_parameters", {}).get("thermal") is not None):
+            raise ValueError('the "thermal" block needs simulation_type "FEM": the cell matrices of DDM mode carry no strut '
+                             "temperatures")
         super().__init__(params, mesh_trimmer, verbose, self._ddm_mode, data_roots=data_roots,
                          reference_compat=reference_compat, ddm_gradient=ddm_gradient)
         self.paired_adjoint = bool(paired_adjoint)
@@ -426,7 +436,7 @@ class LatticeOpti(LatticeSim):
         fixed = self._model._fixed
         dev.set_bc(fixed, None, np.where(fixed, 0.0, q))
         lam, _ = dev.solve(rtol=1e-10, max_iter=200000)
-        dev.set_bc(fixed, self._model._ubar, self._model._f)     # restore the equilibrium problem
+        dev.set_bc(fixed, self._model._ubar, _equilibrium_load(self._model))     # restore the equilibrium problem
         return lam
 
     def _paired_state_adjoints(self, qs):
@@ -437,7 +447,7 @@ class LatticeOpti(LatticeSim):
         fixed = np.asarray(self._model._fixed, dtype=bool).reshape(-1, 6)
         ubar = np.zeros((1 + len(qs),) + fixed.shape)
         ubar[0] = np.asarray(self._model._ubar).reshape(fixed.shape)
-        f = np.stack([np.asarray(self._model._f, dtype=float).reshape(fixed.shape)] +
+        f = np.stack([np.asarray(_equilibrium_load(self._model), dtype=float).reshape(fixed.shape)] +
                      [np.where(fixed, 0.0, np.asarray(q).reshape(fixed.shape)) for q in qs])
         U, _ = dev.solve_multi(ubar, f, rtol=1e-10, max_iter=200000)
         return U[0], list(U[1:])
@@ -449,6 +459,15 @@ class LatticeOpti(LatticeSim):
             np.add.at(q, (np.asarray(nodes, dtype=np.int64), k), 1.0 / (len(nodes) * len(dofs)))
         return q
 
+    def _sens(self, u, lam):
+        """lam^T (dK/dr_b) u minus, under a temperature, lam^T d f_th / d r_b (pl_sens, pl_thermal_sens): the per-strut term
+        every adjoint gradient subtracts, since K du/dr = -dK/dr u + d f_th / dr."""
+        dev = self.device_model()
+        s = dev.sens(u, lam)
+        if self.thermal is not None:
+            s = s - dev.thermal_sens(u if lam is None else lam)
+        return s
+
     def strut_sensitivities(self):
         """s_b such that d(objective)/d r_b = −s_b at fixed segment geometry (compliance: s_b = u_eᵀ ∂K_e/∂r u_e)."""
         dev = self.device_model()
@@ -458,7 +477,7 @@ class LatticeOpti(LatticeSim):
             sign = -1.0 if self.objective_function == "max" else 1.0
             q = sign * self._unit_mean_load(nodes, [_DOF[d] for d in self.objectif_data["DOF"]])
             u2, (lam,) = self._paired_state_adjoints([q])
-            return dev.sens(u2, lam)
+            return self._sens(u2, lam)
         if self.paired_adjoint and self.objective_type == "displacement_ratio":
             # q = -u_in e_out - u_out e_in is linear in two loads that do not depend on the state: three columns
             bd = self.boundary_conditions
@@ -468,12 +487,14 @@ class LatticeOpti(LatticeSim):
                                          [_DOF[d] for d in self.objectif_data["DOF"]])
             e_in = self._unit_mean_load(self._objective_nodes(bd["Load"]["Surface"]), [_DOF[d] for d in bd["Load"]["DOF"]])
             u2, (l_out, l_in) = self._paired_state_adjoints([e_out, e_in])
-            return dev.sens(u2, -u_in * l_out - u_out * l_in)
+            return self._sens(u2, -u_in * l_out - u_out * l_in)
         if self.objective_type == "compliance":
             lam = u
-            if np.any(self._model._ubar != 0.0):      # prescribed displacements: the adjoint is not u itself
+            # prescribed displacements or a thermal load: the adjoint of J = f_ext . u solves K lam = f_ext, the mechanical
+            # loads only, and is not u itself
+            if np.any(self._model._ubar != 0.0) or self.thermal is not None:
                 lam = self._adjoint(self._model._f)
-            return dev.sens(u, None if lam is u else lam)
+            return self._sens(u, None if lam is u else lam)
         if self.objective_type == "displacement":
             nodes = self._objective_nodes(self.objectif_data["Surface"])
             q = np.zeros_like(u)
@@ -481,9 +502,9 @@ class LatticeOpti(LatticeSim):
             sign = -1.0 if self.objective_function == "max" else 1.0
             for d in self.objectif_data["DOF"]:
                 q[nodes, _DOF[d]] += sign / cnt
-            return dev.sens(u, self._adjoint(q))
+            return self._sens(u, self._adjoint(q))
         if self.objective_type == "displacement_ratio":
-            return dev.sens(u, self._adjoint(self._ratio_terms()[2]))
+            return self._sens(u, self._adjoint(self._ratio_terms()[2]))
         raise NotImplementedError(f"Gradient for objective '{self.objective_type}' not implemented yet.")
 
     def _ddm_adjoint(self, q_nodes):
@@ -699,10 +720,10 @@ class LatticeOpti(LatticeSim):
 
     def _aggregate_gradient(self, dq_du, dq_dr):
         """dq/d(theta) of a scalar q(u(r), r) of the equilibrium from its partial derivatives: dq/dr_b = dq/dr_b at fixed u -
-        lam^T (dK/dr_b) u with K lam = dq/du on the free dofs, through _strut_to_cell, the parameterisation's chain and the
-        normalisation of the variables."""
+        lam^T (dK/dr_b) u (+ lam^T d f_th / dr_b under a temperature, _sens) with K lam = dq/du on the free dofs, through
+        _strut_to_cell, the parameterisation's chain and the normalisation of the variables."""
         lam = self._adjoint(dq_du)
-        return self._strut_gradient_to_parameters(dq_dr - self.device_model().sens(self._model.u, lam))
+        return self._strut_gradient_to_parameters(dq_dr - self._sens(self._model.u, lam))
 
     def _strut_gradient_to_parameters(self, s):
         """dq/d(theta) from the total per-strut derivatives dq/dr_b: _strut_to_cell, the parameterisation's chain and the

@@ -114,7 +114,10 @@ class LatticeSim(LatticeViews):
         self._base_radii = [float(r) for r in self.radii]
         self._cell_radii_override = None
         self._device = self._ddm_device = None
+        self.thermal = None                        # (alpha, delta_T, beam_alpha) of set_temperature, None without one
         self._generate_and_prepare()
+        if self._thermal_preset is not None:       # simulation_parameters["thermal"]
+            self.set_temperature(*self._thermal_preset)
         self.cell_schur_index = None       # (C,) index into self.schur_complements
         self.schur_complements = None      # (n_S, 6 n_b, 6 n_b)
         self.iteration = 0
@@ -212,6 +215,8 @@ class LatticeSim(LatticeViews):
         elif self.domain_decomposition_solver:
             raise ValueError("Schur complement computation method must be defined in the input file.")
         self.boundary_conditions = p.get("boundary_conditions", {})
+        th = sim.get("thermal", None)              # {"alpha": a, "delta_T": scalar}: a uniform temperature rise
+        self._thermal_preset = None if th is None else (float(th["delta_T"]), float(th["alpha"]))
         self.young_modulus, self.poisson_ratio = material_properties(self.material_name)
 
     # ------------------------------------------------------------------------------------------------
@@ -619,6 +624,50 @@ class LatticeSim(LatticeViews):
                                       pen_coef=self.penalization_coefficient, **kw)
         return self._device
 
+    # -- temperature (FEM mode; pl_set_thermal) ------------------------------------------------
+    def set_temperature(self, delta_T, alpha, beam_alpha=None):
+        """Temperature rise of the nodes for the solves that follow: delta_T a scalar, an (n_nodes,) array, or a callable of the
+        node coordinates (n_nodes, 3); alpha the expansion coefficient of every strut, or beam_alpha (n_beams,) per strut.  The
+        temperature is linear along a strut and uniform over its section.  solve_FEM_FenicsX then solves K u = f_ext + f_th,
+        the reactions are K u - f_th, and strut_stress / strut_buckling report the mechanical force; global_buckling and
+        solve_DDM refuse while a temperature is set."""
+        n = self.lattice.n_nodes
+        dT = delta_T(np.asarray(self.lattice.node_xyz, dtype=float)) if callable(delta_T) else delta_T
+        dT = np.array(np.broadcast_to(np.asarray(dT, dtype=float), (n,)))
+        ba = None if beam_alpha is None else np.array(np.broadcast_to(np.asarray(beam_alpha, dtype=float),
+                                                                      (self.lattice.n_beams,)))
+        if not (np.isfinite(dT).all() and np.isfinite(alpha) and (ba is None or np.isfinite(ba).all())):
+            raise ValueError("set_temperature: delta_T, alpha and beam_alpha must be finite")
+        self.thermal = (float(alpha), dT, ba)
+        if self._device is not None and not getattr(self, "_compat_rows", False):
+            self._apply_temperature(self._device)
+
+    def clear_temperature(self):
+        """Removes the temperature of set_temperature (and of the preset's "thermal" block)."""
+        self.thermal = None
+        if self._device is not None and not getattr(self, "_compat_rows", False):
+            self._device.clear_thermal()
+
+    def _apply_temperature(self, dev):
+        if getattr(self, "_compat_rows", False):
+            raise NotImplementedError("thermal loads are not available in the reference_compat strut model")
+        alpha, dT, ba = self.thermal
+        dev.set_thermal(alpha, dT, ba)
+
+    def thermal_strut_forces(self):
+        """(n_beams,) restrained thermal force n_free of one copy of every strut (pl_thermal_load): what a strut heated and
+        held at both ends pushes with, ka alpha L mean(dT) / k."""
+        if self.thermal is None:
+            raise RuntimeError("thermal_strut_forces: no temperature is set (set_temperature)")
+        if self._device is None:
+            raise RuntimeError("thermal_strut_forces needs a solve_FEM_FenicsX on this lattice first")
+        return self._device.thermal_load()[1]
+
+    def _no_temperature(self, who):
+        if self.thermal is not None:
+            raise RuntimeError(f"{who}: K_g is built from K_e u_e and would ignore the thermal prestress; "
+                               "clear_temperature() first")
+
     def strut_stress(self, where=0):
         """Section forces and von Mises stress of every strut for the displacements of the last solve_FEM_FenicsX, on the
         device (pl_stress; the reference: generalized_stress / calculate_forces / calculate_moments,
@@ -665,6 +714,7 @@ class LatticeSim(LatticeViews):
         if self._device is None or getattr(self, "_compat_rows", False):
             raise RuntimeError("global_buckling needs a solve_FEM_FenicsX on this lattice first (default strut model; the "
                                "reference_compat model has no device buckling pass)")
+        self._no_temperature("global_buckling")
         model = getattr(self, "_model", None)       # (as strut_stress: LatticeOpti's equilibrium field is passed explicitly)
         out = self._device.buckling_modes(n_modes, None if model is None else model._u_solver, **kw)
         self.buckling_load_factors = out["load_factor"]
@@ -682,6 +732,7 @@ class LatticeSim(LatticeViews):
         if self._device is None or getattr(self, "_compat_rows", False):
             raise RuntimeError("global_buckling needs a solve_FEM_FenicsX on this lattice first (default strut model; the "
                                "reference_compat model has no device buckling pass)")
+        self._no_temperature("global_buckling_sensitivity")
         if getattr(self, "buckling_load_factors", None) is None:
             raise RuntimeError("global_buckling_sensitivity needs a global_buckling on this lattice first")
         from .geometric_host import load_factor_aggregate
@@ -1373,6 +1424,9 @@ class LatticeSim(LatticeViews):
         results, the VTU export - works on the result."""
         if not self.domain_decomposition_solver:
             raise ValueError("LatticeSim was not created with enable_domain_decomposition_solver=True")
+        if self.thermal is not None:
+            raise ValueError("solve_DDM: thermal loads need the FEM strut model (the cell matrices carry no strut "
+                             "temperatures); clear_temperature() first")
         dev = self.ddm_model()
         if self._ddm_precond in (1, 3, 4) and not getattr(self, "_precond_note_done", False):
             print(f"solve_DDM: {6 * (self.max_index_boundary + 1)} boundary dofs exceed the {DDM_DENSE_MAX} the device "

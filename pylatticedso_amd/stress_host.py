@@ -120,7 +120,7 @@ def stations(seg_len, L, pen_coef=1.5, where=0):
     return c, fac, np.stack([~no, h1 & (h2 | h3), h2 & h3, ~no], axis=1)
 
 
-def _evaluate(rec, conn, radius, seg_len, u, pen_coef, mult, where):
+def _evaluate(rec, conn, radius, seg_len, u, pen_coef, mult, where, f_th=None):
     conn = np.asarray(conn).reshape(-1, 2)
     rec = np.asarray(rec, dtype=float).reshape(-1, 8)
     r = np.asarray(radius, dtype=float)
@@ -129,6 +129,8 @@ def _evaluate(rec, conn, radius, seg_len, u, pen_coef, mult, where):
     d = rec[:, 5:8]
     L = np.sqrt(_dot(d, d))
     t = d / L[:, None]
+    if f_th is not None:                                           # mechanical force under a thermal state: F - F_th t
+        F = F - np.asarray(f_th, dtype=float)[:, None] * t
     Ft, Mt = _dot(F, t), _dot(M, t)
     Fp, Mp, tF = F - Ft[:, None] * t, M - Mt[:, None] * t, np.cross(t, F)
     c, fac, on = stations(seg_len, L, pen_coef, where)
@@ -145,9 +147,11 @@ def _evaluate(rec, conn, radius, seg_len, u, pen_coef, mult, where):
     return ev
 
 
-def strut_stress(rec, beam_conn, radius, seg_len, u, pen_coef=1.5, mult=None, where=0):
-    """dict N, V, T, Mb, sigma_vm (B, 4) (NaN at absent stations) and peak (B,) - the outputs of pl_stress."""
-    ev = _evaluate(rec, beam_conn, radius, seg_len, u, pen_coef, mult, where)
+def strut_stress(rec, beam_conn, radius, seg_len, u, pen_coef=1.5, mult=None, where=0, f_th=None):
+    """dict N, V, T, Mb, sigma_vm (B, 4) (NaN at absent stations) and peak (B,) - the outputs of pl_stress.  f_th (B,): the
+    restrained thermal force ka delta of every record (thermal_host.restrained_force), subtracted along t as the device does
+    under pl_set_thermal; None: no thermal state."""
+    ev = _evaluate(rec, beam_conn, radius, seg_len, u, pen_coef, mult, where, f_th)
     on = ev["on"]
     out = {n: np.where(on, np.broadcast_to(ev[n][:, None], on.shape), np.nan) for n in ("N", "V", "T")}
     out["Mb"] = np.where(on, ev["Mb"], np.nan)
@@ -182,11 +186,12 @@ def scatter_tip_gradient(rec, conn, node_count, gF, gM):
 
 
 def stress_pnorm(rec, node_count, beam_conn, radius, seg_len, seg_nsub, u, p, young, poisson, kappa=0.9, pen_coef=1.5,
-                 mult=None, where=0, want_grad=True):
+                 mult=None, where=0, want_grad=True, f_th=None):
     """(phi, sigma_max, dphi_du (N, 6), dphi_dr (B,)) - the outputs of pl_stress_pnorm with the formulas of its kernels;
-    dphi_dr at fixed u and segment geometry, through the record (dscalars_dr) and the section constants."""
+    dphi_dr at fixed u and segment geometry, through the record (dscalars_dr) and the section constants.  f_th: as in
+    ``strut_stress``; its radius derivative (2 / r) f_th t enters dphi_dr."""
     conn = np.asarray(beam_conn).reshape(-1, 2)
-    ev = _evaluate(rec, conn, radius, seg_len, u, pen_coef, mult, where)
+    ev = _evaluate(rec, conn, radius, seg_len, u, pen_coef, mult, where, f_th)
     on, vm = ev["on"], ev["vm"]
     phi, smax = pnorm(np.where(on, vm, np.nan), p)
     if not want_grad:
@@ -213,4 +218,6 @@ def stress_pnorm(rec, node_count, beam_conn, radius, seg_len, seg_nsub, u, p, yo
     f = flexibility(radius, seg_len, seg_nsub, young, poisson, kappa, pen_coef, mult)
     drec = _record(_dscalars_dr(f, ev["r"]), d)
     dF, dM = tip_force(drec, conn, u)
+    if f_th is not None:
+        dF = dF - (2.0 * np.asarray(f_th, dtype=float) / ev["r"])[:, None] * t
     return phi, smax, du, _dot(gF, dF) + _dot(gM, dM) + dsec

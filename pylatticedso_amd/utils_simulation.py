@@ -43,6 +43,13 @@ class FullScaleLatticeSimulation:
         dev = self.device
         dev.set_bc(self._fixed, self._ubar, self._f)
         dev.assemble()
+        self._f_th = None
+        if getattr(self.lattice, "thermal", None) is not None:
+            # K u = f_ext + f_th: the thermal load needs the assembled records, so it is composed on the host here and
+            # handed over under the same mask
+            self.lattice._apply_temperature(dev)
+            self._f_th = dev.thermal_load()[0]
+            dev.set_bc(self._fixed, self._ubar, self._f + self._f_th)
         u, self.stats = dev.solve(rtol=rtol, max_iter=max_iter)
         # dolfinx adds point loads to the RHS AFTER set_bc, so a load on a constrained dof shows up in that dof's
         # value (identity row): u_c = ubar_c + f_c (simulation_base.py:494-498).  Kept for parity.
@@ -84,6 +91,8 @@ class FullScaleLatticeSimulation:
     def set_reaction_force_on_lattice_with_FEM_results(self):
         """full_scale_lattice_simulation.py:111-120: R_i = v_i^T K u for the 6 dofs of every constrained node."""
         R = self.device.reactions(self.u) + self._loaded_constraint_correction()
+        if getattr(self, "_f_th", None) is not None:
+            R = R - self._f_th                       # the supports answer K u - f_th
         nodes = self._fixed.any(axis=1)
         # the reference loops ``for cell: for node in cell.points_cell`` and Point.set_reaction_force ACCUMULATES
         # (point.py:368-380), so a node shared by k cells ends up with k times its reaction.  Kept for parity.
