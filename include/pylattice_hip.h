@@ -432,6 +432,45 @@ int pl_thermal_load(pl_handle h, double *f /*[6N] or NULL*/, double *n_free /*[B
  * dq/dr_b = dq/dr_b at fixed u - lam^T (dK/dr_b) u + lam^T d f_th / d r_b.  Errors as pl_thermal_load; out == NULL: PL_ERR_ARG. */
 int pl_thermal_sens(pl_handle h, const double *lam /*[6N] or NULL*/, double *out /*[B]*/);
 
+/* ---- steady heat conduction on the strut graph: temperatures, strut heat flows, the thermo-elastic adjoint chain ----------------
+ * Each strut is ONE two-node conductor between its lattice nodes (the convention of K_g and M): a uniform circular section of
+ * the plain radius r over the node-to-node length L = |d|; penalised end zones and the overlap at the joints are ignored, a
+ * multiplicity k of pl_set_multiplicity counts k times.
+ *   conductance   g_b = k_b kappa_b pi r_b^2 / L_b,  kappa_b = beam_kappa ? beam_kappa[b] : kappa;  d g_b / d r_b = 2 g_b / r_b
+ *   operator      (K_T T)_i = sum over struts b at i of g_b (T_i - T_other)
+ *   problem       K_T T = q on the free nodes (q the nodal heat inflow), T = T_bar on the nodes of a mask of one byte per node,
+ *                 which is independent of the mechanical mask of pl_set_bc
+ *   heat flow     Q_b = g_b (T_A - T_B) / k_b of ONE copy of strut b from A to B
+ * Coupling to the thermal loads: the solved T minus a reference temperature is the node_dT of pl_set_thermal.  For a mechanical
+ * field lam the transpose of d f_th / d dT is c_i = sum over struts b at i of (1/2) alpha_b L_b ka_b t_b . (lam_u,B - lam_u,A)
+ * (pl_thermal_load_adjoint).  With K_T mu = c on the free thermal nodes and mu = 0 on the others, a scalar q(u(T(r), r), r)
+ * with K lam = dq/du gains dq/dr_b += - mu^T (dK_T/dr_b) T = - (2 g_b / r_b) (mu_A - mu_B) (T_A - T_B) (pl_cond_sens gives the
+ * product without the sign), for heat inflows and T_bar that do not depend on r.
+ *
+ * All calls: the caller's node and strut numbering; single-GPU FEM handles only (PL_ERR_STATE on pl_create_ddm / pl_dist_init
+ * handles); PL_ERR_STATE before pl_set_conduction (the five below) and before pl_assemble; NULL where an array is required:
+ * PL_ERR_ARG.  g is rebuilt from the current radii and records by every call, so the state follows pl_update_radii and
+ * pl_assemble.  The handle's mechanical state (boundary conditions, last solution, warm start, statistics) is not touched.
+ * The per-node and per-strut products have a fixed order of summation and no atomics: two calls return the same bits.  The
+ * solve sums its scalar products with atomics and is NOT bitwise reproducible. */
+/* kappa == 0 && !beam_kappa clears the state; non-positive or non-finite values: PL_ERR_ARG.  Survives pl_update_radii /
+ * pl_update_segments / pl_assemble. */
+int pl_set_conduction(pl_handle h, double kappa, const double *beam_kappa /*[B] or NULL*/);
+/* y = K_T x; masked: y = P K_T P x for the mask `fixed` (P zeroes the fixed nodes; fixed may be NULL when masked == 0). */
+int pl_cond_spmv(pl_handle h, int32_t masked, const uint8_t *fixed /*[N] or NULL*/, const double *x /*[N]*/, double *y /*[N]*/);
+/* Jacobi-preconditioned CG from x0 = 0 on the free nodes, stopped on the device by ||r|| <= rtol ||b||, b = P (q - K_T T_bar).
+ * T_bar == NULL: zeros (only its values on fixed nodes are read, and they come back bit-equal); q == NULL: no inflow (values
+ * of q on fixed nodes are ignored).  A mask without a fixed node: PL_ERR_ARG.  stats as pl_solve_multi fills them.
+ * PL_ERR_NOCONV when rtol is missed within max_iter (T and stats are still written). */
+int pl_cond_solve(pl_handle h, const uint8_t *fixed /*[N]*/, const double *T_bar /*[N] or NULL*/, const double *q /*[N] or NULL*/,
+                  double rtol, int32_t max_iter, double *T /*[N]*/, pl_stats_t *stats);
+/* Q[b] = g_b (T_A - T_B) / k_b. */
+int pl_cond_flux(pl_handle h, const double *T /*[N]*/, double *Q /*[B]*/);
+/* out[b] = (2 g_b / r_b) (mu_A - mu_B) (T_A - T_B) = mu^T (dK_T / dr_b) T. */
+int pl_cond_sens(pl_handle h, const double *T /*[N]*/, const double *mu /*[N]*/, double *out /*[B]*/);
+/* out[i] = c_i above for the field lam.  Needs the alpha of a thermal state: PL_ERR_STATE before pl_set_thermal. */
+int pl_thermal_load_adjoint(pl_handle h, const double *lam /*[6N]*/, double *out /*[N]*/);
+
 /* Strain energy 1/2 u^T K u (LatticeOpti.compute_compliance, lattice_opti.py:645-663 uses u^T K u). */
 int pl_energy(pl_handle h, const double *u, double *energy);
 

@@ -24,6 +24,7 @@ EXPORTS = ["pl_default_opts", "pl_opts_size", "pl_stats_size", "pl_abi_version",
            "pl_spmv_free", "pl_spmv_bsr", "pl_solve", "pl_reactions", "pl_sens", "pl_sens_gram", "pl_energy", "pl_node_mod", "pl_schur",
            "pl_stress", "pl_stress_pnorm", "pl_buckling", "pl_buckling_pnorm",
            "pl_set_thermal", "pl_thermal_load", "pl_thermal_sens",
+           "pl_set_conduction", "pl_cond_spmv", "pl_cond_solve", "pl_cond_flux", "pl_cond_sens", "pl_thermal_load_adjoint",
            "pl_spmv_multi", "pl_solve_multi", "pl_schur_block", "pl_geom_spmv_multi", "pl_buckling_modes", "pl_buckling_modes_sens",
            "pl_set_mass", "pl_mass_spmv_multi", "pl_vibration_modes", "pl_vibration_modes_sens",
            "pl_dyn_spmv_multi", "pl_transient", "pl_transient_sens", "pl_harm_spmv", "pl_harmonic", "pl_harmonic_sens",
@@ -98,6 +99,8 @@ def load_library(path: str | None = None):
            "pl_stress": [V, V, I32, V, V], "pl_stress_pnorm": [V, V, I32, D, V, V, V, V],
            "pl_buckling": [V, V, I32, D, I32, V, V, V], "pl_buckling_pnorm": [V, V, I32, D, I32, D, V, V, V, V],
            "pl_set_thermal": [V, D, V, V], "pl_thermal_load": [V, V, V], "pl_thermal_sens": [V, V, V],
+           "pl_set_conduction": [V, D, V], "pl_cond_spmv": [V, I32, V, V, V], "pl_cond_solve": [V, V, V, V, D, I32, V, V],
+           "pl_cond_flux": [V, V, V], "pl_cond_sens": [V, V, V, V], "pl_thermal_load_adjoint": [V, V, V],
            "pl_schur": [V, V, I32, D, I32, V], "pl_spmv_multi": [V, I32, I32, V, V],
            "pl_solve_multi": [V, I32, V, V, D, I32, V, V], "pl_schur_block": [V, V, I32, D, I32, I32, V],
            "pl_geom_spmv_multi": [V, V, I32, I32, V, V],
@@ -446,6 +449,8 @@ class HipLattice:
         self.last_stats = None
         self._mult = None
         self._thermal = None
+        self._conduction = None
+        self._assembled = False
         if beam_mult is not None:
             self.set_multiplicity(beam_mult)
 
@@ -521,6 +526,7 @@ class HipLattice:
 
     # -- lifetime ---------------------------------------------------------------------------------------
     def _changing(self, why):
+        self._assembled = False               # (update_radii / set_multiplicity / update_segments clear the library's flag)
         cb = getattr(self, "_before_change", None)
         if cb is not None:
             self._before_change = None
@@ -586,6 +592,7 @@ class HipLattice:
 
     def assemble(self):
         _check(self._lib, self._lib.pl_assemble(self._h))
+        self._assembled = True
 
     def assemble_bsr(self, with_bc=False):
         nr, nb = C.c_int64(), C.c_int64()
@@ -807,6 +814,107 @@ class HipLattice:
         if self._thermal is None:
             raise RuntimeError("thermal_sens_host: call set_thermal first")
         return TH.thermal_sens(self.records(), self.beam_conn, self._radius, self._delta_host(), lam)
+
+    # -- steady heat conduction on the strut graph -----------------------------------------------------------
+    def set_conduction(self, kappa, beam_kappa=None):
+        """Conduction state of the handle (pl_set_conduction): conductivity ``kappa`` of every strut, or beam_kappa (B,) per
+        strut; each strut conducts with g = k kappa pi r^2 / L between its nodes.  It survives update_radii / update_segments /
+        assemble, and the conductances follow the radii."""
+        bk = None if beam_kappa is None else _f64(np.asarray(beam_kappa).reshape(-1), self.n_beams)
+        _check(self._lib, self._lib.pl_set_conduction(self._h, float(kappa), _ptr(bk)))
+        self._conduction = bk if bk is not None else float(kappa)
+
+    def clear_conduction(self):
+        """Removes the conduction state (pl_set_conduction with kappa = 0 and no beam_kappa)."""
+        _check(self._lib, self._lib.pl_set_conduction(self._h, 0.0, None))
+        self._conduction = None
+
+    def _mask_n(self, fixed):
+        fx = np.ascontiguousarray(np.asarray(fixed).reshape(-1) != 0, dtype=np.uint8)
+        if fx.size != self.n_nodes:
+            raise ValueError("the thermal mask must have n_nodes entries")
+        return fx
+
+    def cond_spmv(self, x, fixed=None):
+        """(N,) K_T x (pl_cond_spmv); fixed (N,) given: P K_T P x under that mask of one flag per node."""
+        x = _f64(np.asarray(x).reshape(-1), self.n_nodes)
+        fx = None if fixed is None else self._mask_n(fixed)
+        y = np.empty(self.n_nodes, np.float64)
+        _check(self._lib, self._lib.pl_cond_spmv(self._h, int(fx is not None), _ptr(fx), _ptr(x), _ptr(y)))
+        return y
+
+    def cond_solve(self, fixed, t_bar=None, q=None, rtol=1e-10, max_iter=200000, raise_on_noconv=True):
+        """(T (N,), stats) of K_T T = q on the free nodes, T = t_bar on the nodes of ``fixed`` (pl_cond_solve): a Jacobi PCG
+        from zero on the device.  t_bar None = 0, q None = no inflow.  The handle's mechanical state is not touched."""
+        fx = self._mask_n(fixed)
+        tb = None if t_bar is None else _f64(np.broadcast_to(np.asarray(t_bar, dtype=float).reshape(-1), (self.n_nodes,)))
+        qq = None if q is None else _f64(np.asarray(q).reshape(-1), self.n_nodes)
+        T = np.empty(self.n_nodes, np.float64)
+        st = PlStats()
+        st.struct_size = C.sizeof(PlStats)
+        rc = self._lib.pl_cond_solve(self._h, _ptr(fx), _ptr(tb), _ptr(qq), float(rtol), int(max_iter), _ptr(T), C.byref(st))
+        keys = [n for n, _ in PlStats._fields_ if n not in ("reserved", "reserved_i", "struct_size")]
+        stats = {n: getattr(st, n) for n in keys}
+        if rc in (PL_OK, PL_ERR_NOCONV):
+            _timing.device("pl_cond_solve: PCG (HIP events)", st.ms_solve)
+        _check(self._lib, rc, allow=() if raise_on_noconv else (PL_ERR_NOCONV,))
+        return T, stats
+
+    def cond_flux(self, T):
+        """(B,) heat flow Q_b = g (T_A - T_B) / k of one copy of every strut from A to B (pl_cond_flux)."""
+        T = _f64(np.asarray(T).reshape(-1), self.n_nodes)
+        Q = np.empty(self.n_beams, np.float64)
+        _check(self._lib, self._lib.pl_cond_flux(self._h, _ptr(T), _ptr(Q)))
+        return Q
+
+    def cond_sens(self, T, mu):
+        """(B,) mu^T (dK_T / dr_b) T = (2 g / r)(mu_A - mu_B)(T_A - T_B) (pl_cond_sens)."""
+        T = _f64(np.asarray(T).reshape(-1), self.n_nodes)
+        mu = _f64(np.asarray(mu).reshape(-1), self.n_nodes)
+        out = np.empty(self.n_beams, np.float64)
+        _check(self._lib, self._lib.pl_cond_sens(self._h, _ptr(T), _ptr(mu), _ptr(out)))
+        return out
+
+    def thermal_load_adjoint(self, lam):
+        """(N,) c = (d f_th / d dT)^T lam of the thermal state's expansion coefficients (pl_thermal_load_adjoint)."""
+        lam = _f64(np.asarray(lam).reshape(-1), 6 * self.n_nodes)
+        out = np.empty(self.n_nodes, np.float64)
+        _check(self._lib, self._lib.pl_thermal_load_adjoint(self._h, _ptr(lam), _ptr(out)))
+        return out
+
+    def _g_host(self):
+        from . import conduction_host as CH
+        if getattr(self, "_conduction", None) is None:
+            raise RuntimeError("call set_conduction first")
+        return CH.conductance(self.node_xyz, self.beam_conn, self._radius, self._conduction, self._mult)
+
+    def cond_spmv_host(self, x, fixed=None):
+        """The numpy restatement of ``cond_spmv`` (conduction_host.spmv)."""
+        from . import conduction_host as CH
+        return CH.spmv(self.beam_conn, self.n_nodes, self._g_host(), x, fixed)
+
+    def cond_solve_host(self, fixed, t_bar=None, q=None):
+        """The dense host solve of the problem of ``cond_solve`` (conduction_host.solve)."""
+        from . import conduction_host as CH
+        qq = None if q is None else np.where(np.asarray(fixed).reshape(-1) != 0, 0.0, np.asarray(q, dtype=float).reshape(-1))
+        return CH.solve(self.beam_conn, self.n_nodes, self._g_host(), fixed, t_bar, qq)
+
+    def cond_flux_host(self, T):
+        """The numpy restatement of ``cond_flux`` (conduction_host.flux)."""
+        from . import conduction_host as CH
+        return CH.flux(self.beam_conn, self._g_host(), T, self._mult)
+
+    def cond_sens_host(self, T, mu):
+        """The numpy restatement of ``cond_sens`` (conduction_host.cond_sens)."""
+        from . import conduction_host as CH
+        return CH.cond_sens(self.beam_conn, self._radius, self._g_host(), T, mu)
+
+    def thermal_load_adjoint_host(self, lam):
+        """The numpy restatement of ``thermal_load_adjoint`` (conduction_host.thermal_load_adjoint)."""
+        from . import conduction_host as CH
+        if self._thermal is None:
+            raise RuntimeError("thermal_load_adjoint_host: call set_thermal first")
+        return CH.thermal_load_adjoint(self.records(), self.beam_conn, self.n_nodes, self._thermal[0], lam)
 
     def energy(self, u):
         u = _f64(np.asarray(u).reshape(-1), 6 * self.n_nodes)

@@ -8,6 +8,7 @@
 #include "pl_stress.h"
 #include "pl_buckling.h"
 #include "pl_thermal.h"
+#include "pl_conduction.h"
 #include "pl_geom.h"
 #include "pl_mass.h"
 #include "pl_dyn.h"
@@ -2233,6 +2234,159 @@ int pl_schur_block(pl_handle h, const int32_t *boundary_nodes, int32_t nb, doubl
   if (bad) return fail(PL_ERR_NAN, "pl_schur_block: NaN/Inf in a residual norm");
   if (missed) return fail(PL_ERR_NOCONV, "pl_schur_block: " + std::to_string(missed) + " column(s) did not reach rtol within max_iter");
   return PL_OK;
+}
+
+// ---- steady heat conduction on the strut graph (pl_conduction.h) ---------------------------------------------------------
+int pl_set_conduction(pl_handle h, double kappa, const double *beam_kappa) {
+  if (!valid(h)) return fail(PL_ERR_ARG, "pl_set_conduction: null handle");
+  if (h->opkind != 0) return fail(PL_ERR_STATE, "pl_set_conduction: not available on a DDM handle");
+  if (h->dist.active || h->opt.grid_nodes > 0)
+    return fail(PL_ERR_STATE, "pl_set_conduction: single-GPU handles only (this one belongs to a multi-rank run)");
+  if (kappa == 0.0 && !beam_kappa) {
+    h->cond_ws.reset();
+    return PL_OK;
+  }
+  if (!beam_kappa && !(kappa > 0.0 && std::isfinite(kappa)))
+    return fail(PL_ERR_ARG, "pl_set_conduction: kappa must be positive and finite");
+  if (beam_kappa)
+    for (int64_t b = 0; b < h->B; ++b)
+      if (!(beam_kappa[b] > 0.0 && std::isfinite(beam_kappa[b])))
+        return fail(PL_ERR_ARG, "pl_set_conduction: beam_kappa must be positive and finite");
+  PL_HIP(hipSetDevice(h->opt.device));
+  const size_t B = (size_t)h->B, N = (size_t)h->N;
+  auto w = std::make_shared<CondWs>();
+  for (DevBuf<double> *b : {&w->kappa, &w->g, &w->out}) PL_HIP(b->alloc(B));
+  for (DevBuf<double> *b : {&w->X, &w->R, &w->Z, &w->P, &w->AP, &w->KT, &w->TB, &w->QF, &w->T, &w->MU, &w->dinv})
+    PL_HIP(b->alloc(N));
+  PL_HIP(w->fixed.alloc(N));
+  PL_HIP(w->scal.alloc(kCondScal));
+  PL_HIP(w->flags.alloc(2));
+  std::vector<double> ka(B);
+  for (size_t b = 0; b < B; ++b) ka[b] = beam_kappa ? beam_kappa[h->bperm[b]] : kappa;
+  PL_HIP(hipMemcpy(w->kappa.p, ka.data(), B * sizeof(double), hipMemcpyHostToDevice));
+  h->cond_ws = w;
+  return PL_OK;
+}
+
+namespace {
+// what the conduction calls share: the handle checks and the conductances of the current radii and records - k_cond_strut, one
+// thread per strut - so the state follows every pl_update_radii and pl_assemble without a flag
+int cond_begin(pl_handle h, const char *who, CondWs **w) {
+  if (!valid(h)) return fail(PL_ERR_ARG, std::string(who) + ": null handle");
+  if (h->opkind != 0) return fail(PL_ERR_STATE, std::string(who) + ": not available on a DDM handle");
+  if (h->dist.active || h->opt.grid_nodes > 0)
+    return fail(PL_ERR_STATE, std::string(who) + ": single-GPU handles only (this one belongs to a multi-rank run)");
+  if (!h->cond_ws) return fail(PL_ERR_STATE, std::string(who) + ": call pl_set_conduction first");
+  if (!h->assembled) return fail(PL_ERR_STATE, std::string(who) + ": call pl_assemble first");
+  PL_HIP(hipSetDevice(h->opt.device));
+  *w = static_cast<CondWs *>(h->cond_ws.get());
+  EventTimer timer(who, h->stream, "kernel_hip_event");
+  hipLaunchKernelGGL(pl::k_cond_strut, dim3(grid_for(h->B)), dim3(pl::kBlock), 0, h->stream, h->B, (const pl::Record *)h->rec.p,
+                     (const double *)h->radius.p, (const double *)h->mult.p, (const double *)(*w)->kappa.p, (*w)->g.p);
+  PL_HIP(hipGetLastError());
+  timer.stop();
+  return PL_OK;
+}
+}  // namespace
+
+int pl_cond_spmv(pl_handle h, int32_t masked, const uint8_t *fixed, const double *x, double *y) {
+  if (valid(h) && (!x || !y || (masked && !fixed))) return fail(PL_ERR_ARG, "pl_cond_spmv: null argument");
+  CondWs *w = nullptr;
+  if (int rc = cond_begin(h, "pl_cond_spmv", &w)) return rc;
+  if (masked)
+    if (int rc = cond_upload_mask(h, fixed, w->fixed.p)) return rc;
+  if (int rc = cond_upload(h, x, w->X.p, masked ? fixed : nullptr)) return rc;
+  EventTimer timer("pl_cond_spmv", h->stream, "kernel_hip_event");
+  launch_cond_gather(h, w, masked != 0, w->X.p, w->AP.p, nullptr);
+  PL_HIP(hipGetLastError());
+  timer.stop();
+  return cond_download(h, w->AP.p, y);
+}
+
+int pl_cond_solve(pl_handle h, const uint8_t *fixed, const double *T_bar, const double *q, double rtol, int32_t max_iter,
+                  double *T, pl_stats_t *stats) {
+  if (valid(h) && (!fixed || !T)) return fail(PL_ERR_ARG, "pl_cond_solve: null argument");
+  if (valid(h) && (!(rtol > 0.0) || max_iter <= 0)) return fail(PL_ERR_ARG, "pl_cond_solve: rtol and max_iter must be positive");
+  if (valid(h) && stats && stats->struct_size != sizeof(pl_stats_t))
+    return fail(PL_ERR_ARG, "pl_cond_solve: stats->struct_size is " + std::to_string(stats->struct_size) +
+                                ", this library's pl_stats_t has " + std::to_string(sizeof(pl_stats_t)) + " bytes");
+  CondWs *w = nullptr;
+  if (int rc = cond_begin(h, "pl_cond_solve", &w)) return rc;
+  bool any = false;
+  for (int64_t i = 0; i < h->N && !any; ++i) any = fixed[i] != 0;
+  if (!any) return fail(PL_ERR_ARG, "pl_cond_solve: the mask fixes no node (K_T is singular without a prescribed temperature)");
+  if (int rc = cond_upload_mask(h, fixed, w->fixed.p)) return rc;
+  {   // T_bar on the fixed nodes only, zero on the free ones (the lifting K_T T_bar must not see free values)
+    std::vector<double> tb((size_t)h->N, 0.0);
+    if (T_bar)
+      for (int64_t i = 0; i < h->N; ++i)
+        if (fixed[i]) tb[(size_t)i] = T_bar[i];
+    if (int rc = cond_upload(h, tb.data(), w->TB.p)) return rc;
+  }
+  if (q)
+    if (int rc = cond_upload(h, q, w->QF.p)) return rc;
+  double status[pl::M_ST_COUNT] = {};
+  EventTimer timer("pl_cond_solve", h->stream, "kernel_hip_event");
+  PL_HIP(hipEventRecord(h->ev0, h->stream));
+  if (int rc = cond_pcg(h, w, q ? (const double *)w->QF.p : (const double *)nullptr, rtol, max_iter, w->T.p, status)) return rc;
+  PL_HIP(hipEventRecord(h->ev1, h->stream));
+  PL_HIP(hipStreamSynchronize(h->stream));
+  timer.stop();
+  float ms = 0.f;
+  PL_HIP(hipEventElapsedTime(&ms, h->ev0, h->ev1));
+  if (int rc = cond_download(h, w->T.p, T)) return rc;
+  MultiShape s{1, 1, 1, 1, h->N};
+  bool bad = false;
+  const int missed = multi_stats(s, status, rtol, ms, stats, &bad);
+  if (bad) return fail(PL_ERR_NAN, "pl_cond_solve: NaN/Inf in a residual norm");
+  if (missed) return fail(PL_ERR_NOCONV, "pl_cond_solve: rtol not reached within max_iter");
+  return PL_OK;
+}
+
+int pl_cond_flux(pl_handle h, const double *T, double *Q) {
+  if (valid(h) && (!T || !Q)) return fail(PL_ERR_ARG, "pl_cond_flux: null argument");
+  CondWs *w = nullptr;
+  if (int rc = cond_begin(h, "pl_cond_flux", &w)) return rc;
+  if (int rc = cond_upload(h, T, w->T.p)) return rc;
+  EventTimer timer("pl_cond_flux", h->stream, "kernel_hip_event");
+  hipLaunchKernelGGL(pl::k_cond_flux, dim3(grid_for(h->B)), dim3(pl::kBlock), 0, h->stream, h->B, (const int32_t *)h->conn.p,
+                     (const double *)h->mult.p, (const double *)w->g.p, (const double *)w->T.p, w->out.p);
+  PL_HIP(hipGetLastError());
+  timer.stop();
+  return download_struts(h, w->out.p, Q);
+}
+
+int pl_cond_sens(pl_handle h, const double *T, const double *mu, double *out) {
+  if (valid(h) && (!T || !mu || !out)) return fail(PL_ERR_ARG, "pl_cond_sens: null argument");
+  CondWs *w = nullptr;
+  if (int rc = cond_begin(h, "pl_cond_sens", &w)) return rc;
+  if (int rc = cond_upload(h, T, w->T.p)) return rc;
+  if (int rc = cond_upload(h, mu, w->MU.p)) return rc;
+  EventTimer timer("pl_cond_sens", h->stream, "kernel_hip_event");
+  hipLaunchKernelGGL(pl::k_cond_sens, dim3(grid_for(h->B)), dim3(pl::kBlock), 0, h->stream, h->B, (const int32_t *)h->conn.p,
+                     (const double *)h->radius.p, (const double *)w->g.p, (const double *)w->T.p, (const double *)w->MU.p,
+                     w->out.p);
+  PL_HIP(hipGetLastError());
+  timer.stop();
+  return download_struts(h, w->out.p, out);
+}
+
+int pl_thermal_load_adjoint(pl_handle h, const double *lam, double *out) {
+  if (valid(h) && (!lam || !out)) return fail(PL_ERR_ARG, "pl_thermal_load_adjoint: null argument");
+  CondWs *w = nullptr;
+  if (int rc = cond_begin(h, "pl_thermal_load_adjoint", &w)) return rc;
+  ThermalWs *t = static_cast<ThermalWs *>(h->thermal_ws.get());
+  if (!t) return fail(PL_ERR_STATE, "pl_thermal_load_adjoint: call pl_set_thermal first (the expansion coefficients)");
+  if (!w->lam6.p) PL_HIP(w->lam6.alloc((size_t)h->N * 6));
+  std::vector<double> stage;
+  if (int rc = upload6(h, lam, w->lam6.p, stage)) return rc;
+  EventTimer timer("pl_thermal_load_adjoint", h->stream, "kernel_hip_event");
+  hipLaunchKernelGGL(pl::k_thermal_load_adjoint, dim3(grid_for(h->N)), dim3(pl::kBlock), 0, h->stream, h->N,
+                     pl::kWave / h->lpn, (const int64_t *)h->slice_ptr.p, (const int2 *)h->ent.p, (const pl::Record *)h->rec.p,
+                     (const double *)t->alpha.p, (const double *)w->lam6.p, w->MU.p);
+  PL_HIP(hipGetLastError());
+  timer.stop();
+  return cond_download(h, w->MU.p, out);
 }
 
 // ---- global linear buckling (pl_geom.h) --------------------------------------------------------------------------------

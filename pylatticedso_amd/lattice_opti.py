@@ -466,7 +466,22 @@ class LatticeOpti(LatticeSim):
         s = dev.sens(u, lam)
         if self.thermal is not None:
             s = s - dev.thermal_sens(u if lam is None else lam)
+        if self.conduction_driven and self.conduction_chain:
+            # the temperature follows the radii through g = k kappa pi r^2 / L: with c = (d f_th / d dT)^T lam and
+            # K_T mu = c on the free thermal nodes, lam^T (d f_th / d dT) dT/dr_b = -mu^T (dK_T/dr_b) T
+            cd = self.conduction
+            c = dev.thermal_load_adjoint(u if lam is None else lam)
+            mu, _ = dev.cond_solve(cd["fixed"], None, np.where(cd["fixed"], 0.0, c), rtol=1e-10, max_iter=200000)
+            s = s + dev.cond_sens(self.temperature_field, mu)
         return s
+
+    conduction_chain = True     # False leaves dT/dr out of the gradients (tests show what that costs)
+
+    def _no_conduction_driven(self, key):
+        if key in ("max_stress", "buckling") and self.conduction_driven:
+            raise ValueError(f'the "{key}" constraint under a conduction-driven temperature needs dphi/dT of the p-norm '
+                             "kernels (the section force depends on T directly), which is not implemented; give the "
+                             "temperature to set_temperature as an array instead")
 
     def strut_sensitivities(self):
         """s_b such that d(objective)/d r_b = −s_b at fixed segment geometry (compliance: s_b = u_eᵀ ∂K_e/∂r u_e)."""
@@ -697,13 +712,15 @@ class LatticeOpti(LatticeSim):
 
     def _constraint_value(self, key, r):
         c = next(c for c in _RESPONSE_CONSTRAINTS if c.key == key)
+        self._no_conduction_driven(key)
         self._equilibrium_at(r)
         return c.scale(getattr(self, c.aggregate)()[0], self._constraint_limit(c)) - 1.0
 
     def _constraint_gradient(self, key, r):
         c = next(c for c in _RESPONSE_CONSTRAINTS if c.key == key)
+        self._no_conduction_driven(key)
         self._equilibrium_at(r)
-        aggregate = getattr(self, c.aggregate)
+        aggregate =getattr(self, c.aggregate)
         out = aggregate() if c.gradient == "shared" else aggregate(want_grad=True)
         g = self._aggregate_gradient(out[2], out[3]) if c.gradient == "partials" else self._strut_gradient_to_parameters(out[2])
         return c.scale(g, self._constraint_limit(c))

@@ -115,7 +115,13 @@ class LatticeSim(LatticeViews):
         self._cell_radii_override = None
         self._device = self._ddm_device = None
         self.thermal = None                        # (alpha, delta_T, beam_alpha) of set_temperature, None without one
+        self.conduction = None                     # the conduction problem of solve_temperature, None without one
+        self.temperature_field = None              # (n_nodes,) T of its last solve
         self._generate_and_prepare()
+        if self._conduction_preset is not None:    # simulation_parameters["thermal"]["conduction"]
+            c = self._conduction_preset
+            self._set_conduction_problem(c["conductivity"], c["Temperature"], c.get("HeatFlow", None),
+                                         c.get("beam_conductivity", None), c.get("reference", 0.0))
         if self._thermal_preset is not None:       # simulation_parameters["thermal"]
             self.set_temperature(*self._thermal_preset)
         self.cell_schur_index = None       # (C,) index into self.schur_complements
@@ -216,7 +222,16 @@ class LatticeSim(LatticeViews):
             raise ValueError("Schur complement computation method must be defined in the input file.")
         self.boundary_conditions = p.get("boundary_conditions", {})
         th = sim.get("thermal", None)              # {"alpha": a, "delta_T": scalar}: a uniform temperature rise
-        self._thermal_preset = None if th is None else (float(th["delta_T"]), float(th["alpha"]))
+        self._thermal_preset = self._conduction_preset = None
+        if th is not None and th.get("conduction", None) is not None:
+            # {"alpha": a, "conduction": {"conductivity", "reference", "Temperature": {...}, "HeatFlow": {...}}}: the
+            # temperature is the solution of the conduction problem on the struts (solve_temperature)
+            if self.domain_decomposition_solver:
+                raise ValueError('the "conduction" block needs simulation_type "FEM": DDM handles carry no strut graph')
+            self._conduction_preset = dict(th["conduction"])
+            self._thermal_preset = ("conduction", float(th["alpha"]))
+        elif th is not None:
+            self._thermal_preset = (float(th["delta_T"]), float(th["alpha"]))
         self.young_modulus, self.poisson_ratio = material_properties(self.material_name)
 
     # ------------------------------------------------------------------------------------------------
@@ -632,10 +647,21 @@ class LatticeSim(LatticeViews):
         the reactions are K u - f_th, and strut_stress / strut_buckling report the mechanical force; global_buckling and
         solve_DDM refuse while a temperature is set."""
         n = self.lattice.n_nodes
-        dT = delta_T(np.asarray(self.lattice.node_xyz, dtype=float)) if callable(delta_T) else delta_T
-        dT = np.array(np.broadcast_to(np.asarray(dT, dtype=float), (n,)))
         ba = None if beam_alpha is None else np.array(np.broadcast_to(np.asarray(beam_alpha, dtype=float),
                                                                       (self.lattice.n_beams,)))
+        if isinstance(delta_T, str):
+            # delta_T = "conduction": T - reference of the conduction problem of solve_temperature (or of the preset's
+            # "conduction" block), solved again before every mechanical solve so that it follows the radii
+            if delta_T != "conduction":
+                raise ValueError('set_temperature: delta_T must be a number, an array, a callable or "conduction"')
+            if self.conduction is None:
+                raise RuntimeError('set_temperature("conduction"): define the conduction problem first (solve_temperature)')
+            if not (np.isfinite(alpha) and (ba is None or np.isfinite(ba).all())):
+                raise ValueError("set_temperature: alpha and beam_alpha must be finite")
+            self.thermal = (float(alpha), "conduction", ba)
+            return
+        dT = delta_T(np.asarray(self.lattice.node_xyz, dtype=float)) if callable(delta_T) else delta_T
+        dT = np.array(np.broadcast_to(np.asarray(dT, dtype=float), (n,)))
         if not (np.isfinite(dT).all() and np.isfinite(alpha) and (ba is None or np.isfinite(ba).all())):
             raise ValueError("set_temperature: delta_T, alpha and beam_alpha must be finite")
         self.thermal = (float(alpha), dT, ba)
@@ -652,7 +678,123 @@ class LatticeSim(LatticeViews):
         if getattr(self, "_compat_rows", False):
             raise NotImplementedError("thermal loads are not available in the reference_compat strut model")
         alpha, dT, ba = self.thermal
+        if self.conduction_driven:
+            dT = self._solve_conduction(dev) - self.conduction["reference"]
         dev.set_thermal(alpha, dT, ba)
+
+    # -- steady heat conduction on the struts (FEM mode; pl_set_conduction) --------------------
+    @property
+    def conduction_driven(self):
+        """True when the temperature of set_temperature is the solution of the conduction problem."""
+        return self.thermal is not None and isinstance(self.thermal[1], str)
+
+    def _thermal_nodes(self, spec, what, share):
+        """(mask (n,), values (n,)) of a boundary description of the conduction problem: a block {"Surface": [...], "Value": v}
+        or a dict of named blocks, as the presets' boundary conditions are written; share: the value is a total, divided
+        equally over the nodes of its surface."""
+        n = self.lattice.n_nodes
+        mask, val = np.zeros(n, bool), np.zeros(n)
+        blocks = [spec] if "Surface" in spec else list(spec.values())
+        for b in blocks:
+            if "Surface" not in b or "Value" not in b:
+                raise ValueError(f"solve_temperature: a {what} block needs 'Surface' and 'Value'")
+            pts = self.find_point_on_lattice_surface(list(b["Surface"]), b.get("SurfaceCells", None))
+            v = float(np.asarray(b["Value"], dtype=float).reshape(-1)[0])
+            mask[pts] = True
+            if share:
+                val[pts] += v / len(pts)
+            else:
+                val[pts] = v
+        return mask, val
+
+    def _set_conduction_problem(self, conductivity, fixed, heat_flow, beam_conductivity, reference):
+        n = self.lattice.n_nodes
+        if self.domain_decomposition_solver:
+            raise ValueError("solve_temperature: heat conduction needs the FEM strut model (DDM handles carry no strut graph)")
+        if isinstance(fixed, dict):
+            mask, t_bar = self._thermal_nodes(fixed, "Temperature", False)
+        elif isinstance(fixed, (tuple, list)) and len(fixed) == 2:
+            mask = np.array(np.broadcast_to(np.asarray(fixed[0]).reshape(-1) != 0, (n,)))
+            t_bar = np.where(mask, np.broadcast_to(np.asarray(fixed[1], dtype=float), (n,)), 0.0)
+        else:                                      # (n,) temperatures, NaN on the free nodes
+            t = np.array(np.broadcast_to(np.asarray(fixed, dtype=float), (n,)))
+            mask, t_bar = ~np.isnan(t), np.nan_to_num(t)
+        if heat_flow is None:
+            q = None
+        elif isinstance(heat_flow, dict):
+            q = self._thermal_nodes(heat_flow, "HeatFlow", True)[1]
+        else:
+            q = np.array(np.broadcast_to(np.asarray(heat_flow, dtype=float), (n,)))
+        bk = None if beam_conductivity is None else np.array(np.broadcast_to(np.asarray(beam_conductivity, dtype=float),
+                                                                             (self.lattice.n_beams,)))
+        if not mask.any():
+            raise ValueError("solve_temperature: no node has a prescribed temperature")
+        if not (np.isfinite(t_bar).all() and (q is None or np.isfinite(q).all()) and np.isfinite(reference)):
+            raise ValueError("solve_temperature: temperatures, heat flows and the reference must be finite")
+        if not ((bk is None and conductivity > 0 and np.isfinite(conductivity)) or
+                (bk is not None and (bk > 0).all() and np.isfinite(bk).all())):
+            raise ValueError("solve_temperature: conductivities must be positive and finite")
+        self.conduction = {"conductivity": float(conductivity), "beam_conductivity": bk, "fixed": mask, "t_bar": t_bar,
+                           "heat_flow": None if q is None else np.where(mask, 0.0, q), "reference": float(reference)}
+
+    def _assemble_for_conduction(self, dev):
+        """The conduction calls need an assembled handle (the strut records); a handle that never saw boundary conditions
+        gets the lattice's mask first, which the next mechanical solve installs again with its values and loads."""
+        if not dev._assembled:
+            dev.set_bc(self.fixed_DOF)
+            dev.assemble()
+
+    def _solve_conduction(self, dev):
+        """T of the conduction problem on the handle's current radii (pl_cond_solve); the handle must be assembled."""
+        c = self.conduction
+        want = c["conductivity"] if c["beam_conductivity"] is None else c["beam_conductivity"]
+        if dev._conduction is None or not np.array_equal(np.asarray(dev._conduction), np.asarray(want)):
+            dev.set_conduction(c["conductivity"], c["beam_conductivity"])
+        T, self.conduction_stats = dev.cond_solve(c["fixed"], c["t_bar"], c["heat_flow"], rtol=1e-12, max_iter=200000)
+        self.temperature_field = T
+        return T
+
+    def solve_temperature(self, conductivity=None, fixed=None, heat_flow=None, beam_conductivity=None, reference=0.0):
+        """Steady temperatures of the lattice nodes, each strut one conductor g = k kappa pi r^2 / L between its nodes:
+        K_T T = q on the free nodes, T prescribed on the others.  conductivity: kappa of every strut, or beam_conductivity
+        (n_beams,) per strut.  fixed: the prescribed temperatures - a block {"Surface": [...], "Value": T} or a dict of named
+        blocks, as the presets' boundary conditions name surfaces; or (mask, values); or an (n_nodes,) array with NaN on the
+        free nodes.  heat_flow: the heat inflow - blocks whose "Value" is the TOTAL of the surface, shared equally over its
+        nodes, or an (n_nodes,) array of nodal inflows.  reference: the stress-free temperature that
+        set_temperature("conduction", alpha) subtracts.  Returns T (n_nodes,); the problem is kept, and solved again before
+        every mechanical solve under a conduction-driven temperature.  Without arguments: the problem kept last (that of the
+        preset's "conduction" block, for instance) on the current radii."""
+        if getattr(self, "_compat_rows", False):
+            raise NotImplementedError("heat conduction is not available in the reference_compat strut model")
+        if conductivity is None and fixed is None:
+            if self.conduction is None:
+                raise RuntimeError("solve_temperature: no conduction problem is defined (give conductivity and fixed)")
+        elif (conductivity is None and beam_conductivity is None) or fixed is None:
+            raise ValueError("solve_temperature needs a conductivity and the prescribed temperatures")
+        else:
+            self._set_conduction_problem(0.0 if conductivity is None else conductivity, fixed, heat_flow, beam_conductivity,
+                                         reference)
+        dev = self.device_model()
+        self._assemble_for_conduction(dev)
+        return self._solve_conduction(dev).copy()
+
+    def clear_conduction(self):
+        """Removes the conduction problem (and a temperature that is driven by it)."""
+        if self.conduction_driven:
+            self.clear_temperature()
+        self.conduction = None
+        self.temperature_field = None
+        if self._device is not None and not getattr(self, "_compat_rows", False):
+            self._device.clear_conduction()
+
+    def strut_heat_flow(self):
+        """(n_beams,) heat flow Q_b = g (T_A - T_B) / k of one copy of every strut, from its first node to its second, for
+        the temperatures of the last conduction solve (pl_cond_flux)."""
+        if self.conduction is None or self.temperature_field is None:
+            raise RuntimeError("strut_heat_flow: no temperature field (solve_temperature)")
+        dev = self.device_model()
+        self._assemble_for_conduction(dev)
+        return dev.cond_flux(self.temperature_field)
 
     def thermal_strut_forces(self):
         """(n_beams,) restrained thermal force n_free of one copy of every strut (pl_thermal_load): what a strut heated and

@@ -1,0 +1,107 @@
+#!/usr/bin/env python3
+"""Times the conduction gather (pl_cond_spmv) on the 50^3 Octet lattice of bench.py beside its yardstick,
+k_thermal_load of pl_thermal_load in the same run: both walk the same sliced-ELL incidence, one thread per node.  Then one
+pl_cond_solve between a hot and a cold face.  One process, one GPU; one warm-up and --reps timed repetitions per row.  Kernel
+times are HIP events around the launches of one call (the library prints them when PL_TIMING is set; the last line of a call is
+the stage that ends it - for pl_cond_solve the whole PCG with its status downloads).
+
+    python tools/time_conduction.py --out profiles/r18_conduction
+"""
+import argparse
+import json
+import os
+import sys
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+os.environ["PL_TIMING"] = "1"
+
+from time_stress import _summary, _timed                               # noqa: E402
+from pylatticedso_amd.lattice_sim import LatticeSim                    # noqa: E402
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--out", default="profiles/r18_conduction")
+    ap.add_argument("--reps", type=int, default=5)
+    ap.add_argument("--cells", type=int, default=50)
+    ap.add_argument("--geom", default="Octet")
+    ap.add_argument("--rtol", type=float, default=1e-8)
+    a = ap.parse_args()
+    n = a.cells
+    L = LatticeSim({"geometry": {"cell_size": {"x": 1, "y": 1, "z": 1}, "number_of_cells": {"x": n, "y": n, "z": n},
+                                 "radii": [0.05], "geom_types": [a.geom]},
+                    "simulation_parameters": {"enable": True, "material": "VeroClear", "periodicity": False},
+                    "boundary_conditions": {
+                        "Displacement": {"Fixed": {"Surface": ["Xmin"], "DOF": ["X", "Y", "Z", "RX", "RY", "RZ"],
+                                                   "Value": [0, 0, 0, 0, 0, 0]}},
+                        "Force": {"Load": {"Surface": ["Xmax"], "DOF": ["Z"], "Value": [-0.1]}}}})
+    lat = L.lattice
+    dev = L.device_model()
+    dev.set_bc(L.fixed_DOF)
+    dev.assemble()
+    rng = np.random.default_rng(0)
+    T = 20.0 + 60.0 * rng.random(lat.n_nodes)
+    mu = rng.standard_normal(lat.n_nodes)
+    lam = np.ascontiguousarray((rng.standard_normal((lat.n_nodes, 6)) * 1e-3).ravel())
+    fixed = np.zeros(lat.n_nodes, bool)
+    hot, cold = L.find_point_on_lattice_surface(["Zmin"]), L.find_point_on_lattice_surface(["Zmax"])
+    fixed[hot] = fixed[cold] = True
+    t_bar = np.zeros(lat.n_nodes)
+    t_bar[hot], t_bar[cold] = 90.0, 20.0
+    dev.set_conduction(0.2)
+    dev.set_thermal(7e-5, 40.0 + 10.0 * (2.0 * rng.random(lat.n_nodes) - 1.0))
+    res = {"lattice": f"{n}^3 {a.geom}", "n_nodes": int(lat.n_nodes), "n_beams": int(lat.n_beams), "reps": a.reps,
+           "rtol": a.rtol, "rows": {}}
+    solves = []
+
+    def solve():
+        solves.append(dev.cond_solve(fixed, t_bar, None, rtol=a.rtol, max_iter=200000)[1])
+
+    rows = {"pl_thermal_load, f_th and n_free (last stage: k_thermal_load)": lambda: dev.thermal_load(),
+            "pl_cond_spmv (last stage: k_cond_gather<false>)": lambda: dev.cond_spmv(T),
+            "pl_cond_spmv masked (last stage: k_cond_gather<true>)": lambda: dev.cond_spmv(T, fixed),
+            "pl_cond_flux (last stage: k_cond_flux)": lambda: dev.cond_flux(T),
+            "pl_cond_sens (last stage: k_cond_sens)": lambda: dev.cond_sens(T, mu),
+            "pl_thermal_load_adjoint (last stage: k_thermal_load_adjoint)": lambda: dev.thermal_load_adjoint(lam),
+            f"pl_cond_solve rtol {a.rtol:g}, hot Zmin and cold Zmax (last stage: the PCG)": solve}
+    for name, fn in rows.items():
+        walls, kernels = [], []
+        for rep in range(a.reps + 1):
+            w, k, _ = _timed(fn)
+            if rep:
+                walls.append(w)
+                kernels.append(k)
+        res["rows"][name] = {"wall": _summary(walls), "kernel_hip_events": _summary(kernels)}
+    k = {name: r["kernel_hip_events"]["median_ms"] for name, r in res["rows"].items()}
+    st = solves[-1]
+    res["cond_solve"] = {"iterations": int(st["iterations"]), "rel_residual": float(st["rel_residual"]),
+                         "converged": int(st["converged"]), "iterations_of_every_repetition": [int(s["iterations"]) for s in solves]}
+    # what the gather has to move: per strut visit (two per strut) the 8-byte incidence entry, 8 bytes of g and 8 bytes of the
+    # other node's x; per node 8 bytes of x read and 8 bytes of y written
+    res["k_cond_gather_model_bytes"] = int(2 * lat.n_beams * (8 + 8 + 8) + 16 * lat.n_nodes)
+    t = k["pl_cond_spmv (last stage: k_cond_gather<false>)"]
+    res["k_cond_gather_model_GB_per_s"] = res["k_cond_gather_model_bytes"] / (t * 1e-3) / 1e9
+    os.makedirs(os.path.dirname(a.out) or ".", exist_ok=True)
+    with open(a.out + ".json", "w") as fh:
+        json.dump(res, fh, indent=1)
+    lines = [f"{res['lattice']}: {res['n_nodes']} nodes, {res['n_beams']} struts; medians of {a.reps} warm repetitions"]
+    for name, r in res["rows"].items():
+        kk = r["kernel_hip_events"]
+        lines.append(f"  {name:76} wall {r['wall']['median_ms']:9.2f} ms" +
+                     (f"   last stage (HIP events) {kk['median_ms']:8.4f} ms" if kk else ""))
+    lines.append(f"  pl_cond_solve: {res['cond_solve']['iterations']} iterations, rel_residual "
+                 f"{res['cond_solve']['rel_residual']:.2e}")
+    lines.append(f"  k_cond_gather: {res['k_cond_gather_model_bytes']} model bytes, "
+                 f"{res['k_cond_gather_model_GB_per_s']:.0f} GB/s at the measured time")
+    with open(a.out + ".txt", "w") as fh:
+        fh.write("\n".join(lines) + "\n")
+    print("\n".join(lines))
+    dev.close()
+
+
+if __name__ == "__main__":
+    main()
