@@ -471,6 +471,34 @@ int pl_cond_sens(pl_handle h, const double *T /*[N]*/, const double *mu /*[N]*/,
 /* out[i] = c_i above for the field lam.  Needs the alpha of a thermal state: PL_ERR_STATE before pl_set_thermal. */
 int pl_thermal_load_adjoint(pl_handle h, const double *lam /*[6N]*/, double *out /*[N]*/);
 
+/* ---- lumped strut-surface convection and thermal aggregates ---------------------------------------------
+ * Every end of strut b exchanges heat with an ambient at T_inf through the film conductance
+ *   c_b = k_b h_b pi r_b L_b   (half the lateral surface 2 pi r L of every copy times the film coefficient),  d c_b / d r_b = c_b / r_b,
+ *   h_b = beam_film ? beam_film[b] : film.  With H_i = sum over struts b at i of c_b the operator becomes K_T + diag(H) and the
+ * problem (K_T + H) T = q + H T_inf on the free nodes, T = T_bar on the masked ones.  The form is lumped: the operator stays
+ * an M-matrix.  With a positive c_b on every connected component no Dirichlet node is needed.
+ *   loss of one copy   Qc_b = c_b [(T_A - T_inf) + (T_B - T_inf)] / k_b,   dissipated power P = sum_b k_b Qc_b = sum_i H_i (T_i - T_inf)
+ * Under a convection state pl_cond_spmv, pl_cond_solve and pl_cond_sens act on the convective problem: the product gains H x,
+ * pl_cond_solve accepts a mask without a fixed node, and pl_cond_sens gains (c_b / r_b) [mu_A (T_A - T_inf) + mu_B (T_B - T_inf)].
+ *
+ * pl_set_convection needs a conduction state (PL_ERR_STATE) and lives in it: pl_set_conduction - setting, replacing or clearing -
+ * drops it.  film == 0 and beam_film == NULL clears it.  PL_ERR_ARG: a negative or non-finite film, a non-finite T_inf, every
+ * film zero.  The state survives pl_update_radii / pl_update_segments / pl_assemble; handle restrictions as pl_set_conduction. */
+int pl_set_convection(pl_handle h, double film, const double *beam_film /*[B] or NULL*/, double T_inf);
+/* The adjoint problem of a functional J(T): (K_T + H) mu = rhs on the free nodes, mu = 0 on the fixed ones - pl_cond_solve without
+ * T_bar and without the ambient term H T_inf (without a convection state it equals pl_cond_solve(h, fixed, NULL, rhs, ...)). */
+int pl_cond_solve_adjoint(pl_handle h, const uint8_t *fixed /*[N]*/, const double *rhs /*[N]*/, double rtol, int32_t max_iter,
+                          double *mu /*[N]*/, pl_stats_t *stats);
+/* Qc[b] above and total[0] = P, folded in two stages of a fixed order (equal inputs give equal bits).  Either may be NULL, not
+ * both.  PL_ERR_STATE without a convection state. */
+int pl_cond_film(pl_handle h, const double *T /*[N]*/, double *Qc /*[B] or NULL*/, double *total /*[1] or NULL*/);
+/* Phi_p = (sum over the nodes of the set of max(T_i - T_ref, 0)^p)^(1/p), evaluated as v_max (sum (v / v_max)^p)^(1/p) in the
+ * fixed-order stages of pl_stress_pnorm.  nodes: one byte per node, NULL = all; a NaN in T adds nothing.
+ * out = (Phi_p, v_max, sum (v / v_max)^p), dphi_dT[i] = (v_i / v_max)^(p-1) (sum)^(1/p - 1) where v_i > 0, else 0.  Either
+ * output may be NULL, not both.  p < 1 or non-finite: PL_ERR_ARG.  Needs an assembled single-GPU FEM handle, no conduction state. */
+int pl_temp_pnorm(pl_handle h, const double *T /*[N]*/, const uint8_t *nodes /*[N] or NULL*/, double T_ref, double p,
+                  double *out /*[3] or NULL*/, double *dphi_dT /*[N] or NULL*/);
+
 /* Strain energy 1/2 u^T K u (LatticeOpti.compute_compliance, lattice_opti.py:645-663 uses u^T K u). */
 int pl_energy(pl_handle h, const double *u, double *energy);
 

@@ -25,6 +25,7 @@ EXPORTS = ["pl_default_opts", "pl_opts_size", "pl_stats_size", "pl_abi_version",
            "pl_stress", "pl_stress_pnorm", "pl_buckling", "pl_buckling_pnorm",
            "pl_set_thermal", "pl_thermal_load", "pl_thermal_sens",
            "pl_set_conduction", "pl_cond_spmv", "pl_cond_solve", "pl_cond_flux", "pl_cond_sens", "pl_thermal_load_adjoint",
+           "pl_set_convection", "pl_cond_solve_adjoint", "pl_cond_film", "pl_temp_pnorm",
            "pl_spmv_multi", "pl_solve_multi", "pl_schur_block", "pl_geom_spmv_multi", "pl_buckling_modes", "pl_buckling_modes_sens",
            "pl_set_mass", "pl_mass_spmv_multi", "pl_vibration_modes", "pl_vibration_modes_sens",
            "pl_dyn_spmv_multi", "pl_transient", "pl_transient_sens", "pl_harm_spmv", "pl_harmonic", "pl_harmonic_sens",
@@ -101,6 +102,7 @@ def load_library(path: str | None = None):
            "pl_set_thermal": [V, D, V, V], "pl_thermal_load": [V, V, V], "pl_thermal_sens": [V, V, V],
            "pl_set_conduction": [V, D, V], "pl_cond_spmv": [V, I32, V, V, V], "pl_cond_solve": [V, V, V, V, D, I32, V, V],
            "pl_cond_flux": [V, V, V], "pl_cond_sens": [V, V, V, V], "pl_thermal_load_adjoint": [V, V, V],
+           "pl_set_convection": [V, D, V, D], "pl_cond_solve_adjoint": [V, V, V, D, I32, V, V], "pl_cond_film": [V, V, V, V], "pl_temp_pnorm": [V, V, V, D, D, V, V],
            "pl_schur": [V, V, I32, D, I32, V], "pl_spmv_multi": [V, I32, I32, V, V],
            "pl_solve_multi": [V, I32, V, V, D, I32, V, V], "pl_schur_block": [V, V, I32, D, I32, I32, V],
            "pl_geom_spmv_multi": [V, V, I32, I32, V, V],
@@ -450,6 +452,7 @@ class HipLattice:
         self._mult = None
         self._thermal = None
         self._conduction = None
+        self._convection = None
         self._assembled = False
         if beam_mult is not None:
             self.set_multiplicity(beam_mult)
@@ -823,11 +826,27 @@ class HipLattice:
         bk = None if beam_kappa is None else _f64(np.asarray(beam_kappa).reshape(-1), self.n_beams)
         _check(self._lib, self._lib.pl_set_conduction(self._h, float(kappa), _ptr(bk)))
         self._conduction = bk if bk is not None else float(kappa)
+        self._convection = None      # (the convection state lives in the conduction state)
 
     def clear_conduction(self):
         """Removes the conduction state (pl_set_conduction with kappa = 0 and no beam_kappa)."""
         _check(self._lib, self._lib.pl_set_conduction(self._h, 0.0, None))
         self._conduction = None
+        self._convection = None
+
+    def set_convection(self, film, ambient, beam_film=None):
+        """Convection state of the handle (pl_set_convection): film coefficient ``film`` of every strut, or beam_film (B,) per
+        strut, to an ambient at ``ambient``; each strut end exchanges through c = k h pi r L.  Needs a conduction state and is
+        dropped with it (set_conduction included); it survives update_radii / update_segments / assemble.  cond_spmv,
+        cond_solve and cond_sens then act on the convective problem."""
+        bf = None if beam_film is None else _f64(np.asarray(beam_film).reshape(-1), self.n_beams)
+        _check(self._lib, self._lib.pl_set_convection(self._h, float(film), _ptr(bf), float(ambient)))
+        self._convection = (bf if bf is not None else float(film), float(ambient))
+
+    def clear_convection(self):
+        """Removes the convection state (pl_set_convection with film = 0 and no beam_film)."""
+        _check(self._lib, self._lib.pl_set_convection(self._h, 0.0, None, 0.0))
+        self._convection = None
 
     def _mask_n(self, fixed):
         fx = np.ascontiguousarray(np.asarray(fixed).reshape(-1) != 0, dtype=np.uint8)
@@ -843,16 +862,23 @@ class HipLattice:
         _check(self._lib, self._lib.pl_cond_spmv(self._h, int(fx is not None), _ptr(fx), _ptr(x), _ptr(y)))
         return y
 
-    def cond_solve(self, fixed, t_bar=None, q=None, rtol=1e-10, max_iter=200000, raise_on_noconv=True):
+    def cond_solve(self, fixed, t_bar=None, q=None, rtol=1e-10, max_iter=200000, raise_on_noconv=True, adjoint=False):
         """(T (N,), stats) of K_T T = q on the free nodes, T = t_bar on the nodes of ``fixed`` (pl_cond_solve): a Jacobi PCG
-        from zero on the device.  t_bar None = 0, q None = no inflow.  The handle's mechanical state is not touched."""
+        from zero on the device.  t_bar None = 0, q None = no inflow.  The handle's mechanical state is not touched.  Under a
+        convection state: (K_T + H) T = q + H T_inf, and a mask that fixes no node is valid.  adjoint = True
+        (pl_cond_solve_adjoint): (K_T + H) mu = q with mu = 0 on the fixed nodes, no ambient term."""
         fx = self._mask_n(fixed)
         tb = None if t_bar is None else _f64(np.broadcast_to(np.asarray(t_bar, dtype=float).reshape(-1), (self.n_nodes,)))
         qq = None if q is None else _f64(np.asarray(q).reshape(-1), self.n_nodes)
         T = np.empty(self.n_nodes, np.float64)
         st = PlStats()
         st.struct_size = C.sizeof(PlStats)
-        rc = self._lib.pl_cond_solve(self._h, _ptr(fx), _ptr(tb), _ptr(qq), float(rtol), int(max_iter), _ptr(T), C.byref(st))
+        if adjoint:
+            if qq is None or tb is not None:
+                raise ValueError("cond_solve(adjoint=True) takes a right-hand side q and no t_bar")
+            rc = self._lib.pl_cond_solve_adjoint(self._h, _ptr(fx), _ptr(qq), float(rtol), int(max_iter), _ptr(T), C.byref(st))
+        else:
+            rc = self._lib.pl_cond_solve(self._h, _ptr(fx), _ptr(tb), _ptr(qq), float(rtol), int(max_iter), _ptr(T), C.byref(st))
         keys = [n for n, _ in PlStats._fields_ if n not in ("reserved", "reserved_i", "struct_size")]
         stats = {n: getattr(st, n) for n in keys}
         if rc in (PL_OK, PL_ERR_NOCONV):
@@ -867,13 +893,45 @@ class HipLattice:
         _check(self._lib, self._lib.pl_cond_flux(self._h, _ptr(T), _ptr(Q)))
         return Q
 
-    def cond_sens(self, T, mu):
-        """(B,) mu^T (dK_T / dr_b) T = (2 g / r)(mu_A - mu_B)(T_A - T_B) (pl_cond_sens)."""
+    def cond_sens(self, T, mu, convective=True):
+        """(B,) mu^T (dK_T / dr_b) T = (2 g / r)(mu_A - mu_B)(T_A - T_B) (pl_cond_sens); under a convection state plus
+        (c / r)[mu_A (T_A - T_inf) + mu_B (T_B - T_inf)].  convective = False leaves that bracket out (the convection state
+        is lifted for the call): the switch of the tests that show what the term is worth."""
         T = _f64(np.asarray(T).reshape(-1), self.n_nodes)
         mu = _f64(np.asarray(mu).reshape(-1), self.n_nodes)
         out = np.empty(self.n_beams, np.float64)
-        _check(self._lib, self._lib.pl_cond_sens(self._h, _ptr(T), _ptr(mu), _ptr(out)))
+        cv = self._convection if not convective else None
+        if cv is not None:
+            self.clear_convection()
+        try:
+            _check(self._lib, self._lib.pl_cond_sens(self._h, _ptr(T), _ptr(mu), _ptr(out)))
+        finally:
+            if cv is not None:
+                self.set_convection(0.0 if isinstance(cv[0], np.ndarray) else cv[0], cv[1],
+                                    cv[0] if isinstance(cv[0], np.ndarray) else None)
         return out
+
+    def cond_film(self, T, total=False):
+        """(B,) convective loss Qc_b = c [(T_A - T_inf) + (T_B - T_inf)] / k of one copy of every strut (pl_cond_film);
+        total = True: (Qc, P) with the dissipated power P = sum k Qc folded on the device in a fixed order."""
+        T = _f64(np.asarray(T).reshape(-1), self.n_nodes)
+        Qc = np.empty(self.n_beams, np.float64)
+        P = np.zeros(1, np.float64)
+        _check(self._lib, self._lib.pl_cond_film(self._h, _ptr(T), _ptr(Qc), _ptr(P) if total else None))
+        return (Qc, float(P[0])) if total else Qc
+
+    def temp_pnorm(self, T, p=8.0, reference=0.0, nodes=None, gradient=False):
+        """{"phi", "max", "sum"} of the temperature p-norm (sum over the nodes of ``nodes`` (N,) flags, None = all, of
+        max(T - reference, 0)^p)^(1/p) (pl_temp_pnorm); gradient = True adds "dphi_dT" (N,)."""
+        T = _f64(np.asarray(T).reshape(-1), self.n_nodes)
+        nd = None if nodes is None else self._mask_n(nodes)
+        out = np.zeros(3, np.float64)
+        g = np.empty(self.n_nodes, np.float64) if gradient else None
+        _check(self._lib, self._lib.pl_temp_pnorm(self._h, _ptr(T), _ptr(nd), float(reference), float(p), _ptr(out), _ptr(g)))
+        res = {"phi": float(out[0]), "max": float(out[1]), "sum": float(out[2])}
+        if gradient:
+            res["dphi_dT"] = g
+        return res
 
     def thermal_load_adjoint(self, lam):
         """(N,) c = (d f_th / d dT)^T lam of the thermal state's expansion coefficients (pl_thermal_load_adjoint)."""
@@ -888,16 +946,30 @@ class HipLattice:
             raise RuntimeError("call set_conduction first")
         return CH.conductance(self.node_xyz, self.beam_conn, self._radius, self._conduction, self._mult)
 
+    def _c_host(self):
+        """(c (B,), T_inf) of the convection state, (None, 0.0) without one."""
+        from . import conduction_host as CH
+        cv = getattr(self, "_convection", None)
+        if cv is None:
+            return None, 0.0
+        return CH.film_conductance(self.node_xyz, self.beam_conn, self._radius, cv[0], self._mult), cv[1]
+
+    def _H_host(self):
+        from . import conduction_host as CH
+        c, t_inf = self._c_host()
+        return (None if c is None else CH.convection_diag(self.beam_conn, self.n_nodes, c)), t_inf
+
     def cond_spmv_host(self, x, fixed=None):
         """The numpy restatement of ``cond_spmv`` (conduction_host.spmv)."""
         from . import conduction_host as CH
-        return CH.spmv(self.beam_conn, self.n_nodes, self._g_host(), x, fixed)
+        return CH.spmv(self.beam_conn, self.n_nodes, self._g_host(), x, fixed, self._H_host()[0])
 
-    def cond_solve_host(self, fixed, t_bar=None, q=None):
+    def cond_solve_host(self, fixed, t_bar=None, q=None, adjoint=False):
         """The dense host solve of the problem of ``cond_solve`` (conduction_host.solve)."""
         from . import conduction_host as CH
         qq = None if q is None else np.where(np.asarray(fixed).reshape(-1) != 0, 0.0, np.asarray(q, dtype=float).reshape(-1))
-        return CH.solve(self.beam_conn, self.n_nodes, self._g_host(), fixed, t_bar, qq)
+        H, t_inf = self._H_host()
+        return CH.solve(self.beam_conn, self.n_nodes, self._g_host(), fixed, t_bar, qq, H, 0.0 if adjoint else t_inf)
 
     def cond_flux_host(self, T):
         """The numpy restatement of ``cond_flux`` (conduction_host.flux)."""
@@ -907,7 +979,27 @@ class HipLattice:
     def cond_sens_host(self, T, mu):
         """The numpy restatement of ``cond_sens`` (conduction_host.cond_sens)."""
         from . import conduction_host as CH
-        return CH.cond_sens(self.beam_conn, self._radius, self._g_host(), T, mu)
+        c, t_inf = self._c_host()
+        return CH.cond_sens(self.beam_conn, self._radius, self._g_host(), T, mu, c, t_inf)
+
+    def cond_film_host(self, T, total=False):
+        """The numpy restatement of ``cond_film`` (conduction_host.film_loss)."""
+        from . import conduction_host as CH
+        c, t_inf = self._c_host()
+        if c is None:
+            raise RuntimeError("cond_film_host: call set_convection first")
+        Qc = CH.film_loss(self.beam_conn, c, T, t_inf, self._mult)
+        k = 1.0 if self._mult is None else np.asarray(self._mult, dtype=float)
+        return (Qc, float((k * Qc).sum())) if total else Qc
+
+    def temp_pnorm_host(self, T, p=8.0, reference=0.0, nodes=None, gradient=False):
+        """The numpy restatement of ``temp_pnorm`` (conduction_host.temp_pnorm)."""
+        from . import conduction_host as CH
+        phi, vmax, ssum, g = CH.temp_pnorm(T, p, reference, nodes)
+        res = {"phi": phi, "max": vmax, "sum": ssum}
+        if gradient:
+            res["dphi_dT"] = g
+        return res
 
     def thermal_load_adjoint_host(self, lam):
         """The numpy restatement of ``thermal_load_adjoint`` (conduction_host.thermal_load_adjoint)."""

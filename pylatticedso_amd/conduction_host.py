@@ -14,6 +14,19 @@ penalised end zones and the overlap at the joints are ignored, a multiplicity k 
 With dT = T - T_ref as the node_dT of the thermal loads, the transpose of d f_th / d dT applied to a mechanical field lam is
 c_i = sum over struts b at i of (1/2) alpha_b L_b ka_b t_b . (lam_u,B - lam_u,A); with K_T mu = c on the free thermal nodes
 (mu = 0 on the others) every q(u(T(r), r), r) with K lam = dq/du gains dq/dr_b += -(2 g_b / r_b) (mu_A - mu_B) (T_A - T_B).
+
+Lumped strut-surface convection (pl_set_convection / pl_cond_film / pl_temp_pnorm): every strut end
+exchanges with an ambient at T_inf through the film conductance
+
+    c_b = k_b h_b pi r_b L_b,   d c_b / d r_b = c_b / r_b,   H_i = sum over struts b at i of c_b
+    (K_T + diag H) T = q + H T_inf on the free nodes, T = T_bar on the fixed ones
+    Qc_b = c_b [(T_A - T_inf) + (T_B - T_inf)] / k_b,   P = sum_b k_b Qc_b = sum_i H_i (T_i - T_inf)
+
+and for J(T(r), r) with (K_T + H) mu = dJ/dT on the free nodes, mu = 0 on the fixed ones,
+
+    dJ/dr_b = dJ/dr_b at fixed T - (2 g_b / r_b)(mu_A - mu_B)(T_A - T_B) - (c_b / r_b)[mu_A (T_A - T_inf) + mu_B (T_B - T_inf)].
+
+Every function takes the convection through optional arguments (H, c, t_inf) that default to none.
 """
 from __future__ import annotations
 
@@ -50,8 +63,26 @@ def laplacian(beam_conn, node_count, g):
     return K
 
 
-def spmv(beam_conn, node_count, g, x, fixed=None):
-    """K_T x per strut, fixed not None: P K_T P x (what pl_cond_spmv returns)."""
+def film_conductance(node_xyz, beam_conn, radius, film, mult=None):
+    """(B,) c_b = k h pi r L, the film conductance of one strut end; film a scalar or (B,)."""
+    conn = np.asarray(beam_conn).reshape(-1, 2)
+    r = np.asarray(radius, dtype=float).reshape(-1)
+    k = 1.0 if mult is None else np.asarray(mult, dtype=float)
+    return k * np.asarray(film, dtype=float) * (np.pi * r) * _length(node_xyz, conn)
+
+
+def convection_diag(beam_conn, node_count, c):
+    """(N,) H_i = sum over the struts at node i of c_b."""
+    conn = np.asarray(beam_conn).reshape(-1, 2)
+    c = np.broadcast_to(np.asarray(c, dtype=float), (len(conn),))
+    H = np.zeros(node_count)
+    np.add.at(H, conn[:, 0], c)
+    np.add.at(H, conn[:, 1], c)
+    return H
+
+
+def spmv(beam_conn, node_count, g, x, fixed=None, H=None):
+    """K_T x per strut, fixed not None: P K_T P x (what pl_cond_spmv returns).  H (N,) given: K_T + diag(H)."""
     conn = np.asarray(beam_conn).reshape(-1, 2)
     x = np.asarray(x, dtype=float).reshape(-1)
     if fixed is not None:
@@ -60,22 +91,29 @@ def spmv(beam_conn, node_count, g, x, fixed=None):
     y = np.zeros(node_count)
     np.add.at(y, conn[:, 0], flow)
     np.add.at(y, conn[:, 1], -flow)
+    if H is not None:
+        y = y + np.asarray(H, dtype=float) * x
     return y if fixed is None else np.where(np.asarray(fixed).astype(bool), 0.0, y)
 
 
-def solve(beam_conn, node_count, g, fixed, t_bar=None, q=None):
-    """(N,) T of K_T T = q on the free nodes, T = t_bar on the fixed ones: a dense solve."""
+def solve(beam_conn, node_count, g, fixed, t_bar=None, q=None, H=None, t_inf=0.0):
+    """(N,) T of K_T T = q on the free nodes, T = t_bar on the fixed ones: a dense solve.  H (N,) given: the convective
+    problem (K_T + diag H) T = q + H t_inf, for which a mask that fixes no node is valid."""
     import scipy.linalg
     fixed = np.asarray(fixed).astype(bool).reshape(-1)
-    if not fixed.any():
+    if not fixed.any() and H is None:
         raise ValueError("conduction_host.solve: the mask fixes no node")
     K = laplacian(beam_conn, node_count, g)
+    if H is not None:
+        K = K + np.diag(np.asarray(H, dtype=float))
     T = np.zeros(node_count)
     if t_bar is not None:
         T[fixed] = np.broadcast_to(np.asarray(t_bar, dtype=float), (node_count,))[fixed]
     rhs = -K @ T
     if q is not None:
         rhs = rhs + np.asarray(q, dtype=float).reshape(-1)
+    if H is not None:
+        rhs = rhs + np.asarray(H, dtype=float) * t_inf
     free = np.flatnonzero(~fixed)
     if len(free):
         T[free] = scipy.linalg.solve(K[np.ix_(free, free)], rhs[free], assume_a="pos")
@@ -90,13 +128,78 @@ def flux(beam_conn, g, T, mult=None):
     return np.asarray(g, dtype=float) * (T[conn[:, 0]] - T[conn[:, 1]]) / k
 
 
-def cond_sens(beam_conn, radius, g, T, mu):
-    """(B,) mu^T (dK_T / dr_b) T = (2 g / r) (mu_A - mu_B) (T_A - T_B) - the output of pl_cond_sens."""
+def cond_sens(beam_conn, radius, g, T, mu, c=None, t_inf=0.0):
+    """(B,) mu^T (dK_T / dr_b) T = (2 g / r) (mu_A - mu_B) (T_A - T_B) - the output of pl_cond_sens.  c (B,) given: plus the
+    convective bracket (c / r) [mu_A (T_A - t_inf) + mu_B (T_B - t_inf)]."""
     conn = np.asarray(beam_conn).reshape(-1, 2)
     T = np.asarray(T, dtype=float).reshape(-1)
     mu = np.asarray(mu, dtype=float).reshape(-1)
-    return (2.0 * np.asarray(g, dtype=float) / np.asarray(radius, dtype=float) *
-            (mu[conn[:, 0]] - mu[conn[:, 1]]) * (T[conn[:, 0]] - T[conn[:, 1]]))
+    r = np.asarray(radius, dtype=float)
+    a, b = conn[:, 0], conn[:, 1]
+    out = 2.0 * np.asarray(g, dtype=float) / r * (mu[a] - mu[b]) * (T[a] - T[b])
+    if c is not None:
+        out = out + np.asarray(c, dtype=float) / r * (mu[a] * (T[a] - t_inf) + mu[b] * (T[b] - t_inf))
+    return out
+
+
+def film_loss(beam_conn, c, T, t_inf, mult=None):
+    """(B,) Qc_b = c [(T_A - t_inf) + (T_B - t_inf)] / k, the convective loss of one copy of every strut - the output of
+    pl_cond_film; the dissipated power is P = sum k Qc."""
+    conn = np.asarray(beam_conn).reshape(-1, 2)
+    T = np.asarray(T, dtype=float).reshape(-1)
+    k = 1.0 if mult is None else np.asarray(mult, dtype=float)
+    return np.asarray(c, dtype=float) * ((T[conn[:, 0]] - t_inf) + (T[conn[:, 1]] - t_inf)) / k
+
+
+def temp_pnorm(T, p, reference=0.0, nodes=None):
+    """(Phi_p, v_max, sum (v / v_max)^p, dPhi/dT (N,)) of v = max(T - reference, 0) over the nodes of ``nodes`` (flags, None =
+    all), evaluated as v_max (sum (v / v_max)^p)^(1/p) - the outputs of pl_temp_pnorm.  A NaN adds nothing."""
+    T = np.asarray(T, dtype=float).reshape(-1)
+    with np.errstate(invalid="ignore"):
+        v = np.where(T - reference > 0.0, T - reference, 0.0)
+    if nodes is not None:
+        v = np.where(np.asarray(nodes).reshape(-1) != 0, v, 0.0)
+    vmax = float(v.max()) if v.size else 0.0
+    if not vmax > 0.0:
+        return 0.0, 0.0, 0.0, np.zeros_like(v)
+    ratio = v / vmax
+    ssum = float((ratio[v > 0.0] ** p).sum())
+    grad = np.where(v > 0.0, ratio ** (p - 1.0), 0.0) * ssum ** (1.0 / p - 1.0)
+    return vmax * ssum ** (1.0 / p), vmax, ssum, grad
+
+
+def thermal_gradient(functional, node_xyz, beam_conn, radius, kappa, fixed, t_bar=None, q=None, film=None, t_inf=0.0,
+                     mult=None, p=8.0, reference=None, nodes=None, convective_bracket=True):
+    """(J, dJ/dr (B,)) of a thermal functional of the conduction problem with lumped convection, the adjoint chain on dense
+    matrices.  functional: "thermal_compliance" J = q . (T - t_inf) over the free nodes; "heat_dissipation" J = P;
+    "temp_pnorm" J = Phi_p of T - reference (default t_inf) over ``nodes`` (default the free nodes).  film None: no convection
+    (heat_dissipation is then undefined).  convective_bracket = False leaves the (c / r) [...] term of the chain out - the
+    gradient that is wrong."""
+    conn = np.asarray(beam_conn).reshape(-1, 2)
+    r = np.asarray(radius, dtype=float).reshape(-1)
+    N = len(np.asarray(node_xyz).reshape(-1, 3))
+    fx = np.asarray(fixed).astype(bool).reshape(-1)
+    g = conductance(node_xyz, conn, r, kappa, mult)
+    c = None if film is None else film_conductance(node_xyz, conn, r, film, mult)
+    H = None if c is None else convection_diag(conn, N, c)
+    qq = np.zeros(N) if q is None else np.where(fx, 0.0, np.asarray(q, dtype=float).reshape(-1))
+    T = solve(conn, N, g, fx, t_bar, qq, H, t_inf)
+    partial = np.zeros(len(conn))
+    if functional == "thermal_compliance":
+        J, dJdT = float(qq @ (T - t_inf)), qq
+    elif functional == "heat_dissipation":
+        if c is None:
+            raise ValueError("heat_dissipation needs convection")
+        k = 1.0 if mult is None else np.asarray(mult, dtype=float)
+        kQc = k * film_loss(conn, c, T, t_inf, mult)
+        J, dJdT, partial = float(kQc.sum()), H, kQc / r
+    elif functional == "temp_pnorm":
+        J, _, _, dJdT = temp_pnorm(T, p, t_inf if reference is None else reference, ~fx if nodes is None else nodes)
+    else:
+        raise ValueError(f"unknown functional {functional!r}")
+    mu = solve(conn, N, g, fx, None, np.where(fx, 0.0, dJdT), H, 0.0)
+    grad = partial - cond_sens(conn, r, g, T, mu, c if convective_bracket else None, t_inf)
+    return J, grad
 
 
 def thermal_load_adjoint(rec, beam_conn, node_count, alpha, lam):
@@ -114,7 +217,7 @@ def thermal_load_adjoint(rec, beam_conn, node_count, alpha, lam):
 
 
 def coupled_state(node_xyz, beam_conn, radius, seg_len, seg_nsub, material, mult, fixed_dof, f_ext, alpha, kappa, t_fixed,
-                  t_bar, heat_in, reference=0.0):
+                  t_bar, heat_in, reference=0.0, film=None, t_inf=0.0):
     """The thermo-elastic equilibrium on dense matrices: T of the conduction problem, f_th of T - reference, and u (N, 6) of
     K u = f_ext + f_th on the free dofs (zero on the fixed ones).  material = (E, nu, kappa_shear, pen).  Returns a dict."""
     import scipy.linalg
@@ -123,7 +226,9 @@ def coupled_state(node_xyz, beam_conn, radius, seg_len, seg_nsub, material, mult
     N = len(np.asarray(node_xyz).reshape(-1, 3))
     rec = SH.records(node_xyz, conn, radius, seg_len, seg_nsub, *material, mult)
     g = conductance(node_xyz, conn, radius, kappa, mult)
-    T = solve(conn, N, g, t_fixed, t_bar, heat_in)
+    c = None if film is None else film_conductance(node_xyz, conn, radius, film, mult)
+    H = None if c is None else convection_diag(conn, N, c)
+    T = solve(conn, N, g, t_fixed, t_bar, heat_in, H, t_inf)
     delta = TH.elongation(node_xyz, conn, alpha, T - reference)
     f_th = TH.thermal_load(rec, conn, N, delta, mult)[0]
     K = GH.elastic_matrix(rec, conn, N)
@@ -132,11 +237,11 @@ def coupled_state(node_xyz, beam_conn, radius, seg_len, seg_nsub, material, mult
     Kff = K[np.ix_(free, free)]
     u = np.zeros(6 * N)
     u[free] = scipy.linalg.solve(Kff, (np.asarray(f_ext, dtype=float) + f_th).ravel()[free], assume_a="pos")
-    return {"rec": rec, "g": g, "T": T, "delta": delta, "f_th": f_th, "u": u.reshape(N, 6), "K": K, "free": free}
+    return {"rec": rec, "g": g, "c": c, "H": H, "T": T, "delta": delta, "f_th": f_th, "u": u.reshape(N, 6), "K": K, "free": free}
 
 
 def coupled_gradient(node_xyz, beam_conn, radius, seg_len, seg_nsub, material, mult, fixed_dof, f_ext, q, alpha, kappa,
-                     t_fixed, t_bar, heat_in, reference=0.0, chain=True):
+                     t_fixed, t_bar, heat_in, reference=0.0, chain=True, film=None, t_inf=0.0):
     """(B,) d(q . u)/dr_b of the thermo-elastic equilibrium of coupled_state at fixed segment geometry - the whole chain on
     dense matrices: -lam^T (dK/dr) u + lam^T d f_th/dr at fixed T, and (chain) -(2 g / r)(mu_A - mu_B)(T_A - T_B) with
     K lam = q on the free dofs, c = thermal_load_adjoint(lam), K_T mu = c on the free thermal nodes.  t_bar and heat_in do not
@@ -145,7 +250,7 @@ def coupled_gradient(node_xyz, beam_conn, radius, seg_len, seg_nsub, material, m
     from . import geometric_host as GH
     conn = np.asarray(beam_conn).reshape(-1, 2)
     st = coupled_state(node_xyz, conn, radius, seg_len, seg_nsub, material, mult, fixed_dof, f_ext, alpha, kappa, t_fixed,
-                       t_bar, heat_in, reference)
+                       t_bar, heat_in, reference, film, t_inf)
     N = len(st["T"])
     free = st["free"]
     lam = np.zeros(6 * N)
@@ -156,6 +261,6 @@ def coupled_gradient(node_xyz, beam_conn, radius, seg_len, seg_nsub, material, m
     if chain:
         c = thermal_load_adjoint(st["rec"], conn, N, alpha, lam)
         tf = np.asarray(t_fixed).astype(bool).reshape(-1)
-        mu = solve(conn, N, st["g"], tf, None, np.where(tf, 0.0, c))
-        grad = grad - cond_sens(conn, radius, st["g"], st["T"], mu)
+        mu = solve(conn, N, st["g"], tf, None, np.where(tf, 0.0, c), st["H"], 0.0)
+        grad = grad - cond_sens(conn, radius, st["g"], st["T"], mu, st["c"], t_inf)
     return grad

@@ -2281,13 +2281,62 @@ int cond_begin(pl_handle h, const char *who, CondWs **w) {
   PL_HIP(hipSetDevice(h->opt.device));
   *w = static_cast<CondWs *>(h->cond_ws.get());
   EventTimer timer(who, h->stream, "kernel_hip_event");
-  hipLaunchKernelGGL(pl::k_cond_strut, dim3(grid_for(h->B)), dim3(pl::kBlock), 0, h->stream, h->B, (const pl::Record *)h->rec.p,
-                     (const double *)h->radius.p, (const double *)h->mult.p, (const double *)(*w)->kappa.p, (*w)->g.p);
+  if ((*w)->conv) {   // the film conductances and their nodal sums follow the radii in the same pass
+    hipLaunchKernelGGL(pl::k_cond_strut<true>, dim3(grid_for(h->B)), dim3(pl::kBlock), 0, h->stream, h->B,
+                       (const pl::Record *)h->rec.p, (const double *)h->radius.p, (const double *)h->mult.p,
+                       (const double *)(*w)->kappa.p, (*w)->g.p, (const double *)(*w)->film.p, (*w)->c.p);
+    hipLaunchKernelGGL(pl::k_cond_hdiag, dim3(grid_for(h->N)), dim3(pl::kBlock), 0, h->stream, h->N, pl::kWave / h->lpn,
+                       (const int64_t *)h->slice_ptr.p, (const int2 *)h->ent.p, (const double *)(*w)->c.p, (*w)->H.p);
+  } else {
+    hipLaunchKernelGGL(pl::k_cond_strut<false>, dim3(grid_for(h->B)), dim3(pl::kBlock), 0, h->stream, h->B,
+                       (const pl::Record *)h->rec.p, (const double *)h->radius.p, (const double *)h->mult.p,
+                       (const double *)(*w)->kappa.p, (*w)->g.p, (const double *)nullptr, (double *)nullptr);
+  }
   PL_HIP(hipGetLastError());
   timer.stop();
   return PL_OK;
 }
 }  // namespace
+
+int pl_set_convection(pl_handle h, double film, const double *beam_film, double T_inf) {
+  if (!valid(h)) return fail(PL_ERR_ARG, "pl_set_convection: null handle");
+  if (h->opkind != 0) return fail(PL_ERR_STATE, "pl_set_convection: not available on a DDM handle");
+  if (h->dist.active || h->opt.grid_nodes > 0)
+    return fail(PL_ERR_STATE, "pl_set_convection: single-GPU handles only (this one belongs to a multi-rank run)");
+  if (!h->cond_ws) return fail(PL_ERR_STATE, "pl_set_convection: call pl_set_conduction first");
+  CondWs *w = static_cast<CondWs *>(h->cond_ws.get());
+  if (film == 0.0 && !beam_film) {
+    w->conv = false;
+    return PL_OK;
+  }
+  if (!beam_film && !(film > 0.0 && std::isfinite(film)))
+    return fail(PL_ERR_ARG, "pl_set_convection: film must be positive and finite");
+  if (!std::isfinite(T_inf)) return fail(PL_ERR_ARG, "pl_set_convection: T_inf must be finite");
+  if (beam_film) {
+    bool any = false;
+    for (int64_t b = 0; b < h->B; ++b) {
+      if (!(beam_film[b] >= 0.0 && std::isfinite(beam_film[b])))
+        return fail(PL_ERR_ARG, "pl_set_convection: beam_film must be non-negative and finite");
+      any = any || beam_film[b] > 0.0;
+    }
+    if (!any) return fail(PL_ERR_ARG, "pl_set_convection: every film coefficient is zero");
+  }
+  PL_HIP(hipSetDevice(h->opt.device));
+  const size_t B = (size_t)h->B, N = (size_t)h->N;
+  if (!w->film.p) {
+    PL_HIP(w->film.alloc(B));
+    PL_HIP(w->c.alloc(B));
+    PL_HIP(w->H.alloc(N));
+    PL_HIP(w->part.alloc(std::max<size_t>(grid_for(h->B), 1)));
+    PL_HIP(w->total.alloc(1));
+  }
+  std::vector<double> hf(B);
+  for (size_t b = 0; b < B; ++b) hf[b] = beam_film ? beam_film[h->bperm[b]] : film;
+  PL_HIP(hipMemcpy(w->film.p, hf.data(), B * sizeof(double), hipMemcpyHostToDevice));
+  w->T_inf = T_inf;
+  w->conv = true;
+  return PL_OK;
+}
 
 int pl_cond_spmv(pl_handle h, int32_t masked, const uint8_t *fixed, const double *x, double *y) {
   if (valid(h) && (!x || !y || (masked && !fixed))) return fail(PL_ERR_ARG, "pl_cond_spmv: null argument");
@@ -2303,18 +2352,21 @@ int pl_cond_spmv(pl_handle h, int32_t masked, const uint8_t *fixed, const double
   return cond_download(h, w->AP.p, y);
 }
 
-int pl_cond_solve(pl_handle h, const uint8_t *fixed, const double *T_bar, const double *q, double rtol, int32_t max_iter,
-                  double *T, pl_stats_t *stats) {
-  if (valid(h) && (!fixed || !T)) return fail(PL_ERR_ARG, "pl_cond_solve: null argument");
-  if (valid(h) && (!(rtol > 0.0) || max_iter <= 0)) return fail(PL_ERR_ARG, "pl_cond_solve: rtol and max_iter must be positive");
+namespace {
+// pl_cond_solve and pl_cond_solve_adjoint (ambient = false: no H T_inf on the right-hand side, and T_bar is NULL)
+int cond_solve_call(pl_handle h, const std::string &who, const uint8_t *fixed, const double *T_bar, const double *q, double rtol,
+                    int32_t max_iter, double *T, pl_stats_t *stats, bool ambient) {
+  if (valid(h) && (!fixed || !T)) return fail(PL_ERR_ARG, who + ": null argument");
+  if (valid(h) && (!(rtol > 0.0) || max_iter <= 0)) return fail(PL_ERR_ARG, who + ": rtol and max_iter must be positive");
   if (valid(h) && stats && stats->struct_size != sizeof(pl_stats_t))
-    return fail(PL_ERR_ARG, "pl_cond_solve: stats->struct_size is " + std::to_string(stats->struct_size) +
+    return fail(PL_ERR_ARG, who + ": stats->struct_size is " + std::to_string(stats->struct_size) +
                                 ", this library's pl_stats_t has " + std::to_string(sizeof(pl_stats_t)) + " bytes");
   CondWs *w = nullptr;
-  if (int rc = cond_begin(h, "pl_cond_solve", &w)) return rc;
+  if (int rc = cond_begin(h, who.c_str(), &w)) return rc;
   bool any = false;
   for (int64_t i = 0; i < h->N && !any; ++i) any = fixed[i] != 0;
-  if (!any) return fail(PL_ERR_ARG, "pl_cond_solve: the mask fixes no node (K_T is singular without a prescribed temperature)");
+  if (!any && !w->conv)   // (with convection K_T + H is positive definite on its own)
+    return fail(PL_ERR_ARG, who + ": the mask fixes no node (K_T is singular without a prescribed temperature)");
   if (int rc = cond_upload_mask(h, fixed, w->fixed.p)) return rc;
   {   // T_bar on the fixed nodes only, zero on the free ones (the lifting K_T T_bar must not see free values)
     std::vector<double> tb((size_t)h->N, 0.0);
@@ -2326,9 +2378,10 @@ int pl_cond_solve(pl_handle h, const uint8_t *fixed, const double *T_bar, const 
   if (q)
     if (int rc = cond_upload(h, q, w->QF.p)) return rc;
   double status[pl::M_ST_COUNT] = {};
-  EventTimer timer("pl_cond_solve", h->stream, "kernel_hip_event");
+  EventTimer timer(who.c_str(), h->stream, "kernel_hip_event");
   PL_HIP(hipEventRecord(h->ev0, h->stream));
-  if (int rc = cond_pcg(h, w, q ? (const double *)w->QF.p : (const double *)nullptr, rtol, max_iter, w->T.p, status)) return rc;
+  if (int rc = cond_pcg(h, w, q ? (const double *)w->QF.p : (const double *)nullptr, rtol, max_iter, w->T.p, status, ambient))
+    return rc;
   PL_HIP(hipEventRecord(h->ev1, h->stream));
   PL_HIP(hipStreamSynchronize(h->stream));
   timer.stop();
@@ -2338,9 +2391,21 @@ int pl_cond_solve(pl_handle h, const uint8_t *fixed, const double *T_bar, const 
   MultiShape s{1, 1, 1, 1, h->N};
   bool bad = false;
   const int missed = multi_stats(s, status, rtol, ms, stats, &bad);
-  if (bad) return fail(PL_ERR_NAN, "pl_cond_solve: NaN/Inf in a residual norm");
-  if (missed) return fail(PL_ERR_NOCONV, "pl_cond_solve: rtol not reached within max_iter");
+  if (bad) return fail(PL_ERR_NAN, who + ": NaN/Inf in a residual norm");
+  if (missed) return fail(PL_ERR_NOCONV, who + ": rtol not reached within max_iter");
   return PL_OK;
+}
+}  // namespace
+
+int pl_cond_solve(pl_handle h, const uint8_t *fixed, const double *T_bar, const double *q, double rtol, int32_t max_iter,
+                  double *T, pl_stats_t *stats) {
+  return cond_solve_call(h, "pl_cond_solve", fixed, T_bar, q, rtol, max_iter, T, stats, true);
+}
+
+int pl_cond_solve_adjoint(pl_handle h, const uint8_t *fixed, const double *rhs, double rtol, int32_t max_iter, double *mu,
+                          pl_stats_t *stats) {
+  if (valid(h) && !rhs) return fail(PL_ERR_ARG, "pl_cond_solve_adjoint: null argument");
+  return cond_solve_call(h, "pl_cond_solve_adjoint", fixed, nullptr, rhs, rtol, max_iter, mu, stats, false);
 }
 
 int pl_cond_flux(pl_handle h, const double *T, double *Q) {
@@ -2363,12 +2428,92 @@ int pl_cond_sens(pl_handle h, const double *T, const double *mu, double *out) {
   if (int rc = cond_upload(h, T, w->T.p)) return rc;
   if (int rc = cond_upload(h, mu, w->MU.p)) return rc;
   EventTimer timer("pl_cond_sens", h->stream, "kernel_hip_event");
-  hipLaunchKernelGGL(pl::k_cond_sens, dim3(grid_for(h->B)), dim3(pl::kBlock), 0, h->stream, h->B, (const int32_t *)h->conn.p,
-                     (const double *)h->radius.p, (const double *)w->g.p, (const double *)w->T.p, (const double *)w->MU.p,
-                     w->out.p);
+  hipLaunchKernelGGL(w->conv ? pl::k_cond_sens<true> : pl::k_cond_sens<false>, dim3(grid_for(h->B)), dim3(pl::kBlock), 0,
+                     h->stream, h->B, (const int32_t *)h->conn.p, (const double *)h->radius.p, (const double *)w->g.p,
+                     (const double *)w->T.p, (const double *)w->MU.p, w->out.p,
+                     w->conv ? (const double *)w->c.p : (const double *)nullptr, w->T_inf);
   PL_HIP(hipGetLastError());
   timer.stop();
   return download_struts(h, w->out.p, out);
+}
+
+int pl_cond_film(pl_handle h, const double *T, double *Qc, double *total) {
+  if (valid(h) && (!T || (!Qc && !total))) return fail(PL_ERR_ARG, "pl_cond_film: null argument");
+  CondWs *w = nullptr;
+  if (int rc = cond_begin(h, "pl_cond_film", &w)) return rc;
+  if (!w->conv) return fail(PL_ERR_STATE, "pl_cond_film: call pl_set_convection first");
+  if (int rc = cond_upload(h, T, w->T.p)) return rc;
+  const unsigned grid = grid_for(h->B);
+  EventTimer timer("pl_cond_film", h->stream, "kernel_hip_event");
+  hipLaunchKernelGGL(pl::k_cond_film, dim3(grid), dim3(pl::kBlock), 0, h->stream, h->B, (const int32_t *)h->conn.p,
+                     (const double *)h->mult.p, (const double *)w->c.p, (const double *)w->T.p, w->T_inf,
+                     Qc ? w->out.p : (double *)nullptr, total ? w->part.p : (double *)nullptr);
+  if (total)
+    hipLaunchKernelGGL(pl::k_cond_film_fold, dim3(1), dim3(pl::kBlock), 0, h->stream, (int64_t)grid, (const double *)w->part.p,
+                       w->total.p);
+  PL_HIP(hipGetLastError());
+  timer.stop();
+  if (total) {
+    PL_HIP(hipMemcpyAsync(total, w->total.p, sizeof(double), hipMemcpyDeviceToHost, h->stream));
+    PL_HIP(hipStreamSynchronize(h->stream));
+  }
+  if (Qc) return download_struts(h, w->out.p, Qc);
+  return PL_OK;
+}
+
+namespace {
+// work arrays of pl_temp_pnorm (pl_context::temp_ws), allocated by the first call
+struct TempWs {
+  DevBuf<double> T, V, G, part, red;   // [N] [N] [N] [blocks] [4]
+  DevBuf<uint8_t> nodes;               // [N]
+};
+}  // namespace
+
+int pl_temp_pnorm(pl_handle h, const double *T, const uint8_t *nodes, double T_ref, double p, double *out, double *dphi_dT) {
+  if (!valid(h)) return fail(PL_ERR_ARG, "pl_temp_pnorm: null handle");
+  if (!T || (!out && !dphi_dT)) return fail(PL_ERR_ARG, "pl_temp_pnorm: null argument");
+  if (!(p >= 1.0) || !std::isfinite(p)) return fail(PL_ERR_ARG, "pl_temp_pnorm: p must be >= 1 and finite");
+  if (!std::isfinite(T_ref)) return fail(PL_ERR_ARG, "pl_temp_pnorm: T_ref must be finite");
+  if (h->opkind != 0) return fail(PL_ERR_STATE, "pl_temp_pnorm: not available on a DDM handle");
+  if (h->dist.active || h->opt.grid_nodes > 0)
+    return fail(PL_ERR_STATE, "pl_temp_pnorm: single-GPU handles only (this one belongs to a multi-rank run)");
+  if (!h->assembled) return fail(PL_ERR_STATE, "pl_temp_pnorm: call pl_assemble first");
+  PL_HIP(hipSetDevice(h->opt.device));
+  const int64_t N = h->N;
+  const unsigned grid = grid_for(N);
+  if (!h->temp_ws) {
+    auto t = std::make_shared<TempWs>();
+    for (DevBuf<double> *b : {&t->T, &t->V, &t->G}) PL_HIP(b->alloc((size_t)N));
+    PL_HIP(t->part.alloc(std::max<size_t>(grid, 1)));
+    PL_HIP(t->red.alloc(4));
+    PL_HIP(t->nodes.alloc((size_t)N));
+    h->temp_ws = t;
+  }
+  TempWs *t = static_cast<TempWs *>(h->temp_ws.get());
+  if (int rc = cond_upload(h, T, t->T.p)) return rc;
+  if (nodes)
+    if (int rc = cond_upload_mask(h, nodes, t->nodes.p)) return rc;
+  EventTimer timer("pl_temp_pnorm", h->stream, "kernel_hip_event");
+  hipLaunchKernelGGL(pl::k_temp_values, dim3(grid), dim3(pl::kBlock), 0, h->stream, N, (const double *)t->T.p,
+                     nodes ? (const uint8_t *)t->nodes.p : (const uint8_t *)nullptr, T_ref, t->V.p, t->part.p);
+  hipLaunchKernelGGL(pl::k_stress_fold<true>, dim3(1), dim3(pl::kBlock), 0, h->stream, (int64_t)grid, t->part.p, p, t->red.p);
+  hipLaunchKernelGGL((pl::k_pnorm_psum<1, false>), dim3(grid), dim3(pl::kBlock), 0, h->stream, N, t->V.p, t->red.p, p, t->part.p);
+  hipLaunchKernelGGL(pl::k_stress_fold<false>, dim3(1), dim3(pl::kBlock), 0, h->stream, (int64_t)grid, t->part.p, p, t->red.p);
+  if (dphi_dT)
+    hipLaunchKernelGGL(pl::k_temp_pnorm_grad, dim3(grid), dim3(pl::kBlock), 0, h->stream, N, (const double *)t->V.p,
+                       (const double *)t->red.p, p, t->G.p);
+  PL_HIP(hipGetLastError());
+  timer.stop();
+  if (out) {
+    double red[3] = {0, 0, 0};
+    PL_HIP(hipMemcpyAsync(red, t->red.p, sizeof(red), hipMemcpyDeviceToHost, h->stream));
+    PL_HIP(hipStreamSynchronize(h->stream));
+    out[0] = red[2];
+    out[1] = red[0];
+    out[2] = red[1];
+  }
+  if (dphi_dT) return cond_download(h, t->G.p, dphi_dT);
+  return PL_OK;
 }
 
 int pl_thermal_load_adjoint(pl_handle h, const double *lam, double *out) {

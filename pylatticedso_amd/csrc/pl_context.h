@@ -280,6 +280,7 @@ struct pl_context {
   std::shared_ptr<void> mass_ws;    // density, rotary flag, point masses and mass records (pl_mass.h), set by pl_set_mass
   std::shared_ptr<void> thermal_ws; // expansion coefficients, nodal temperatures and elongations (pl_thermal.h), set by pl_set_thermal
   std::shared_ptr<void> cond_ws;    // conductivities, conductances and the scalar PCG vectors (pl_conduction.h), set by pl_set_conduction
+  std::shared_ptr<void> temp_ws;    // work arrays of pl_temp_pnorm (pl_conduction.h), allocated by its first call
   std::shared_ptr<void> dyn_ws;     // state, loads and histories of pl_transient (pl_dyn.h), created by the first call
   std::shared_ptr<void> dyn_sens_ws;   // histories and adjoint state of pl_transient_sens (pl_dyn_sens.h), likewise
   std::shared_ptr<void> harm_ws;    // diagonals, coefficients, scalars and probes of pl_harmonic (pl_harm.h), likewise

@@ -81,7 +81,11 @@ _RESPONSE_CONSTRAINTS = (
                         f"the transient response of {_INTERIORS} is not implemented", "peak_displacement_aggregate", _over, "shared"),
     _ResponseConstraint("resonance_peak", "resonance_peak", "resonance_peak",
                         f"the frequency response of {_INTERIORS} is not implemented", "resonance_peak_aggregate", _over, "shared"),
+    _ResponseConstraint("max_temperature", "max_temperature", "max_temperature",
+                        "DDM handles carry no strut graph to conduct heat on", "max_temperature_aggregate", _over, "total"),
 )
+# objectives of the conduction problem alone: no mechanical equilibrium, no mechanical adjoint
+_THERMAL_OBJECTIVES = ("thermal_compliance", "heat_dissipation")
 
 
 class LatticeOpti(LatticeSim):
@@ -114,6 +118,9 @@ class LatticeOpti(LatticeSim):
         for c in _RESPONSE_CONSTRAINTS:
             if self._ddm_mode and c.key in (info.get("constraints") or {}):
                 raise NotImplementedError(f'the "{c.key}" constraint needs simulation_type "FEM": {c.reason}')
+        if self._ddm_mode and info.get("objective_type", None) in _THERMAL_OBJECTIVES:
+            raise NotImplementedError(f'the "{info["objective_type"]}" objective needs simulation_type "FEM": DDM handles carry no '
+                                      "strut graph to conduct heat on")
         comp = ((params.get("simulation_parameters", {}).get("DDM") or {}).get("schur_complement_computation") or {})
         if ddm_gradient is None:
             ddm_gradient = comp.get("gradient", "finite_difference") if self._ddm_mode else "finite_difference"
@@ -151,6 +158,12 @@ class LatticeOpti(LatticeSim):
                          "parameters": [], "timestamp": []}
         lat = self.lattice
         self._get_optimization_parameters(name_file)
+        if self.objective_type in _THERMAL_OBJECTIVES or "max_temperature" in self.constraints_dict:
+            if self.conduction is None:
+                raise ValueError('thermal objectives and the "max_temperature" constraint need a conduction problem '
+                                 '(simulation_parameters["thermal"]["conduction"])')
+            if self.objective_type == "heat_dissipation" and self.conduction.get("convection", None) is None:
+                raise ValueError('the "heat_dissipation" objective needs the "Convection" block of the conduction problem')
         for c in _RESPONSE_CONSTRAINTS:
             setattr(self, "_last_" + c.stem, None)
             if c.key in self.constraints_dict:
@@ -352,8 +365,36 @@ class LatticeOpti(LatticeSim):
             if xsol is None:
                 raise RuntimeError("solve_DDM: zero right-hand side")
         else:
-            _, self._model = solve_FEM_FenicsX(self)
+            if self._needs_mechanics:
+                _, self._model = solve_FEM_FenicsX(self)
+            if self._needs_temperature and not (self._needs_mechanics and self.conduction_driven):
+                # (under a conduction-driven temperature the mechanical solve has just solved the conduction problem)
+                dev = self.device_model()
+                self._assemble_for_conduction(dev)
+                self._solve_conduction(dev)
         self._sim_is_current = True
+
+    @property
+    def _needs_mechanics(self):
+        """False when neither the objective nor a constraint reads the displacements: only the conduction problem is solved."""
+        return (self.objective_type not in _THERMAL_OBJECTIVES or
+                any(c.key in self.constraints_dict for c in _RESPONSE_CONSTRAINTS if c.key != "max_temperature"))
+
+    @property
+    def _needs_temperature(self):
+        return self.objective_type in _THERMAL_OBJECTIVES or "max_temperature" in self.constraints_dict
+
+    def _ambient(self):
+        cv = self.conduction.get("convection", None)
+        return self.conduction["reference"] if cv is None else cv["ambient"]
+
+    def _thermal_adjoint_sens(self, dJ_dT):
+        """mu^T d[(K_T + H) T - H T_inf]/dr_b with (K_T + H) mu = dJ/dT on the free thermal nodes, mu = 0 on the others
+        (pl_cond_solve_adjoint, pl_cond_sens): what every functional of the temperature subtracts from its partial derivative."""
+        dev = self.device_model()
+        fixed = self.conduction["fixed"]
+        mu, _ = dev.cond_solve(fixed, None, np.where(fixed, 0.0, dJ_dT), rtol=1e-10, max_iter=200000, adjoint=True)
+        return dev.cond_sens(self.temperature_field, mu, convective=self.convection_chain)
 
     def _equilibrium_at(self, r):
         """The design r set and its equilibrium solved, unless the last solve is already that of r."""
@@ -369,6 +410,13 @@ class LatticeOpti(LatticeSim):
         return self.find_point_on_lattice_surface(surfaces)
 
     def calculate_objective(self):
+        if self.objective_type == "thermal_compliance":     # q . (T - T_inf) over the free nodes
+            q = self.conduction["heat_flow"]
+            if q is None:
+                return 0.0
+            return float((q * (self.temperature_field - self._ambient()))[~self.conduction["fixed"]].sum())
+        if self.objective_type == "heat_dissipation":       # P = sum_i H_i (T_i - T_inf)
+            return self.dissipated_power()
         if self.objective_type == "compliance":
             return self.compute_compliance()
         if self.objective_type == "displacement":
@@ -471,11 +519,13 @@ class LatticeOpti(LatticeSim):
             # K_T mu = c on the free thermal nodes, lam^T (d f_th / d dT) dT/dr_b = -mu^T (dK_T/dr_b) T
             cd = self.conduction
             c = dev.thermal_load_adjoint(u if lam is None else lam)
-            mu, _ = dev.cond_solve(cd["fixed"], None, np.where(cd["fixed"], 0.0, c), rtol=1e-10, max_iter=200000)
-            s = s + dev.cond_sens(self.temperature_field, mu)
+            # (under convection the adjoint operator is K_T + H and cond_sens carries the convective bracket, section 10m)
+            mu, _ = dev.cond_solve(cd["fixed"], None, np.where(cd["fixed"], 0.0, c), rtol=1e-10, max_iter=200000, adjoint=True)
+            s = s + dev.cond_sens(self.temperature_field, mu, convective=self.convection_chain)
         return s
 
     conduction_chain = True     # False leaves dT/dr out of the gradients (tests show what that costs)
+    convection_chain = True     # False leaves the convective bracket of cond_sens out (the same kind of switch)
 
     def _no_conduction_driven(self, key):
         if key in ("max_stress", "buckling") and self.conduction_driven:
@@ -486,6 +536,13 @@ class LatticeOpti(LatticeSim):
     def strut_sensitivities(self):
         """s_b such that d(objective)/d r_b = −s_b at fixed segment geometry (compliance: s_b = u_eᵀ ∂K_e/∂r u_e)."""
         dev = self.device_model()
+        if self.objective_type == "thermal_compliance":     # dJ/dT = q, no explicit dependence on r
+            q = self.conduction["heat_flow"]
+            return self._thermal_adjoint_sens(np.zeros(self.lattice.n_nodes) if q is None else q)
+        if self.objective_type == "heat_dissipation":       # dJ/dT = H on the free nodes, dJ/dr_b at fixed T = k_b Qc_b / r_b
+            Qc = dev.cond_film(self.temperature_field)
+            k = 1.0 if dev._mult is None else np.asarray(dev._mult, dtype=float)
+            return self._thermal_adjoint_sens(dev._H_host()[0]) - k * Qc / dev._radius
         u = self._model.u
         if self.paired_adjoint and self.objective_type == "displacement":
             nodes = self._objective_nodes(self.objectif_data["Surface"])
@@ -777,6 +834,28 @@ class LatticeOpti(LatticeSim):
         """d(buckling_constraint)/d(theta) by the adjoint chain of stress_constraint_gradient: dB/dr_b at fixed u -
         lam^T (dK/dr_b) u with K lam = dB/du on the free dofs."""
         return self._constraint_gradient("buckling", r)
+
+    # -- temperature constraint (FEM mode): p-norm of the nodal temperature over the free thermal nodes, pl_temp_pnorm ------------
+    def _max_temperature_settings(self):
+        c = self.constraints_dict["max_temperature"]
+        ref = c.get("reference", None)
+        return float(c["limit"]), float(c.get("p", 8)), float(self._ambient() if ref is None else ref)
+
+    def max_temperature_aggregate(self, want_grad=False):
+        """(Phi_p, peak, dPhi/dr_b or None) of T - reference over the free nodes of the conduction problem at the current
+        design (Phi_p >= the peak).  dPhi/dr_b is total: Phi depends on r through T alone, -mu^T d[(K_T + H) T - H T_inf]/dr_b."""
+        _, p, ref = self._max_temperature_settings()
+        res = self.device_model().temp_pnorm(self.temperature_field, p, ref, ~self.conduction["fixed"], gradient=want_grad)
+        self._last_max_temperature = (res["phi"], res["max"])
+        return res["phi"], res["max"], (-self._thermal_adjoint_sens(res["dphi_dT"]) if want_grad else None)
+
+    def max_temperature_constraint(self, r):
+        """Phi_p / limit - 1 (<= 0 when feasible: Phi_p >= max(T - reference) over the free thermal nodes)."""
+        return self._constraint_value("max_temperature", r)
+
+    def max_temperature_constraint_gradient(self, r):
+        """d(max_temperature_constraint)/d(theta): dPhi/dr_b / limit through _strut_gradient_to_parameters."""
+        return self._constraint_gradient("max_temperature", r)
 
     # -- global buckling constraint (FEM mode): p-norm of 1 / lambda_i, pl_buckling_modes + pl_buckling_modes_sens ------------
     def _global_buckling_settings(self):

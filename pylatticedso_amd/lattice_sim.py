@@ -120,8 +120,8 @@ class LatticeSim(LatticeViews):
         self._generate_and_prepare()
         if self._conduction_preset is not None:    # simulation_parameters["thermal"]["conduction"]
             c = self._conduction_preset
-            self._set_conduction_problem(c["conductivity"], c["Temperature"], c.get("HeatFlow", None),
-                                         c.get("beam_conductivity", None), c.get("reference", 0.0))
+            self._set_conduction_problem(c["conductivity"], c.get("Temperature", None), c.get("HeatFlow", None),
+                                         c.get("beam_conductivity", None), c.get("reference", 0.0), c.get("Convection", None))
         if self._thermal_preset is not None:       # simulation_parameters["thermal"]
             self.set_temperature(*self._thermal_preset)
         self.cell_schur_index = None       # (C,) index into self.schur_complements
@@ -707,11 +707,25 @@ class LatticeSim(LatticeViews):
                 val[pts] = v
         return mask, val
 
-    def _set_conduction_problem(self, conductivity, fixed, heat_flow, beam_conductivity, reference):
+    def _set_conduction_problem(self, conductivity, fixed, heat_flow, beam_conductivity, reference, convection=None):
         n = self.lattice.n_nodes
         if self.domain_decomposition_solver:
             raise ValueError("solve_temperature: heat conduction needs the FEM strut model (DDM handles carry no strut graph)")
-        if isinstance(fixed, dict):
+        conv = None
+        if convection is not None:     # {"film": h, "ambient": T_inf, "beam_film": optional (n_beams,)}
+            if "ambient" not in convection or ("film" not in convection and convection.get("beam_film", None) is None):
+                raise ValueError('solve_temperature: convection needs "film" (or "beam_film") and "ambient"')
+            bf = convection.get("beam_film", None)
+            bf = None if bf is None else np.array(np.broadcast_to(np.asarray(bf, dtype=float), (self.lattice.n_beams,)))
+            film, amb = float(convection.get("film", 0.0)), float(convection["ambient"])
+            if not (np.isfinite(amb) and ((bf is None and film > 0 and np.isfinite(film)) or
+                                          (bf is not None and (bf >= 0).all() and np.isfinite(bf).all() and bf.any()))):
+                raise ValueError("solve_temperature: film coefficients must be non-negative, finite and not all zero, "
+                                 "the ambient temperature finite")
+            conv = {"film": film, "ambient": amb, "beam_film": bf}
+        if fixed is None:              # (the caller has checked that convection makes this a valid problem)
+            mask, t_bar = np.zeros(n, bool), np.zeros(n)
+        elif isinstance(fixed, dict):
             mask, t_bar = self._thermal_nodes(fixed, "Temperature", False)
         elif isinstance(fixed, (tuple, list)) and len(fixed) == 2:
             mask = np.array(np.broadcast_to(np.asarray(fixed[0]).reshape(-1) != 0, (n,)))
@@ -727,7 +741,7 @@ class LatticeSim(LatticeViews):
             q = np.array(np.broadcast_to(np.asarray(heat_flow, dtype=float), (n,)))
         bk = None if beam_conductivity is None else np.array(np.broadcast_to(np.asarray(beam_conductivity, dtype=float),
                                                                              (self.lattice.n_beams,)))
-        if not mask.any():
+        if not mask.any() and conv is None:
             raise ValueError("solve_temperature: no node has a prescribed temperature")
         if not (np.isfinite(t_bar).all() and (q is None or np.isfinite(q).all()) and np.isfinite(reference)):
             raise ValueError("solve_temperature: temperatures, heat flows and the reference must be finite")
@@ -735,7 +749,8 @@ class LatticeSim(LatticeViews):
                 (bk is not None and (bk > 0).all() and np.isfinite(bk).all())):
             raise ValueError("solve_temperature: conductivities must be positive and finite")
         self.conduction = {"conductivity": float(conductivity), "beam_conductivity": bk, "fixed": mask, "t_bar": t_bar,
-                           "heat_flow": None if q is None else np.where(mask, 0.0, q), "reference": float(reference)}
+                           "heat_flow": None if q is None else np.where(mask, 0.0, q), "reference": float(reference),
+                           "convection": conv}
 
     def _assemble_for_conduction(self, dev):
         """The conduction calls need an assembled handle (the strut records); a handle that never saw boundary conditions
@@ -750,11 +765,21 @@ class LatticeSim(LatticeViews):
         want = c["conductivity"] if c["beam_conductivity"] is None else c["beam_conductivity"]
         if dev._conduction is None or not np.array_equal(np.asarray(dev._conduction), np.asarray(want)):
             dev.set_conduction(c["conductivity"], c["beam_conductivity"])
+        cv = c.get("convection", None)
+        if cv is None:
+            if dev._convection is not None:
+                dev.clear_convection()
+        else:
+            want = cv["film"] if cv["beam_film"] is None else cv["beam_film"]
+            have = dev._convection
+            if have is None or have[1] != cv["ambient"] or not np.array_equal(np.asarray(have[0]), np.asarray(want)):
+                dev.set_convection(cv["film"], cv["ambient"], cv["beam_film"])
         T, self.conduction_stats = dev.cond_solve(c["fixed"], c["t_bar"], c["heat_flow"], rtol=1e-12, max_iter=200000)
         self.temperature_field = T
         return T
 
-    def solve_temperature(self, conductivity=None, fixed=None, heat_flow=None, beam_conductivity=None, reference=0.0):
+    def solve_temperature(self, conductivity=None, fixed=None, heat_flow=None, beam_conductivity=None, reference=0.0,
+                          convection=None):
         """Steady temperatures of the lattice nodes, each strut one conductor g = k kappa pi r^2 / L between its nodes:
         K_T T = q on the free nodes, T prescribed on the others.  conductivity: kappa of every strut, or beam_conductivity
         (n_beams,) per strut.  fixed: the prescribed temperatures - a block {"Surface": [...], "Value": T} or a dict of named
@@ -763,17 +788,20 @@ class LatticeSim(LatticeViews):
         nodes, or an (n_nodes,) array of nodal inflows.  reference: the stress-free temperature that
         set_temperature("conduction", alpha) subtracts.  Returns T (n_nodes,); the problem is kept, and solved again before
         every mechanical solve under a conduction-driven temperature.  Without arguments: the problem kept last (that of the
-        preset's "conduction" block, for instance) on the current radii."""
+        preset's "conduction" block, for instance) on the current radii.
+        convection = {"film": h, "ambient": T_inf, "beam_film": optional (n_beams,)}: every strut end also exchanges with
+        an ambient at T_inf through c = k h pi r L (lumped: (K_T + diag H) T = q + H T_inf); ``fixed`` may then be None -
+        the convection alone makes the problem well posed."""
         if getattr(self, "_compat_rows", False):
             raise NotImplementedError("heat conduction is not available in the reference_compat strut model")
         if conductivity is None and fixed is None:
             if self.conduction is None:
                 raise RuntimeError("solve_temperature: no conduction problem is defined (give conductivity and fixed)")
-        elif (conductivity is None and beam_conductivity is None) or fixed is None:
+        elif (conductivity is None and beam_conductivity is None) or (fixed is None and convection is None):
             raise ValueError("solve_temperature needs a conductivity and the prescribed temperatures")
         else:
             self._set_conduction_problem(0.0 if conductivity is None else conductivity, fixed, heat_flow, beam_conductivity,
-                                         reference)
+                                         reference, convection)
         dev = self.device_model()
         self._assemble_for_conduction(dev)
         return self._solve_conduction(dev).copy()
@@ -795,6 +823,40 @@ class LatticeSim(LatticeViews):
         dev = self.device_model()
         self._assemble_for_conduction(dev)
         return dev.cond_flux(self.temperature_field)
+
+    def _convective_field(self, who):
+        if self.conduction is None or self.temperature_field is None:
+            raise RuntimeError(f"{who}: no temperature field (solve_temperature)")
+        if self.conduction.get("convection", None) is None:
+            raise RuntimeError(f"{who}: the conduction problem has no convection")
+        dev = self.device_model()
+        self._assemble_for_conduction(dev)
+        if dev._convection is None:              # (a handle made after the last solve)
+            self._solve_conduction(dev)
+        return dev
+
+    def strut_heat_loss(self):
+        """(n_beams,) convective loss Qc_b = c [(T_A - T_inf) + (T_B - T_inf)] / k of one copy of every strut for the
+        temperatures of the last conduction solve (pl_cond_film)."""
+        return self._convective_field("strut_heat_loss").cond_film(self.temperature_field)
+
+    def dissipated_power(self):
+        """P = sum_i H_i (T_i - T_inf), what the lattice gives to the ambient at the temperatures of the last conduction
+        solve, summed on the device in a fixed order (pl_cond_film)."""
+        return self._convective_field("dissipated_power").cond_film(self.temperature_field, total=True)[1]
+
+    def max_temperature(self, p=None, reference=None):
+        """Peak of T - reference over the free nodes of the conduction problem for the temperatures of its last solve; with
+        p: (peak, p-norm) of pl_temp_pnorm.  reference: default the ambient of the convection, else the problem's reference."""
+        if self.conduction is None or self.temperature_field is None:
+            raise RuntimeError("max_temperature: no temperature field (solve_temperature)")
+        c = self.conduction
+        if reference is None:
+            reference = c["convection"]["ambient"] if c.get("convection", None) is not None else c["reference"]
+        dev = self.device_model()
+        self._assemble_for_conduction(dev)
+        res = dev.temp_pnorm(self.temperature_field, 1.0 if p is None else p, reference, ~c["fixed"])
+        return res["max"] if p is None else (res["max"], res["phi"])
 
     def thermal_strut_forces(self):
         """(n_beams,) restrained thermal force n_free of one copy of every strut (pl_thermal_load): what a strut heated and

@@ -3,9 +3,11 @@
 k_thermal_load of pl_thermal_load in the same run: both walk the same sliced-ELL incidence, one thread per node.  Then one
 pl_cond_solve between a hot and a cold face.  One process, one GPU; one warm-up and --reps timed repetitions per row.  Kernel
 times are HIP events around the launches of one call (the library prints them when PL_TIMING is set; the last line of a call is
-the stage that ends it - for pl_cond_solve the whole PCG with its status downloads).
+the stage that ends it - for pl_cond_solve the whole PCG with its status downloads).  The rows under convection (DESIGN.md
+section 10m) follow in the same process, after the plain ones: the convective gather beside the plain gather of the same run,
+pl_cond_film (k_cond_film and its fold), the temperature p-norm pass and one pl_cond_solve with convection.
 
-    python tools/time_conduction.py --out profiles/r18_conduction
+    python tools/time_conduction.py --out profiles/r19_convection
 """
 import argparse
 import json
@@ -25,7 +27,9 @@ from pylatticedso_amd.lattice_sim import LatticeSim                    # noqa: E
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--out", default="profiles/r18_conduction")
+    ap.add_argument("--out", default="profiles/r19_convection")
+    ap.add_argument("--film", type=float, default=0.05)
+    ap.add_argument("--ambient", type=float, default=20.0)
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--cells", type=int, default=50)
     ap.add_argument("--geom", default="Octet")
@@ -68,7 +72,25 @@ def main():
             "pl_cond_sens (last stage: k_cond_sens)": lambda: dev.cond_sens(T, mu),
             "pl_thermal_load_adjoint (last stage: k_thermal_load_adjoint)": lambda: dev.thermal_load_adjoint(lam),
             f"pl_cond_solve rtol {a.rtol:g}, hot Zmin and cold Zmax (last stage: the PCG)": solve}
+    conv_solves = []
+
+    def conv_solve():
+        conv_solves.append(dev.cond_solve(fixed, t_bar, None, rtol=a.rtol, max_iter=200000)[1])
+
+    plain_gather = "pl_cond_spmv (last stage: k_cond_gather<false>)"
+    conv_gather = "convection: pl_cond_spmv (last stage: k_cond_gather<false, true>)"
+    conv_rows = {conv_gather: lambda: dev.cond_spmv(T),
+                 "convection: pl_cond_spmv masked (last stage: k_cond_gather<true, true>)": lambda: dev.cond_spmv(T, fixed),
+                 "convection: pl_cond_sens (last stage: k_cond_sens<true>)": lambda: dev.cond_sens(T, mu),
+                 "convection: pl_cond_film, Qc and P (last stage: k_cond_film + fold)": lambda: dev.cond_film(T, total=True),
+                 "pl_temp_pnorm p 8 with dphi_dT (last stage: values, fold, p-sum, fold, grad)":
+                     lambda: dev.temp_pnorm(T, 8.0, a.ambient, ~fixed, gradient=True),
+                 f"convection: pl_cond_solve rtol {a.rtol:g}, hot Zmin and cold Zmax (last stage: the PCG)": conv_solve}
+    first_conv = next(iter(conv_rows))
+    rows.update(conv_rows)
     for name, fn in rows.items():
+        if name == first_conv:                    # the plain rows are done: from here on the CONV kernels run
+            dev.set_convection(a.film, a.ambient)
         walls, kernels = [], []
         for rep in range(a.reps + 1):
             w, k, _ = _timed(fn)
@@ -85,18 +107,30 @@ def main():
     res["k_cond_gather_model_bytes"] = int(2 * lat.n_beams * (8 + 8 + 8) + 16 * lat.n_nodes)
     t = k["pl_cond_spmv (last stage: k_cond_gather<false>)"]
     res["k_cond_gather_model_GB_per_s"] = res["k_cond_gather_model_bytes"] / (t * 1e-3) / 1e9
+    # the convective gather reads H once per node on top of that
+    st = conv_solves[-1]
+    res["convection"] = {"film": a.film, "ambient": a.ambient,
+                         "cond_solve": {"iterations": int(st["iterations"]), "rel_residual": float(st["rel_residual"]),
+                                        "converged": int(st["converged"])},
+                         "k_cond_gather_conv_model_bytes": int(res["k_cond_gather_model_bytes"] + 8 * lat.n_nodes),
+                         "k_cond_gather_conv_over_plain": k[conv_gather] / k[plain_gather]}
     os.makedirs(os.path.dirname(a.out) or ".", exist_ok=True)
     with open(a.out + ".json", "w") as fh:
         json.dump(res, fh, indent=1)
     lines = [f"{res['lattice']}: {res['n_nodes']} nodes, {res['n_beams']} struts; medians of {a.reps} warm repetitions"]
     for name, r in res["rows"].items():
         kk = r["kernel_hip_events"]
-        lines.append(f"  {name:76} wall {r['wall']['median_ms']:9.2f} ms" +
+        lines.append(f"  {name:82} wall {r['wall']['median_ms']:9.2f} ms" +
                      (f"   last stage (HIP events) {kk['median_ms']:8.4f} ms" if kk else ""))
     lines.append(f"  pl_cond_solve: {res['cond_solve']['iterations']} iterations, rel_residual "
                  f"{res['cond_solve']['rel_residual']:.2e}")
     lines.append(f"  k_cond_gather: {res['k_cond_gather_model_bytes']} model bytes, "
                  f"{res['k_cond_gather_model_GB_per_s']:.0f} GB/s at the measured time")
+    cv = res["convection"]
+    lines.append(f"  pl_cond_solve under convection: {cv['cond_solve']['iterations']} iterations, rel_residual "
+                 f"{cv['cond_solve']['rel_residual']:.2e}")
+    lines.append(f"  k_cond_gather<false, true>: {cv['k_cond_gather_conv_model_bytes']} model bytes, "
+                 f"{cv['k_cond_gather_conv_over_plain']:.3f} x the plain gather of this run")
     with open(a.out + ".txt", "w") as fh:
         fh.write("\n".join(lines) + "\n")
     print("\n".join(lines))
