@@ -499,6 +499,51 @@ int pl_cond_film(pl_handle h, const double *T /*[N]*/, double *Qc /*[B] or NULL*
 int pl_temp_pnorm(pl_handle h, const double *T /*[N]*/, const uint8_t *nodes /*[N] or NULL*/, double T_ref, double p,
                   double *out /*[3] or NULL*/, double *dphi_dT /*[N] or NULL*/);
 
+/* ---- transient heat conduction: implicit theta steps on the strut graph ---------------------------------
+ * Lumped heat capacity, conventions of the conductance (plain radius r, node-to-node length L, multiplicity k):
+ *   C_i = sum over struts b at i of (1/2) k_b (rho c)_b pi r_b^2 L_b + node_capacity_i,  (rho c)_b = beam_rho_c ? beam_rho_c[b] : rho_c
+ * (half of every copy's volume to each end times the volumetric heat capacity), rebuilt from the current radii by every call.
+ *   problem   C dT/dt + (K_T + H) T = q(t) + H T_inf on the free nodes, T = T_bar(t) on the masked ones (H = 0 without convection)
+ *   step      (C/dt + theta (K_T + H)) dT = q_theta + H T_inf - (K_T + H) W on the free rows, dT = T_{n+1} - T_n, 1/2 <= theta <= 1,
+ *             W_j = T_n,j on a free node and (1 - theta) T_n,j + theta T_bar,n+1,j on a fixed one, q_theta = theta q_{n+1} + (1 - theta) q_n
+ * The capacity matrix is diagonal on purpose: the step matrix is an M-matrix and backward Euler (theta = 1) cannot undershoot.
+ * Every strut has rho c > 0, so the step matrix is positive definite for any mask, an all-zero mask without convection (an
+ * insulated lattice) included.
+ *
+ * pl_set_heat_capacity needs a conduction state (PL_ERR_STATE) and lives in it, as pl_set_convection does: pl_set_conduction
+ * drops it.  rho_c == 0 and beam_rho_c == NULL clears it.  PL_ERR_ARG: a non-positive or non-finite strut value, a negative or
+ * non-finite node_capacity.  Survives pl_update_radii / pl_update_segments / pl_assemble; handle restrictions as pl_set_conduction. */
+int pl_set_heat_capacity(pl_handle h, double rho_c, const double *beam_rho_c /*[B] or NULL*/, const double *node_capacity /*[N] >= 0 or NULL*/);
+/* n_steps steps of size dt from the initial state T0 (NULL: T_inf everywhere, 0 without a convection state) with the fixed nodes
+ * at their row-0 value.  Caller's node numbering throughout.
+ *   loads      q_n = sum_p amp[n][p] pattern[p], n_pat <= 4 (values on fixed nodes are ignored)
+ *   mask       fixed: one byte per node, NULL = no fixed node.  The prescribed temperature of row n on a fixed node i is
+ *              T0_i + s_n (T_bar_i - T0_i), evaluated in this order without a fused multiply-add; s = bar_amp, NULL: s_n = 1.
+ *              T_bar == NULL: zeros.
+ *   probe      [n_steps + 1][n_probe]: the temperature of the probed nodes in every row
+ *   heat       [n_steps + 1][4]: U_n = sum_i C_i (T_i - T_inf), the stored heat, and three cumulative heats that are zero in row 0:
+ *              Q_in += dt sum_free q_theta,i;  Q_c += dt sum over ALL nodes of H_i (T_theta,i - T_inf);
+ *              Q_R += dt sum_fixed [C_i dT_i/dt + ((K_T + H) T_theta)_i - H_i T_inf], the heat the prescribed nodes supply, with
+ *              T_theta = T_n + theta dT.  U_n - U_0 = Q_in + Q_R - Q_c up to the PCG residuals.
+ *   snaps      row k * snap_every lands in snaps[k - 1], k = 1 ... n_steps / snap_every
+ *   state      the last row; a later call with T0 = state (and the same data) continues the history
+ *   iters      PCG iterations of every step, iters[0] = 0
+ * Every step is one Jacobi PCG solve from dT = 0 on the device, stopped by ||r|| <= rtol ||b||; a field at rest takes no
+ * iteration.  The whole history stays on the device and comes down once at the end.
+ * PL_ERR_ARG: dt <= 0, n_steps < 1, theta outside [1/2, 1], n_pat outside 0 ... 4, a probe index out of range, a non-positive
+ * rtol or max_iter, a value of T0, T_bar, bar_amp, pattern or amp that is not finite.  PL_ERR_STATE: before pl_set_heat_capacity, before pl_assemble, on a pl_create_ddm or pl_dist_init handle.
+ * PL_ERR_NOCONV names the step whose solve missed rtol; the outputs are then not written.  The handle's mechanical state is not
+ * touched, and neither is steady conduction: pl_cond_solve before and after gives the same result.  Device memory: the probe
+ * block and the snapshots are released when the call returns; its other buffers (a few arrays of N, the patterns and tables)
+ * stay in the heat-capacity state at the largest size asked for so far, until that state is dropped. */
+int pl_cond_transient(pl_handle h, int32_t n_steps, double dt, double theta, const uint8_t *fixed /*[N] or NULL*/,
+                      const double *T_bar /*[N] or NULL*/, const double *bar_amp /*[n_steps+1] or NULL*/, int32_t n_pat,
+                      const double *pattern /*[n_pat][N] or NULL*/, const double *amp /*[n_steps+1][n_pat]*/,
+                      const double *T0 /*[N] or NULL*/, double rtol, int32_t max_iter, int32_t n_probe,
+                      const int32_t *probe_nodes, double *probe /*[n_steps+1][n_probe]*/, double *heat /*[n_steps+1][4] or NULL*/,
+                      int32_t snap_every, double *snaps /*[n_steps/snap_every][N] or NULL*/, double *state /*[N] or NULL*/,
+                      int32_t *iters /*[n_steps+1] or NULL*/);
+
 /* Strain energy 1/2 u^T K u (LatticeOpti.compute_compliance, lattice_opti.py:645-663 uses u^T K u). */
 int pl_energy(pl_handle h, const double *u, double *energy);
 

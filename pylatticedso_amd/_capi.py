@@ -26,6 +26,7 @@ EXPORTS = ["pl_default_opts", "pl_opts_size", "pl_stats_size", "pl_abi_version",
            "pl_set_thermal", "pl_thermal_load", "pl_thermal_sens",
            "pl_set_conduction", "pl_cond_spmv", "pl_cond_solve", "pl_cond_flux", "pl_cond_sens", "pl_thermal_load_adjoint",
            "pl_set_convection", "pl_cond_solve_adjoint", "pl_cond_film", "pl_temp_pnorm",
+           "pl_set_heat_capacity", "pl_cond_transient",
            "pl_spmv_multi", "pl_solve_multi", "pl_schur_block", "pl_geom_spmv_multi", "pl_buckling_modes", "pl_buckling_modes_sens",
            "pl_set_mass", "pl_mass_spmv_multi", "pl_vibration_modes", "pl_vibration_modes_sens",
            "pl_dyn_spmv_multi", "pl_transient", "pl_transient_sens", "pl_harm_spmv", "pl_harmonic", "pl_harmonic_sens",
@@ -103,6 +104,8 @@ def load_library(path: str | None = None):
            "pl_set_conduction": [V, D, V], "pl_cond_spmv": [V, I32, V, V, V], "pl_cond_solve": [V, V, V, V, D, I32, V, V],
            "pl_cond_flux": [V, V, V], "pl_cond_sens": [V, V, V, V], "pl_thermal_load_adjoint": [V, V, V],
            "pl_set_convection": [V, D, V, D], "pl_cond_solve_adjoint": [V, V, V, D, I32, V, V], "pl_cond_film": [V, V, V, V], "pl_temp_pnorm": [V, V, V, D, D, V, V],
+           "pl_set_heat_capacity": [V, D, V, V],
+           "pl_cond_transient": [V, I32, D, D, V, V, V, I32, V, V, V, D, I32, I32, V, V, V, I32, V, V, V],
            "pl_schur": [V, V, I32, D, I32, V], "pl_spmv_multi": [V, I32, I32, V, V],
            "pl_solve_multi": [V, I32, V, V, D, I32, V, V], "pl_schur_block": [V, V, I32, D, I32, I32, V],
            "pl_geom_spmv_multi": [V, V, I32, I32, V, V],
@@ -453,6 +456,7 @@ class HipLattice:
         self._thermal = None
         self._conduction = None
         self._convection = None
+        self._heat_capacity = None
         self._assembled = False
         if beam_mult is not None:
             self.set_multiplicity(beam_mult)
@@ -827,12 +831,14 @@ class HipLattice:
         _check(self._lib, self._lib.pl_set_conduction(self._h, float(kappa), _ptr(bk)))
         self._conduction = bk if bk is not None else float(kappa)
         self._convection = None      # (the convection state lives in the conduction state)
+        self._heat_capacity = None   # (and so does the heat capacity)
 
     def clear_conduction(self):
         """Removes the conduction state (pl_set_conduction with kappa = 0 and no beam_kappa)."""
         _check(self._lib, self._lib.pl_set_conduction(self._h, 0.0, None))
         self._conduction = None
         self._convection = None
+        self._heat_capacity = None
 
     def set_convection(self, film, ambient, beam_film=None):
         """Convection state of the handle (pl_set_convection): film coefficient ``film`` of every strut, or beam_film (B,) per
@@ -938,6 +944,90 @@ class HipLattice:
         lam = _f64(np.asarray(lam).reshape(-1), 6 * self.n_nodes)
         out = np.empty(self.n_nodes, np.float64)
         _check(self._lib, self._lib.pl_thermal_load_adjoint(self._h, _ptr(lam), _ptr(out)))
+        return out
+
+    # -- transient heat conduction ----------------------------------------------------------------------------
+    def set_heat_capacity(self, rho_c, beam_rho_c=None, node_capacity=None):
+        """Heat capacity of the handle (pl_set_heat_capacity): volumetric heat capacity ``rho_c`` of every strut, or beam_rho_c
+        (B,) per strut, lumped to the nodes as C_i = sum (1/2) k rho_c pi r^2 L + node_capacity_i (node_capacity (N,) >= 0 or
+        None).  Needs a conduction state and is dropped with it (set_conduction included); it survives update_radii /
+        update_segments / assemble, and C follows the radii."""
+        br = None if beam_rho_c is None else _f64(np.asarray(beam_rho_c).reshape(-1), self.n_beams)
+        nc = None if node_capacity is None else _f64(np.asarray(node_capacity).reshape(-1), self.n_nodes)
+        _check(self._lib, self._lib.pl_set_heat_capacity(self._h, float(rho_c), _ptr(br), _ptr(nc)))
+        self._heat_capacity = (br if br is not None else float(rho_c), nc)
+
+    def clear_heat_capacity(self):
+        """Removes the heat capacity (pl_set_heat_capacity with rho_c = 0 and no beam_rho_c)."""
+        _check(self._lib, self._lib.pl_set_heat_capacity(self._h, 0.0, None, None))
+        self._heat_capacity = None
+
+    def _transient_args(self, n_steps, patterns, amp, bar_amp):
+        n_steps = int(n_steps)
+        rows = max(n_steps, 0) + 1
+        pat = am = None
+        n_pat = 0
+        if patterns is not None:
+            pat = np.ascontiguousarray(np.asarray(patterns, dtype=np.float64)).reshape(-1, self.n_nodes)
+            n_pat = pat.shape[0]
+            am = np.ascontiguousarray(np.asarray(amp, dtype=np.float64).reshape(-1))
+            if am.size != rows * n_pat:
+                raise ValueError(f"amp must have shape ({rows}, {n_pat})")
+        ba = None if bar_amp is None else _f64(np.asarray(bar_amp).reshape(-1), rows)
+        return n_steps, rows, n_pat, pat, am, ba
+
+    def cond_transient(self, dt, n_steps, theta=1.0, fixed=None, t_bar=None, bar_amp=None, patterns=None, amp=None, t0=None,
+                       rtol=1e-10, max_iter=100000, probes=None, snap_every=0, want_state=True):
+        """n_steps implicit theta steps of C dT/dt + (K_T + H) T = amp[n] @ patterns + H T_inf on the free nodes of ``fixed``
+        (N,) flags (None = none), T = t0 + bar_amp[n] (t_bar - t0) on the fixed ones (pl_cond_transient).  patterns (n_pat, N),
+        n_pat <= 4, amp (n_steps + 1, n_pat); bar_amp (n_steps + 1,) or None = 1; t0 (N,) or None = the ambient; probes: node
+        indices.  Returns a dict: times (n_steps + 1,), probe (n_steps + 1, n_probe), heat (n_steps + 1, 4) = stored heat U and
+        the cumulative Q_in, Q_c, Q_R (U_n - U_0 = Q_in + Q_R - Q_c), iters (n_steps + 1,), state (N,) = the last row (a call
+        started from it continues the history), and snaps (n_steps // snap_every, N) if snap_every > 0."""
+        n_steps, rows, n_pat, pat, am, ba = self._transient_args(n_steps, patterns, amp, bar_amp)
+        fx = None if fixed is None else self._mask_n(fixed)
+        tb = None if t_bar is None else _f64(np.broadcast_to(np.asarray(t_bar, dtype=float).reshape(-1), (self.n_nodes,)))
+        tt0 = None if t0 is None else _f64(np.broadcast_to(np.asarray(t0, dtype=float).reshape(-1), (self.n_nodes,)))
+        pr = np.zeros(0, np.int32) if probes is None else np.ascontiguousarray(np.asarray(probes).reshape(-1), dtype=np.int32)
+        probe = np.zeros((rows, pr.size), np.float64)
+        heat = np.zeros((rows, 4), np.float64)
+        iters = np.zeros(rows, np.int32)
+        snap_every = int(snap_every)
+        snaps = np.zeros((n_steps // snap_every, self.n_nodes), np.float64) if snap_every > 0 and n_steps > 0 else None
+        state = np.zeros(self.n_nodes, np.float64) if want_state else None
+        _check(self._lib, self._lib.pl_cond_transient(self._h, n_steps, float(dt), float(theta), _ptr(fx), _ptr(tb), _ptr(ba),
+                                                      n_pat, _ptr(pat), _ptr(am), _ptr(tt0), float(rtol), int(max_iter), pr.size,
+                                                      _ptr(pr) if pr.size else None, _ptr(probe) if pr.size else None,
+                                                      _ptr(heat), snap_every, _ptr(snaps), _ptr(state), _ptr(iters)))
+        out = {"times": float(dt) * np.arange(rows), "probe": probe, "heat": heat, "iters": iters}
+        if want_state:
+            out["state"] = state
+        if snaps is not None:
+            out["snaps"] = snaps
+        return out
+
+    def heat_capacity_host(self):
+        """(N,) the lumped heat capacity C of the current radii (conduction_host.heat_capacity)."""
+        from . import conduction_host as CH
+        hc = getattr(self, "_heat_capacity", None)
+        if hc is None:
+            raise RuntimeError("call set_heat_capacity first")
+        return CH.heat_capacity(self.node_xyz, self.beam_conn, self._radius, hc[0], self._mult, hc[1])
+
+    def cond_transient_host(self, dt, n_steps, theta=1.0, fixed=None, t_bar=None, bar_amp=None, patterns=None, amp=None, t0=None,
+                            probes=None, snap_every=0):
+        """The dense numpy restatement of ``cond_transient`` (conduction_host.transient), the same dict without iters; "T"
+        (n_steps + 1, N) holds every row."""
+        from . import conduction_host as CH
+        H, t_inf = self._H_host()
+        res = CH.transient(self.beam_conn, self.n_nodes, self._g_host(), self.heat_capacity_host(), dt, n_steps, theta, fixed,
+                           t_bar, bar_amp, patterns, amp, t0, H, t_inf)
+        T = res["T"]
+        pr = np.zeros(0, np.int64) if probes is None else np.asarray(probes).reshape(-1)
+        out = {"times": float(dt) * np.arange(int(n_steps) + 1), "probe": T[:, pr], "heat": res["heat"], "state": T[-1].copy(),
+               "T": T, "bar": res["bar"]}
+        if snap_every > 0:
+            out["snaps"] = T[snap_every::snap_every][:int(n_steps) // snap_every].copy()
         return out
 
     def _g_host(self):

@@ -27,6 +27,14 @@ and for J(T(r), r) with (K_T + H) mu = dJ/dT on the free nodes, mu = 0 on the fi
     dJ/dr_b = dJ/dr_b at fixed T - (2 g_b / r_b)(mu_A - mu_B)(T_A - T_B) - (c_b / r_b)[mu_A (T_A - T_inf) + mu_B (T_B - T_inf)].
 
 Every function takes the convection through optional arguments (H, c, t_inf) that default to none.
+
+Transient conduction (pl_set_heat_capacity / pl_cond_transient; csrc/pl_heat.h): the lumped capacity
+
+    C_i = sum over struts b at i of (1/2) k_b (rho c)_b pi r_b^2 L_b + node_capacity_i,
+    C dT/dt + (K_T + H) T = q(t) + H T_inf on the free nodes, T = T_bar(t) on the fixed ones,
+
+stepped by the one-step theta scheme in increment form (``transient``), and solved exactly for data constant in time by the
+generalised eigen-decomposition of (K_T + H, C) on the free nodes (``transient_exact``).
 """
 from __future__ import annotations
 
@@ -200,6 +208,109 @@ def thermal_gradient(functional, node_xyz, beam_conn, radius, kappa, fixed, t_ba
     mu = solve(conn, N, g, fx, None, np.where(fx, 0.0, dJdT), H, 0.0)
     grad = partial - cond_sens(conn, r, g, T, mu, c if convective_bracket else None, t_inf)
     return J, grad
+
+
+def heat_capacity(node_xyz, beam_conn, radius, rho_c, mult=None, node_capacity=None):
+    """(N,) lumped heat capacity C_i = sum over the struts at node i of (1/2) k rho_c pi r^2 L + node_capacity_i: half of every
+    copy's volume to each end times the volumetric heat capacity; rho_c a scalar or (B,)."""
+    conn = np.asarray(beam_conn).reshape(-1, 2)
+    r = np.asarray(radius, dtype=float).reshape(-1)
+    k = 1.0 if mult is None else np.asarray(mult, dtype=float)
+    cap = np.broadcast_to(0.5 * k * np.asarray(rho_c, dtype=float) * (np.pi * r * r) * _length(node_xyz, conn), (len(conn),))
+    N = len(np.asarray(node_xyz).reshape(-1, 3))
+    C = np.zeros(N)
+    np.add.at(C, conn[:, 0], cap)
+    np.add.at(C, conn[:, 1], cap)
+    return C if node_capacity is None else C + np.asarray(node_capacity, dtype=float).reshape(-1)
+
+
+def row_value(t0, t_bar, s):
+    """The prescribed temperature of a fixed node in a row of ramp value s: t0 + s (t_bar - t0), in this order (the device
+    evaluates the same three roundings, so fixed nodes compare bit for bit)."""
+    t0 = np.asarray(t0, dtype=float)
+    d = np.asarray(t_bar, dtype=float) - t0
+    return t0 + s * d
+
+
+def transient(beam_conn, node_count, g, C, dt, n_steps, theta=1.0, fixed=None, t_bar=None, bar_amp=None, patterns=None,
+              amp=None, t0=None, H=None, t_inf=0.0):
+    """The one-step theta scheme of pl_cond_transient on dense matrices (numpy.linalg.solve): C dT/dt + (K_T + H) T = q(t) + H t_inf
+    on the free nodes, T = t0 + s_n (t_bar - t0) on the fixed ones (s = bar_amp (n_steps + 1,), None = 1), in increment form
+
+        (C/dt + theta (K_T + H)) dT = q_theta + H t_inf - (K_T + H) W on the free rows,
+        W = T_n on free nodes, (1 - theta) T_n + theta T_bar,n+1 on fixed ones, q_theta = theta q_{n+1} + (1 - theta) q_n,
+
+    q_n = amp[n] @ patterns (values on fixed nodes ignored).  t0 None = t_inf everywhere, t_bar None = 0, fixed None = no fixed
+    node.  Returns a dict: T (n_steps + 1, N); heat (n_steps + 1, 4) = U, Q_in, Q_c, Q_R (the stored heat sum C (T - t_inf) and
+    the cumulative inflow, convective loss and heat supplied by the fixed nodes: U_n - U_0 = Q_in + Q_R - Q_c); bar
+    (n_steps + 1, N) the prescribed row values (read on the fixed nodes only)."""
+    N, n_steps = int(node_count), int(n_steps)
+    rows = n_steps + 1
+    fx = np.zeros(N, bool) if fixed is None else (np.asarray(fixed).reshape(-1) != 0)
+    free = np.flatnonzero(~fx)
+    C = np.asarray(C, dtype=float).reshape(-1)
+    Hd = np.zeros(N) if H is None else np.asarray(H, dtype=float).reshape(-1)
+    A = laplacian(beam_conn, N, g) + np.diag(Hd)
+    start = np.full(N, float(t_inf)) if t0 is None else np.array(t0, dtype=float).reshape(-1)
+    tb = np.zeros(N) if t_bar is None else np.broadcast_to(np.asarray(t_bar, dtype=float).reshape(-1), (N,))
+    s = np.ones(rows) if bar_amp is None else np.asarray(bar_amp, dtype=float).reshape(-1)
+    bar = np.stack([row_value(start, tb, s[n]) for n in range(rows)])
+    if patterns is None:
+        q = np.zeros((rows, N))
+    else:
+        pat = np.asarray(patterns, dtype=float).reshape(-1, N)
+        q = np.asarray(amp, dtype=float).reshape(rows, pat.shape[0]) @ pat
+    q = np.where(fx[None, :], 0.0, q)
+    T = np.zeros((rows, N))
+    T[0] = np.where(fx, bar[0], start)
+    heat = np.zeros((rows, 4))
+    heat[0, 0] = C @ (T[0] - t_inf)
+    S = np.diag(C / dt) + theta * A
+    Sff = S[np.ix_(free, free)]
+    for n in range(n_steps):
+        W = np.where(fx, (1.0 - theta) * T[n] + theta * bar[n + 1], T[n])
+        qt = theta * q[n + 1] + (1.0 - theta) * q[n]
+        rhs = qt + Hd * t_inf - A @ W
+        d = np.where(fx, bar[n + 1] - T[n], 0.0)
+        if len(free):
+            d[free] = np.linalg.solve(Sff, rhs[free])
+        T[n + 1] = np.where(fx, bar[n + 1], T[n] + d)
+        Tt = T[n] + theta * d
+        heat[n + 1, 0] = C @ (T[n + 1] - t_inf)
+        heat[n + 1, 1] = heat[n, 1] + dt * qt[free].sum()
+        heat[n + 1, 2] = heat[n, 2] + dt * (Hd @ (Tt - t_inf))
+        heat[n + 1, 3] = heat[n, 3] + (C * d + dt * (A @ Tt - Hd * t_inf))[fx].sum()
+    return {"T": T, "heat": heat, "bar": bar}
+
+
+def transient_exact(beam_conn, node_count, g, C, t, fixed=None, t_bar=None, q=None, t0=None, H=None, t_inf=0.0):
+    """(N,) the solution at time t of C dT/dt + (K_T + H) T = q + H t_inf on the free nodes with loads and boundary data constant
+    in time (T = t_bar on the fixed nodes from t = 0 on, start field t0, None = t_inf), from the generalised eigen-decomposition
+    (K_T + H) v = lam C v on the free nodes: each mode relaxes as exp(-lam t); a mode with lam = 0 (an insulated lattice) grows
+    linearly with its load."""
+    import scipy.linalg
+    N = int(node_count)
+    fx = np.zeros(N, bool) if fixed is None else (np.asarray(fixed).reshape(-1) != 0)
+    free = np.flatnonzero(~fx)
+    C = np.asarray(C, dtype=float).reshape(-1)
+    Hd = np.zeros(N) if H is None else np.asarray(H, dtype=float).reshape(-1)
+    A = laplacian(beam_conn, N, g) + np.diag(Hd)
+    start = np.full(N, float(t_inf)) if t0 is None else np.asarray(t0, dtype=float).reshape(-1)
+    T = np.zeros(N)
+    if t_bar is not None:
+        T[fx] = np.broadcast_to(np.asarray(t_bar, dtype=float).reshape(-1), (N,))[fx]
+    b = Hd * t_inf - A @ T
+    if q is not None:
+        b = b + np.asarray(q, dtype=float).reshape(-1)
+    if len(free):
+        lam, V = scipy.linalg.eigh(A[np.ix_(free, free)], np.diag(C[free]))
+        a0 = V.T @ (C[free] * start[free])
+        beta = V.T @ b[free]
+        lt = lam * t
+        small = np.abs(lt) < 1e-12
+        growth = np.where(small, t, -np.expm1(-lt) / np.where(small, 1.0, lam))
+        T[free] = V @ (a0 * np.exp(-lt) + beta * growth)
+    return T
 
 
 def thermal_load_adjoint(rec, beam_conn, node_count, alpha, lam):

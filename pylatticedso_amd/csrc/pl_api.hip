@@ -9,6 +9,7 @@
 #include "pl_buckling.h"
 #include "pl_thermal.h"
 #include "pl_conduction.h"
+#include "pl_heat.h"
 #include "pl_geom.h"
 #include "pl_mass.h"
 #include "pl_dyn.h"
@@ -2954,6 +2955,258 @@ int pl_vibration_modes_sens(pl_handle h, int32_t n_modes, const double *omega2, 
     return rc;
   timer.stop();
   return mode_sens_end(h, g, ms, domega2_dr, dsum_dr);
+}
+
+// ---- transient heat conduction: implicit theta steps on the strut graph (pl_heat.h) --------------------------------------
+int pl_set_heat_capacity(pl_handle h, double rho_c, const double *beam_rho_c, const double *node_capacity) {
+  if (!valid(h)) return fail(PL_ERR_ARG, "pl_set_heat_capacity: null handle");
+  if (h->opkind != 0) return fail(PL_ERR_STATE, "pl_set_heat_capacity: not available on a DDM handle");
+  if (h->dist.active || h->opt.grid_nodes > 0)
+    return fail(PL_ERR_STATE, "pl_set_heat_capacity: single-GPU handles only (this one belongs to a multi-rank run)");
+  if (!h->cond_ws) return fail(PL_ERR_STATE, "pl_set_heat_capacity: call pl_set_conduction first");
+  CondWs *w = static_cast<CondWs *>(h->cond_ws.get());
+  if (rho_c == 0.0 && !beam_rho_c) {
+    w->heat.reset();
+    return PL_OK;
+  }
+  if (!beam_rho_c && !(rho_c > 0.0 && std::isfinite(rho_c)))
+    return fail(PL_ERR_ARG, "pl_set_heat_capacity: rho_c must be positive and finite");
+  if (beam_rho_c)
+    for (int64_t b = 0; b < h->B; ++b)
+      if (!(beam_rho_c[b] > 0.0 && std::isfinite(beam_rho_c[b])))
+        return fail(PL_ERR_ARG, "pl_set_heat_capacity: beam_rho_c must be positive and finite");
+  if (node_capacity)
+    for (int64_t i = 0; i < h->N; ++i)
+      if (!(node_capacity[i] >= 0.0 && std::isfinite(node_capacity[i])))
+        return fail(PL_ERR_ARG, "pl_set_heat_capacity: node_capacity must be non-negative and finite");
+  PL_HIP(hipSetDevice(h->opt.device));
+  const size_t B = (size_t)h->B, N = (size_t)h->N;
+  auto hw = std::make_shared<HeatWs>();
+  for (DevBuf<double> *b : {&hw->rho_c, &hw->cap}) PL_HIP(b->alloc(B));
+  for (DevBuf<double> *b : {&hw->node_cap, &hw->C, &hw->S}) PL_HIP(b->alloc(N));
+  std::vector<double> rc(B);
+  for (size_t b = 0; b < B; ++b) rc[b] = beam_rho_c ? beam_rho_c[h->bperm[b]] : rho_c;
+  PL_HIP(hipMemcpy(hw->rho_c.p, rc.data(), B * sizeof(double), hipMemcpyHostToDevice));
+  if (int rcode = cond_upload(h, node_capacity, hw->node_cap.p)) return rcode;
+  PL_HIP(hipStreamSynchronize(h->stream));
+  w->heat = hw;
+  return PL_OK;
+}
+
+int pl_cond_transient(pl_handle h, int32_t n_steps, double dt, double theta, const uint8_t *fixed, const double *T_bar,
+                      const double *bar_amp, int32_t n_pat, const double *pattern, const double *amp, const double *T0, double rtol,
+                      int32_t max_iter, int32_t n_probe, const int32_t *probe_nodes, double *probe, double *heat, int32_t snap_every,
+                      double *snaps, double *state, int32_t *iters) {
+  const char *who = "pl_cond_transient";
+  const std::string whos = who;
+  // every check on the host, before any launch
+  if (!valid(h)) return fail(PL_ERR_ARG, whos + ": null handle");
+  if (n_steps < 1) return fail(PL_ERR_ARG, whos + ": n_steps must be at least 1");
+  if (!(dt > 0.0) || !std::isfinite(dt)) return fail(PL_ERR_ARG, whos + ": dt must be positive and finite");
+  if (!(theta >= 0.5 && theta <= 1.0)) return fail(PL_ERR_ARG, whos + ": theta must lie in [1/2, 1] (unconditionally stable schemes only)");
+  if (n_pat < 0 || n_pat > pl::kHeatMaxPat) return fail(PL_ERR_ARG, whos + ": n_pat must be 0 ... 4");
+  if (n_pat > 0 && (!pattern || !amp)) return fail(PL_ERR_ARG, whos + ": n_pat > 0 needs pattern and amp");
+  if (n_probe < 0 || (n_probe > 0 && (!probe_nodes || !probe))) return fail(PL_ERR_ARG, whos + ": n_probe > 0 needs probe_nodes and probe");
+  if (snap_every < 0 || (snaps && snap_every < 1)) return fail(PL_ERR_ARG, whos + ": snaps needs snap_every >= 1");
+  if (int rc = check_solve(whos, rtol, max_iter)) return rc;
+  if (int rc = check_probes(whos, n_probe, probe_nodes, h->N)) return rc;
+  {   // a NaN in the data would otherwise surface as a missed solve, or silently through a fixed node's row value
+    const size_t Nh = (size_t)h->N, rows_h = (size_t)n_steps + 1;
+    auto finite = [](const double *v, size_t n) {
+      for (size_t i = 0; v && i < n; ++i)
+        if (!std::isfinite(v[i])) return false;
+      return true;
+    };
+    if (!finite(T0, Nh) || !finite(T_bar, Nh) || !finite(bar_amp, rows_h) || !finite(pattern, Nh * (size_t)n_pat) ||
+        !finite(n_pat > 0 ? amp : nullptr, rows_h * (size_t)n_pat))
+      return fail(PL_ERR_ARG, whos + ": T0, T_bar, bar_amp, pattern and amp must be finite");
+  }
+  if (h->opkind != 0) return fail(PL_ERR_STATE, whos + ": not available on a DDM handle");
+  if (h->dist.active || h->opt.grid_nodes > 0)
+    return fail(PL_ERR_STATE, whos + ": single-GPU handles only (this one belongs to a multi-rank run)");
+  if (!h->cond_ws) return fail(PL_ERR_STATE, whos + ": call pl_set_conduction first");
+  CondWs *w = static_cast<CondWs *>(h->cond_ws.get());
+  if (!w->heat) return fail(PL_ERR_STATE, whos + ": call pl_set_heat_capacity first");
+  if (!h->assembled) return fail(PL_ERR_STATE, whos + ": call pl_assemble first");
+  HeatWs *hw = static_cast<HeatWs *>(w->heat.get());
+  PL_HIP(hipSetDevice(h->opt.device));
+  // the two blocks that grow with the length of the history do not outlive the call, however it returns
+  struct HistoryRelease {
+    HeatWs *hw;
+    ~HistoryRelease() {
+      hw->probe.release();
+      hw->snaps.release();
+    }
+  } history_release{hw};
+
+  const int64_t N = h->N;
+  const size_t Ns = (size_t)N;
+  const int rows = n_steps + 1;
+  const int n_snap = snaps ? n_steps / snap_every : 0;
+  const double T_inf = w->conv ? w->T_inf : 0.0;
+  std::vector<int32_t> slot_of, probe_to_slot;
+  const int n_slot = probe_map(h, n_probe, probe_nodes, slot_of, probe_to_slot);
+  PL_HIP(heat_grow(hw->T2, 2 * Ns));
+  PL_HIP(heat_grow(hw->T0, Ns));
+  PL_HIP(heat_grow(hw->Tbar, Ns));
+  PL_HIP(heat_grow(hw->pattern, Ns * (size_t)std::max(n_pat, 1)));
+  PL_HIP(heat_grow(hw->amp, (size_t)rows * std::max(n_pat, 1)));
+  PL_HIP(heat_grow(hw->bar_amp, (size_t)rows));
+  PL_HIP(heat_grow(hw->probe_slot, Ns));
+  PL_HIP(heat_grow(hw->probe, (size_t)rows * std::max(n_slot, 1)));
+  PL_HIP(heat_grow(hw->heat, (size_t)rows * pl::HEAT_COUNT * pl::kSlots));
+  if (n_snap > 0) PL_HIP(heat_grow(hw->snaps, (size_t)n_snap * Ns));
+  if (w->conv && !w->H.p) return fail(PL_ERR_STATE, whos + ": the convection state holds no film sums");
+  // uploads, once per call: the mask, the start field, the end values, the patterns, the two tables and the probe map
+  if (fixed) {
+    if (int rc = cond_upload_mask(h, fixed, w->fixed.p)) return rc;
+  } else {
+    PL_HIP(hipMemsetAsync(w->fixed.p, 0, Ns, h->stream));
+  }
+  {
+    std::vector<double> t0(Ns, T_inf);
+    if (T0) std::memcpy(t0.data(), T0, Ns * sizeof(double));
+    if (int rc = cond_upload(h, t0.data(), hw->T0.p)) return rc;
+  }
+  if (int rc = cond_upload(h, T_bar, hw->Tbar.p)) return rc;
+  for (int p = 0; p < n_pat; ++p)
+    if (int rc = cond_upload(h, pattern + (size_t)p * Ns, hw->pattern.p + (size_t)p * Ns)) return rc;
+  if (n_pat > 0)
+    PL_HIP(hipMemcpyAsync(hw->amp.p, amp, (size_t)rows * n_pat * sizeof(double), hipMemcpyHostToDevice, h->stream));
+  if (bar_amp) PL_HIP(hipMemcpyAsync(hw->bar_amp.p, bar_amp, (size_t)rows * sizeof(double), hipMemcpyHostToDevice, h->stream));
+  PL_HIP(hipMemcpyAsync(hw->probe_slot.p, slot_of.data(), Ns * sizeof(int32_t), hipMemcpyHostToDevice, h->stream));
+  PL_HIP(hipStreamSynchronize(h->stream));         // (the tables and slot_of are pageable host memory)
+  PL_HIP(hipMemsetAsync(hw->heat.p, 0, (size_t)rows * pl::HEAT_COUNT * pl::kSlots * sizeof(double), h->stream));
+
+  const pl::HeatStep q = {dt, theta, T_inf, n_pat, (const uint8_t *)w->fixed.p, (const double *)hw->T0.p,
+                          (const double *)hw->Tbar.p, bar_amp ? (const double *)hw->bar_amp.p : (const double *)nullptr,
+                          (const double *)hw->pattern.p, (const double *)hw->amp.p};
+  const int SN = pl::kWave / h->lpn;
+  const int64_t *sp = (const int64_t *)h->slice_ptr.p;
+  const int2 *ent = (const int2 *)h->ent.p;
+  const double *g = (const double *)w->g.p;
+  const double *H = w->conv ? (const double *)w->H.p : (const double *)nullptr;
+  const dim3 gn(grid_for(N)), gs(grid_stream(N)), blk(pl::kBlock);
+  const bool timing = std::getenv("PL_TIMING") != nullptr;
+  const auto t_begin = std::chrono::steady_clock::now();
+  EventTimer timer(who, h->stream, "refresh_hip_event");
+  // refresh: g, c and cap of the current radii, then ONE per-node walk for C, H, the step diagonal and the Jacobi diagonal
+  if (w->conv) {
+    hipLaunchKernelGGL(pl::k_heat_strut<true>, dim3(grid_for(h->B)), blk, 0, h->stream, h->B, (const pl::Record *)h->rec.p,
+                       (const double *)h->radius.p, (const double *)h->mult.p, (const double *)w->kappa.p, w->g.p,
+                       (const double *)w->film.p, w->c.p, (const double *)hw->rho_c.p, hw->cap.p);
+    hipLaunchKernelGGL(pl::k_heat_diag<true>, gn, blk, 0, h->stream, N, SN, sp, ent, g, (const double *)w->c.p,
+                       (const double *)hw->cap.p, (const double *)hw->node_cap.p, (const uint8_t *)w->fixed.p, dt, theta, w->H.p,
+                       hw->C.p, hw->S.p, w->dinv.p);
+  } else {
+    hipLaunchKernelGGL(pl::k_heat_strut<false>, dim3(grid_for(h->B)), blk, 0, h->stream, h->B, (const pl::Record *)h->rec.p,
+                       (const double *)h->radius.p, (const double *)h->mult.p, (const double *)w->kappa.p, w->g.p,
+                       (const double *)nullptr, (double *)nullptr, (const double *)hw->rho_c.p, hw->cap.p);
+    hipLaunchKernelGGL(pl::k_heat_diag<false>, gn, blk, 0, h->stream, N, SN, sp, ent, g, (const double *)nullptr,
+                       (const double *)hw->cap.p, (const double *)hw->node_cap.p, (const uint8_t *)w->fixed.p, dt, theta,
+                       (double *)nullptr, hw->C.p, hw->S.p, w->dinv.p);
+  }
+  hipLaunchKernelGGL(pl::k_heat_start, gn, blk, 0, h->stream, N, q, (const double *)hw->C.p, hw->T2.p,
+                     (const int32_t *)hw->probe_slot.p, n_slot, hw->probe.p, hw->heat.p);
+  PL_HIP(hipGetLastError());
+  timer.mark("time_loop_hip_event");
+
+  // the time loop: nothing comes down but the status block, once per look
+  const MultiScal m = cond_scal(w);
+  const int every = h->opt.check_every > 0 ? h->opt.check_every : 16;
+  const size_t st_bytes = (size_t)pl::M_ST_COUNT * sizeof(double);
+  double status[pl::M_ST_COUNT] = {};
+  std::vector<int32_t> its((size_t)rows, 0);
+  long looks = 0, total_iters = 0;
+  double ms_begin = 0.0, ms_end = 0.0;
+  for (int row = 1; row <= n_steps; ++row) {
+    const double *Tn = hw->T2.p + (size_t)((row - 1) & 1) * Ns;
+    double *Tnew = hw->T2.p + (size_t)(row & 1) * Ns;
+    const bool time_row = timing && row == n_steps;   // the two fused kernels of the last step, timed on their own
+    PL_HIP(hipMemsetAsync(w->scal.p, 0, kCondScal * sizeof(double), h->stream));
+    PL_HIP(hipMemsetAsync(w->flags.p, 0, 2 * sizeof(int), h->stream));
+    {
+      EventTimer tk(who, h->stream);
+      if (time_row) tk.mark("k_heat_begin");
+      hipLaunchKernelGGL(w->conv ? pl::k_heat_begin<true> : pl::k_heat_begin<false>, gn, blk, 0, h->stream, N, SN, sp, ent, g, H, q,
+                         row, Tn, (const double *)w->dinv.p, w->X.p, w->R.p, w->Z.p, w->P.p, m.set[0], m.bb);
+      if (time_row) ms_begin = tk.lap();
+    }
+    hipLaunchKernelGGL(pl::k_multi_begin, dim3(1), dim3(pl::kWave), 0, h->stream, 1, rtol, (const double *)m.bb, m.thresh,
+                       m.status, m.flag[0]);
+    int it = 0, all = 0;
+    do {   // the first look comes after min(check_every, max_iter) iterations: past convergence they are no-ops
+      const int stop = std::min((int)max_iter, it + every);
+      for (; it < stop; ++it) {
+        const int a = it & 1, b = a ^ 1;
+        hipLaunchKernelGGL(pl::k_heat_gather, gn, blk, 0, h->stream, N, SN, sp, ent, g, (const double *)hw->S.p,
+                           (const uint8_t *)w->fixed.p, theta, (const double *)w->P.p, w->AP.p,
+                           m.set[a] + (size_t)pl::M_PAP * pl::kSlots);
+        hipLaunchKernelGGL((pl::k_multi_update<1>), gs, blk, 0, h->stream, N, (const double *)w->P.p, (const double *)w->AP.p,
+                           (const double *)w->dinv.p, w->X.p, w->R.p, w->Z.p, m.set[a], (const int *)m.flag[a], 1, N);
+        hipLaunchKernelGGL((pl::k_multi_direction<1>), gs, blk, 0, h->stream, N, (const double *)w->Z.p, w->P.p,
+                           (const double *)m.set[a], m.set[b], (const int *)m.flag[a], m.flag[b], (const double *)m.thresh,
+                           m.status, it, 1, N);
+      }
+      PL_HIP(hipGetLastError());
+      if (hipMemcpyAsync(status, m.status, st_bytes, hipMemcpyDeviceToHost, h->stream) != hipSuccess ||
+          hipStreamSynchronize(h->stream) != hipSuccess)
+        return fail(PL_ERR_HIP, whos + ": download of the status block failed");
+      ++looks;
+      all = status[pl::M_ST_FROZEN] == 0.0 ? 0 : 1;
+    } while (all == 0 && it < max_iter);
+    const double rr = status[pl::M_ST_RR], bb = status[pl::M_ST_BB];
+    if (!std::isfinite(rr) || !std::isfinite(bb))
+      return fail(PL_ERR_NAN, whos + ": NaN/Inf in a residual norm of step " + std::to_string(row));
+    if (!(rr <= rtol * rtol * bb))
+      return fail(PL_ERR_NOCONV, whos + ": the solve of step " + std::to_string(row) + " did not reach rtol within max_iter");
+    its[(size_t)row] = (int32_t)status[pl::M_ST_ITER];
+    total_iters += its[(size_t)row];
+    double *snap = nullptr;
+    if (n_snap > 0 && row % snap_every == 0) snap = hw->snaps.p + (size_t)(row / snap_every - 1) * Ns;
+    {
+      EventTimer tk(who, h->stream);
+      if (time_row) tk.mark("k_heat_end");
+      hipLaunchKernelGGL(w->conv ? pl::k_heat_end<true> : pl::k_heat_end<false>, gn, blk, 0, h->stream, N, SN, sp, ent, g, H,
+                         (const double *)hw->C.p, q, row, Tn, (const double *)w->X.p, Tnew, (const int32_t *)hw->probe_slot.p,
+                         hw->probe.p + (size_t)row * std::max(n_slot, 1), snap,
+                         hw->heat.p + (size_t)row * pl::HEAT_COUNT * pl::kSlots);
+      if (time_row) ms_end = tk.lap();
+    }
+    PL_HIP(hipGetLastError());
+  }
+  timer.stop();
+
+  // the histories come down once
+  if (heat) {
+    if (int rc = download_slot_sums(h, hw->heat.p, (size_t)rows * pl::HEAT_COUNT, heat)) return rc;
+    for (int r = 1; r < rows; ++r)     // the three exchanged heats are cumulative
+      for (int v : {pl::HEAT_QIN, pl::HEAT_QC, pl::HEAT_QR}) heat[r * pl::HEAT_COUNT + v] += heat[(r - 1) * pl::HEAT_COUNT + v];
+  }
+  if (n_probe > 0) {
+    const size_t ld = (size_t)std::max(n_slot, 1);
+    std::vector<double> ph((size_t)rows * ld);
+    PL_HIP(hipMemcpyAsync(ph.data(), hw->probe.p, ph.size() * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+    PL_HIP(hipStreamSynchronize(h->stream));
+    for (size_t r = 0; r < (size_t)rows; ++r)
+      for (int i = 0; i < n_probe; ++i) probe[r * n_probe + i] = ph[r * ld + probe_to_slot[(size_t)i]];
+  }
+  for (int k = 0; k < n_snap; ++k)
+    if (int rc = cond_download(h, hw->snaps.p + (size_t)k * Ns, snaps + (size_t)k * Ns)) return rc;
+  if (state)
+    if (int rc = cond_download(h, hw->T2.p + (size_t)(n_steps & 1) * Ns, state)) return rc;
+  if (iters) std::memcpy(iters, its.data(), (size_t)rows * sizeof(int32_t));
+  if (timing) {
+    PL_HIP(hipStreamSynchronize(h->stream));
+    const double ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_begin).count();
+    timing_ms(who, "whole_call_host_clock", ms);
+    timing_count(who, "steps", (int)n_steps);
+    timing_ms(who, "k_heat_begin_last_step", ms_begin);
+    timing_ms(who, "k_heat_end_last_step", ms_end);
+    timing_mean(who, "iterations_per_step", (double)total_iters / n_steps);
+    timing_mean(who, "host_syncs_per_step", (double)looks / n_steps);
+  }
+  return PL_OK;
 }
 
 // ---- transient response (pl_dyn.h) -------------------------------------------------------------------------------------

@@ -36,6 +36,22 @@
 
 namespace pl {
 
+// What the strut passes share (k_cond_strut, k_heat_strut of pl_heat.h), so that every call forms the same bits: the squared
+// node-to-node length of the record, g = k kappa pi r^2 / L and c = k h pi r L.
+__device__ __forceinline__ double strut_length2(const Record *__restrict__ rec, int64_t b) {
+  const double2 *q = reinterpret_cast<const double2 *>(rec + b);
+  const double2 q2 = q[2], q3 = q[3];
+  return q2.y * q2.y + q3.x * q3.x + q3.y * q3.y;
+}
+__device__ __forceinline__ double strut_conductance(const double *__restrict__ mult, const double *__restrict__ kappa, int64_t b,
+                                                    double r, double L2) {
+  return (mult ? mult[b] : 1.0) * kappa[b] * (3.14159265358979323846 * r * r) / sqrt(L2);
+}
+__device__ __forceinline__ double strut_film(const double *__restrict__ mult, const double *__restrict__ film, int64_t b, double r,
+                                             double L2) {
+  return (mult ? mult[b] : 1.0) * film[b] * (3.14159265358979323846 * r) * sqrt(L2);
+}
+
 // One thread per strut: g[b] = k kappa pi r^2 / L from the current radius and record; CONV: also c[b] = k h pi r L.
 template <bool CONV = false>
 __global__ __launch_bounds__(kBlock) void k_cond_strut(int64_t B, const Record *__restrict__ rec,
@@ -44,12 +60,10 @@ __global__ __launch_bounds__(kBlock) void k_cond_strut(int64_t B, const Record *
                                                        const double *__restrict__ film, double *__restrict__ c) {
   const int64_t b = (int64_t)blockIdx.x * kBlock + threadIdx.x;
   if (b >= B) return;
-  const double2 *q = reinterpret_cast<const double2 *>(rec + b);
-  const double2 q2 = q[2], q3 = q[3];
-  const double L2 = q2.y * q2.y + q3.x * q3.x + q3.y * q3.y;
+  const double L2 = strut_length2(rec, b);
   const double r = radius[b];
-  g[b] = (mult ? mult[b] : 1.0) * kappa[b] * (3.14159265358979323846 * r * r) / sqrt(L2);
-  if (CONV) c[b] = (mult ? mult[b] : 1.0) * film[b] * (3.14159265358979323846 * r) * sqrt(L2);
+  g[b] = strut_conductance(mult, kappa, b, r, L2);
+  if (CONV) c[b] = strut_film(mult, film, b, r, L2);
 }
 
 // CONV only, one thread per node, its struts in their stored order: H_i = sum c_b.
@@ -278,6 +292,7 @@ struct CondWs {
   DevBuf<uint8_t> fixed;                                 // [N]
   DevBuf<double> scal;   // [2 sets][M_COUNT][kSlots] | bb [kSlots] | thresh | status [M_ST_COUNT]   (one column)
   DevBuf<int> flags;     // [2]
+  std::shared_ptr<void> heat;   // heat capacity and the device data of pl_cond_transient (pl_heat.h), set by pl_set_heat_capacity
 };
 
 inline MultiScal cond_scal(CondWs *w) {

@@ -117,6 +117,7 @@ class LatticeSim(LatticeViews):
         self.thermal = None                        # (alpha, delta_T, beam_alpha) of set_temperature, None without one
         self.conduction = None                     # the conduction problem of solve_temperature, None without one
         self.temperature_field = None              # (n_nodes,) T of its last solve
+        self.temperature_history = None            # the dict of the last transient_temperature
         self._generate_and_prepare()
         if self._conduction_preset is not None:    # simulation_parameters["thermal"]["conduction"]
             c = self._conduction_preset
@@ -759,8 +760,8 @@ class LatticeSim(LatticeViews):
             dev.set_bc(self.fixed_DOF)
             dev.assemble()
 
-    def _solve_conduction(self, dev):
-        """T of the conduction problem on the handle's current radii (pl_cond_solve); the handle must be assembled."""
+    def _conduction_states(self, dev):
+        """The conduction and convection states of the kept problem on the handle, set where they differ."""
         c = self.conduction
         want = c["conductivity"] if c["beam_conductivity"] is None else c["beam_conductivity"]
         if dev._conduction is None or not np.array_equal(np.asarray(dev._conduction), np.asarray(want)):
@@ -774,6 +775,11 @@ class LatticeSim(LatticeViews):
             have = dev._convection
             if have is None or have[1] != cv["ambient"] or not np.array_equal(np.asarray(have[0]), np.asarray(want)):
                 dev.set_convection(cv["film"], cv["ambient"], cv["beam_film"])
+
+    def _solve_conduction(self, dev):
+        """T of the conduction problem on the handle's current radii (pl_cond_solve); the handle must be assembled."""
+        c = self.conduction
+        self._conduction_states(dev)
         T, self.conduction_stats = dev.cond_solve(c["fixed"], c["t_bar"], c["heat_flow"], rtol=1e-12, max_iter=200000)
         self.temperature_field = T
         return T
@@ -805,6 +811,62 @@ class LatticeSim(LatticeViews):
         dev = self.device_model()
         self._assemble_for_conduction(dev)
         return self._solve_conduction(dev).copy()
+
+    def transient_temperature(self, dt, n_steps, heat_capacity, theta=1.0, initial=None, amplitude=None, fixed_amplitude=None,
+                              probes=None, snap_every=0, beam_heat_capacity=None, node_capacity=None, rtol=1e-10,
+                              max_iter=100000):
+        """Temperatures in time of the conduction problem kept by the last ``solve_temperature`` - its mask, prescribed values,
+        heat flow and convection - on the device (pl_set_heat_capacity, pl_cond_transient): n_steps implicit theta steps
+        (theta = 1 backward Euler, 1/2 Crank-Nicolson) of C dT/dt + (K_T + H) T = a(t) q + H T_inf, C the lumped capacity of the
+        struts at the volumetric heat capacity ``heat_capacity`` (or beam_heat_capacity (n_beams,) per strut) plus
+        node_capacity (n_nodes,).  initial: the start field, (n_nodes,) or a scalar; None = the ambient of the convection,
+        else the problem's reference.  The heat flow is load pattern 0 with the factor ``amplitude``; the prescribed nodes go
+        from the start field to their values with the factor ``fixed_amplitude`` (None = at their values from the first row
+        on: a thermal shock).  Both: a callable of the time, an array (n_steps + 1,), or None = 1 throughout, as in
+        ``transient_response``.  probes: node indices (default: every node).  Returns the device call's dict - times, probe,
+        heat (U, Q_in, Q_c, Q_R), iters, state, snaps - and keeps it as ``temperature_history``; ``temperature_field`` is left
+        alone, and ``set_temperature`` takes any row of the history."""
+        if getattr(self, "_compat_rows", False) or self.domain_decomposition_solver:
+            raise NotImplementedError("heat conduction is not available in the reference_compat strut model or on a "
+                                      "domain-decomposition lattice")
+        if self.conduction is None:
+            raise RuntimeError("transient_temperature: no conduction problem is defined (solve_temperature)")
+        c = self.conduction
+        n, rows = self.lattice.n_nodes, int(n_steps) + 1
+        time = float(dt) * np.arange(rows)
+
+        def factor(a, what):
+            if a is None:
+                return None
+            if callable(a):
+                return np.array([float(a(t)) for t in time])
+            a = np.asarray(a, float).reshape(-1)
+            if a.size != rows:
+                raise ValueError(f"{what} must have {rows} entries")
+            return a
+
+        amp0, bar_amp = factor(amplitude, "amplitude"), factor(fixed_amplitude, "fixed_amplitude")
+        cv = c.get("convection", None)
+        if initial is None:
+            initial = cv["ambient"] if cv is not None else c["reference"]
+        t0 = np.array(np.broadcast_to(np.asarray(initial, dtype=float), (n,)))
+        dev = self.device_model()
+        self._assemble_for_conduction(dev)
+        self._conduction_states(dev)
+        bh = None if beam_heat_capacity is None else np.array(np.broadcast_to(np.asarray(beam_heat_capacity, dtype=float),
+                                                                              (self.lattice.n_beams,)))
+        nc = None if node_capacity is None else np.array(np.broadcast_to(np.asarray(node_capacity, dtype=float), (n,)))
+        have = dev._heat_capacity
+        if have is None or not np.array_equal(np.asarray(have[0]), np.asarray(float(heat_capacity) if bh is None else bh)) or \
+                (have[1] is None) != (nc is None) or (nc is not None and not np.array_equal(have[1], nc)):
+            dev.set_heat_capacity(0.0 if bh is not None else heat_capacity, bh, nc)
+        q = c["heat_flow"]
+        out = dev.cond_transient(dt, n_steps, theta, c["fixed"], c["t_bar"], bar_amp, None if q is None else q[None],
+                                 None if q is None else (np.ones(rows) if amp0 is None else amp0)[:, None], t0, rtol=rtol,
+                                 max_iter=max_iter, probes=np.arange(n) if probes is None else np.asarray(probes, int).reshape(-1),
+                                 snap_every=snap_every)
+        self.temperature_history = out
+        return out
 
     def clear_conduction(self):
         """Removes the conduction problem (and a temperature that is driven by it)."""

@@ -6,13 +6,21 @@ times are HIP events around the launches of one call (the library prints them wh
 the stage that ends it - for pl_cond_solve the whole PCG with its status downloads).  The rows under convection (DESIGN.md
 section 10m) follow in the same process, after the plain ones: the convective gather beside the plain gather of the same run,
 pl_cond_film (k_cond_film and its fold), the temperature p-norm pass and one pl_cond_solve with convection.
+Last, the transient (pl_cond_transient): --steps backward-Euler steps between the hot and the cold face,
+without and with the film, with the iterations per step, the device time per step and per iteration, k_heat_begin and k_heat_end
+of the last step beside one plain k_cond_gather of the same run, and the host synchronisations per step; they go to
+<out>_transient.json / .txt (--only-transient skips the rows above).
 
-    python tools/time_conduction.py --out profiles/r19_convection
+    python tools/time_conduction.py --out profiles/r20_heat                     (r19_convection: the record of section 10m)
+    python tools/time_conduction.py --out profiles/r20_heat --only-transient
 """
 import argparse
 import json
 import os
+import re
 import sys
+import tempfile
+import time
 
 import numpy as np
 
@@ -25,9 +33,76 @@ from time_stress import _summary, _timed                               # noqa: E
 from pylatticedso_amd.lattice_sim import LatticeSim                    # noqa: E402
 
 
+def _captured(fn):
+    """(wall ms, the library's PL_TIMING lines of the call as {label: value}, result)."""
+    sys.stderr.flush()
+    saved = os.dup(2)
+    with tempfile.TemporaryFile(mode="w+b") as tmp:
+        os.dup2(tmp.fileno(), 2)
+        try:
+            t0 = time.perf_counter()
+            out = fn()
+            wall = 1e3 * (time.perf_counter() - t0)
+        finally:
+            os.dup2(saved, 2)
+            os.close(saved)
+        tmp.seek(0)
+        text = tmp.read().decode(errors="replace")
+    return wall, {m[0]: float(m[1]) for m in re.findall(r"\[pl_cond_transient\]\s+(\S+)\s+([0-9.]+)", text)}, out
+
+
+def transient_rows(a, dev, fixed, t_bar, T):
+    """The transient with and without the film on the handle's lattice: medians and spreads of a.reps warm repetitions."""
+    res = {"steps": a.steps, "dt": a.dt, "rho_c": a.rho_c, "rtol": a.rtol, "theta": 1.0, "reps": a.reps, "cases": {}}
+    for name, film in (("no film", None), (f"film {a.film:g}", a.film)):
+        dev.set_conduction(0.2)
+        if film is not None:
+            dev.set_convection(film, a.ambient)
+        dev.set_heat_capacity(a.rho_c)
+        t0 = np.full(dev.n_nodes, a.ambient)
+        keep = {}
+        for rep in range(a.reps + 1):
+            wall, lines, out = _captured(lambda: dev.cond_transient(a.dt, a.steps, 1.0, fixed, t_bar, t0=t0, rtol=a.rtol,
+                                                                    max_iter=200000))
+            _, gather, _ = _timed(lambda: dev.cond_spmv(T))
+            if rep:
+                its = int(out["iters"].sum())
+                row = {"wall_ms": wall, "time_loop_ms": lines["time_loop_hip_event"], "refresh_ms": lines["refresh_hip_event"],
+                       "device_ms_per_step": lines["time_loop_hip_event"] / a.steps,
+                       "device_ms_per_iteration": lines["time_loop_hip_event"] / max(its, 1),
+                       "k_heat_begin_ms": lines["k_heat_begin_last_step"], "k_heat_end_ms": lines["k_heat_end_last_step"],
+                       "k_cond_gather_ms": gather, "host_syncs_per_step": lines["host_syncs_per_step"],
+                       "iterations_per_step": its / a.steps}
+                for k, v in row.items():
+                    keep.setdefault(k, []).append(v)
+        res["cases"][name] = {k: _summary(v) for k, v in keep.items()}
+        res["cases"][name]["iterations_of_every_step"] = out["iters"].tolist()
+    return res
+
+
+def transient_report(a, res, head):
+    lines = [f"{head}; pl_cond_transient, {res['steps']} backward-Euler steps of dt {res['dt']:g}, rho_c {res['rho_c']:g}, "
+             f"rtol {res['rtol']:g}, hot Zmin and cold Zmax from the ambient; medians [min, max] of {a.reps} warm repetitions"]
+    for name, c in res["cases"].items():
+        lines.append(f"  {name}:")
+        for k, r in c.items():
+            if isinstance(r, dict):
+                lines.append(f"    {k:28} {r['median_ms']:10.4f}   [{r['min_ms']:.4f}, {r['max_ms']:.4f}]")
+        lines.append(f"    iterations of every step     {c['iterations_of_every_step']}")
+    with open(a.out + "_transient.json", "w") as fh:
+        json.dump(res, fh, indent=1)
+    with open(a.out + "_transient.txt", "w") as fh:
+        fh.write("\n".join(lines) + "\n")
+    print("\n".join(lines))
+
+
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--out", default="profiles/r19_convection")
+    ap.add_argument("--steps", type=int, default=20)
+    ap.add_argument("--dt", type=float, default=0.5)
+    ap.add_argument("--rho-c", dest="rho_c", type=float, default=2.0)
+    ap.add_argument("--only-transient", action="store_true")
+    ap.add_argument("--out", default="profiles/r20_heat")
     ap.add_argument("--film", type=float, default=0.05)
     ap.add_argument("--ambient", type=float, default=20.0)
     ap.add_argument("--reps", type=int, default=5)
@@ -60,6 +135,12 @@ def main():
     dev.set_thermal(7e-5, 40.0 + 10.0 * (2.0 * rng.random(lat.n_nodes) - 1.0))
     res = {"lattice": f"{n}^3 {a.geom}", "n_nodes": int(lat.n_nodes), "n_beams": int(lat.n_beams), "reps": a.reps,
            "rtol": a.rtol, "rows": {}}
+    os.makedirs(os.path.dirname(a.out) or ".", exist_ok=True)
+    head = f"{res['lattice']}: {res['n_nodes']} nodes, {res['n_beams']} struts"
+    if a.only_transient:
+        transient_report(a, transient_rows(a, dev, fixed, t_bar, T), head)
+        dev.close()
+        return
     solves = []
 
     def solve():
@@ -114,7 +195,6 @@ def main():
                                         "converged": int(st["converged"])},
                          "k_cond_gather_conv_model_bytes": int(res["k_cond_gather_model_bytes"] + 8 * lat.n_nodes),
                          "k_cond_gather_conv_over_plain": k[conv_gather] / k[plain_gather]}
-    os.makedirs(os.path.dirname(a.out) or ".", exist_ok=True)
     with open(a.out + ".json", "w") as fh:
         json.dump(res, fh, indent=1)
     lines = [f"{res['lattice']}: {res['n_nodes']} nodes, {res['n_beams']} struts; medians of {a.reps} warm repetitions"]
@@ -134,6 +214,7 @@ def main():
     with open(a.out + ".txt", "w") as fh:
         fh.write("\n".join(lines) + "\n")
     print("\n".join(lines))
+    transient_report(a, transient_rows(a, dev, fixed, t_bar, T), head)
     dev.close()
 
 
